@@ -14,6 +14,11 @@ only collective is one RCCL all-reduce of three int64 episodic sums per pass, in
 `--gpus N` is binding: without WORLD_SIZE in the environment the process becomes a launcher (it never touches the
 GPU) that starts N rank processes -- the one-command form of the reference driver (multiprocess.py:89-97); with
 WORLD_SIZE set (torch.distributed.run) it must equal N, anything else is a non-zero exit.
+
+A plain run does what the headline figure needs: set-up (placement of the trajectory tensor, pre-roll), W warm-up passes, exactly K
+timed passes, the outputs of the last timed pass if `--dump-outputs DIR` is given, the result line.  `--full` adds everything else,
+after the clock has stopped: the write-ceiling probe, the retiming of a stalled region, the checks (trajectory, full pass against the
+tile kernel, parity with the CPU oracle), the tile-major layout, the other configurations and the CPU baseline.
 """
 import argparse
 import gc
@@ -50,7 +55,11 @@ def parse_args(argv=None):
     ap.add_argument("--static", action="store_true")
     ap.add_argument("--T", type=int, default=0, help="vector steps per pass (default: total_step)")
     ap.add_argument("--obs-f32", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the write-ceiling probe, retiming, checks, tile-major layout, other configurations and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed pass's outputs to DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -326,6 +335,29 @@ def measured_write_peak(torch, dev, nbytes=1 << 31, ms_budget=50.0, alloc=None):
     return nbytes * k / (ms * 1e-3) / 1e9 if ms else None
 
 
+DUMP_SAMPLES = 1 << 16                                            # (tick, env) pairs of the last pass written by --dump-outputs
+DUMP_BYTES = 48 << 20                                             # ... at most this many bytes of them (the limit is 64 MB in all)
+
+
+def dump_outputs(path, obs, reward, done, sums):
+    """--dump-outputs: what the timed path returned in its last pass -- rollout()'s rows [T, N, D], rewards and done flags [T, N] --
+    and the episodic sums the pass ends with, as .npy files in `path`.  The rows are 16 GB at the headline size, so the same seeded
+    sample of (tick, env) pairs is taken in every run of the same arguments, in ascending order of t * N + env: obs [M, D] in the rows'
+    dtype, reward [M] float32, done [M] float32 (0 / 1), episodic [3] float64 (episodes, return sum, IoU fixed-point sum)."""
+    import numpy as np
+    import torch
+
+    T, n, D = obs.shape
+    m = min(T * n, DUMP_SAMPLES, DUMP_BYTES // (D * obs.element_size() + 8))
+    flat = np.sort(np.random.default_rng(0).choice(T * n, size=m, replace=False))
+    flat = torch.from_numpy(flat).to(obs.device)
+    t, e = flat // n, flat % n
+    os.makedirs(path, exist_ok=True)
+    arrays = {"obs": obs[t, e], "reward": reward[t, e], "done": done[t, e].to(torch.float32), "episodic": sums.to(torch.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+
+
 def main():
     args = parse_args()
     if args.gpus < 1:
@@ -442,12 +474,12 @@ def main():
         s = allreduce_(env.stats_tensor())  # RCCL over xGMI: episodic [episodes, return sum, IoU fixed-point sum]
         stats.copy_(s)
 
-    # The write-ceiling probe (~60 ms of hipMemsetAsync) runs FIRST, on every rank: a GPU that comes from idle needs some tens
+    # The write-ceiling probe (~60 ms of hipMemsetAsync, --full) runs FIRST, on every rank: a GPU that comes from idle needs some tens
     # of milliseconds of load before it holds its sustained clocks (tools/b2b_time.py: the same launch takes 1.51 ms right
     # after an idle gap and 1.29 ms ten launches later), and W warm-up passes of 3 ms each do not get it there.
-    wpeak_malloc = measured_write_peak(torch, dev)
+    wpeak_malloc = measured_write_peak(torch, dev) if args.full else None
     wpeak_vmm = None
-    if traj_alloc:
+    if traj_alloc and args.full:
         try:
             wpeak_vmm = measured_write_peak(torch, dev, alloc=traj_alloc)
         except Exception as e:
@@ -495,8 +527,10 @@ def main():
         pending = []
         for i in range(args.steps):
             ev[i][0].record()
-            env.rollout(T, obs="all", out=obs)
+            ret = env.rollout(T, obs="all", out=obs)
             ev[i][1].record()
+            if i < args.steps - 1:
+                ret = None                                      # (released before the next pass allocates its reward / done)
             s = env.stats_tensor(out=stats) if not use_dist else env.stats_tensor()   # no group: the sums land where they are kept
             if not use_dist:
                 continue
@@ -516,28 +550,37 @@ def main():
         sync()
         dt_ = time.perf_counter() - t0
         dt_ = float(allreduce_(torch.tensor([dt_], dtype=torch.float64, device=dev), dist.ReduceOp.MAX).item())
-        return dt_, [a.elapsed_time(b) for a, b in ev], len(pending)
+        return dt_, [a.elapsed_time(b) for a, b in ev], len(pending), ret
 
     # The boxes of this pool stall for tens of milliseconds now and then (a group of bench extras: 362 instead of 8.6 us per launch, twice
     # in this round's runs; round 4's driver run: 396 instead of 38) -- as long as the whole timed region of the headline.  A timed region
     # that shows such a stall (its slowest pass > 2 x its median pass, or its wall time > 1.3 x the sum of its kernels + 1 ms per pass) is
     # timed ONCE more, by every rank together, and the second region is the one reported; both are in `timed_regions`, `retimed` says so.
-    # SNAC_BENCH_RETIME=0 switches that off.
+    # --full only (a plain run times exactly K passes); SNAC_BENCH_RETIME=0 switches it off.  The second region starts from the state the
+    # first one started from, so it repeats the same passes and --dump-outputs writes the same outputs either way.
     def stalled(dt_, ms_):
         srt = sorted(ms_)
         med = srt[len(srt) // 2]
         wall = (not use_dist or backend == "nccl") and dt_ * 1e3 > 1.3 * sum(ms_) + 1.0 * len(ms_)   # (gloo: the exchange itself takes milliseconds of host time)
         return bool(srt[-1] > 2.0 * med or wall)
 
-    dt, per_step_ms, n_async = timed_region()
+    retime = args.full and os.environ.get("SNAC_BENCH_RETIME", "1") != "0"
+    before = env.state_dict() if retime else None
+    dt, per_step_ms, n_async, last = timed_region()
     timed_regions = [{"ms_per_step": dt / args.steps * 1e3, "kernel_ms_per_step": [round(x, 4) for x in per_step_ms], "stalled": stalled(dt, per_step_ms)}]
     retimed = False
-    if os.environ.get("SNAC_BENCH_RETIME", "1") != "0":
+    if retime:
         flag = float(allreduce_(torch.tensor([1.0 if timed_regions[0]["stalled"] else 0.0], dtype=torch.float64, device=dev), dist.ReduceOp.MAX).item())
         if flag > 0:
-            dt, per_step_ms, n_async = timed_region()
+            last = None
+            env.load_state_dict(before)
+            dt, per_step_ms, n_async, last = timed_region()
             timed_regions.append({"ms_per_step": dt / args.steps * 1e3, "kernel_ms_per_step": [round(x, 4) for x in per_step_ms], "stalled": stalled(dt, per_step_ms)})
             retimed = True
+        del before
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0], last[1], last[2], stats)
+    del last
     # a group of one: what came back from the collective must be this rank's own sums
     collective_check = bool(torch.equal(stats, env.stats_tensor())) if (use_dist and world == 1) else None
     kern_ms = sum(per_step_ms) / max(args.steps, 1)
@@ -559,10 +602,10 @@ def main():
 
     kernel_name = _lib.lib().snac_last_kernel().decode()        # what the timed launches went to, as the library's dispatch says
 
-    # integrity of what the timed passes wrote (after the clock stopped): the last step's rows in the trajectory tensor must be the
-    # batch's current observation, read through a different kernel into ordinary memory
-    traj_ok = bool(torch.equal(obs[T - 1], env.observe()))
-    if not traj_ok:
+    # --full: integrity of what the timed passes wrote (after the clock stopped): the last step's rows in the trajectory tensor must be
+    # the batch's current observation, read through a different kernel into ordinary memory
+    traj_ok = bool(torch.equal(obs[T - 1], env.observe())) if args.full else None
+    if traj_ok is False:
         sys.stderr.write("bench.py: the trajectory tensor's last step differs from observe() -- the measurement is INVALID\n")
     # ... "bit-exact vs CPU" as something THIS run proves: a fresh batch with the measured batch's seed, table and env ids makes one
     # full pass (the same launch shape, the same kernel) into the measured trajectory block, and its reset observation and the first
@@ -571,7 +614,7 @@ def main():
     # run's own certificate, a fraction of a second.)
     PARITY_TICKS = 10
     parity = None
-    if os.environ.get("SNAC_BENCH_PARITY", "1") != "0":
+    if args.full and os.environ.get("SNAC_BENCH_PARITY", "1") != "0":
         try:
             first, oo, ro, do = oracle_first_ticks(args.kind, dynamic, n, 1, rank * n, PARITY_TICKS, min(16, os.cpu_count() or 1))
             fresh = BatchedDMPEnv(args.kind, dynamic, n, device=dev, seed=1, env_id_base=rank * n,
@@ -604,14 +647,15 @@ def main():
     lay_code = {"one run": 1, "three runs 32 GiB apart": 2, "measured: two slices in turn": 3}.get((blk or {}).get("layout"), 0)
     mine = torch.zeros((world, 8), dtype=torch.float64, device=dev)
     mine[rank] = torch.tensor([kern_ms, lay_code, (blk or {}).get("us_per_gib", {}).get("block", 0.0), (blk or {}).get("us_per_gib", {}).get("fast", 0.0),
-                               (blk or {}).get("windows_slow", 0), (blk or {}).get("rebuilds", 0), 1.0 if traj_ok else 0.0,
+                               (blk or {}).get("windows_slow", 0), (blk or {}).get("rebuilds", 0), -1.0 if traj_ok is None else float(traj_ok),
                                1.0 if parity is True else (0.0 if parity is False else -1.0)], dtype=torch.float64)
     mine = allreduce_(mine).tolist()
     lay_names = {0: "hipMalloc", 1: "one run", 2: "three runs 32 GiB apart", 3: "measured: two slices in turn"}
     per_rank_report = [{"rank": i, "kernel_ms": round(r[0], 4), "block_layout": lay_names[int(r[1])], "block_us_per_gib": r[2], "fast_us_per_gib": r[3],
-                        "windows_slow": int(r[4]), "rebuilds": int(r[5]), "trajectory_check": bool(r[6]), "parity_vs_oracle": (None if r[7] < 0 else bool(r[7]))}
+                        "windows_slow": int(r[4]), "rebuilds": int(r[5]), "trajectory_check": (None if r[6] < 0 else bool(r[6])),
+                        "parity_vs_oracle": (None if r[7] < 0 else bool(r[7]))}
                        for i, r in enumerate(mine)]
-    all_ok = all(r["trajectory_check"] for r in per_rank_report)
+    all_ok = all(r["trajectory_check"] is not False for r in per_rank_report)
     parity_all = None if any(r["parity_vs_oracle"] is None for r in per_rank_report) else all(r["parity_vs_oracle"] for r in per_rank_report)
     # N RCCL ranks must sit on N distinct GPUs
     devices_ok = backend != "nccl" or world == 1 or len(set(ranks_devices)) == world
@@ -622,7 +666,7 @@ def main():
     # (an output that is not 16-byte aligned cannot take k_rollout2d's 16-byte stores, snac_hip.hip roll2d_ok()) into ordinary memory;
     # all T x N rows, rewards and done flags of the two passes must be equal.  After the clock has stopped; one GPU, rank 0.
     full_check = None
-    if world == 1 and os.environ.get("SNAC_BENCH_FULLCHECK", "1") != "0":
+    if args.full and world == 1 and os.environ.get("SNAC_BENCH_FULLCHECK", "1") != "0":
         try:
             twin = env.fork(torch.arange(n, device=dev))
             raw = torch.empty(T * n * env.obs_dim + 1, dtype=env.obs_dtype, device=dev)
@@ -990,7 +1034,7 @@ def main():
         return res
 
     extras = None
-    if world == 1 and rank == 0 and os.environ.get("SNAC_BENCH_EXTRAS", "1") != "0" and (args.kind, dynamic, n, args.obs_f32) == (2, True, 65536, False) and T == 600:
+    if args.full and world == 1 and rank == 0 and os.environ.get("SNAC_BENCH_EXTRAS", "1") != "0" and (args.kind, dynamic, n, args.obs_f32) == (2, True, 65536, False) and T == 600:
         try:
             extras = extra_configs()
         except Exception as e:                                   # informational only: never take the headline line down with it
@@ -998,7 +1042,7 @@ def main():
             extras = {"error": repr(e)}
 
     try:
-        tiled = tiled_extra() if (world == 1 and args.kind == 2 and n % 64 == 0 and not args.static and os.environ.get("SNAC_BENCH_TILED", "1") != "0") else None
+        tiled = tiled_extra() if (args.full and world == 1 and args.kind == 2 and n % 64 == 0 and not args.static and os.environ.get("SNAC_BENCH_TILED", "1") != "0") else None
     except Exception as e:                                       # informational only: never take the headline line down with it
         sys.stderr.write("bench.py: tile-major extra measurement failed (%r)\n" % (e,))
         tiled = {"error": repr(e)}
@@ -1080,7 +1124,7 @@ def main():
             "episodic": {"episodes": s[0], "mean_return": (s[1] / s[0]) if s[0] else None,
                          "mean_iou": (s[2] / 2.0 ** 40 / s[0]) if s[0] else None},
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args.kind, dynamic, n, T, 1)
         # The driver parses the LAST stdout line and keeps only a tail of stdout: the line stays a few KB (round 5's 22 KB line was
         # cut and could not be parsed).  Everything else -- extras with their timing spreads, placement, per-rank accounts, timed
@@ -1098,7 +1142,7 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
-    if not (traj_ok and all_ok and devices_ok) or parity_all is False or collective_check is False:
+    if traj_ok is False or not (all_ok and devices_ok) or parity_all is False or collective_check is False:
         sys.exit(4)
 
 

@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <sys/mman.h>
+#include <sys/resource.h>
 #include <unistd.h>
 
 #include <algorithm>
@@ -48,6 +49,17 @@ double g_clock_us = 0.0;                             // one simulated clock for 
 std::atomic<uint64_t> g_launches{0};
 long g_fail_at = -1, g_calls = 0;
 bool g_fired = false;
+
+// every simulated physical allocation is a memfd: a measured 16 "GiB" block holds more of them at once than the common soft limit of
+// 1024 open files, so the soft limit is raised to the hard one (at most 65536) when the process starts
+const bool g_nofile_raised = [] {
+    rlimit r;
+    if (getrlimit(RLIMIT_NOFILE, &r) != 0) return false;
+    const rlim_t want = std::min<rlim_t>(r.rlim_max, 65536);
+    if (r.rlim_cur >= want) return true;
+    r.rlim_cur = want;
+    return setrlimit(RLIMIT_NOFILE, &r) == 0;
+}();
 
 hipError_t set(hipError_t e) { t_last = e; return e; }
 // a call that a test may make fail

@@ -76,7 +76,7 @@ def _bench(cmd, env, check=True):
 
 def _run(cmd, env=None):
     e = dict(os.environ)
-    e["SNAC_BENCH_RETIME"] = "0"                                  # (a retimed region runs K more passes: the episodic sums compared below would differ)
+    e["SNAC_BENCH_RETIME"] = "0"                                  # (--full runs: one timed region per line)
     e.update(env or {})
     return _bench(cmd, e)[1]
 
@@ -90,7 +90,7 @@ def _port():
 
 
 def test_bench_line_and_two_rank_path():
-    one = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--envs", "8192", "--T", "120"])
+    one = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--envs", "8192", "--T", "120", "--full"])
     assert KEYS <= set(one) and "cpu_baseline" in one
     assert one["n_gpus"] == 1 and one["unit"] == "env-steps/s" and one["dtype"] == "f64" and one["scaling"] == "weak"
     assert one["vs_baseline"] is None and one["higher_is_better"] is True and "workload" in one["config"]
@@ -118,7 +118,7 @@ def test_gpus_flag_starts_the_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["SNAC_BENCH_BACKEND"] = "gloo"
     env["SNAC_BENCH_RETIME"] = "0"
-    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--T", "120", "--no-cpu"]
+    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--T", "120", "--no-cpu", "--full"]
     out, two = _bench(cmd + ["--gpus", "2", "--envs", "4096"], env)
     one = _run(cmd + ["--envs", "8192"])
     assert two["n_gpus"] == 2 and two["ranks"] == 2 and two["backend"] == "gloo"
@@ -189,7 +189,7 @@ def test_bench_takes_its_rccl_path_with_one_rank():
     MAX over ranks of the wall time.  What came back must be the rank's own sums, and the line must say RCCL saw one rank."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(SNAC_BENCH_FORCE_DIST="1", SNAC_BENCH_BACKEND="nccl", SNAC_BENCH_RETIME="0")
-    cmd = [sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--envs", "8192", "--T", "120", "--no-cpu"]
+    cmd = [sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--envs", "8192", "--T", "120", "--no-cpu", "--full"]
     out, forced = _bench(cmd, env)
     assert forced["backend"] == "nccl" and forced["rccl_ranks"] == 1 and forced["ranks"] == 1 and forced["n_gpus"] == 1
     assert forced["collective_check"] is True and forced["rccl_async_exchanges"] == 4
@@ -204,10 +204,44 @@ def test_a_stalled_timed_region_is_timed_once_more():
     """The boxes of the pool stall for tens of milliseconds now and then; a headline region that shows it (slowest pass > 2 x the median
     pass) is timed once more and both regions are reported.  Forced here with a pass count of 3 and a sleep-free trick: the first
     region of a cold process carries the clock ramp when the pre-roll is switched off and the batch is tiny."""
-    one = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "0", "--envs", "8192", "--T", "120", "--no-cpu"],
+    one = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "0", "--envs", "8192", "--T", "120", "--no-cpu", "--full"],
                env={"SNAC_BENCH_RETIME": "1", "SNAC_BENCH_PREROLL_MS": "0"})
     assert isinstance(one["retimed"], bool) and 1 <= len(one["timed_regions"]) <= 2
     assert one["retimed"] == (len(one["timed_regions"]) == 2)
     assert one["timed_regions"][0]["stalled"] == one["retimed"]
     last = one["timed_regions"][-1]
     assert abs(last["ms_per_step"] - one["ms_per_step"]) < 1e-9 and len(last["kernel_ms_per_step"]) == 3
+
+
+def test_plain_run_times_k_passes_and_dumps_the_last_one(tmp_path):
+    """Without --full the run sets up, warms up, times exactly K passes and prints the line (no checks, extras or CPU baseline);
+    --dump-outputs DIR writes the same sample of the last timed pass in every run, and it is what a fresh batch with the run's seed
+    returns after W + K passes of its own."""
+    import numpy as np
+    import torch
+
+    import bench
+    from snac_amd import BatchedDMPEnv
+
+    W, K, n, T = 1, 3, 8192, 120
+    cmd = [sys.executable, "bench.py", "--steps", str(K), "--warmup", str(W), "--envs", str(n), "--T", str(T)]
+    for d in ("a", "b"):
+        line = _bench(cmd + ["--dump-outputs", str(tmp_path / d)], os.environ)[1]
+        assert line["steps"] == K and len(line["kernel_ms_per_step"]) == K and line["retimed"] is False and len(line["timed_regions"]) == 1
+        assert "cpu_baseline" not in line and line["extra"]["configs"] is None and line["tiled_layout"] is None
+        assert line["parity_vs_oracle"] is None and line["trajectory_full_pass_check"] is None
+        assert line["roofline"]["peak_measured_write"] is None and line["ms_per_step"] > 0
+    env = BatchedDMPEnv(2, True, n, device="cuda:0", seed=1)
+    env.reset()
+    for _ in range(W + K):
+        o, r, dn = env.rollout(T)
+    bench.dump_outputs(str(tmp_path / "c"), o, r, dn, env.stats_tensor())
+    torch.cuda.synchronize()
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["done.npy", "episodic.npy", "obs.npy", "reward.npy"] and sorted(os.listdir(tmp_path / "c")) == names
+    total = 0
+    for name in names:
+        a, b, c = (np.load(tmp_path / d / name) for d in ("a", "b", "c"))
+        assert a.dtype in (np.float32, np.float64) and a.tobytes() == b.tobytes() == c.tobytes(), name
+        total += a.nbytes
+    assert total <= 64 << 20 and np.load(tmp_path / "a" / "obs.npy").shape[1] == env.obs_dim
