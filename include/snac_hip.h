@@ -470,6 +470,42 @@ int snac_transition_nodes2d(const snac_env_desc* desc, const snac_state* st, sna
                             const int32_t* src_index, const int32_t* dst_index, uint32_t t, const int8_t* actions, const int8_t* step_size,
                             void* obs, float* reward, uint8_t* done, void* stream);
 
+/* ---- 1D and 3D node pools with ONE record per node: the same idea and the same index, clamping and error conventions as the 2D
+ * pools above, for transition(state, action) of Env/1D/DMP_Env_1D_dynamic_MCTS.py:82-139 (static: DMP_Env_1D_static_MCTS.py) and
+ * Env/3D/DMP_simulator_3d_static_circle_MCTS.py:215-288, DMP_simulator_3d_dynamic_triangle_MCTS.py:195-277.  In the arrays of
+ * snac_state a 1D parent is three lines for 84 bytes (header, episode counter, 64-byte grid record) and a 3D parent nine lines (the
+ * 800 bytes of heights at offset r * 800 span seven, plus the header's and the counter's); a snac_node1d is one line, a snac_node3d
+ * seven whole lines.  Every pad word is zero after a pack and stays zero after a transition.  Each entry point accepts its own kind
+ * only and the canonical observation layout (layout variants: SNAC_ERR_UNSUPPORTED); no auto-reset, no episodic sums. */
+typedef struct snac_node1d {    /* 128 bytes, 128-byte aligned: ONE line */
+    snac_env_hdr hdr;
+    int32_t episode;
+    int32_t zero0[3];
+    int16_t cells[32];          /* the grid record of the 1D kinds: 30 interior heights + 2 pad (zero) */
+    uint32_t zero1[8];
+} snac_node1d;
+typedef struct snac_node3d {    /* 896 bytes, 128-byte aligned: seven lines */
+    snac_env_hdr hdr;
+    int32_t episode;
+    int32_t zero0[3];
+    int16_t heights[400];       /* the grid record of the 3D kinds: the 20x20 interior, row-major */
+    uint32_t zero1[16];
+} snac_node3d;
+int snac_nodes1d_pack(const snac_env_desc* desc, const snac_state* st, const int32_t* rows, int32_t m, snac_node1d* nodes, int32_t pool_rows,
+                      const int32_t* node_rows, void* stream);
+int snac_nodes1d_unpack(const snac_env_desc* desc, const snac_node1d* nodes, int32_t pool_rows, const int32_t* node_rows, int32_t m, snac_state* st,
+                        const int32_t* rows, void* stream);
+int snac_transition_nodes1d(const snac_env_desc* desc, const snac_state* st, snac_node1d* nodes, int32_t pool_rows, int32_t m,
+                            const int32_t* src_index, const int32_t* dst_index, uint32_t t, const int8_t* actions, const int8_t* step_size,
+                            void* obs, float* reward, uint8_t* done, void* stream);
+int snac_nodes3d_pack(const snac_env_desc* desc, const snac_state* st, const int32_t* rows, int32_t m, snac_node3d* nodes, int32_t pool_rows,
+                      const int32_t* node_rows, void* stream);
+int snac_nodes3d_unpack(const snac_env_desc* desc, const snac_node3d* nodes, int32_t pool_rows, const int32_t* node_rows, int32_t m, snac_state* st,
+                        const int32_t* rows, void* stream);
+int snac_transition_nodes3d(const snac_env_desc* desc, const snac_state* st, snac_node3d* nodes, int32_t pool_rows, int32_t m,
+                            const int32_t* src_index, const int32_t* dst_index, uint32_t t, const int8_t* actions, const int8_t* step_size,
+                            void* obs, float* reward, uint8_t* done, void* stream);
+
 /* (position, environment_memory, count_brick, count_step) tuples of the reference (the `state` of the MCTS variants,
  * Env/2D/DMP_ENV_2D_dynamic_MCTS.py:88-91) -> pool rows dst_index[i] (NULL: row i); the inverse of snac_export_grid plus
  * the header.  position int32[m][2] (row, col; 1D: position, ignored), count_brick / count_step int32[m],

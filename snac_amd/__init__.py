@@ -6,7 +6,7 @@ implementation.  See DESIGN.md / INTEGRATION.md.
 from ._lib import SnacError, build  # noqa: F401
 from . import plans  # noqa: F401
 
-__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "NodePool2D", "SnacError", "build", "plans"]
+__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "SnacError", "build", "plans"]
 
 
 def __getattr__(name):  # torch is imported lazily so that `import snac_amd` stays cheap
@@ -18,10 +18,10 @@ def __getattr__(name):  # torch is imported lazily so that `import snac_amd` sta
         from .replay import ReplayRing
 
         return ReplayRing
-    if name == "NodePool2D":
-        from .nodes import NodePool2D
+    if name in ("NodePool", "NodePool1D", "NodePool2D", "NodePool3D"):
+        from . import nodes
 
-        return NodePool2D
+        return getattr(nodes, name)
     if name == "VectorizedEnvWrapper":
         from .vector import VectorizedEnvWrapper
 

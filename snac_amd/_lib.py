@@ -25,7 +25,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_import_state", "snac_obs_equal", "snac_discounted_return", "snac_plans_from_grids", "snac_mailbox_create", "snac_mailbox_row", "snac_mailbox_touch", "snac_mailbox_step", "snac_mailbox_step_n", "snac_mailbox_reward", "snac_mailbox_done",
            "snac_mailbox_quit", "snac_mailbox_settle", "snac_mailbox_destroy", "snac_mailbox_stats", "snac_stream_sync", "snac_rollout_tiled", "snac_replay_gather_tiled", "snac_traj_alloc",
            "snac_traj_alloc_ex", "snac_traj_free", "snac_traj_layout", "snac_traj_describe", "snac_traj_reserved_bytes", "snac_last_kernel", "snac_tuning",
-           "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d")
+           "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d", "snac_nodes1d_pack", "snac_nodes1d_unpack",
+           "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d")
 
 
 class Sizes(C.Structure):
@@ -129,6 +130,10 @@ def lib():
         L.snac_nodes2d_pack.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, vp, C.c_int32, vp, vp]
         L.snac_nodes2d_unpack.argtypes = [C.POINTER(EnvDesc), vp, C.c_int32, vp, C.c_int32, C.POINTER(State), vp, vp]
         L.snac_transition_nodes2d.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+        for k in ("1d", "3d"):
+            getattr(L, "snac_nodes%s_pack" % k).argtypes = L.snac_nodes2d_pack.argtypes
+            getattr(L, "snac_nodes%s_unpack" % k).argtypes = L.snac_nodes2d_unpack.argtypes
+            getattr(L, "snac_transition_nodes%s" % k).argtypes = L.snac_transition_nodes2d.argtypes
         L.snac_import_state.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_plans_from_grids.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, C.POINTER(State), C.c_int32, vp, vp, vp, vp]
         L.snac_mailbox_create.argtypes = [C.POINTER(EnvDesc), C.c_uint32, C.POINTER(vp)]

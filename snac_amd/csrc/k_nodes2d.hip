@@ -188,7 +188,7 @@ extern "C" {
 static int nodes_check(const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m) {
     using namespace snac_detail;
     if (!d || !st || !nodes) return fail(SNAC_ERR_ARG, "null desc / state / nodes");
-    if (d->kind != SNAC_ENV_2D) return fail(SNAC_ERR_UNSUPPORTED, "node records exist for the 2D kinds (a 3D record is 820 bytes: seven lines either way)");
+    if (d->kind != SNAC_ENV_2D) return fail(SNAC_ERR_UNSUPPORTED, "snac_node2d records are for the 2D kinds (1D / 3D: snac_node1d / snac_node3d)");
     if (int rc = check_common(d, st)) return rc;
     if (pool_rows < 1) return fail(SNAC_ERR_ARG, "pool_rows must be >= 1");
     if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");

@@ -17,6 +17,7 @@
 //   k_step1d.hip    k_step1d, k_edges1d   the 1D snac_step (canonical rows and the layout variants) and 1D tree edges
 //   k_reset.hip     k_reset, k_iou        whole-batch resets without reading the old state; snac_iou lane-per-env
 //   k_nodes2d.hip   k_edges2dp    2D tree edges on node pools of one 128-byte record per node
+//   k_nodes.hip     k_edges1dp, k_edges3dp   1D / 3D tree edges on node pools (one line / seven whole lines per node), k_nodes_copy
 //   k_mailbox.hip   k_mailbox     the resident stepper behind the drop-in classes (mailbox_host.h: the host half of its protocol)
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows
 //   k_tile{1,2,3}d.hip  the tile kernels k_rollout / k_transition / k_aux (rounds 1-2) behind all of them (templates: k_tile.inc)

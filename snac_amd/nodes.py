@@ -11,6 +11,10 @@ script/MCTS/utils/mcts_Qvalue_dynamic.py:88,118 -- here m edges per launch.
     pool.load(rows=root_rows, node_rows=root_nodes)                     # batch rows -> node records
     obs, reward, done = pool.transition(actions, step_size, src=parents, dst=children)
     pool.store(node_rows=leaves, rows=leaf_rows)                        # node records -> batch rows (evaluate(), observe(), ...)
+
+NodePool1D (snac_node1d: one 128-byte line per node) and NodePool3D (snac_node3d: seven whole lines) do the same for the other two
+kinds (transition(state, action): Env/1D/DMP_Env_1D_dynamic_MCTS.py:82-139, Env/3D/DMP_simulator_3d_dynamic_triangle_MCTS.py:195-277);
+NodePool(env, rows) picks the class of env.kind, so a search written against one pool runs unchanged on the others.
 """
 import ctypes as C
 
@@ -23,18 +27,21 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class NodePool2D:
+class _NodePool:
+    """What the pools of the three kinds share; a subclass names its kind, its record's int32 words and its three entry points."""
+    KIND, WORDS, CANONICAL_OBS, PACK, UNPACK, TRANSITION = None, None, None, None, None, None
+
     def __init__(self, env, rows):
-        """env: a 2D BatchedDMPEnv -- its rules, plan table, observation dtype and device are the pool's; rows: node records."""
-        if env.kind != 2:
-            raise ValueError("node records exist for the 2D kinds")
-        if env.obs_dim != 51:
+        """env: a BatchedDMPEnv of the pool's kind -- its rules, plan table, observation dtype and device are the pool's; rows: node records."""
+        if env.kind != self.KIND:
+            raise ValueError("node records exist for the %dD kinds" % self.KIND)
+        if env.obs_dim != self.CANONICAL_OBS:
             raise ValueError("a node pool writes the canonical observation rows")
         self.env, self.rows = env, int(rows)
         if self.rows < 1:
             raise ValueError("rows must be >= 1")
-        # torch allocations are at least 512-byte aligned: one record = one 128-byte line
-        self.records = torch.zeros((self.rows, 32), dtype=torch.int32, device=env.device)
+        # torch allocations are at least 512-byte aligned: every record starts a 128-byte line
+        self.records = torch.zeros((self.rows, self.WORDS), dtype=torch.int32, device=env.device)
         assert self.records.data_ptr() % 128 == 0
         self._lib = env._lib
 
@@ -63,7 +70,7 @@ class NodePool2D:
         m = self._count(rows, node_rows, min(env.num_envs, self.rows))
         ri, ni = self._idx(rows, m, env.num_envs, "rows"), self._idx(node_rows, m, self.rows, "node_rows")
         with torch.cuda.device(env.device):
-            _lib.check(self._lib.snac_nodes2d_pack(C.byref(env._desc), C.byref(env._state), _ptr(ri), m, _ptr(self.records), self.rows, _ptr(ni),
+            _lib.check(getattr(self._lib, self.PACK)(C.byref(env._desc), C.byref(env._state), _ptr(ri), m, _ptr(self.records), self.rows, _ptr(ni),
                                                    env._stream()))
         return m
 
@@ -73,7 +80,7 @@ class NodePool2D:
         m = self._count(rows, node_rows, min(env.num_envs, self.rows))
         ri, ni = self._idx(rows, m, env.num_envs, "rows"), self._idx(node_rows, m, self.rows, "node_rows")
         with torch.cuda.device(env.device):
-            _lib.check(self._lib.snac_nodes2d_unpack(C.byref(env._desc), _ptr(self.records), self.rows, _ptr(ni), m, C.byref(env._state), _ptr(ri),
+            _lib.check(getattr(self._lib, self.UNPACK)(C.byref(env._desc), _ptr(self.records), self.rows, _ptr(ni), m, C.byref(env._state), _ptr(ri),
                                                      env._stream()))
         env._was_reset = True
         return m
@@ -82,7 +89,7 @@ class NodePool2D:
     def transition(self, actions, step_size=None, src=None, dst=None, t=0, want_obs=True, check=True):
         """m tree edges in one launch: record dst[i] <- step(record src[i], actions[i], step_size[i]); src / dst None = record i.
         Same rules and outputs as BatchedDMPEnv.transition(): no auto-reset, a dst record must not be the src record of another
-        edge of the same call (check=False skips that test: a host round trip per wave).  Returns (obs [m, 51], reward [m], done [m])."""
+        edge of the same call (check=False skips that test: a host round trip per wave).  Returns (obs [m, obs_dim], reward [m], done [m])."""
         env = self.env
         a = torch.as_tensor(actions, device=env.device) if not torch.is_tensor(actions) else actions.to(env.device)
         m = int(a.numel())
@@ -98,7 +105,7 @@ class NodePool2D:
         reward = torch.empty((m,), dtype=torch.float32, device=env.device)
         done = torch.empty((m,), dtype=torch.uint8, device=env.device)
         with torch.cuda.device(env.device):
-            _lib.check(self._lib.snac_transition_nodes2d(C.byref(env._desc), C.byref(env._state), _ptr(self.records), self.rows, m, _ptr(si), _ptr(di),
+            _lib.check(getattr(self._lib, self.TRANSITION)(C.byref(env._desc), C.byref(env._state), _ptr(self.records), self.rows, m, _ptr(si), _ptr(di),
                                                          int(t) & 0xFFFFFFFF, _ptr(a), _ptr(k), _ptr(obs), _ptr(reward), _ptr(done), env._stream()))
         return obs, reward, done.view(torch.bool)
 
@@ -133,7 +140,45 @@ class NodePool2D:
     def plan_idx(self):
         return self._hdr16()[:, 5].to(torch.int32)
 
+
+class NodePool2D(_NodePool):
+    """2D node records (snac_node2d: 32 int32 words, one line)."""
+    KIND, WORDS, CANONICAL_OBS = 2, 32, 51
+    PACK, UNPACK, TRANSITION = "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d"
+
     @property
     def boards(self):
         """[rows, 20] row words of the bit boards (bit j of word q = interior cell (q, j))."""
         return self.records[:, 8:28]
+
+
+class NodePool1D(_NodePool):
+    """1D node records (snac_node1d: 32 int32 words, one line)."""
+    KIND, WORDS, CANONICAL_OBS = 1, 32, 7
+    PACK, UNPACK, TRANSITION = "snac_nodes1d_pack", "snac_nodes1d_unpack", "snac_transition_nodes1d"
+
+    @property
+    def heights(self):
+        """[rows, 30] int16 heights of the interior cells (a view of the records)."""
+        return self.records[:, 8:24].view(torch.int16)[:, :30]
+
+
+class NodePool3D(_NodePool):
+    """3D node records (snac_node3d: 224 int32 words, seven lines)."""
+    KIND, WORDS, CANONICAL_OBS = 3, 224, 51
+    PACK, UNPACK, TRANSITION = "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d"
+
+    @property
+    def heights(self):
+        """[rows, 20, 20] int16 heights of the interior, row-major (a view of the records)."""
+        return self.records[:, 8:208].view(torch.int16).view(self.rows, 20, 20)
+
+
+_POOLS = {1: NodePool1D, 2: NodePool2D, 3: NodePool3D}
+
+
+def NodePool(env, rows):
+    """The node pool of env.kind (NodePool1D / NodePool2D / NodePool3D) with `rows` records."""
+    if env.kind not in _POOLS:
+        raise ValueError("unknown env kind %r" % (env.kind,))
+    return _POOLS[env.kind](env, rows)

@@ -2,7 +2,7 @@
 Modes: `one` = every edge has its own random parent (what bench.py's extras time), `all` = random parents x all actions (children of a
 parent share its record: tools/bench_configs.py).  SNAC_EDGES3D=0 keeps 3D edges on k_transition3d.
 
-    gpurun -- python tools/edges_time.py [kind] [m] [one|all] [reps] [nodes]        nodes: 2D on one-record-per-node pools (snac_transition_nodes2d)
+    python tools/edges_time.py [kind] [m] [one|all] [reps] [nodes]        nodes: on one-record-per-node pools (snac_transition_nodes1d / 2d / 3d)
 """
 import ctypes as C
 import os
@@ -42,15 +42,16 @@ def main():
     vp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     nodes = None
     if len(sys.argv) > 5 and sys.argv[5] == "nodes":
-        from snac_amd import NodePool2D
+        from snac_amd import NodePool
 
-        nodes = NodePool2D(env, pool)
+        nodes = NodePool(env, pool)
         nodes.load()
+        entry = getattr(env._lib, nodes.TRANSITION)
 
     def call():
         if nodes is not None:
-            _lib.check(env._lib.snac_transition_nodes2d(C.byref(env._desc), C.byref(env._state), vp(nodes.records), pool, m, vp(src), vp(dst), 0, vp(acts), None,
-                                                        vp(obs), vp(rew), vp(done), env._stream()))
+            _lib.check(entry(C.byref(env._desc), C.byref(env._state), vp(nodes.records), pool, m, vp(src), vp(dst), 0, vp(acts), None, vp(obs), vp(rew),
+                             vp(done), env._stream()))
             return
         _lib.check(env._lib.snac_transition(C.byref(env._desc), C.byref(env._state), m, vp(src), vp(dst), 0, vp(acts), None, vp(obs), vp(rew), vp(done), env._stream()))
 

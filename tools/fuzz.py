@@ -130,10 +130,10 @@ def trial(rng, idx):
                 src = np.where(inplace | (len(free) == 0), dst, rng.choice(free if len(free) else dst, n_dst)).astype(np.int32)
                 acts = rng.integers(0, A, n_dst).astype(np.int8)
                 ks = rng.integers(1, 4, n_dst).astype(np.int8) if rng.random() < 0.5 else None
-                if dim == 2 and not lay and rng.random() < 0.5:      # the same wave on node records (one 128-byte record per node): pack, step, unpack
-                    from snac_amd import NodePool2D
+                if not lay and rng.random() < 0.5:                   # the same wave on node records (one record per node, any kind): pack, step, unpack
+                    from snac_amd import NodePool
 
-                    pool = NodePool2D(env, n)
+                    pool = NodePool(env, n)
                     pool.load()
                     o, r, d = pool.transition(acts, ks, src, dst, t=w)
                     pool.store()
