@@ -533,6 +533,25 @@ int snac_obs_equal(const snac_env_desc* desc, const void* obs_a, const int32_t* 
 int snac_discounted_return(int32_t H, int32_t m, const float* reward, const uint8_t* done, const uint8_t* terminal, const double* gpow,
                            double* est, int64_t* steps, void* stream);
 
+/* The same evaluation IN PLACE on a node pool (snac_node1d / 2d / 3d above), one fused launch: no fork, no reward / done arrays.  For every
+ * leaf i in [0, m), from record node_rows[i] (NULL: i; clamped into the pool as in snac_transition_nodes*), what snac_discounted_return
+ * computes over a rollout of the forked leaf (script/MCTS/utils/mcts.py:100-110):
+ *     alive = !(record.hdr.flags & SNAC_FLAG_NEED_RESET)
+ *     for t in 0 .. H - 1 while alive:  (action, k) = counter RNG stream 0 keyed by (env_id_base + i, t0 + t);  step the leaf with the
+ *                                       rules of (kind, dynamic, desc->rules);  est[i] += (double)reward * gpow[t];  steps[i] += 1;  alive = !done
+ * product and sum each rounded to float64 (no fused multiply-add).  est [m] in / out as in snac_discounted_return (in: the first reward);
+ * steps [m] out, may be NULL; gpow [H] device memory.  st supplies the plan table (plans, plan_tb) only.  The pool is READ ONLY: no
+ * record, batch row or episodic sum changes, and there is no auto-reset.  H == 0: est stays, steps are written as zero; m == 0: nothing.
+ * With t0 = 0 the actions are those BatchedDMPEnv.evaluate (fork + snac_rollout + snac_discounted_return) draws for the same leaves.
+ * Each entry point accepts its own kind and the canonical layout only (SNAC_ERR_UNSUPPORTED), with the argument checks of the other
+ * node entry points, before any HIP call. */
+int snac_evaluate_nodes1d(const snac_env_desc* desc, const snac_state* st, const snac_node1d* nodes, int32_t pool_rows, int32_t m,
+                          const int32_t* node_rows, int32_t H, uint32_t t0, const double* gpow, double* est, int64_t* steps, void* stream);
+int snac_evaluate_nodes2d(const snac_env_desc* desc, const snac_state* st, const snac_node2d* nodes, int32_t pool_rows, int32_t m,
+                          const int32_t* node_rows, int32_t H, uint32_t t0, const double* gpow, double* est, int64_t* steps, void* stream);
+int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const snac_node3d* nodes, int32_t pool_rows, int32_t m,
+                          const int32_t* node_rows, int32_t H, uint32_t t0, const double* gpow, double* est, int64_t* steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

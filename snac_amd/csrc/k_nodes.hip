@@ -18,6 +18,25 @@ static_assert(sizeof(snac_node1d) == 128 && offsetof(snac_node1d, episode) == 16
 static_assert(sizeof(snac_node3d) == 896 && offsetof(snac_node3d, episode) == 16 && offsetof(snac_node3d, heights) == 32 &&
               offsetof(snac_node3d, zero1) == 832, "snac_node3d: seven lines");
 
+namespace snac_detail {
+
+// the argument checks every node-pool entry point of the 1D / 3D records and snac_evaluate_nodes{1,2,3}d share (snac_dev.h)
+int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m) {
+    if (!d || !st || !nodes) return fail(SNAC_ERR_ARG, "null desc / state / nodes");
+    if (d->kind != kind)
+        return fail(SNAC_ERR_UNSUPPORTED, kind == SNAC_ENV_1D   ? "snac_node1d records are for the 1D kinds"
+                                          : kind == SNAC_ENV_2D ? "snac_node2d records are for the 2D kinds (1D / 3D: snac_node1d / snac_node3d)"
+                                                                : "snac_node3d records are for the 3D kinds");
+    if (int rc = check_common(d, st)) return rc;
+    if (pool_rows < 1) return fail(SNAC_ERR_ARG, "pool_rows must be >= 1");
+    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
+    if (((uintptr_t)nodes & 127) != 0) return fail(SNAC_ERR_ARG, "the node pool must be 128-byte aligned (records of whole lines)");
+    if (make_args(d, st).variant) return fail(SNAC_ERR_UNSUPPORTED, "node pools write the canonical observation rows (layout variants: snac_transition)");
+    return SNAC_OK;
+}
+
+}  // namespace snac_detail
+
 namespace {
 
 constexpr int N1_PIECES = 8, N1_WORDS = 32, N1_CELLS = 8;           // 1D: 16-byte pieces / 4-byte words per record; the cells' first word
@@ -311,19 +330,6 @@ void launch_edges3dp(const KArgs& a, hipStream_t s) {
         if (vec) hipLaunchKernelGGL((k_edges3dp<DYN, OT, 2, true>), grid, block, 0, s, b);
         else hipLaunchKernelGGL((k_edges3dp<DYN, OT, 2, false>), grid, block, 0, s, b);
     });
-}
-
-int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m) {
-    using namespace snac_detail;
-    if (!d || !st || !nodes) return fail(SNAC_ERR_ARG, "null desc / state / nodes");
-    if (d->kind != kind)
-        return fail(SNAC_ERR_UNSUPPORTED, kind == SNAC_ENV_1D ? "snac_node1d records are for the 1D kinds" : "snac_node3d records are for the 3D kinds");
-    if (int rc = check_common(d, st)) return rc;
-    if (pool_rows < 1) return fail(SNAC_ERR_ARG, "pool_rows must be >= 1");
-    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
-    if (((uintptr_t)nodes & 127) != 0) return fail(SNAC_ERR_ARG, "the node pool must be 128-byte aligned (records of whole lines)");
-    if (make_args(d, st).variant) return fail(SNAC_ERR_UNSUPPORTED, "node pools write the canonical observation rows (layout variants: snac_transition)");
-    return SNAC_OK;
 }
 
 template <bool PACK, int NP, int GP>

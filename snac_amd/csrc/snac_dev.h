@@ -18,6 +18,7 @@
 //   k_reset.hip     k_reset, k_iou        whole-batch resets without reading the old state; snac_iou lane-per-env
 //   k_nodes2d.hip   k_edges2dp    2D tree edges on node pools of one 128-byte record per node
 //   k_nodes.hip     k_edges1dp, k_edges3dp   1D / 3D tree edges on node pools (one line / seven whole lines per node), k_nodes_copy
+//   k_eval.hip      k_eval        default-policy evaluation of tree leaves in place on node pools: lane = leaf, the rollout and the sum fused
 //   k_mailbox.hip   k_mailbox     the resident stepper behind the drop-in classes (mailbox_host.h: the host half of its protocol)
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows
 //   k_tile{1,2,3}d.hip  the tile kernels k_rollout / k_transition / k_aux (rounds 1-2) behind all of them (templates: k_tile.inc)
@@ -103,6 +104,8 @@ int base_obs_dim(int kind);
 int tail_len(int kind, int tail);
 int check_common(const snac_env_desc* d, const snac_state* st);
 KArgs make_args(const snac_env_desc* d, const snac_state* st);
+// the checks of the node-pool entry points (kind: the record's kind), defined in k_nodes.hip
+int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m);
 int launch(Op op, const snac_env_desc* d, const KArgs& a, void* stream);
 
 // ---- the launch functions of the kernel families (each defined beside its kernels; the dispatch decides, they only launch)

@@ -10,7 +10,8 @@ script/MCTS/utils/mcts_Qvalue_dynamic.py:88,118 -- here m edges per launch.
     pool = NodePool2D(env, 1 << 20)
     pool.load(rows=root_rows, node_rows=root_nodes)                     # batch rows -> node records
     obs, reward, done = pool.transition(actions, step_size, src=parents, dst=children)
-    pool.store(node_rows=leaves, rows=leaf_rows)                        # node records -> batch rows (evaluate(), observe(), ...)
+    pool.store(node_rows=leaves, rows=leaf_rows)                        # node records -> batch rows (observe(), ...)
+    est, steps = pool.evaluate(leaves, H, gamma, first_reward=reward)  # default-policy evaluation in place (script/MCTS/utils/mcts.py:100-110)
 
 NodePool1D (snac_node1d: one 128-byte line per node) and NodePool3D (snac_node3d: seven whole lines) do the same for the other two
 kinds (transition(state, action): Env/1D/DMP_Env_1D_dynamic_MCTS.py:82-139, Env/3D/DMP_simulator_3d_dynamic_triangle_MCTS.py:195-277);
@@ -29,7 +30,7 @@ def _ptr(t):
 
 class _NodePool:
     """What the pools of the three kinds share; a subclass names its kind, its record's int32 words and its three entry points."""
-    KIND, WORDS, CANONICAL_OBS, PACK, UNPACK, TRANSITION = None, None, None, None, None, None
+    KIND, WORDS, CANONICAL_OBS, PACK, UNPACK, TRANSITION, EVALUATE = None, None, None, None, None, None, None
 
     def __init__(self, env, rows):
         """env: a BatchedDMPEnv of the pool's kind -- its rules, plan table, observation dtype and device are the pool's; rows: node records."""
@@ -44,6 +45,7 @@ class _NodePool:
         self.records = torch.zeros((self.rows, self.WORDS), dtype=torch.int32, device=env.device)
         assert self.records.data_ptr() % 128 == 0
         self._lib = env._lib
+        self._gpow = {}                                              # (gamma, H) -> gamma**t on the device, for evaluate()
 
     # ---- records <-> batch rows ---------------------------------------------------------------------------------
     def _idx(self, x, m, limit, what):
@@ -109,6 +111,43 @@ class _NodePool:
                                                          int(t) & 0xFFFFFFFF, _ptr(a), _ptr(k), _ptr(obs), _ptr(reward), _ptr(done), env._stream()))
         return obs, reward, done.view(torch.bool)
 
+    # ---- leaf evaluation --------------------------------------------------------------------------------------------
+    def evaluate(self, node_rows, horizon, gamma, first_reward=None, t0=0, check=True):
+        """Default-policy evaluation of tree leaves in place (script/MCTS/utils/mcts.py:100-110), one launch on the records: from each
+        record node_rows[i] (None: record i, m = len(first_reward) or every record), up to `horizon` uniformly random steps that stop
+        at the first `done`, estimate = first_reward + sum_t reward_t * gamma**t in float64 -- what BatchedDMPEnv.evaluate() computes
+        for the same states, bit for bit.  Actions come from the counter RNG keyed by (env_id_base + i, t0 + t): t0 = 0 draws those of
+        BatchedDMPEnv.evaluate(), another t0 fresh ones.  A terminal leaf is not rolled out.  The records are not changed.  check=False
+        skips the range test of node_rows (a host round trip).  Enqueued on the env's stream.
+        Returns (estimate float64 [m], steps int64 [m]: the number of steps actually taken)."""
+        env = self.env
+        m, H = self._count(node_rows, first_reward, self.rows), int(horizon)
+        if check or node_rows is None:
+            ni = self._idx(node_rows, m, self.rows, "node_rows")
+        else:
+            ni = torch.as_tensor(node_rows, device=env.device).reshape(-1)
+            if int(ni.numel()) != m:
+                raise ValueError("node_rows must have %d entries" % m)
+            ni = ni.to(torch.int32).contiguous()
+        if first_reward is None:
+            est = torch.zeros(m, dtype=torch.float64, device=env.device)
+        else:
+            est = torch.as_tensor(first_reward, device=env.device).to(torch.float64).reshape(-1).clone()
+            if int(est.numel()) != m:
+                raise ValueError("first_reward must have %d entries" % m)
+        steps = torch.zeros(m, dtype=torch.int64, device=env.device)
+        if m == 0 or H <= 0:
+            return est, steps
+        key = (float(gamma), H)
+        gpow = self._gpow.get(key)
+        if gpow is None:                                             # gamma**t as python computes it (BatchedDMPEnv.evaluate)
+            gpow = torch.tensor([float(gamma) ** t for t in range(H)], dtype=torch.float64).to(env.device)
+            self._gpow[key] = gpow
+        with torch.cuda.device(env.device):
+            _lib.check(getattr(self._lib, self.EVALUATE)(C.byref(env._desc), C.byref(env._state), _ptr(self.records), self.rows, m, _ptr(ni), H,
+                                                       int(t0) & 0xFFFFFFFF, _ptr(gpow), _ptr(est), _ptr(steps), env._stream()))
+        return est, steps
+
     # ---- what a search reads of its nodes (decoded from the records: snac_env_hdr) -----------------------------------
     def _hdr16(self):
         return self.records[:, :4].contiguous().view(torch.int16).view(self.rows, 8)
@@ -145,6 +184,7 @@ class NodePool2D(_NodePool):
     """2D node records (snac_node2d: 32 int32 words, one line)."""
     KIND, WORDS, CANONICAL_OBS = 2, 32, 51
     PACK, UNPACK, TRANSITION = "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d"
+    EVALUATE = "snac_evaluate_nodes2d"
 
     @property
     def boards(self):
@@ -156,6 +196,7 @@ class NodePool1D(_NodePool):
     """1D node records (snac_node1d: 32 int32 words, one line)."""
     KIND, WORDS, CANONICAL_OBS = 1, 32, 7
     PACK, UNPACK, TRANSITION = "snac_nodes1d_pack", "snac_nodes1d_unpack", "snac_transition_nodes1d"
+    EVALUATE = "snac_evaluate_nodes1d"
 
     @property
     def heights(self):
@@ -167,6 +208,7 @@ class NodePool3D(_NodePool):
     """3D node records (snac_node3d: 224 int32 words, seven lines)."""
     KIND, WORDS, CANONICAL_OBS = 3, 224, 51
     PACK, UNPACK, TRANSITION = "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d"
+    EVALUATE = "snac_evaluate_nodes3d"
 
     @property
     def heights(self):
