@@ -15,8 +15,9 @@
  * Conventions
  *   - Plain C types only.  Every pointer inside snac_state and every array argument is a DEVICE pointer
  *     owned by the caller (e.g. torch tensors).  The env entry points allocate nothing and keep no state of their own
- *     beyond a thread-local error string; the one exception is the optional trajectory-memory allocator
- *     (snac_traj_alloc / snac_traj_free below), which keeps a mutex-protected table of the blocks it has handed out.
+ *     beyond a thread-local error string; the exceptions are the optional trajectory-memory allocator
+ *     (snac_traj_alloc / snac_traj_free below), which keeps a mutex-protected table of the blocks it has handed out, and the
+ *     table of action distributions (snac_action_dist).
  *     Input and output ARRAYS (actions, step sizes, obs, reward, done) may also lie in
  *     page-locked host memory, which is mapped into the device's address space: the kernels then read / write them over the
  *     bus themselves and a host-side caller only waits (snac_stream_sync) -- no copy command.
@@ -48,6 +49,12 @@
  *   word(seed,stream,env,t) = mix32(mix32(e0 ^ (0x9E3779B9*t)) + e1)
  *   stream 0 (per env, tick t):     action = ((word>>16) * num_actions) >> 16
  *                                   step_size = 1 + (((word & 0xffff) * 3) >> 16)
+ *     with an action distribution (snac_env_desc.action_dist != 0, a handle of snac_action_dist): A = num_actions,
+ *     thresholds cdf[0 .. A-2], nondecreasing, each in [0, 65536], u = word >> 16:
+ *                                   action = #{ j < A-1 : u >= cdf[j] }
+ *                                   (action j has probability (cdf[j] - cdf[j-1]) / 65536, cdf[-1] = 0, cdf[A-1] = 65536)
+ *     and the step size as above.  The uniform table cdf[j] = ceil(65536 * (j+1) / A) draws exactly the actions of the
+ *     multiply: floor(u * A / 65536) counts the j >= 1 with u * A >= 65536 * j, i.e. u >= ceil(65536 * j / A).
  *   stream 1 (per env, episode e):  plan_idx = (word * num_plans) >> 32
  *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.
  */
@@ -139,7 +146,9 @@ typedef struct snac_env_desc {
     int32_t frame_value;        /* 0 / -1: the canonical -1; 2: the 2D L-Net frame (1D / 2D only) */
     int32_t obs_scalars;        /* SNAC_SCALARS_* */
     int32_t obs_tail;           /* SNAC_TAIL_* bits */
-    int32_t reserved;           /* 0 */
+    int32_t action_dist;        /* 0: uniform counter-RNG actions; else a handle of snac_action_dist registered for the kind's
+                                   num_actions: the distribution of the actions the counter RNG draws (explicit actions are
+                                   unaffected) */
 } snac_env_desc;
 
 typedef struct snac_state {
@@ -162,6 +171,12 @@ const char* snac_last_kernel(void);
 /* the dispatch table: one line "ENV_VARIABLE=value  # what it decides" per batch-size threshold / switch that selects a kernel
  * (effective values: the defaults measured on the build pool, or their environment overrides); tools/retune.py re-measures them */
 int snac_tuning(char* out, int32_t cap);
+
+/* Register an action distribution for the counter RNG ("Counter RNG" above): the num_actions - 1 thresholds cdf[], nondecreasing,
+ * each in [0, 65536].  *handle (>= 1) is what snac_env_desc.action_dist takes.  The entries live in a process-wide table (mutex-
+ * protected, entries immutable, handles process-local); registering the same table again returns the same handle.  SNAC_ERR_ARG
+ * for num_actions outside 2 .. 8, invalid thresholds, or a full table (1024 distinct entries).  No device is needed. */
+int snac_action_dist(int32_t num_actions, const uint32_t* cdf, int32_t* handle);
 
 /* constants of (kind, dynamic); replaces the attribute reads of the reference constructors */
 int snac_env_sizes(int kind, int dynamic, snac_sizes* out);

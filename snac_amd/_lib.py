@@ -4,6 +4,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SNAC_HIP_LIB") or os.path.join(HERE, "libsnac_hip.so")  # override: A/B builds
 CSRC = os.path.join(HERE, "csrc")
@@ -27,7 +29,7 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_traj_alloc_ex", "snac_traj_free", "snac_traj_layout", "snac_traj_describe", "snac_traj_reserved_bytes", "snac_last_kernel", "snac_tuning",
            "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d", "snac_nodes1d_pack", "snac_nodes1d_unpack",
            "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d",
-           "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d")
+           "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist")
 
 
 class Sizes(C.Structure):
@@ -40,7 +42,7 @@ class EnvDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("dynamic", C.c_int32), ("num_envs", C.c_int32), ("num_plans", C.c_int32),
                 ("obs_dtype", C.c_int32), ("static_plan", C.c_int32), ("seed", C.c_uint64), ("env_id_base", C.c_int64),
                 ("total_step", C.c_int32), ("rules", C.c_int32), ("frame_value", C.c_int32), ("obs_scalars", C.c_int32),
-                ("obs_tail", C.c_int32), ("reserved", C.c_int32)]
+                ("obs_tail", C.c_int32), ("action_dist", C.c_int32)]
 
 
 class RolloutRecord(C.Structure):
@@ -153,6 +155,7 @@ def lib():
         for k in ("1d", "2d", "3d"):
             getattr(L, "snac_evaluate_nodes%s" % k).argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_uint32,
                                                                 vp, vp, vp, vp]
+        L.snac_action_dist.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]
         L.snac_traj_alloc_ex.argtypes = [C.c_size_t, C.c_int, C.c_size_t, vp, C.POINTER(vp)]
         L.snac_traj_free.argtypes = [vp]
@@ -182,6 +185,32 @@ def tuning():
 def check(rc):
     if rc != SNAC_OK:
         raise SnacError("libsnac_hip: %s (code %d)" % (lib().snac_last_error().decode(), rc))
+
+
+def action_cdf(probs, num_actions):
+    """Thresholds of the counter RNG's action draw (include/snac_hip.h, "Counter RNG") for `num_actions` weights: finite,
+    non-negative, with a positive sum.  C = the float64 cumulative sum of probs / sum(probs), in order;
+    cdf[j] = min(65536, ceil(65536 * C[j])) for j < num_actions - 1 (uint32 array)."""
+    p = np.asarray(probs, dtype=np.float64)
+    if p.shape != (num_actions,):
+        raise ValueError("action_probs must hold %d weights, one per action" % num_actions)
+    if not np.all(np.isfinite(p)) or np.any(p < 0):
+        raise ValueError("action_probs must be finite and non-negative")
+    total = p.sum()
+    if not total > 0:
+        raise ValueError("action_probs must have a positive sum")
+    c = np.cumsum(p / total)[:-1]
+    return np.minimum(65536.0, np.ceil(65536.0 * c)).astype(np.uint32)
+
+
+def action_dist(num_actions, cdf):
+    """snac_action_dist: the handle (>= 1) of the thresholds `cdf` for `num_actions` actions (the same table, the same handle)."""
+    if len(cdf) != num_actions - 1:
+        raise ValueError("cdf must hold num_actions - 1 thresholds")
+    arr = (C.c_uint32 * max(1, num_actions - 1))(*[int(x) for x in cdf])
+    h = C.c_int32(0)
+    check(lib().snac_action_dist(int(num_actions), arr, C.byref(h)))
+    return h.value
 
 
 def env_sizes(kind, dynamic):

@@ -42,6 +42,9 @@ class BatchedDMPEnv:
     seed      counter-RNG seed (include/snac_hip.h); env_id_base: global id of local env 0 (multi-GPU shards)
     brick_gt / time_gt   the strict termination tests of the env copies under script/PPO (SNAC_RULE_* in snac_hip.h):
               done when count_brick > total_brick / count_step > total_step instead of >=
+    action_probs  A weights (finite, >= 0, positive sum) over the kind's actions: the distribution of the actions the counter RNG
+              draws when no `actions` are passed (step, rollout, ReplayRing.collect, evaluate, the node pools' evaluate); step sizes
+              stay uniform.  None = uniform.  Thresholds and draw: include/snac_hip.h "Counter RNG"; env.action_probs / env.action_cdf show them
     empty_plans   P: a device plan table of P empty rows (total_brick 1) that plans_from_grids() / generate_plans() fill on the
               device -- nothing is packed or uploaded by the host (the hindsight relabel path)
     layout    observation layout of the reference's env copies, produced by the same kernels (snac_env_desc.frame_value /
@@ -59,7 +62,7 @@ class BatchedDMPEnv:
     def __init__(self, kind, dynamic, num_envs, plans=None, plan_choose=0, density="dense", split="train",
                  device="cuda", seed=1, obs_dtype=torch.float64, env_id_base=0, total_step=None, plan_tb=None,
                  brick_gt=False, time_gt=False, layout=None, frame_value=None, obs_scalars=None, obs_tail=None, static_plan=0,
-                 empty_plans=None):
+                 empty_plans=None, action_probs=None):
         if not torch.cuda.is_available():
             raise _lib.SnacError("BatchedDMPEnv needs a ROCm GPU: there is no CPU fallback")
         self.kind = _KINDS[kind]
@@ -128,6 +131,7 @@ class BatchedDMPEnv:
                                   self.frame_value,
                                   {None: _lib.SCALARS_DEFAULT, "raw": _lib.SCALARS_RAW, "norm": _lib.SCALARS_NORM}[self.obs_scalars],
                                   self.obs_tail, 0)
+        self.set_action_probs(action_probs)
         self.obs_dim = self._lib.snac_obs_dim(C.byref(self._desc))   # values per observation row, tail included
         if self.obs_dim < 0:
             _lib.check(self.obs_dim)
@@ -149,6 +153,18 @@ class BatchedDMPEnv:
         self._host_ok = None                                         # the new_host_obs() row validated last
         self._mapped = {}                                            # page-locked host tensors seen by _is_mapped
         self._mb, self._mb_dirty, self._mb_final = None, False, None  # the resident single-env stepper (mailbox_open)
+
+    def set_action_probs(self, action_probs):
+        """Set (or with None clear) the distribution of the counter-RNG actions; calls enqueued before are unaffected."""
+        if action_probs is None:
+            self._action_weights, self.action_probs, self.action_cdf = None, None, None
+            self._desc.action_dist = 0
+            return
+        cdf = _lib.action_cdf(action_probs, self.num_actions)
+        handle = _lib.action_dist(self.num_actions, cdf)        # uniform weights too: a table, never handle 0
+        w = np.array(action_probs, dtype=np.float64)
+        self._action_weights, self.action_probs, self.action_cdf = w, w / w.sum(), cdf
+        self._desc.action_dist = handle
 
     # ---- helpers -------------------------------------------------------------------------------
     def _settle(self):
@@ -750,7 +766,8 @@ class BatchedDMPEnv:
         child = BatchedDMPEnv(self.kind, self.dynamic, int(index.numel()), plans=self.plans_full, device=self.device, seed=self.seed,
                               obs_dtype=self.obs_dtype, env_id_base=self.env_id_base, total_step=self.total_step,
                               brick_gt=self.brick_gt, time_gt=self.time_gt, frame_value=self.frame_value,
-                              obs_scalars=self.obs_scalars, obs_tail=self.obs_tail, static_plan=self.static_plan)
+                              obs_scalars=self.obs_scalars, obs_tail=self.obs_tail, static_plan=self.static_plan,
+                              action_probs=self._action_weights)
         child._plan_tb.copy_(self._plan_tb)                          # caller-supplied total_brick rows travel with the fork
         child._table_version += 1
         child._hdr.copy_(self._hdr[index]); child._episode.copy_(self._episode[index]); child._grid.copy_(self._grid[index])
@@ -801,7 +818,7 @@ class BatchedDMPEnv:
 
     def evaluate(self, rows, horizon, gamma, first_reward=None):
         """Default-policy evaluation of tree leaves, the "Evaluation" block of the vanilla MCTS procedure
-        (script/MCTS/utils/mcts.py:100-110): from each pool row in `rows`, up to `horizon` uniformly random steps that stop
+        (script/MCTS/utils/mcts.py:100-110): from each pool row in `rows`, up to `horizon` random steps (actions uniform or by action_probs) that stop
         at the first `done`, and   estimate = first_reward + sum_t reward_t * gamma**t   accumulated in that order in
         float64 (gamma**t as python computes it), so that it equals the reference loop bit for bit given the same
         actions.  Actions and step sizes come from the counter RNG (tick t of leaf i is keyed by (env_id_base + i, t));

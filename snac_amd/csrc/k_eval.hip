@@ -127,7 +127,7 @@ __global__ __launch_bounds__(64) void k_eval(const KArgs a, const EvalArgs v) {
         const double g = v.gpow[t];                                  // t is uniform: one scalar load
         if (alive) {
             const uint32_t w = rng_word(sk, a.t0 + (uint32_t)t);
-            const int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+            const int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
             int reward = 0;
             bool done = false;
             K::step(lds, a, s, act, k, a.ts_done, a.brick_gt, lane, reward, done);

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout1dl(const KArgs a) {
             hold = (int)hrow[s.r]; pcell = (int)prow[s.r - 2];       // the fetched cells are another episode's
         }
         // ---- the 1D step, lane = env
-        int act = (int)(((w32 >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w32 & 0xffffu) * 3u) >> 16);
+        int act = draw_action<K::A>(w32, a), k = 1 + (int)(((w32 & 0xffffu) * 3u) >> 16);
         if constexpr (EXPL) {
             if (a.actions) act = na;
             if (a.step_size) k = min(max(nk, 1), 3);

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a) {
         }
         // ---- phase 1: K2D::step (DMP_Env_2D_dynamic_usedata_plan.py:85-147), plan bit from the block's table
         const uint32_t w32 = rng_word(sk, a.t0 + (uint32_t)t);
-        int act = (int)(((w32 >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w32 & 0xffffu) * 3u) >> 16);
+        int act = draw_action<K::A>(w32, a), k = 1 + (int)(((w32 & 0xffffu) * 3u) >> 16);
         if constexpr (EXPL) {
             if (a.actions) act = na;
             if (a.step_size) k = min(max(nk, 1), 3);

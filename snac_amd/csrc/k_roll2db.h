@@ -99,7 +99,7 @@ __global__ __launch_bounds__((NS + 8) * 64) void k_rollout2db(const KArgs a) {
         long long d_iou = 0;
         auto inputs_of = [&](int t, int& aa, int& kk) {              // counter RNG of tick t
             const uint32_t w = rng_word(sk, a.t0 + (uint32_t)t);
-            aa = (int)(((w >> 16) * (uint32_t)K::A) >> 16); kk = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+            aa = draw_action<K::A>(w, a); kk = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
         };
         auto load_inputs = [&](int t, int& aa, int& kk) {            // EXPL: the caller's bytes of tick t over the counter-RNG values
             inputs_of(t, aa, kk);

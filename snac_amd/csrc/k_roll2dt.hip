@@ -193,7 +193,7 @@ __global__ __launch_bounds__((EB + WR) * 64) void k_rollout2dt(const KArgs a) {
         const int t = t0 + lane;
         const size_t row = (size_t)t * (size_t)a.n + (size_t)env;
         const uint32_t w = rng_word(sk, a.t0 + (uint32_t)t);
-        int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+        int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
         if constexpr (EXPL) {
             if (a.actions && valid) act = (int)a.actions[row];
             if (a.step_size && valid) k = min(max((int)a.step_size[row], 1), 3);

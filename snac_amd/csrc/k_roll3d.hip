@@ -194,7 +194,7 @@ struct Roll3D {
         // (env e, tick t + j) -- and a tick fetches its word with one bpermute
         if ((t & 7) == 0) wq = rng_word(sk, a.t0 + (uint32_t)t + (uint32_t)(lane >> 3));
         const uint32_t w = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane & 7) + 8 * (t & 7)) << 2, (int)wq);
-        int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+        int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
         if constexpr (EXPL) {
             const int idx = ((t >> 4) & 1) * 128 + (t & 15) * 8 + (lane & 7);
             if (a.actions) act = (int)sin[idx];

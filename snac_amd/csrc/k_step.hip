@@ -80,7 +80,7 @@ __global__ __launch_bounds__(WPB * 64) void k_step2d(const KArgs a) {
         }
     } else {
         const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-        act = (int)(((w >> 16) * (uint32_t)K::A) >> 16); k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+        act = draw_action<K::A>(w, a); k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
         if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
         if (a.actions && active) act = (int)a.actions[env];
         if (a.step_size && active) k = (int)a.step_size[env];
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(WPB * 64) void k_step3d(const KArgs a) {
     for (int i = 0; i < 7; ++i) { *(uint32_t*)(mine + R0 + i * RB) = ~0u; *(uint32_t*)(mine + R0 + i * RB + 20) = ~0u; }
     const uint64_t gid = (uint64_t)(a.env_id_base + env);
     const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-    int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+    int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
     if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
     if (a.actions && active) act = (int)a.actions[env];
     if (a.step_size && active) k = (int)a.step_size[env];
@@ -420,7 +420,7 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(3, 3))
     if (active) { s.unpack(a.hdr[env]); episode = a.episode[env]; }
     const uint64_t gid = (uint64_t)(a.env_id_base + env);
     const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-    int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+    int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
     if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
     if (a.actions && active) act = (int)a.actions[env];
     if (a.step_size && active) k = (int)a.step_size[env];

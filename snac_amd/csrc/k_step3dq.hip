@@ -60,7 +60,7 @@ __global__ __launch_bounds__(WPB * 64) void k_step3dq(const KArgs a) {
         }
     } else {
         const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-        act = (int)(((w >> 16) * (uint32_t)K::A) >> 16); k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+        act = draw_action<K::A>(w, a); k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
         if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
         if (a.actions && active) act = (int)a.actions[env];
         if (a.step_size && active) k = (int)a.step_size[env];

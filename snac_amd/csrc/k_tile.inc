@@ -72,7 +72,7 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout(const KArgs a) {
         }
         if (active) {
             const uint32_t w = rng_word(sk, a.t0 + (uint32_t)t);
-            int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+            int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
             if constexpr (EXPL) {
                 if (a.actions) act = (int)a.actions[row + lane];
                 if (a.step_size) k = min(max((int)a.step_size[row + lane], 1), 3);
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(WPB * 64) void k_transition(const KArgs a) {
     bool done = false;
     if (active) {
         const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-        int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+        int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
         if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }   // snac_step_scalar: by value, no input arrays
         if (a.actions) act = (int)a.actions[edge];
         if (a.step_size) k = (int)a.step_size[edge];

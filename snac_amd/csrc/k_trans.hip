@@ -39,7 +39,7 @@ __global__ __launch_bounds__(WPB * 64) void k_transition3d(const KArgs a) {
         if (pidx == old_pidx) { s.pidx = old_pidx; s.tb = old_tb; }
     }
     const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-    int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+    int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
     if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
     if (a.actions) act = (int)a.actions[edge];
     if (a.step_size) k = (int)a.step_size[edge];
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(WPB * 64) void k_edges3d(const KArgs a) {
         if (pidx == old_pidx) { s.pidx = old_pidx; s.tb = old_tb; }
     }
     const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-    int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+    int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
     if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
     if (a.actions) act = (int)a.actions[edge];
     if (a.step_size) k = (int)a.step_size[edge];
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(WPB * 64) void k_transition2d(const KArgs a) {
         if (pidx == old_pidx) { s.pidx = old_pidx; s.tb = old_tb; }
     }
     const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-    int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+    int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
     if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
     if (a.actions) act = (int)a.actions[edge];
     if (a.step_size) k = (int)a.step_size[edge];
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(WPB * 64) void k_edges2d(const KArgs a) {
     int episode = a.episode[srow];
     const uint64_t gid = (uint64_t)(a.env_id_base + edge);
     const uint32_t w = rng_word(env_keys(a.key_step, gid), a.t0);
-    int act = (int)(((w >> 16) * (uint32_t)K::A) >> 16), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
+    int act = draw_action<K::A>(w, a), k = 1 + (int)(((w & 0xffffu) * 3u) >> 16);
     if (a.use_scalar) { act = a.act_scalar; k = a.k_scalar; }
     if (a.actions) act = (int)a.actions[edge];
     if (a.step_size) k = (int)a.step_size[edge];

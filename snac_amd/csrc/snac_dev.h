@@ -53,6 +53,8 @@ struct KArgs {
     int32_t ts_done;           // count_step >= ts_done ends the episode: total_step (+ 1 with SNAC_RULE_TIME_GT)
     int32_t brick_gt;          // 1: count_brick > total_brick ends the episode (SNAC_RULE_BRICK_GT), 0: >=
     uint32_t t0, key_step, key_plan;
+    int32_t act_dist;          // 1: counter-RNG actions by the thresholds act_cdf (snac_env_desc.action_dist), 0: the uniform multiply
+    uint32_t act_cdf[7];       // the distribution's num_actions - 1 thresholds (draw_action); kernel arguments, so scalars
     int64_t env_id_base;
     int4* hdr;                 // snac_env_hdr[N] as 16-byte words
     int32_t* episode;
@@ -152,6 +154,21 @@ __device__ inline EnvKeys env_keys(uint32_t key, uint64_t env) {
     return k;
 }
 __device__ inline uint32_t rng_word(EnvKeys k, uint32_t t) { return mix32(mix32(k.e0 ^ (0x9E3779B9u * t)) + k.e1); }
+// the action of stream-0 word w: uniform by the multiply, or with a distribution (a.act_dist) the number of thresholds at or below
+// w >> 16 -- A - 1 compares.  a.act_dist and a.act_cdf are kernel arguments: the test is a scalar branch, the thresholds scalar loads.
+// The thresholds are loaded where they are compared, through a pointer the compiler cannot see through: hoisted out of the tick loops
+// they would hold up to seven more scalar registers across them, and kernels at the scalar-register limit (k_rollout2d) spill.
+template <int A>
+__device__ __forceinline__ int draw_action(uint32_t w, const KArgs& a) {
+    const uint32_t u = w >> 16;
+    if (!a.act_dist) return (int)((u * (uint32_t)A) >> 16);
+    int j0 = 0;
+    asm volatile("" : "+s"(j0));
+    int act = 0;
+#pragma unroll
+    for (int j = 0; j < A - 1; ++j) act += u >= a.act_cdf[j0 + j] ? 1 : 0;
+    return act;
+}
 
 
 enum { AUX_RESET = 0, AUX_OBSERVE = 1, AUX_IOU = 2 };

@@ -2,6 +2,8 @@
 // k_*.hip translation units beside this one (snac_dev.h has the map), trajectory memory in snac_traj.hip.
 #include "snac_dev.h"
 
+#include <atomic>
+
 namespace snac_detail {
 void launch_step3dq(const snac_env_desc* d, const KArgs& a, hipStream_t s);                   // k_step3dq.hip
 void launch_step1d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_step1d.hip
@@ -19,13 +21,30 @@ thread_local const char* g_kernel = "";
 
 // ------------------------------------------------------------------------------------------------
 // host side
-// the layout flags of the descriptor (include/snac_hip.h "Observation-layout variants")
+// the action distributions of snac_action_dist: handle h is entry h - 1.  Entries are written once, under the mutex, before the count
+// that publishes them; readers (every entry point, through check_layout / make_args) take no lock.
+struct ActDist { int32_t num_actions; uint32_t cdf[7]; };
+constexpr int ACT_DIST_CAP = 1024;
+ActDist g_dists[ACT_DIST_CAP];
+std::atomic<int> g_ndists{0};
+std::mutex g_dists_mu;
+
+const ActDist* act_dist(int32_t handle) {
+    return handle >= 1 && handle <= g_ndists.load(std::memory_order_acquire) ? &g_dists[handle - 1] : nullptr;
+}
+int num_actions_of(int kind) { return kind == SNAC_ENV_1D ? 3 : (kind == SNAC_ENV_2D ? 5 : 8); }
+
+// the layout flags of the descriptor (include/snac_hip.h "Observation-layout variants") and its action distribution
 int check_layout(const snac_env_desc* d) {
     if (d->frame_value != 0 && d->frame_value != -1 && d->frame_value != 2) return fail(SNAC_ERR_ARG, "frame_value must be -1 (or 0) or 2");
     if (d->frame_value == 2 && d->kind == SNAC_ENV_3D) return fail(SNAC_ERR_UNSUPPORTED, "frame_value 2 is a 1D / 2D layout (the 3D rules test the frame for -1)");
     if (d->obs_scalars < SNAC_SCALARS_DEFAULT || d->obs_scalars > SNAC_SCALARS_NORM) return fail(SNAC_ERR_ARG, "unknown obs_scalars");
     if (d->obs_tail & ~(SNAC_TAIL_POSITION | SNAC_TAIL_PLAN | SNAC_TAIL_RECORD)) return fail(SNAC_ERR_ARG, "unknown bits in obs_tail");
-    if (d->reserved != 0) return fail(SNAC_ERR_ARG, "snac_env_desc.reserved must be 0");
+    if (d->action_dist != 0) {
+        const ActDist* e = act_dist(d->action_dist);
+        if (!e) return fail(SNAC_ERR_ARG, "snac_env_desc.action_dist is not a handle of snac_action_dist");
+        if (e->num_actions != num_actions_of(d->kind)) return fail(SNAC_ERR_ARG, "snac_env_desc.action_dist was registered for another num_actions than the kind's");
+    }
     return SNAC_OK;
 }
 int base_obs_dim(int kind) { return kind == SNAC_ENV_1D ? 7 : 51; }
@@ -60,6 +79,10 @@ KArgs make_args(const snac_env_desc* d, const snac_state* st) {
     a.brick_gt = (d->rules & SNAC_RULE_BRICK_GT) ? 1 : 0;
     a.ts_done = a.total_step + ((d->rules & SNAC_RULE_TIME_GT) ? 1 : 0);
     a.key_step = stream_key(d->seed, 0); a.key_plan = stream_key(d->seed, 1);
+    if (const ActDist* e = d->action_dist ? act_dist(d->action_dist) : nullptr) {   // (checked by check_layout)
+        a.act_dist = 1;
+        std::memcpy(a.act_cdf, e->cdf, sizeof(a.act_cdf));
+    }
     a.env_id_base = d->env_id_base;
     a.hdr = (int4*)st->hdr; a.episode = st->episode; a.grid = st->grid; a.plans = st->plans; a.plan_tb = st->plan_tb;
     a.stat_episodes = st->stat_episodes; a.stat_return = st->stat_return; a.stat_iou_fx = st->stat_iou_fx;
@@ -368,6 +391,27 @@ int snac_tuning(char* out, int32_t cap) {
 int snac_stream_sync(void* stream) {
     const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "hipStreamSynchronize");
+}
+
+int snac_action_dist(int32_t num_actions, const uint32_t* cdf, int32_t* handle) {
+    if (!cdf || !handle) return fail(SNAC_ERR_ARG, "null cdf / handle");
+    if (num_actions < 2 || num_actions > 8) return fail(SNAC_ERR_ARG, "num_actions out of range (2..8)");
+    ActDist e;
+    std::memset(&e, 0, sizeof(e));
+    e.num_actions = num_actions;
+    for (int j = 0; j < num_actions - 1; ++j) {
+        if (cdf[j] > 65536u || (j > 0 && cdf[j] < cdf[j - 1])) return fail(SNAC_ERR_ARG, "thresholds must be nondecreasing and in [0, 65536]");
+        e.cdf[j] = cdf[j];
+    }
+    std::lock_guard<std::mutex> lk(g_dists_mu);
+    const int n = g_ndists.load(std::memory_order_relaxed);
+    for (int i = 0; i < n; ++i)
+        if (std::memcmp(&g_dists[i], &e, sizeof(e)) == 0) { *handle = i + 1; return SNAC_OK; }
+    if (n == ACT_DIST_CAP) return fail(SNAC_ERR_ARG, "the table of action distributions is full (1024 entries)");
+    g_dists[n] = e;
+    g_ndists.store(n + 1, std::memory_order_release);
+    *handle = n + 1;
+    return SNAC_OK;
 }
 
 int snac_env_sizes(int kind, int dynamic, snac_sizes* o) {

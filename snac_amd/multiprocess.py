@@ -6,7 +6,8 @@
 Default: the reference's loop shape -- T = total_step vector steps, one VectorizedEnvWrapper.step per tick, uniform
 random actions from np.random (over the env's own action_dim; --reference-actions reproduces the reference's
 `np.random.randint(3, size=N)`), then the three shapes are printed.  --fused runs the same T ticks as one
-snac_rollout launch (counter RNG, auto-reset) and prints env-steps/s.
+snac_rollout launch (counter RNG, auto-reset) and prints env-steps/s; with --reference-actions its counter-RNG actions are
+drawn from randint(3)'s distribution, weights [1, 1, 1, 0, ...] over action_dist (BatchedDMPEnv.action_probs).
 """
 import argparse
 import time
@@ -46,6 +47,8 @@ def main(args):
     observations = env.reset()
     if args.fused:
         b = env.batched
+        if args.reference_actions:
+            b.set_action_probs([1.0] * 3 + [0.0] * (env.action_dim - 3))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         obs, rewards, dones = b.rollout(T, obs="last")

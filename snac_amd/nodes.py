@@ -114,7 +114,7 @@ class _NodePool:
     # ---- leaf evaluation --------------------------------------------------------------------------------------------
     def evaluate(self, node_rows, horizon, gamma, first_reward=None, t0=0, check=True):
         """Default-policy evaluation of tree leaves in place (script/MCTS/utils/mcts.py:100-110), one launch on the records: from each
-        record node_rows[i] (None: record i, m = len(first_reward) or every record), up to `horizon` uniformly random steps that stop
+        record node_rows[i] (None: record i, m = len(first_reward) or every record), up to `horizon` random steps (the env's action_probs, else uniform) that stop
         at the first `done`, estimate = first_reward + sum_t reward_t * gamma**t in float64 -- what BatchedDMPEnv.evaluate() computes
         for the same states, bit for bit.  Actions come from the counter RNG keyed by (env_id_base + i, t0 + t): t0 = 0 draws those of
         BatchedDMPEnv.evaluate(), another t0 fresh ones.  A terminal leaf is not rolled out.  The records are not changed.  check=False
