@@ -567,6 +567,43 @@ int snac_evaluate_nodes2d(const snac_env_desc* desc, const snac_state* st, const
 int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const snac_node3d* nodes, int32_t pool_rows, int32_t m,
                           const int32_t* node_rows, int32_t H, uint32_t t0, const double* gpow, double* est, int64_t* steps, void* stream);
 
+/* ---- UCT tree search over node pools: selection and backup (k_uct.hip).  B independent trees, one path per tree per iteration;
+ * tree b owns node rows [b * cap, (b + 1) * cap) of a node pool and of the statistics array below (its root: row b * cap; its j-th
+ * allocated node: row b * cap + j), and rows B * cap + b are per-tree scratch rows that never become nodes.  An iteration is
+ *     snac_uct_select -> snac_transition_nodes{1,2,3}d (B edges src[b] -> dst[b], action[b], step_size NULL)
+ *                     -> est[b] = expanded[b] ? reward[b] : r_leaf[b] -> snac_evaluate_nodes{1,2,3}d (node_rows = leaf) -> snac_uct_backup
+ * all on one stream, with no host synchronisation (snac_amd/uct.py: UCTSearch).
+ * Selection, per tree, from the root, at most cap steps; at node n:
+ *   terminal: stop, leaf = n;  else an untried action (child[a] == -1) and fewer than cap nodes used (used[b]): expand the lowest such a
+ *   into row b * cap + used[b] (child[a] set, used[b] += 1), leaf = that row;  else children: descend to the one with the largest
+ *       U = child_value[a] / child_visits[a] + c * (log_table[visits(n)] * rsqrt_table[child_visits[a]])
+ *   in float64, no contraction, in that order (ties: the lowest a; table indices clamped to [0, table_len - 1]);  else stop, leaf = n.
+ *   Expanded: src = n, dst = the new row, action = a.  Not expanded: src = leaf, dst = B * cap + b, action = 0 (the result is unused),
+ *   r_leaf = the leaf's stored reward.  log_table[i] = sqrt(log(i)), rsqrt_table[i] = 1 / sqrt(i), computed by the caller.
+ * Backup, per tree: an expanded leaf's row is written whole (parent = src, action, reward and terminal = the transition's reward /
+ *   done, no children, no visits); then G = est[b] and, from the leaf up to the root, visits += 1, value_sum += G (mirrored into the
+ *   parent's child_visits / child_value), G = reward(parent) + gamma * G, each operation rounded to float64 (no contraction).
+ * Child row indices are clamped into their tree's rows.  Both entry points check every argument before any HIP call: num_actions
+ * 3, 5 or 8; no null pointer; B >= 1; cap >= 1; B * (cap + 1) within stats_rows and int32; table_len >= 2; stats 128-byte aligned. */
+typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
+    int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
+    int32_t child_visits[8];    /* N of child[a] */
+    double child_value[8];      /* W of child[a] */
+    int32_t parent;             /* -1 at a root */
+    int32_t action;             /* the edge from the parent (-1 at a root) */
+    int32_t terminal;           /* the edge's done (a root: its record's SNAC_FLAG_NEED_RESET) */
+    int32_t visits;             /* N */
+    double value_sum;           /* W */
+    float reward;               /* the edge's transition reward, 0 at a root */
+    int32_t zero[25];
+} snac_uct_node;
+int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double c, const double* log_table,
+                    const double* rsqrt_table, int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf,
+                    uint8_t* expanded, float* r_leaf, void* stream);
+int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double gamma, const int32_t* src,
+                    const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward, const uint8_t* done,
+                    const double* est, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ implementation.  See DESIGN.md / INTEGRATION.md.
 from ._lib import SnacError, build  # noqa: F401
 from . import plans  # noqa: F401
 
-__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "SnacError", "build", "plans"]
+__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "UCTSearch", "SnacError", "build", "plans"]
 
 
 def __getattr__(name):  # torch is imported lazily so that `import snac_amd` stays cheap
@@ -22,6 +22,10 @@ def __getattr__(name):  # torch is imported lazily so that `import snac_amd` sta
         from . import nodes
 
         return getattr(nodes, name)
+    if name == "UCTSearch":
+        from .uct import UCTSearch
+
+        return UCTSearch
     if name == "VectorizedEnvWrapper":
         from .vector import VectorizedEnvWrapper
 

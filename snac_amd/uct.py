@@ -1,0 +1,211 @@
+"""Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup: include/snac_hip.h;
+snac_amd/csrc/k_uct.hip).
+
+B independent trees, one path per tree per iteration.  An iteration is enqueued on the env's stream with no host synchronisation:
+selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b), each leaf's first reward (the new edge's
+or the stored one: two small torch ops), the default-policy evaluation of the B leaves (snac_evaluate_nodes*,
+script/MCTS/utils/mcts.py:100-110) and the backup (k_uct_backup).
+
+    env = BatchedDMPEnv(2, True, 4096, seed=1); env.reset()
+    search = UCTSearch(env, nodes_per_tree=256, horizon=600, gamma=0.99)
+    search.reset()                       # root b <- env row b
+    search.run(200)
+    a = search.best_actions()            # [B] the most-visited root action
+
+Root parallelism over one state: give G states `copies` trees each (reset(rows=...) with each row repeated); the copies draw different
+counter-RNG words because their slots differ, and their root statistics add up:
+
+    search = UCTSearch(env, 128, 600, 0.99, trees=G * copies)
+    search.reset(rows=torch.arange(G, device=env.device).repeat_interleave(copies))
+    search.run(100)
+    visits = search.root_visits().view(G, copies, -1).sum(1)      # [G, A]
+
+Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
+t0 = it * (H + 1) + 1, so no two iterations share a word.  A captured graph freezes these arguments: a graph of run(n), replayed after
+reset(), repeats run(n) exactly; a graph of one iteration replayed n times would draw iteration 0's words every time.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from .nodes import NodePool
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+WORDS = 64                                                           # int32 words per snac_uct_node (256 bytes)
+
+
+def uct_tables(n):
+    """(log_table, rsqrt_table) of length n as python floats: [sqrt(log(i))], [1.0 / sqrt(i)]; entry 0 is 0.0 (never read: a node with
+    children has been visited)."""
+    lt = [0.0] + [math.sqrt(math.log(i)) for i in range(1, n)]
+    rt = [0.0] + [1.0 / math.sqrt(i) for i in range(1, n)]
+    return lt, rt
+
+
+class UCTSearch:
+    """UCT over `trees` independent trees of `nodes_per_tree` nodes each on one NodePool of env's kind (include/snac_hip.h, "UCT tree
+    search", has the exact selection and backup rules).  Everything is allocated here; run() only enqueues work."""
+
+    def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None):
+        self.env = env
+        self.trees = int(env.num_envs if trees is None else trees)
+        self.nodes_per_tree, self.horizon, self.gamma, self.c = int(nodes_per_tree), int(horizon), float(gamma), float(c)
+        self.max_iterations = int(max_iterations)
+        B, cap = self.trees, self.nodes_per_tree
+        if B < 1 or cap < 1:
+            raise ValueError("trees and nodes_per_tree must be >= 1")
+        if self.horizon < 0 or self.max_iterations < 1:
+            raise ValueError("horizon must be >= 0 and max_iterations >= 1")
+        if B * (cap + 1) > 0x7FFFFFFF:
+            raise ValueError("trees * (nodes_per_tree + 1) rows exceed int32")
+        self.num_actions = env.num_actions
+        self.rows = B * (cap + 1)
+        dev = env.device
+        self.pool = NodePool(env, self.rows)
+        self.stats = torch.zeros((self.rows, WORDS), dtype=torch.int32, device=dev)
+        assert self.stats.data_ptr() % 128 == 0
+        lt, rt = uct_tables(self.max_iterations + 1)
+        self.log_table = torch.tensor(lt, dtype=torch.float64, device=dev)
+        self.rsqrt_table = torch.tensor(rt, dtype=torch.float64, device=dev)
+        self._gpow = torch.tensor([self.gamma ** t for t in range(max(1, self.horizon))], dtype=torch.float64, device=dev)
+
+        def slot(dtype):
+            return torch.zeros(B, dtype=dtype, device=dev)
+
+        self._used, self._src, self._dst, self._leaf = slot(torch.int32), slot(torch.int32), slot(torch.int32), slot(torch.int32)
+        self._action, self._expanded = slot(torch.int8), slot(torch.uint8)
+        self._r_leaf, self._reward, self._first = slot(torch.float32), slot(torch.float32), slot(torch.float32)
+        self._done, self._est = slot(torch.uint8), slot(torch.float64)
+        self._iteration = 0
+        self._roots = torch.arange(B, device=dev) * cap
+        self._lib = env._lib
+        P = self.pool
+        self._select_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, self.c, _ptr(self.log_table), _ptr(self.rsqrt_table),
+                             int(self.log_table.numel()), _ptr(self._used), _ptr(self._src), _ptr(self._dst), _ptr(self._action),
+                             _ptr(self._leaf), _ptr(self._expanded), _ptr(self._r_leaf))
+        self._backup_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, self.gamma, _ptr(self._src), _ptr(self._action),
+                             _ptr(self._leaf), _ptr(self._expanded), _ptr(self._reward), _ptr(self._done), _ptr(self._est))
+        self._transition = getattr(self._lib, P.TRANSITION)
+        self._evaluate_fn = getattr(self._lib, P.EVALUATE)
+        self._edge_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._src), _ptr(self._dst))
+        self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
+        self._eval_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._leaf), self.horizon)
+        self._est_ptrs = (_ptr(self._gpow), _ptr(self._est), None)
+
+    # ---- the search ---------------------------------------------------------------------------------------------------
+    def reset(self, rows=None):
+        """Root b <- env row rows[b] (None: row b), also copied into the tree's scratch record; the statistics and the iteration
+        count start over.  A root whose row has NEED_RESET is terminal."""
+        env, B, cap = self.env, self.trees, self.nodes_per_tree
+        if rows is None:
+            if B > env.num_envs:
+                raise ValueError("%d trees, %d env rows: give rows" % (B, env.num_envs))
+            rows = torch.arange(B, device=env.device)
+        rows = torch.as_tensor(rows, device=env.device).reshape(-1)
+        if int(rows.numel()) != B:
+            raise ValueError("rows must have %d entries" % B)
+        roots = self._roots
+        self.pool.load(rows=rows, node_rows=roots)
+        self.pool.load(rows=rows, node_rows=B * cap + torch.arange(B, device=env.device))
+        self.stats.zero_()
+        self.stats[:, 0:8] = -1                                      # child[]
+        self.stats[:, 32:34] = -1                                    # parent, action
+        self.stats[roots, 34] = self.pool.need_reset[roots].to(torch.int32)
+        self._used.fill_(1)
+        self._iteration = 0
+
+    def run(self, iterations):
+        """Enqueue `iterations` iterations (select, transition, evaluate, backup) on the env's stream; no host synchronisation."""
+        n = int(iterations)
+        if n < 0:
+            raise ValueError("iterations must be >= 0")
+        if self._iteration + n > self.max_iterations:
+            raise ValueError("%d iterations after %d exceed max_iterations = %d" % (n, self._iteration, self.max_iterations))
+        with torch.cuda.device(self.env.device):
+            for _ in range(n):
+                self._select()
+                self._edges()
+                self._evaluate()
+                self._backup()
+
+    # the four phases of an iteration (tools/uct_time.py times them one by one); the caller holds the env's device
+    def _t(self):
+        return (self._iteration * (self.horizon + 1)) & 0xFFFFFFFF
+
+    def _select(self):
+        _lib.check(self._lib.snac_uct_select(*self._select_args, self.env._stream()))
+
+    def _edges(self):
+        env = self.env
+        _lib.check(self._transition(C.byref(env._desc), C.byref(env._state), *self._edge_ptrs, self._t(), *self._step_ptrs, env._stream()))
+
+    def _evaluate(self):
+        env = self.env
+        torch.where(self._expanded.view(torch.bool), self._reward, self._r_leaf, out=self._first)   # the new edge's reward or the stored one
+        self._est.copy_(self._first)
+        _lib.check(self._evaluate_fn(C.byref(env._desc), C.byref(env._state), *self._eval_ptrs, (self._t() + 1) & 0xFFFFFFFF, *self._est_ptrs,
+                                     env._stream()))
+
+    def _backup(self):
+        _lib.check(self._lib.snac_uct_backup(*self._backup_args, self.env._stream()))
+        self._iteration += 1
+
+    @property
+    def iterations(self):
+        """Iterations enqueued since reset()."""
+        return self._iteration
+
+    # ---- readers ----------------------------------------------------------------------------------------------------------
+    def root_visits(self):
+        """[B, A] int32: the visits of each root child (0 where untried)."""
+        return self.stats[self._roots][:, 8:8 + self.num_actions].clone()
+
+    def root_q(self):
+        """[B, A] float64: W / N of each root child, NaN where untried."""
+        r = self.stats[self._roots]
+        w = r[:, 16:32].contiguous().view(torch.float64)[:, :self.num_actions]
+        q = w / r[:, 8:8 + self.num_actions].to(torch.float64)
+        return torch.where(r[:, :self.num_actions] >= 0, q, torch.full_like(q, float("nan")))
+
+    def best_actions(self):
+        """[B] int64: the most-visited root action, ties to the lowest."""
+        return torch.argmax(self.root_visits(), dim=1)
+
+    def tree_sizes(self):
+        """[B] int32: nodes used by each tree (the root counts)."""
+        return self._used.clone()
+
+    # views over all node rows (scratch rows included), decoded from snac_uct_node
+    @property
+    def children(self):
+        return self.stats[:, :self.num_actions]
+
+    @property
+    def parent(self):
+        return self.stats[:, 32]
+
+    @property
+    def action(self):
+        return self.stats[:, 33]
+
+    @property
+    def terminal(self):
+        return self.stats[:, 34] != 0
+
+    @property
+    def visits(self):
+        return self.stats[:, 35]
+
+    @property
+    def value_sum(self):
+        return self.stats[:, 36:38].view(torch.float64)[:, 0]
+
+    @property
+    def reward(self):
+        return self.stats[:, 38:39].view(torch.float32)[:, 0]
