@@ -567,7 +567,7 @@ int snac_evaluate_nodes2d(const snac_env_desc* desc, const snac_state* st, const
 int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const snac_node3d* nodes, int32_t pool_rows, int32_t m,
                           const int32_t* node_rows, int32_t H, uint32_t t0, const double* gpow, double* est, int64_t* steps, void* stream);
 
-/* ---- UCT tree search over node pools: selection and backup (k_uct.hip).  B independent trees, one path per tree per iteration;
+/* ---- UCT tree search over node pools: selection, backup and re-rooting (k_uct.hip).  B independent trees, one path per tree per iteration;
  * tree b owns node rows [b * cap, (b + 1) * cap) of a node pool and of the statistics array below (its root: row b * cap; its j-th
  * allocated node: row b * cap + j), and rows B * cap + b are per-tree scratch rows that never become nodes.  An iteration is
  *     snac_uct_select -> snac_transition_nodes{1,2,3}d (B edges src[b] -> dst[b], action[b], step_size NULL)
@@ -584,7 +584,24 @@ int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const
  *   done, no children, no visits); then G = est[b] and, from the leaf up to the root, visits += 1, value_sum += G (mirrored into the
  *   parent's child_visits / child_value), G = reward(parent) + gamma * G, each operation rounded to float64 (no contraction).
  * Child row indices are clamped into their tree's rows.  Both entry points check every argument before any HIP call: num_actions
- * 3, 5 or 8; no null pointer; B >= 1; cap >= 1; B * (cap + 1) within stats_rows and int32; table_len >= 2; stats 128-byte aligned. */
+ * 3, 5 or 8; no null pointer; B >= 1; cap >= 1; B * (cap + 1) within stats_rows and int32; table_len >= 2; stats 128-byte aligned.
+ * Re-rooting after a move (snac_uct_advance): tree b plays actions[b] (clamped into [0, num_actions)); base = b * cap, R = its root.
+ *   Terminal root (R.terminal != 0): the tree is unchanged (statistics, records, used[b]); reward_out[b] = 0, done_out[b] = 1.
+ *   Tried action (c = R.child[actions[b]] >= 0): the new tree is the subtree of c -- c and every node whose parent chain reaches c,
+ *     renumbered in increasing old row order (c -> base), used[b] = their number.  A child's row is always above its parent's, so the
+ *     compacted tree again has its root at base, its nodes in [base, base + used[b]) and parent < child: selection and backup run on
+ *     it unchanged.  child[] and parent are remapped to the new rows; every other field moves bit for bit (child_visits, child_value,
+ *     action, terminal, visits, value_sum, reward, zero), except that the new root gets parent = -1, action = -1, reward = 0 (its
+ *     terminal, visits and value_sum stay).  Each kept node's record (record_bytes: 128 for 1D / 2D, 896 for 3D) moves with its
+ *     statistics row, byte for byte.  reward_out[b] / done_out[b] = c's stored reward / terminal.
+ *   Untried action (child == -1): the new tree is one node, the transition of R by actions[b]: the caller has run that edge just before
+ *     into the tree's scratch record (B * cap + b), with its reward / done in edge_reward[b] / edge_done[b]; that record goes to base,
+ *     the root's statistics start fresh (children -1, no visits, W = 0, terminal = edge_done[b]), used[b] = 1; the outputs are the
+ *     edge's reward and done.
+ *   Rows [base + used[b], base + cap) and the scratch rows hold unspecified contents afterwards (statistics and records); nothing reads
+ *   them before they are written whole.  work: caller scratch of 2 * B * cap int32 (an old -> new and a new -> old map per tree).  No
+ *   host synchronisation.  Checks before any HIP call, beside those above: records non-null and 128-byte aligned; record_bytes 128 or
+ *   896; B * (cap + 1) within record_rows; no null per-tree array; work non-null. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -603,6 +620,9 @@ int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
 int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double gamma, const int32_t* src,
                     const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward, const uint8_t* done,
                     const double* est, void* stream);
+int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
+                     int32_t record_rows, const int8_t* actions, const float* edge_reward, const uint8_t* edge_done, int32_t* used,
+                     int32_t* work, float* reward_out, uint8_t* done_out, void* stream);
 
 #ifdef __cplusplus
 }

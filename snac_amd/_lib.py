@@ -29,7 +29,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_traj_alloc_ex", "snac_traj_free", "snac_traj_layout", "snac_traj_describe", "snac_traj_reserved_bytes", "snac_last_kernel", "snac_tuning",
            "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d", "snac_nodes1d_pack", "snac_nodes1d_unpack",
            "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d",
-           "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist", "snac_uct_select", "snac_uct_backup")
+           "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist", "snac_uct_select", "snac_uct_backup",
+           "snac_uct_advance")
 
 
 class Sizes(C.Structure):
@@ -158,6 +159,7 @@ def lib():
         L.snac_action_dist.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.snac_uct_select.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_uct_backup.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.snac_uct_advance.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]
         L.snac_traj_alloc_ex.argtypes = [C.c_size_t, C.c_int, C.c_size_t, vp, C.POINTER(vp)]
         L.snac_traj_free.argtypes = [vp]

@@ -1,4 +1,5 @@
-// k_uct.hip -- UCT selection and backup over node pools: snac_uct_select / snac_uct_backup (include/snac_hip.h has the semantics)
+// k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance
+// (include/snac_hip.h has the semantics)
 #include <cstddef>
 
 #include "snac_dev.h"
@@ -185,6 +186,140 @@ __global__ __launch_bounds__(64) void k_uct_backup(const UctBack v) {
     }
 }
 
+struct UctAdv {
+    uint4* stats;
+    uint4* records;
+    int32_t B, cap;
+    const int8_t* actions;
+    const float* edge_reward;
+    const uint8_t* edge_done;
+    int32_t* used;
+    int32_t* work;
+    float* reward_out;
+    uint8_t* done_out;
+};
+
+constexpr int ADV_ROWS = 32;                                         // new rows per move chunk
+
+// a kept node's child or parent row -> its new row; -1 (untried) and anything outside the kept rows read as -1
+__device__ __forceinline__ uint32_t remap(uint32_t r, const int32_t* o2n, int c, int end, int base) {
+    const int x = (int)r;
+    if (x < c || x >= end) return 0xFFFFFFFFu;
+    const int k = o2n[x - base];
+    return k < 0 ? 0xFFFFFFFFu : (uint32_t)(base + k);
+}
+
+// workgroup = tree.  Walk: a lane per candidate row, in chunks of 256 rows from c up; a walk follows parents only while they stay in
+// its own chunk, since every row below the chunk already has its kept flag (its old -> new entry in `work`).  Scan: ballots and
+// popcounts per wave, the four wave counts through LDS.  Move: ADV_ROWS new rows per chunk, each thread holding its 16-byte pieces of
+// the chunk's source rows (stats row, then record) in registers across one barrier.  Compaction keeps the old order, so a chunk's
+// stores land at or below its sources, and no chunk reads a row an earlier chunk wrote: the move is safe in place.
+template <int A, int RP>                                             // RP: 16-byte pieces of a node record (8: 1D / 2D, 56: 3D)
+__global__ __launch_bounds__(256) void k_uct_advance(const UctAdv v) {
+    constexpr int P = PIECES + RP, PER = ADV_ROWS * P / 256;
+    static_assert(ADV_ROWS * P % 256 == 0, "whole pieces per thread");
+    __shared__ int wave_kept[4];
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cap = v.cap, base = b * cap;
+    const uint4* const root = v.stats + (size_t)base * PIECES;
+    const uint4 hdr = root[P_HDR];
+    const int a = min(max((int)v.actions[b], 0), A - 1);
+    const int ch = reinterpret_cast<const int32_t*>(root)[a];
+    const int used = min(max(v.used[b], 1), cap);
+    __syncthreads();                                                 // every read of the root before the untried case rewrites it
+    if (hdr.z != 0u) {                                               // terminal root: nothing changes
+        if (tid == 0) {
+            v.reward_out[b] = 0.f;
+            v.done_out[b] = 1;
+        }
+        return;
+    }
+    if (ch < 0) {                                                    // untried: the edge's record alone, fresh statistics
+        const bool done = v.edge_done[b] != 0;
+        if (tid < RP) {
+            v.records[(size_t)base * RP + tid] = v.records[(size_t)(v.B * cap + b) * RP + tid];
+        } else if (tid >= 64 && tid < 64 + PIECES) {
+            const int q = tid - 64;
+            const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu), zero = make_uint4(0u, 0u, 0u, 0u);
+            v.stats[(size_t)base * PIECES + q] =
+                q < P_VISITS ? none : q == P_HDR ? make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, done ? 1u : 0u, 0u) : zero;
+        }
+        if (tid == 0) {
+            v.used[b] = 1;
+            v.reward_out[b] = v.edge_reward[b];
+            v.done_out[b] = done ? 1 : 0;
+        }
+        return;
+    }
+    const int c = clamp_row(ch, base, cap), end = base + used;
+    const uint4 cown = v.stats[(size_t)c * PIECES + P_OWN], chdr = v.stats[(size_t)c * PIECES + P_HDR];
+    int32_t* const o2n = v.work + (size_t)b * 2 * cap;               // old row - base -> new index (-1: dropped), rows [c, end) only
+    int32_t* const n2o = o2n + cap;                                  // new index -> old row
+    int kept = 0;
+    for (int s = c; s < end; s += 256) {
+        const int i = s + tid;
+        bool keep = false;
+        if (i < end) {
+            int x = i;
+            for (int d = 0; d < cap && x >= s && x > c; ++d)         // bounded, as select and backup
+                x = clamp_row(reinterpret_cast<const int32_t*>(v.stats + (size_t)x * PIECES)[32], base, cap);
+            keep = x == c || (x > c && x < s && o2n[x - base] >= 0);
+        }
+        const unsigned long long m = __ballot(keep);
+        if (lane == 0) wave_kept[wave] = __popcll(m);
+        __syncthreads();
+        int before = kept + __popcll(m & ((1ull << lane) - 1ull)), total = kept;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int n = wave_kept[w];
+            before += w < wave ? n : 0;
+            total += n;
+        }
+        if (i < end) {
+            o2n[i - base] = keep ? before : -1;
+            if (keep) n2o[before] = i;
+        }
+        kept = total;
+        __syncthreads();                                             // the chunk's flags before the next chunk's walks; LDS reuse
+    }
+    for (int j0 = 0; j0 < kept; j0 += ADV_ROWS) {
+        uint4 val[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int q = k * 256 + tid, j = j0 + q / P, p = q % P;
+            if (j >= kept) continue;
+            const int o = n2o[j];
+            uint4 x = p < PIECES ? v.stats[(size_t)o * PIECES + p] : v.records[(size_t)o * RP + (p - PIECES)];
+            if (p < P_VISITS) {
+                x.x = remap(x.x, o2n, c, end, base);
+                x.y = remap(x.y, o2n, c, end, base);
+                x.z = remap(x.z, o2n, c, end, base);
+                x.w = remap(x.w, o2n, c, end, base);
+            } else if (p == P_HDR) {
+                x.x = j == 0 ? 0xFFFFFFFFu : remap(x.x, o2n, c, end, base);
+                x.y = j == 0 ? 0xFFFFFFFFu : x.y;
+            } else if (p == P_OWN && j == 0) {
+                x.z = 0u;                                            // a root's reward
+            }
+            val[k] = x;
+        }
+        __syncthreads();                                             // every load of the chunk before any of its stores
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int q = k * 256 + tid, j = j0 + q / P, p = q % P;
+            if (j >= kept) continue;
+            if (p < PIECES) v.stats[(size_t)(base + j) * PIECES + p] = val[k];
+            else v.records[(size_t)(base + j) * RP + (p - PIECES)] = val[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        v.used[b] = kept;
+        v.reward_out[b] = __uint_as_float(cown.z);
+        v.done_out[b] = chdr.z != 0u ? 1 : 0;
+    }
+}
+
 int uct_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     using namespace snac_detail;
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
@@ -241,6 +376,29 @@ int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
     });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_backup");
+}
+
+int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
+                     int32_t record_rows, const int8_t* actions, const float* edge_reward, const uint8_t* edge_done, int32_t* used,
+                     int32_t* work, float* reward_out, uint8_t* done_out, void* stream) {
+    using namespace snac_detail;
+    if (int rc = uct_check(num_actions, stats, stats_rows, B, cap)) return rc;
+    if (!records) return fail(SNAC_ERR_ARG, "null records");
+    if (((uintptr_t)records & 127) != 0) return fail(SNAC_ERR_ARG, "records must be 128-byte aligned");
+    if (record_bytes != 128 && record_bytes != 896) return fail(SNAC_ERR_ARG, "record_bytes must be 128 or 896");
+    if ((long long)B * ((long long)cap + 1) > record_rows) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed record_rows");
+    if (!actions || !edge_reward || !edge_done || !used || !reward_out || !done_out)
+        return fail(SNAC_ERR_ARG, "null per-tree array (actions / edge_reward / edge_done / used / reward_out / done_out)");
+    if (!work) return fail(SNAC_ERR_ARG, "null work");
+    const UctAdv v{(uint4*)stats, (uint4*)records, B, cap, actions, edge_reward, edge_done, used, work, reward_out, done_out};
+    g_kernel = "k_uct_advance";
+    by_actions(num_actions, [&](auto k) {
+        constexpr int A = decltype(k)::value;
+        if (record_bytes == 128) hipLaunchKernelGGL((k_uct_advance<A, 8>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, v);
+        else hipLaunchKernelGGL((k_uct_advance<A, 56>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, v);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_advance");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup: include/snac_hip.h;
-snac_amd/csrc/k_uct.hip).
+"""Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance:
+include/snac_hip.h; snac_amd/csrc/k_uct.hip).
 
 B independent trees, one path per tree per iteration.  An iteration is enqueued on the env's stream with no host synchronisation:
 selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b), each leaf's first reward (the new edge's
@@ -11,6 +11,15 @@ script/MCTS/utils/mcts.py:100-110) and the backup (k_uct_backup).
     search.reset()                       # root b <- env row b
     search.run(200)
     a = search.best_actions()            # [B] the most-visited root action
+
+Playing an episode: advance() plays one action per tree and keeps the played child's subtree (its visits, values and nodes) as the
+new tree, compacted on the device with no host synchronisation:
+
+    search.reset()
+    for move in range(moves):
+        search.run(50)
+        r, d = search.advance(search.best_actions())   # reward / done of the move, per tree
+    search.store_roots()                 # env row b <- root b: observe(), iou() of the played states
 
 Root parallelism over one state: give G states `copies` trees each (reset(rows=...) with each row repeated); the copies draw different
 counter-RNG words because their slots differ, and their root statistics add up:
@@ -97,6 +106,15 @@ class UCTSearch:
         self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
         self._eval_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._leaf), self.horizon)
         self._est_ptrs = (_ptr(self._gpow), _ptr(self._est), None)
+        # advance(): the B root edges into the scratch records, then the re-rooting (work: an old -> new and a new -> old map per tree)
+        self._adv_action, self._adv_reward, self._adv_done = slot(torch.int8), slot(torch.float32), slot(torch.uint8)
+        self._adv_src = self._roots.to(torch.int32)
+        self._adv_dst = (B * cap + torch.arange(B, device=dev)).to(torch.int32)
+        self._work = torch.empty(2 * B * cap, dtype=torch.int32, device=dev)
+        self._adv_edge_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._adv_src), _ptr(self._adv_dst))
+        self._adv_step_ptrs = (_ptr(self._adv_action), None, None, _ptr(self._adv_reward), _ptr(self._adv_done))
+        self._advance_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, _ptr(P.records), P.WORDS * 4, P.rows, _ptr(self._adv_action),
+                              _ptr(self._adv_reward), _ptr(self._adv_done), _ptr(self._used), _ptr(self._work))
 
     # ---- the search ---------------------------------------------------------------------------------------------------
     def reset(self, rows=None):
@@ -133,6 +151,44 @@ class UCTSearch:
                 self._edges()
                 self._evaluate()
                 self._backup()
+
+    def advance(self, actions, check=True):
+        """Play actions[b] in tree b and re-root it (include/snac_hip.h, "Re-rooting after a move"): a tried action keeps its child's
+        subtree, compacted to the tree's first rows; an untried one leaves a single node, the root's transition by that action; a
+        terminal root stays as it is.  Enqueues the B root edges (into the scratch records, with this iteration's counter words) and
+        the re-rooting on the env's stream.  check=True rejects actions of the wrong length or outside [0, A) (a host read);
+        check=False does no host synchronisation (out-of-range actions are clamped on the device).
+        The iteration count is not reset: later iterations keep drawing fresh counter words, and max_iterations keeps bounding the
+        iterations since reset(), which also keeps every visit count inside the U tables.
+        Returns (reward float32 [B], done bool [B]): the move's reward and done (a terminal root: 0, True)."""
+        env, B = self.env, self.trees
+        a = actions.to(env.device) if torch.is_tensor(actions) else torch.as_tensor(actions, device=env.device)
+        a = a.reshape(-1)
+        if int(a.numel()) != B:
+            raise ValueError("actions must have %d entries" % B)
+        if a.is_floating_point() or a.is_complex() or a.dtype == torch.bool:
+            raise ValueError("actions must be integers")
+        if check and (int(a.min()) < 0 or int(a.max()) >= self.num_actions):
+            raise ValueError("actions must be in [0, %d)" % self.num_actions)
+        reward = torch.empty(B, dtype=torch.float32, device=env.device)
+        done = torch.empty(B, dtype=torch.uint8, device=env.device)
+        with torch.cuda.device(env.device):
+            self._adv_action.copy_(a.clamp(0, self.num_actions - 1))
+            self._root_edges()
+            self._reroot(reward, done)
+        return reward, done.view(torch.bool)
+
+    # the two phases of advance() (tools/uct_advance_time.py times them one by one); the caller holds the env's device
+    def _root_edges(self):
+        env = self.env
+        _lib.check(self._transition(C.byref(env._desc), C.byref(env._state), *self._adv_edge_ptrs, self._t(), *self._adv_step_ptrs, env._stream()))
+
+    def _reroot(self, reward, done):
+        _lib.check(self._lib.snac_uct_advance(*self._advance_args, _ptr(reward), _ptr(done), self.env._stream()))
+
+    def store_roots(self, rows=None):
+        """Env row rows[b] <- the record of root b (None: row b), so that observe() / iou() read the played states."""
+        self.pool.store(node_rows=self._roots, rows=rows)
 
     # the four phases of an iteration (tools/uct_time.py times them one by one); the caller holds the env's device
     def _t(self):
