@@ -601,7 +601,38 @@ int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const
  *   Rows [base + used[b], base + cap) and the scratch rows hold unspecified contents afterwards (statistics and records); nothing reads
  *   them before they are written whole.  work: caller scratch of 2 * B * cap int32 (an old -> new and a new -> old map per tree).  No
  *   host synchronisation.  Checks before any HIP call, beside those above: records non-null and 128-byte aligned; record_bytes 128 or
- *   896; B * (cap + 1) within record_rows; no null per-tree array; work non-null. */
+ *   896; B * (cap + 1) within record_rows; no null per-tree array; work non-null.
+ * K paths per tree and iteration (snac_uct_select_paths / snac_uct_backup_paths; paths = K >= 1, tree parallelism with virtual loss).
+ *   Slot s = b * K + k is path k of tree b.  Every per-slot array (src, dst, action, leaf, expanded, r_leaf, reward, done, est,
+ *   first_slot) has B * K entries; used keeps B.  The scratch row of slot s is row B * cap + s, so the node pool and the statistics
+ *   array need B * (cap + K) rows (snac_uct_advance keeps using scratch row B * cap + b, which lies inside that range; nothing reads a
+ *   scratch row across calls).  An iteration is
+ *     snac_uct_select_paths -> snac_transition_nodes* (B * K edges) -> est[s] = first_slot[s] >= 0 ? reward[first_slot[s]] : r_leaf[s]
+ *                           -> snac_evaluate_nodes* (B * K leaves, several slots may name one row) -> snac_uct_backup_paths.
+ *   Selection, per tree, paths k = 0 .. K - 1 strictly in that order.  u0 = used[b] on entry; a row >= b * cap + u0 is FRESH (made by
+ *   an earlier path of this launch: its record and its header do not exist yet).  P(x) = the number of earlier paths of this launch
+ *   that pass through or end at node x (the in-flight count); 0 everywhere when the launch starts.  Path k walks from the root as in
+ *   snac_uct_select, except:
+ *     - arriving at a fresh row stops the path there: leaf = that row, not expanded, first_slot[s] = the slot that expanded it;
+ *     - U of child a of node n is, in float64, no contraction, in this order:
+ *         Np = N_c + P_c;  q = (W_c - virtual_loss * (double)P_c) / (double)Np;  e = log_table[N(n) + P(n)] * rsqrt_table[Np];
+ *         U = q + c * e     (table indices clamped as above; ties: the lowest a; every P = 0 gives snac_uct_select's U bit for bit);
+ *     - when the path has its leaf, P += 1 on every node of the path, the leaf included, and an expansion (child[a] = the new row,
+ *       used[b] += 1) is visible to path k + 1.
+ *   Outputs per slot as snac_uct_select's, with dst = B * cap + s when not expanded, and: an expanded slot has first_slot[s] = s; a
+ *   slot that is neither expanded nor on a fresh leaf has first_slot[s] = -1.  A not-expanded slot's src is its leaf, EXCEPT on a fresh
+ *   leaf, where src is the tree's root row (the fresh row is the destination of its expander's edge in the same transition launch,
+ *   and no destination may be another edge's source); its r_leaf is 0 there (unused).  The caller's tables must reach
+ *   N(root) + K: table_len > the largest visit count + K.
+ *   Backup, per tree: first every expanded slot's row is written whole as in snac_uct_backup; then paths k = 0 .. K - 1 in that order
+ *   each walk from their leaf to the root as there (G = est[s]).  Shared ancestors receive their additions in slot order.  After the
+ *   backup every in-flight count is 0 again.
+ *   Where P lives: P of child a of node n is n's zero[1 + a], counted up by the selection on the way down and cleared by the backup's
+ *   walks; a node's own P is that entry of its parent and the root's is k.  zero[0] of a fresh row holds its expander's slot until the
+ *   backup writes the row.  The one-path entry points and snac_uct_advance neither read nor write these words (advance moves them,
+ *   zero, bit for bit).
+ *   Checks before any HIP call: those of the one-path entry points with B * (cap + paths) rows; paths >= 1; B * paths within int32;
+ *   virtual_loss finite; first_slot non-null. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -612,7 +643,8 @@ typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all th
     int32_t visits;             /* N */
     double value_sum;           /* W */
     float reward;               /* the edge's transition reward, 0 at a root */
-    int32_t zero[25];
+    int32_t zero[25];           /* in-flight counts during a multi-path iteration (zero[1 + a]: of child[a]; zero[0]: a fresh row's
+                                   expander slot), zero outside one */
 } snac_uct_node;
 int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double c, const double* log_table,
                     const double* rsqrt_table, int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf,
@@ -623,6 +655,14 @@ int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
 int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
                      int32_t record_rows, const int8_t* actions, const float* edge_reward, const uint8_t* edge_done, int32_t* used,
                      int32_t* work, float* reward_out, uint8_t* done_out, void* stream);
+
+int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                          double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
+                          int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf, int32_t* first_slot,
+                          void* stream);
+int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
+                          const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
+                          const uint8_t* done, const double* est, void* stream);
 
 #ifdef __cplusplus
 }

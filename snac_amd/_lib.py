@@ -30,7 +30,7 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d", "snac_nodes1d_pack", "snac_nodes1d_unpack",
            "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d",
            "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist", "snac_uct_select", "snac_uct_backup",
-           "snac_uct_advance")
+           "snac_uct_advance", "snac_uct_select_paths", "snac_uct_backup_paths")
 
 
 class Sizes(C.Structure):
@@ -160,6 +160,9 @@ def lib():
         L.snac_uct_select.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_uct_backup.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_uct_advance.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.snac_uct_select_paths.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, vp, vp, C.c_int32,
+                                            vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.snac_uct_backup_paths.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]
         L.snac_traj_alloc_ex.argtypes = [C.c_size_t, C.c_int, C.c_size_t, vp, C.POINTER(vp)]
         L.snac_traj_free.argtypes = [vp]

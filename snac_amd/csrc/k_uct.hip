@@ -1,5 +1,6 @@
-// k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance
-// (include/snac_hip.h has the semantics)
+// k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance, and the
+// K-paths-per-tree iteration snac_uct_select_paths / snac_uct_backup_paths (include/snac_hip.h has the semantics)
+#include <cmath>
 #include <cstddef>
 
 #include "snac_dev.h"
@@ -320,6 +321,176 @@ __global__ __launch_bounds__(256) void k_uct_advance(const UctAdv v) {
     }
 }
 
+// ---- K paths per tree and iteration (virtual loss) ----------------------------------------------------------------------------------
+// lane = tree, its K paths one after the other: path k + 1 reads the in-flight counts path k left, so a tree is one serial chain and
+// every word a path reads back was stored by the same lane.  The in-flight count P of child a of node n is n's zero[1 + a] (pieces
+// P_FLY, P_FLY + 1), incremented on the way down and cleared by the backup; a node's own count is that entry of its parent, carried
+// down in a register, and the root's is the path index k.  A fresh row (>= base + used on entry) has no record and no header yet; its
+// word 39 (zero[0]) holds the slot that expanded it until the backup writes the row whole.
+constexpr int P_FLY = 10;
+
+struct UctSelPaths {
+    UctSel s;
+    int32_t K;
+    double vl;
+    int32_t* first_slot;
+};
+
+struct UctBackPaths {
+    UctBack s;
+    int32_t K;
+};
+
+template <int A>
+__global__ __launch_bounds__(64) void k_uct_select_paths(const UctSelPaths w) {
+    constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
+    const UctSel& v = w.s;
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= v.B) return;
+    const int base = b * v.cap, K = w.K;
+    const int used0 = v.used[b];
+    const int fresh = base + used0;                                  // rows from here up are made by this launch
+    int used = used0;
+    for (int k = 0; k < K; ++k) {
+        const int s = b * K + k;
+        int n = base, leaf = base, act = 0, src = base, first = -1, fly = k;   // fly: earlier paths through n
+        bool expanded = false;
+        float r = 0.f;
+        for (int depth = 0; depth < v.cap; ++depth) {
+            const uint4* const rec = v.stats + (size_t)n * PIECES;
+            uint4 pc[CI], pn[CI], pf[CI], pw[CW];
+#pragma unroll
+            for (int q = 0; q < CI; ++q) { pc[q] = rec[P_CHILD + q]; pn[q] = rec[P_VISITS + q]; pf[q] = rec[P_FLY + q]; }
+#pragma unroll
+            for (int q = 0; q < CW; ++q) pw[q] = rec[P_VALUE + q];
+            const uint4 hdr = rec[P_HDR], own = rec[P_OWN];
+            leaf = src = n;
+            r = __uint_as_float(own.z);
+            if (hdr.z != 0u) break;                                  // terminal
+            int child[A], cn[A], cf[A];
+            double cw[A];
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+                const uint4 c4 = pc[a / 4], n4 = pn[a / 4], f4 = pf[a / 4], w2 = pw[a / 2];
+                const int j = a % 4;
+                child[a] = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
+                cn[a] = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
+                cf[a] = (int)(j == 0 ? f4.x : j == 1 ? f4.y : j == 2 ? f4.z : f4.w);
+                cw[a] = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
+            }
+            int untried = -1;
+#pragma unroll
+            for (int a = A - 1; a >= 0; --a)
+                if (child[a] < 0) untried = a;
+            int32_t* const words = reinterpret_cast<int32_t*>(v.stats + (size_t)n * PIECES);
+            if (untried >= 0 && used < v.cap) {                      // expand the lowest untried action into the tree's next row
+                const int row = base + used;
+                used += 1;
+                words[untried] = row;
+                words[4 * P_FLY + untried] = 1;
+                reinterpret_cast<int32_t*>(v.stats + (size_t)row * PIECES)[39] = s;
+                leaf = row;
+                act = untried;
+                expanded = true;
+                first = s;
+                break;
+            }
+            const double lg = v.ltab[min(max((int)hdr.w + fly, 0), v.tlen - 1)];
+            int best = -1, bf = 0;
+            double bu = 0.0;
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+                if (child[a] < 0) continue;
+                double u;
+                {
+#pragma clang fp contract(off)
+                    const int np = cn[a] + cf[a];
+                    const double q = (cw[a] - w.vl * (double)cf[a]) / (double)np;
+                    const double e = lg * v.rtab[min(max(np, 0), v.tlen - 1)];
+                    u = q + v.c * e;
+                }
+                if (best < 0 || u > bu) { best = a; bu = u; bf = cf[a]; }
+            }
+            if (best < 0) break;                                     // no children and the budget spent
+            words[4 * P_FLY + best] = bf + 1;
+            fly = bf;
+            n = clamp_row(child[best], base, v.cap);
+            if (n >= fresh) {                                        // made by an earlier path of this launch: stop on it
+                leaf = n;
+                src = base;                                          // the row is another edge's destination: step the root instead
+                r = 0.f;
+                first = reinterpret_cast<const int32_t*>(v.stats + (size_t)n * PIECES)[39];
+                break;
+            }
+        }
+        v.src[s] = src;
+        v.dst[s] = expanded ? leaf : v.B * v.cap + s;
+        v.action[s] = (int8_t)act;
+        v.leaf[s] = leaf;
+        v.expanded[s] = expanded ? 1 : 0;
+        v.r_leaf[s] = expanded ? 0.f : r;
+        w.first_slot[s] = first;
+    }
+    v.used[b] = used;
+}
+
+template <int A>
+__global__ __launch_bounds__(64) void k_uct_backup_paths(const UctBackPaths w) {
+    const UctBack& v = w.s;
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= v.B) return;
+    const int base = b * v.cap, K = w.K;
+    for (int k = 0; k < K; ++k) {                                    // the new nodes' rows, whole, before any walk reads one
+        const int s = b * K + k;
+        if (!v.expanded[s]) continue;
+        uint4* const rec = v.stats + (size_t)clamp_row(v.leaf[s], base, v.cap) * PIECES;
+        const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu), zero = make_uint4(0u, 0u, 0u, 0u);
+        rec[P_CHILD] = none;
+        rec[P_CHILD + 1] = none;
+#pragma unroll
+        for (int q = P_VISITS; q < P_HDR; ++q) rec[q] = zero;
+        rec[P_HDR] = make_uint4((uint32_t)clamp_row(v.src[s], base, v.cap), (uint32_t)v.action[s], v.done[s] ? 1u : 0u, 0u);
+        rec[P_OWN] = make_uint4(0u, 0u, __float_as_uint(v.reward[s]), 0u);
+#pragma unroll
+        for (int q = P_OWN + 1; q < PIECES; ++q) rec[q] = zero;
+    }
+    for (int k = 0; k < K; ++k) {                                    // the walks, in slot order: shared ancestors add in that order
+        const int s = b * K + k;
+        int x = clamp_row(v.leaf[s], base, v.cap);
+        double g = v.est[s];
+        const uint4* const rec = v.stats + (size_t)x * PIECES;
+        uint4 hdr = rec[P_HDR], own = rec[P_OWN];
+        for (int depth = 0; depth < v.cap; ++depth) {                // leaf .. root, bounded as the selection
+            int32_t* const me = reinterpret_cast<int32_t*>(v.stats + (size_t)x * PIECES);
+            const int visits = (int)hdr.w + 1;
+            double sum;
+            {
+#pragma clang fp contract(off)
+                sum = f64(own.x, own.y) + g;
+            }
+            me[35] = visits;
+            *reinterpret_cast<double*>(me + 36) = sum;
+            const int parent = (int)hdr.x;
+            if (parent < 0) break;
+            const int p = clamp_row(parent, base, v.cap);
+            const int a = min(max((int)hdr.y, 0), A - 1);
+            uint4* const prec = v.stats + (size_t)p * PIECES;
+            hdr = prec[P_HDR];
+            own = prec[P_OWN];
+            int32_t* const pw = reinterpret_cast<int32_t*>(prec);
+            pw[8 + a] = visits;                                      // the mirror in the parent's line 0
+            *reinterpret_cast<double*>(pw + 16 + 2 * a) = sum;
+            pw[4 * P_FLY + a] = 0;                                   // the edge's in-flight count
+            {
+#pragma clang fp contract(off)
+                const double t = v.gamma * g;
+                g = (double)__uint_as_float(own.z) + t;
+            }
+            x = p;
+        }
+    }
+}
+
 int uct_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     using namespace snac_detail;
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
@@ -329,6 +500,22 @@ int uct_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     const long long need = (long long)B * ((long long)cap + 1);
     if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed int32");
     if (need > rows) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed stats_rows");
+    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    return SNAC_OK;
+}
+
+// the checks of uct_check for K paths per tree: B * K slots, B * (cap + K) rows
+int uct_check_paths(int A, const void* stats, int32_t rows, int32_t B, int32_t cap, int32_t K) {
+    using namespace snac_detail;
+    if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
+    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
+    if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
+    if (cap < 1) return fail(SNAC_ERR_ARG, "cap must be >= 1");
+    if (K < 1) return fail(SNAC_ERR_ARG, "paths must be >= 1");
+    if ((long long)B * (long long)K > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * paths slots exceed int32");
+    const long long need = (long long)B * ((long long)cap + (long long)K);
+    if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * (cap + paths) rows exceed int32");
+    if (need > rows) return fail(SNAC_ERR_ARG, "B * (cap + paths) rows exceed stats_rows");
     if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
     return SNAC_OK;
 }
@@ -399,6 +586,43 @@ int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
     });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_advance");
+}
+
+int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                          double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
+                          int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf, int32_t* first_slot,
+                          void* stream) {
+    using namespace snac_detail;
+    if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
+    if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
+    if (!log_table || !rsqrt_table) return fail(SNAC_ERR_ARG, "null log_table / rsqrt_table");
+    if (table_len < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
+    if (!used || !src || !dst || !action || !leaf || !expanded || !r_leaf || !first_slot)
+        return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
+    const UctSelPaths v{{(uint4*)stats, B, cap, c, log_table, rsqrt_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
+                        paths, virtual_loss, first_slot};
+    g_kernel = "k_uct_select_paths";
+    by_actions(num_actions, [&](auto k) {
+        hipLaunchKernelGGL((k_uct_select_paths<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_select_paths");
+}
+
+int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
+                          const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
+                          const uint8_t* done, const double* est, void* stream) {
+    using namespace snac_detail;
+    if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
+    if (!src || !action || !leaf || !expanded || !reward || !done || !est)
+        return fail(SNAC_ERR_ARG, "null per-slot array (src / action / leaf / expanded / reward / done / est)");
+    const UctBackPaths v{{(uint4*)stats, B, cap, gamma, src, action, leaf, expanded, reward, done, est}, paths};
+    g_kernel = "k_uct_backup_paths";
+    by_actions(num_actions, [&](auto k) {
+        hipLaunchKernelGGL((k_uct_backup_paths<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_backup_paths");
 }
 
 }  // extern "C"

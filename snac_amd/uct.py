@@ -1,10 +1,10 @@
-"""Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance:
-include/snac_hip.h; snac_amd/csrc/k_uct.hip).
+"""Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
+snac_uct_select_paths / snac_uct_backup_paths: include/snac_hip.h; snac_amd/csrc/k_uct.hip).
 
-B independent trees, one path per tree per iteration.  An iteration is enqueued on the env's stream with no host synchronisation:
-selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b), each leaf's first reward (the new edge's
-or the stored one: two small torch ops), the default-policy evaluation of the B leaves (snac_evaluate_nodes*,
-script/MCTS/utils/mcts.py:100-110) and the backup (k_uct_backup).
+B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
+stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
+each leaf's first reward (the new edge's or the stored one: two small torch ops), the default-policy evaluation of the B leaves
+(snac_evaluate_nodes*, script/MCTS/utils/mcts.py:100-110) and the backup (k_uct_backup).
 
     env = BatchedDMPEnv(2, True, 4096, seed=1); env.reset()
     search = UCTSearch(env, nodes_per_tree=256, horizon=600, gamma=0.99)
@@ -29,9 +29,22 @@ counter-RNG words because their slots differ, and their root statistics add up:
     search.run(100)
     visits = search.root_visits().view(G, copies, -1).sum(1)      # [G, A]
 
+Tree parallelism for a few trees: paths=K sends K paths through EACH tree per iteration, kept apart by virtual loss (a path counts as
+a visit, and as a return of -virtual_loss, on every node under it until the backup), so that an iteration hands B * K edges and B * K
+leaves to the transition and evaluation kernels.  One tree keeps the whole budget and advance() keeps its subtree, which root
+parallelism cannot do.  Root visits after n iterations are n * K; virtual_loss of the order of a step reward spreads the K paths
+wider than the default 0.0 (virtual visits only) at some cost in search quality:
+
+    env = BatchedDMPEnv(2, True, 64, seed=1); env.reset()
+    search = UCTSearch(env, nodes_per_tree=8192, horizon=100, gamma=0.99, max_iterations=256, paths=16)
+    search.reset()
+    search.run(256)                      # 4096 leaf evaluations per tree
+    r, d = search.advance(search.best_actions())
+
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
-t0 = it * (H + 1) + 1, so no two iterations share a word.  A captured graph freezes these arguments: a graph of run(n), replayed after
-reset(), repeats run(n) exactly; a graph of one iteration replayed n times would draw iteration 0's words every time.
+t0 = it * (H + 1) + 1, so no two iterations share a word (the slot index b * K + k keys the stream, so no two paths do either).  A
+captured graph freezes these arguments: a graph of run(n), replayed after reset(), repeats run(n) exactly; a graph of one iteration
+replayed n times would draw iteration 0's words every time.
 """
 import ctypes as C
 import math
@@ -59,35 +72,45 @@ def uct_tables(n):
 
 class UCTSearch:
     """UCT over `trees` independent trees of `nodes_per_tree` nodes each on one NodePool of env's kind (include/snac_hip.h, "UCT tree
-    search", has the exact selection and backup rules).  Everything is allocated here; run() only enqueues work."""
+    search", has the exact selection and backup rules).  paths=K > 1: K paths per tree and iteration with `virtual_loss` per in-flight
+    path ("K paths per tree and iteration" there).  Everything is allocated here; run() only enqueues work."""
 
-    def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None):
+    def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None, paths=1, virtual_loss=0.0):
         self.env = env
         self.trees = int(env.num_envs if trees is None else trees)
         self.nodes_per_tree, self.horizon, self.gamma, self.c = int(nodes_per_tree), int(horizon), float(gamma), float(c)
         self.max_iterations = int(max_iterations)
-        B, cap = self.trees, self.nodes_per_tree
+        self.paths, self.virtual_loss = int(paths), float(virtual_loss)
+        B, cap, K = self.trees, self.nodes_per_tree, self.paths
         if B < 1 or cap < 1:
             raise ValueError("trees and nodes_per_tree must be >= 1")
         if self.horizon < 0 or self.max_iterations < 1:
             raise ValueError("horizon must be >= 0 and max_iterations >= 1")
-        if B * (cap + 1) > 0x7FFFFFFF:
-            raise ValueError("trees * (nodes_per_tree + 1) rows exceed int32")
+        if K < 1 or K != paths:
+            raise ValueError("paths must be an integer >= 1")
+        if not math.isfinite(self.virtual_loss):
+            raise ValueError("virtual_loss must be finite")
+        if B * (cap + K) > 0x7FFFFFFF:
+            raise ValueError("trees * (nodes_per_tree + %s) rows exceed int32" % ("1" if K == 1 else "paths"))
+        if self.max_iterations * K + 1 > 0x7FFFFFFF:
+            raise ValueError("max_iterations * paths visits exceed int32")
         self.num_actions = env.num_actions
-        self.rows = B * (cap + 1)
+        self.rows = B * (cap + K)                                    # the trees' rows, then a scratch row per slot b * K + k
+        S = B * K
         dev = env.device
         self.pool = NodePool(env, self.rows)
         self.stats = torch.zeros((self.rows, WORDS), dtype=torch.int32, device=dev)
         assert self.stats.data_ptr() % 128 == 0
-        lt, rt = uct_tables(self.max_iterations + 1)
+        lt, rt = uct_tables(self.max_iterations * K + 1)                 # the root's N + P reaches max_iterations * K
         self.log_table = torch.tensor(lt, dtype=torch.float64, device=dev)
         self.rsqrt_table = torch.tensor(rt, dtype=torch.float64, device=dev)
         self._gpow = torch.tensor([self.gamma ** t for t in range(max(1, self.horizon))], dtype=torch.float64, device=dev)
 
         def slot(dtype):
-            return torch.zeros(B, dtype=dtype, device=dev)
+            return torch.zeros(S, dtype=dtype, device=dev)
 
-        self._used, self._src, self._dst, self._leaf = slot(torch.int32), slot(torch.int32), slot(torch.int32), slot(torch.int32)
+        self._used = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._src, self._dst, self._leaf = slot(torch.int32), slot(torch.int32), slot(torch.int32)
         self._action, self._expanded = slot(torch.int8), slot(torch.uint8)
         self._r_leaf, self._reward, self._first = slot(torch.float32), slot(torch.float32), slot(torch.float32)
         self._done, self._est = slot(torch.uint8), slot(torch.float64)
@@ -102,12 +125,21 @@ class UCTSearch:
                              _ptr(self._leaf), _ptr(self._expanded), _ptr(self._reward), _ptr(self._done), _ptr(self._est))
         self._transition = getattr(self._lib, P.TRANSITION)
         self._evaluate_fn = getattr(self._lib, P.EVALUATE)
-        self._edge_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._src), _ptr(self._dst))
+        if K > 1:                                                    # paths=1 keeps the one-path entry points
+            self._first_slot, self._first_idx = slot(torch.int32), slot(torch.int32)
+            self._first_new, self._first_has = slot(torch.float32), slot(torch.bool)
+            self._select_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, K, self.c, self.virtual_loss, _ptr(self.log_table),
+                                 _ptr(self.rsqrt_table), int(self.log_table.numel()), _ptr(self._used), _ptr(self._src), _ptr(self._dst),
+                                 _ptr(self._action), _ptr(self._leaf), _ptr(self._expanded), _ptr(self._r_leaf), _ptr(self._first_slot))
+            self._backup_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, K, self.gamma, _ptr(self._src), _ptr(self._action),
+                                 _ptr(self._leaf), _ptr(self._expanded), _ptr(self._reward), _ptr(self._done), _ptr(self._est))
+        self._edge_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._src), _ptr(self._dst))
         self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
-        self._eval_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._leaf), self.horizon)
+        self._eval_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), self.horizon)
         self._est_ptrs = (_ptr(self._gpow), _ptr(self._est), None)
         # advance(): the B root edges into the scratch records, then the re-rooting (work: an old -> new and a new -> old map per tree)
-        self._adv_action, self._adv_reward, self._adv_done = slot(torch.int8), slot(torch.float32), slot(torch.uint8)
+        self._adv_action = torch.zeros(B, dtype=torch.int8, device=dev)
+        self._adv_reward, self._adv_done = torch.zeros(B, dtype=torch.float32, device=dev), torch.zeros(B, dtype=torch.uint8, device=dev)
         self._adv_src = self._roots.to(torch.int32)
         self._adv_dst = (B * cap + torch.arange(B, device=dev)).to(torch.int32)
         self._work = torch.empty(2 * B * cap, dtype=torch.int32, device=dev)
@@ -139,7 +171,8 @@ class UCTSearch:
         self._iteration = 0
 
     def run(self, iterations):
-        """Enqueue `iterations` iterations (select, transition, evaluate, backup) on the env's stream; no host synchronisation."""
+        """Enqueue `iterations` iterations (select, transition, evaluate, backup; `paths` paths per tree each) on the env's stream; no host
+        synchronisation."""
         n = int(iterations)
         if n < 0:
             raise ValueError("iterations must be >= 0")
@@ -195,7 +228,8 @@ class UCTSearch:
         return (self._iteration * (self.horizon + 1)) & 0xFFFFFFFF
 
     def _select(self):
-        _lib.check(self._lib.snac_uct_select(*self._select_args, self.env._stream()))
+        fn = self._lib.snac_uct_select if self.paths == 1 else self._lib.snac_uct_select_paths
+        _lib.check(fn(*self._select_args, self.env._stream()))
 
     def _edges(self):
         env = self.env
@@ -203,13 +237,20 @@ class UCTSearch:
 
     def _evaluate(self):
         env = self.env
-        torch.where(self._expanded.view(torch.bool), self._reward, self._r_leaf, out=self._first)   # the new edge's reward or the stored one
+        if self.paths == 1:
+            torch.where(self._expanded.view(torch.bool), self._reward, self._r_leaf, out=self._first)   # the new edge's reward or the stored one
+        else:                                                        # the expander's edge reward (a fresh leaf: another slot's) or the stored
+            torch.clamp(self._first_slot, min=0, out=self._first_idx)
+            torch.index_select(self._reward, 0, self._first_idx, out=self._first_new)
+            torch.ge(self._first_slot, 0, out=self._first_has)
+            torch.where(self._first_has, self._first_new, self._r_leaf, out=self._first)
         self._est.copy_(self._first)
         _lib.check(self._evaluate_fn(C.byref(env._desc), C.byref(env._state), *self._eval_ptrs, (self._t() + 1) & 0xFFFFFFFF, *self._est_ptrs,
                                      env._stream()))
 
     def _backup(self):
-        _lib.check(self._lib.snac_uct_backup(*self._backup_args, self.env._stream()))
+        fn = self._lib.snac_uct_backup if self.paths == 1 else self._lib.snac_uct_backup_paths
+        _lib.check(fn(*self._backup_args, self.env._stream()))
         self._iteration += 1
 
     @property

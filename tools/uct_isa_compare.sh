@@ -1,0 +1,24 @@
+#!/bin/sh
+# Compare the gfx950 instruction streams of k_uct_select / k_uct_backup / k_uct_advance between two k_uct objects (hipcc -c outputs).
+#   tools/uct_isa_compare.sh OLD.o NEW.o
+# Each object's gfx950 code object is extracted, disassembled, and cut into one listing per kernel symbol with addresses, raw encodings and
+# branch-target comments dropped; the listings of the one-path kernels must be identical.
+set -e
+ROCM=${ROCM_PATH:-/opt/rocm}
+T=$(mktemp -d)
+trap 'rm -rf "$T"' EXIT
+for side in old new; do
+    [ $side = old ] && obj=$1 || obj=$2
+    cp "$obj" "$T/$side.o"
+    "$ROCM"/lib/llvm/bin/llvm-objdump --offloading "$T/$side.o" > /dev/null    # writes $side.o.0.hipv4-amdgcn-amd-amdhsa--gfx950
+    "$ROCM"/lib/llvm/bin/llvm-objdump -d --no-show-raw-insn "$T/$side.o".*gfx950 |
+        awk '/^[0-9a-f]+ <.*>:$/ { keep = ($2 ~ /k_uct_(select|backup|advance)I/); if (keep) print $2; next }
+             keep { sub(/^[ \t]*/, ""); sub(/[ \t]*\/\/.*$/, ""); if ($0 != "" && $0 != "...") print }' > "$T/$side.txt"
+done
+n=$(grep -c '^<' "$T/old.txt")
+if cmp -s "$T/old.txt" "$T/new.txt"; then
+    echo "identical: $n kernels, $(wc -l < "$T/old.txt") lines"
+else
+    diff "$T/old.txt" "$T/new.txt" | head -40
+    exit 1
+fi
