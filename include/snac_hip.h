@@ -567,6 +567,19 @@ int snac_evaluate_nodes2d(const snac_env_desc* desc, const snac_state* st, const
 int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const snac_node3d* nodes, int32_t pool_rows, int32_t m,
                           const int32_t* node_rows, int32_t H, uint32_t t0, const double* gpow, double* est, int64_t* steps, void* stream);
 
+/* The observation rows of node records (what a policy / value network reads of a search's leaves; k_nodes_obs.hip): for i in [0, m),
+ * obs[i] = the canonical row (obs_dim values of desc->obs_dtype) of record node_rows[i] (NULL: record i; clamped into the pool as in
+ * snac_transition_nodes*) -- byte for byte what snac_observe writes for a batch row into which that record was unpacked, for every record,
+ * one with SNAC_FLAG_NEED_RESET included (no reset, no step: the record's own position, grid and counters).  st supplies the plan table
+ * only; the pool is READ ONLY; several i may name one record.  Each entry point accepts its own kind and the canonical layout only
+ * (SNAC_ERR_UNSUPPORTED), with the argument checks of the other node entry points and obs non-null, before any HIP call; m == 0: nothing. */
+int snac_observe_nodes1d(const snac_env_desc* desc, const snac_state* st, const snac_node1d* nodes, int32_t pool_rows, int32_t m,
+                         const int32_t* node_rows, void* obs, void* stream);
+int snac_observe_nodes2d(const snac_env_desc* desc, const snac_state* st, const snac_node2d* nodes, int32_t pool_rows, int32_t m,
+                         const int32_t* node_rows, void* obs, void* stream);
+int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const snac_node3d* nodes, int32_t pool_rows, int32_t m,
+                         const int32_t* node_rows, void* obs, void* stream);
+
 /* ---- UCT tree search over node pools: selection, backup and re-rooting (k_uct.hip).  B independent trees, one path per tree per iteration;
  * tree b owns node rows [b * cap, (b + 1) * cap) of a node pool and of the statistics array below (its root: row b * cap; its j-th
  * allocated node: row b * cap + j), and rows B * cap + b are per-tree scratch rows that never become nodes.  An iteration is
@@ -632,7 +645,32 @@ int snac_evaluate_nodes3d(const snac_env_desc* desc, const snac_state* st, const
  *   backup writes the row.  The one-path entry points and snac_uct_advance neither read nor write these words (advance moves them,
  *   zero, bit for bit).
  *   Checks before any HIP call: those of the one-path entry points with B * (cap + paths) rows; paths >= 1; B * paths within int32;
- *   virtual_loss finite; first_slot non-null. */
+ *   virtual_loss finite; first_slot non-null.
+ * PUCT: a caller's policy / value function in place of UCB1 and the rollout (snac_uct_select_puct / snac_uct_set_priors; UCTSearch(evaluator=)).
+ *   A node carries a prior per action (prior[a], float32, words 48-55).  An iteration is
+ *     snac_uct_select_puct -> snac_transition_nodes* (B * K edges) -> snac_observe_nodes* (the B * K leaves) -> the caller's function:
+ *     priors [B * K][A], value [B * K] -> est[s] = (double)first[s] + (leaf_terminal[s] ? 0 : (double)value[s]), where first[s] =
+ *     first_slot[s] >= 0 ? reward[first_slot[s]] : r_leaf[s] and leaf_terminal[s] = first_slot[s] >= 0 ? done[first_slot[s]] : the leaf's
+ *     stored terminal -> snac_uct_backup_paths (unchanged: an expanded row is written whole, priors zero) -> snac_uct_set_priors on the
+ *     expanded slots' rows.  A root gets its priors when it is made (reset / re-rooting by an untried action).
+ *   snac_uct_select_puct: one entry point for every paths >= 1 (K = 1: every P is 0).  Slots, scratch rows, fresh rows, first_slot, the
+ *   in-flight counts and every output are those of snac_uct_select_paths; it differs only at a non-terminal node n that was not reached
+ *   as a fresh row.  There, in float64, no contraction, in this order, for every action a in [0, num_actions):
+ *         tried (child[a] >= 0):  Np = N_a + P_a;   q = (W_a - virtual_loss * (double)P_a) / (double)Np
+ *         untried:                Np = 0;           q = first_play_value
+ *         e = ((double)prior_n[a] * sqrt_table[N(n) + P(n)]) * inv_table[Np];    U = q + c * e
+ *     (table indices clamped to [0, table_len - 1]; the caller computes sqrt_table[i] = sqrt(max(i, 1)), inv_table[i] = 1 / (1 + i)).
+ *     best = the largest U, ties to the lowest a.  Then:
+ *       - best untried and used[b] < cap: expand best (not the lowest untried action) into row b * cap + used[b], as
+ *         snac_uct_select_paths expands;
+ *       - best untried and the budget spent: best = the largest U over the tried children only (ties to the lowest a); none: stop, leaf = n;
+ *       - best tried: descend, P += 1 as there; arriving at a fresh row stops the path as there.
+ *   Checks before any HIP call: those of snac_uct_select_paths; first_play_value finite.
+ *   snac_uct_set_priors: for i in [0, m), node rows[i] gets prior[a] = priors[i * num_actions + a] (a >= num_actions: 0); with
+ *   only_unvisited != 0 a node whose visits != 0 is left alone; a rows[i] outside [0, stats_rows) is skipped (how a caller masks the
+ *   slots that did not expand: the backup has already counted a visit on every leaf).  One 32-byte span per node; no other word
+ *   changes.  Checks before any HIP call: num_actions 3, 5 or 8; stats non-null and 128-byte aligned; stats_rows >= 1; m >= 0; rows and
+ *   priors non-null.  snac_uct_advance moves the priors of a kept node with it, bit for bit. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -643,9 +681,12 @@ typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all th
     int32_t visits;             /* N */
     double value_sum;           /* W */
     float reward;               /* the edge's transition reward, 0 at a root */
-    int32_t zero[25];           /* in-flight counts during a multi-path iteration (zero[1 + a]: of child[a]; zero[0]: a fresh row's
-                                   expander slot), zero outside one */
+    int32_t zero[25];           /* zero[0 .. 8]: in-flight counts during a multi-path iteration (zero[1 + a]: of child[a]; zero[0]: a fresh
+                                   row's expander slot), zero outside one.  zero[9 + a] (words 48-55 of the record, pieces 12 and 13): the
+                                   PUCT prior of action a as a float32 bit pattern (snac_uct_set_priors; a >= num_actions: 0); the
+                                   rollout search never writes these words: zero there.  zero[17 .. 24]: zero */
 } snac_uct_node;
+#define SNAC_UCT_PRIOR_WORD 48  /* int32 word of prior[0] in a snac_uct_node: ((const float*)node)[SNAC_UCT_PRIOR_WORD + a] */
 int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double c, const double* log_table,
                     const double* rsqrt_table, int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf,
                     uint8_t* expanded, float* r_leaf, void* stream);
@@ -663,6 +704,13 @@ int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t sta
 int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
                           const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
                           const uint8_t* done, const double* est, void* stream);
+
+int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                         double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table, int32_t table_len,
+                         int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                         int32_t* first_slot, void* stream);
+int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                        int32_t only_unvisited, void* stream);
 
 #ifdef __cplusplus
 }

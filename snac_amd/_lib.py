@@ -30,7 +30,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d", "snac_nodes1d_pack", "snac_nodes1d_unpack",
            "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d",
            "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist", "snac_uct_select", "snac_uct_backup",
-           "snac_uct_advance", "snac_uct_select_paths", "snac_uct_backup_paths")
+           "snac_uct_advance", "snac_uct_select_paths", "snac_uct_backup_paths", "snac_observe_nodes1d", "snac_observe_nodes2d",
+           "snac_observe_nodes3d", "snac_uct_select_puct", "snac_uct_set_priors")
 
 
 class Sizes(C.Structure):
@@ -163,6 +164,11 @@ def lib():
         L.snac_uct_select_paths.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, vp, vp, C.c_int32,
                                             vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.snac_uct_backup_paths.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.snac_uct_select_puct.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp,
+                                           C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.snac_uct_set_priors.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
+        for k in ("1d", "2d", "3d"):
+            getattr(L, "snac_observe_nodes%s" % k).argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, vp, vp]
         L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]
         L.snac_traj_alloc_ex.argtypes = [C.c_size_t, C.c_int, C.c_size_t, vp, C.POINTER(vp)]
         L.snac_traj_free.argtypes = [vp]

@@ -1,5 +1,6 @@
 // k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance, and the
-// K-paths-per-tree iteration snac_uct_select_paths / snac_uct_backup_paths (include/snac_hip.h has the semantics)
+// K-paths-per-tree iteration snac_uct_select_paths / snac_uct_backup_paths, and PUCT: snac_uct_select_puct / snac_uct_set_priors
+// (include/snac_hip.h has the semantics)
 #include <cmath>
 #include <cstddef>
 
@@ -491,6 +492,131 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const UctBackPaths w) {
     }
 }
 
+// ---- PUCT: a policy / value network in place of UCB1 and the rollout ----------------------------------------------------------------
+// k_uct_select_paths with another rule at a stored, non-terminal node: every action has a score, tried or not,
+//     U = q + c * ((prior[a] * sqrt_table[N(n) + P(n)]) * inv_table[Np]),   q = (W_a - vl * P_a) / Np tried, first_play_value untried,
+// and the best one is expanded or descended.  The priors are words 48-55 of the record (pieces P_PRIOR ..): two more pieces of line 1,
+// issued with the others before the first is used; the chain of dependent loads per level is the one of k_uct_select_paths.
+constexpr int P_PRIOR = 12;
+
+static_assert(4 * SNAC_UCT_PRIOR_WORD == 16 * P_PRIOR && offsetof(snac_uct_node, zero) + 9 * 4 == 16 * P_PRIOR, "the priors' pieces");
+
+struct UctSelPuct {
+    UctSelPaths p;                                                   // p.s.ltab / p.s.rtab: sqrt_table / inv_table
+    double fpv;
+};
+
+template <int A>
+__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuct z) {
+    constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
+    const UctSelPaths& w = z.p;
+    const UctSel& v = w.s;
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= v.B) return;
+    const int base = b * v.cap, K = w.K;
+    const int used0 = v.used[b];
+    const int fresh = base + used0;                                  // rows from here up are made by this launch
+    int used = used0;
+    for (int k = 0; k < K; ++k) {
+        const int s = b * K + k;
+        int n = base, leaf = base, act = 0, src = base, first = -1, fly = k;   // fly: earlier paths through n
+        bool expanded = false;
+        float r = 0.f;
+        for (int depth = 0; depth < v.cap; ++depth) {
+            const uint4* const rec = v.stats + (size_t)n * PIECES;
+            uint4 pc[CI], pn[CI], pf[CI], pp[CI], pw[CW];
+#pragma unroll
+            for (int q = 0; q < CI; ++q) { pc[q] = rec[P_CHILD + q]; pn[q] = rec[P_VISITS + q]; pf[q] = rec[P_FLY + q]; pp[q] = rec[P_PRIOR + q]; }
+#pragma unroll
+            for (int q = 0; q < CW; ++q) pw[q] = rec[P_VALUE + q];
+            const uint4 hdr = rec[P_HDR], own = rec[P_OWN];
+            leaf = src = n;
+            r = __uint_as_float(own.z);
+            if (hdr.z != 0u) break;                                  // terminal
+            const double sq = v.ltab[min(max((int)hdr.w + fly, 0), v.tlen - 1)];
+            int best = -1, bf = 0, tried = -1, tf = 0, bchild = -1, tchild = -1;
+            double bu = 0.0, tu = 0.0;
+#pragma unroll
+            for (int a = 0; a < A; ++a) {
+                const uint4 c4 = pc[a / 4], n4 = pn[a / 4], f4 = pf[a / 4], p4 = pp[a / 4], w2 = pw[a / 2];
+                const int j = a % 4;
+                const int child = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
+                const int cn = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
+                const int cf = (int)(j == 0 ? f4.x : j == 1 ? f4.y : j == 2 ? f4.z : f4.w);
+                const float pr = __uint_as_float(j == 0 ? p4.x : j == 1 ? p4.y : j == 2 ? p4.z : p4.w);
+                const double cw = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
+                const bool has = child >= 0;
+                double u;
+                {
+#pragma clang fp contract(off)                                      // no fma: U rounded step by step, as a host restatement computes it
+                    const int np = has ? cn + cf : 0;
+                    const double t = w.vl * (double)cf;
+                    const double q = has ? (cw - t) / (double)np : z.fpv;
+                    const double e0 = (double)pr * sq;
+                    const double e = e0 * v.rtab[min(max(np, 0), v.tlen - 1)];
+                    const double ce = v.c * e;
+                    u = q + ce;
+                }
+                if (best < 0 || u > bu) { best = a; bu = u; bf = cf; bchild = child; }
+                if (has && (tried < 0 || u > tu)) { tried = a; tu = u; tf = cf; tchild = child; }
+            }
+            int32_t* const words = reinterpret_cast<int32_t*>(v.stats + (size_t)n * PIECES);
+            if (bchild < 0) {                                        // the best action is untried
+                if (used < v.cap) {                                  // expand it into the tree's next row
+                    const int row = base + used;
+                    used += 1;
+                    words[best] = row;
+                    words[4 * P_FLY + best] = 1;
+                    reinterpret_cast<int32_t*>(v.stats + (size_t)row * PIECES)[39] = s;
+                    leaf = row;
+                    act = best;
+                    expanded = true;
+                    first = s;
+                    break;
+                }
+                if (tried < 0) break;                                // no children and the budget spent
+                best = tried; bf = tf; bchild = tchild;              // the budget spent: the best of the tried children
+            }
+            words[4 * P_FLY + best] = bf + 1;
+            fly = bf;
+            n = clamp_row(bchild, base, v.cap);
+            if (n >= fresh) {                                        // made by an earlier path of this launch: stop on it
+                leaf = n;
+                src = base;                                          // the row is another edge's destination: step the root instead
+                r = 0.f;
+                first = reinterpret_cast<const int32_t*>(v.stats + (size_t)n * PIECES)[39];
+                break;
+            }
+        }
+        v.src[s] = src;
+        v.dst[s] = expanded ? leaf : v.B * v.cap + s;
+        v.action[s] = (int8_t)act;
+        v.leaf[s] = leaf;
+        v.expanded[s] = expanded ? 1 : 0;
+        v.r_leaf[s] = expanded ? 0.f : r;
+        w.first_slot[s] = first;
+    }
+    v.used[b] = used;
+}
+
+// priors into nodes: thread = node, the node's 32-byte span (pieces P_PRIOR, P_PRIOR + 1) as two 16-byte stores; a row outside the
+// array is skipped
+template <int A>
+__global__ __launch_bounds__(256) void k_uct_set_priors(uint4* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                                                        int only_unvisited) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= m) return;
+    const int row = rows[i];
+    if (row < 0 || row >= stats_rows) return;
+    uint4* const rec = stats + (size_t)row * PIECES;
+    if (only_unvisited && rec[P_HDR].w != 0u) return;
+    uint32_t p[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) p[a] = a < A ? __float_as_uint(priors[(size_t)i * A + a]) : 0u;
+    rec[P_PRIOR] = make_uint4(p[0], p[1], p[2], p[3]);
+    rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
+}
+
 int uct_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     using namespace snac_detail;
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
@@ -623,6 +749,48 @@ int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t sta
     });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_backup_paths");
+}
+
+int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                         double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table, int32_t table_len,
+                         int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                         int32_t* first_slot, void* stream) {
+    using namespace snac_detail;
+    if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
+    if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
+    if (!std::isfinite(first_play_value)) return fail(SNAC_ERR_ARG, "first_play_value must be finite");
+    if (!sqrt_table || !inv_table) return fail(SNAC_ERR_ARG, "null sqrt_table / inv_table");
+    if (table_len < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
+    if (!used || !src || !dst || !action || !leaf || !expanded || !r_leaf || !first_slot)
+        return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
+    const UctSelPuct v{{{(uint4*)stats, B, cap, c, sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
+                        paths, virtual_loss, first_slot},
+                       first_play_value};
+    g_kernel = "k_uct_select_puct";
+    by_actions(num_actions, [&](auto k) {
+        hipLaunchKernelGGL((k_uct_select_puct<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_select_puct");
+}
+
+int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                        int32_t only_unvisited, void* stream) {
+    using namespace snac_detail;
+    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
+    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
+    if (stats_rows < 1) return fail(SNAC_ERR_ARG, "stats_rows must be >= 1");
+    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
+    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    if (!rows || !priors) return fail(SNAC_ERR_ARG, "null rows / priors");
+    if (m == 0) return SNAC_OK;
+    g_kernel = "k_uct_set_priors";
+    by_actions(num_actions, [&](auto k) {
+        hipLaunchKernelGGL((k_uct_set_priors<decltype(k)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint4*)stats,
+                           stats_rows, m, rows, priors, only_unvisited != 0 ? 1 : 0);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_set_priors");
 }
 
 }  // extern "C"

@@ -30,7 +30,7 @@ def _ptr(t):
 
 class _NodePool:
     """What the pools of the three kinds share; a subclass names its kind, its record's int32 words and its three entry points."""
-    KIND, WORDS, CANONICAL_OBS, PACK, UNPACK, TRANSITION, EVALUATE = None, None, None, None, None, None, None
+    KIND, WORDS, CANONICAL_OBS, PACK, UNPACK, TRANSITION, EVALUATE, OBSERVE = None, None, None, None, None, None, None, None
 
     def __init__(self, env, rows):
         """env: a BatchedDMPEnv of the pool's kind -- its rules, plan table, observation dtype and device are the pool's; rows: node records."""
@@ -148,6 +148,32 @@ class _NodePool:
                                                        int(t0) & 0xFFFFFFFF, _ptr(gpow), _ptr(est), _ptr(steps), env._stream()))
         return est, steps
 
+    # ---- observation rows of records ---------------------------------------------------------------------------------
+    def observe(self, node_rows=None, out=None, check=True):
+        """The canonical observation rows of records (snac_observe_nodes*): row i = what env.observe() shows for a batch row holding record
+        node_rows[i] (None: record i; m = out's rows, else every record), for every record, a terminal one (NEED_RESET) included.  One
+        launch, the records are not changed, several i may name one record.  out: a contiguous [m, obs_dim] tensor of the env's obs_dtype
+        on its device to write into.  check=False skips the range test of node_rows (a host round trip; the kernel clamps).  Enqueued on
+        the env's stream.  Returns the rows [m, obs_dim]."""
+        env = self.env
+        if node_rows is None:
+            m = self.rows if out is None else int(out.shape[0])
+            ni = self._idx(None, m, self.rows, "node_rows")
+        elif check:
+            m = int(torch.as_tensor(node_rows).numel())
+            ni = self._idx(node_rows, m, self.rows, "node_rows")
+        else:
+            ni = torch.as_tensor(node_rows, device=env.device).reshape(-1).to(torch.int32).contiguous()
+            m = int(ni.numel())
+        if out is None:
+            out = torch.empty((m, env.obs_dim), dtype=env.obs_dtype, device=env.device)
+        elif tuple(out.shape) != (m, env.obs_dim) or out.dtype != env.obs_dtype or out.device != env.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous [%d, %d] %s tensor on %s" % (m, env.obs_dim, env.obs_dtype, env.device))
+        with torch.cuda.device(env.device):
+            _lib.check(getattr(self._lib, self.OBSERVE)(C.byref(env._desc), C.byref(env._state), _ptr(self.records), self.rows, m, _ptr(ni), _ptr(out),
+                                                      env._stream()))
+        return out
+
     # ---- what a search reads of its nodes (decoded from the records: snac_env_hdr) -----------------------------------
     def _hdr16(self):
         return self.records[:, :4].contiguous().view(torch.int16).view(self.rows, 8)
@@ -184,7 +210,7 @@ class NodePool2D(_NodePool):
     """2D node records (snac_node2d: 32 int32 words, one line)."""
     KIND, WORDS, CANONICAL_OBS = 2, 32, 51
     PACK, UNPACK, TRANSITION = "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d"
-    EVALUATE = "snac_evaluate_nodes2d"
+    EVALUATE, OBSERVE = "snac_evaluate_nodes2d", "snac_observe_nodes2d"
 
     @property
     def boards(self):
@@ -196,7 +222,7 @@ class NodePool1D(_NodePool):
     """1D node records (snac_node1d: 32 int32 words, one line)."""
     KIND, WORDS, CANONICAL_OBS = 1, 32, 7
     PACK, UNPACK, TRANSITION = "snac_nodes1d_pack", "snac_nodes1d_unpack", "snac_transition_nodes1d"
-    EVALUATE = "snac_evaluate_nodes1d"
+    EVALUATE, OBSERVE = "snac_evaluate_nodes1d", "snac_observe_nodes1d"
 
     @property
     def heights(self):
@@ -208,7 +234,7 @@ class NodePool3D(_NodePool):
     """3D node records (snac_node3d: 224 int32 words, seven lines)."""
     KIND, WORDS, CANONICAL_OBS = 3, 224, 51
     PACK, UNPACK, TRANSITION = "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d"
-    EVALUATE = "snac_evaluate_nodes3d"
+    EVALUATE, OBSERVE = "snac_evaluate_nodes3d", "snac_observe_nodes3d"
 
     @property
     def heights(self):

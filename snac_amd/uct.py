@@ -1,5 +1,5 @@
 """Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
-snac_uct_select_paths / snac_uct_backup_paths: include/snac_hip.h; snac_amd/csrc/k_uct.hip).
+snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors: include/snac_hip.h; snac_amd/csrc/k_uct.hip).
 
 B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
 stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
@@ -41,6 +41,25 @@ wider than the default 0.0 (virtual visits only) at some cost in search quality:
     search.run(256)                      # 4096 leaf evaluations per tree
     r, d = search.advance(search.best_actions())
 
+A policy / value network in place of the rollout: evaluator=fn makes the search PUCT ("PUCT" in include/snac_hip.h).  Once per iteration
+fn gets the observation rows of the B * K leaves, in slot order, on the env's device with the env's stream current, and returns
+(priors [S, A] probabilities, value [S]); the priors are stored in the expanded nodes as float32 as given (softmax, masking and root noise
+are the caller's: root_priors() / set_root_priors(p)), and first reward + value (0 at a terminal leaf) is backed up in place of a rollout
+estimate.  c is then the PUCT constant, first_play_value the q of an untried action; horizon only spaces the counter words (0 is allowed).
+reset() and advance() call fn on the B roots for the priors of the new roots.
+
+    net = torch.nn.Sequential(torch.nn.Linear(env.obs_dim, 128), torch.nn.ReLU(), torch.nn.Linear(128, env.num_actions + 1)).to(env.device)
+
+    @torch.no_grad()
+    def fn(obs):
+        y = net(obs.to(torch.float32))
+        return torch.softmax(y[:, :-1], 1), torch.tanh(y[:, -1])
+
+    search = UCTSearch(env, nodes_per_tree=512, horizon=0, gamma=0.99, c=1.25, paths=16, evaluator=fn)
+    search.reset()
+    search.run(32)
+    r, d = search.advance(search.best_actions())
+
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
 t0 = it * (H + 1) + 1, so no two iterations share a word (the slot index b * K + k keys the stream, so no two paths do either).  A
 captured graph freezes these arguments: a graph of run(n), replayed after reset(), repeats run(n) exactly; a graph of one iteration
@@ -75,7 +94,18 @@ class UCTSearch:
     search", has the exact selection and backup rules).  paths=K > 1: K paths per tree and iteration with `virtual_loss` per in-flight
     path ("K paths per tree and iteration" there).  Everything is allocated here; run() only enqueues work."""
 
-    def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None, paths=1, virtual_loss=0.0):
+    def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None, paths=1, virtual_loss=0.0,
+                 evaluator=None, first_play_value=None):
+        """evaluator: None (the rollout search) or a callable obs [S, obs_dim] -> (priors [S, A], value [S]) that guides a PUCT search
+        (the module docstring); first_play_value (PUCT only, default 0.0): the q of an untried action."""
+        if evaluator is not None and not callable(evaluator):
+            raise ValueError("evaluator must be callable: obs [S, obs_dim] -> (priors [S, A], value [S])")
+        if first_play_value is not None and evaluator is None:
+            raise ValueError("first_play_value belongs to the PUCT search: give an evaluator")
+        fpv = 0.0 if first_play_value is None else float(first_play_value)
+        if not math.isfinite(fpv):
+            raise ValueError("first_play_value must be finite")
+        self.evaluator, self.first_play_value = evaluator, fpv
         self.env = env
         self.trees = int(env.num_envs if trees is None else trees)
         self.nodes_per_tree, self.horizon, self.gamma, self.c = int(nodes_per_tree), int(horizon), float(gamma), float(c)
@@ -125,7 +155,8 @@ class UCTSearch:
                              _ptr(self._leaf), _ptr(self._expanded), _ptr(self._reward), _ptr(self._done), _ptr(self._est))
         self._transition = getattr(self._lib, P.TRANSITION)
         self._evaluate_fn = getattr(self._lib, P.EVALUATE)
-        if K > 1:                                                    # paths=1 keeps the one-path entry points
+        self._multi = K > 1 or evaluator is not None                 # the rollout search with paths=1 keeps the one-path entry points
+        if self._multi:
             self._first_slot, self._first_idx = slot(torch.int32), slot(torch.int32)
             self._first_new, self._first_has = slot(torch.float32), slot(torch.bool)
             self._select_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, K, self.c, self.virtual_loss, _ptr(self.log_table),
@@ -133,6 +164,25 @@ class UCTSearch:
                                  _ptr(self._action), _ptr(self._leaf), _ptr(self._expanded), _ptr(self._r_leaf), _ptr(self._first_slot))
             self._backup_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, K, self.gamma, _ptr(self._src), _ptr(self._action),
                                  _ptr(self._leaf), _ptr(self._expanded), _ptr(self._reward), _ptr(self._done), _ptr(self._est))
+        if evaluator is not None:                                    # PUCT: priors in the nodes, the evaluator's value in place of a rollout
+            A, n = self.num_actions, self.max_iterations * K + 1
+            self.sqrt_table = torch.tensor([math.sqrt(max(i, 1)) for i in range(n)], dtype=torch.float64, device=dev)
+            self.inv_table = torch.tensor([1.0 / (1 + i) for i in range(n)], dtype=torch.float64, device=dev)
+            self._select_args = (A, _ptr(self.stats), self.rows, B, cap, K, self.c, self.virtual_loss, self.first_play_value,
+                                 _ptr(self.sqrt_table), _ptr(self.inv_table), n, _ptr(self._used), _ptr(self._src), _ptr(self._dst),
+                                 _ptr(self._action), _ptr(self._leaf), _ptr(self._expanded), _ptr(self._r_leaf), _ptr(self._first_slot))
+            self._obs = torch.zeros((S, env.obs_dim), dtype=env.obs_dtype, device=dev)
+            self._root_obs = torch.zeros((B, env.obs_dim), dtype=env.obs_dtype, device=dev)
+            self._priors = torch.zeros((S, A), dtype=torch.float32, device=dev)
+            self._root_priors = torch.zeros((B, A), dtype=torch.float32, device=dev)
+            self._prior_rows, self._none = slot(torch.int32), torch.full((S,), -1, dtype=torch.int32, device=dev)
+            self._term_new, self._term_old, self._term = slot(torch.uint8), slot(torch.int32), slot(torch.bool)
+            self._value, self._zero = slot(torch.float64), slot(torch.float64)
+            self._root_rows = self._roots.to(torch.int32)
+            self._observe = getattr(self._lib, P.OBSERVE)
+            self._obs_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), _ptr(self._obs))
+            self._root_obs_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._root_rows), _ptr(self._root_obs))
+            self._prior_args = (A, _ptr(self.stats), self.rows, S, _ptr(self._prior_rows), _ptr(self._priors), 0)
         self._edge_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._src), _ptr(self._dst))
         self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
         self._eval_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), self.horizon)
@@ -169,6 +219,9 @@ class UCTSearch:
         self.stats[roots, 34] = self.pool.need_reset[roots].to(torch.int32)
         self._used.fill_(1)
         self._iteration = 0
+        if self.evaluator is not None:
+            with torch.cuda.device(env.device):
+                self._prime_roots()
 
     def run(self, iterations):
         """Enqueue `iterations` iterations (select, transition, evaluate, backup; `paths` paths per tree each) on the env's stream; no host
@@ -184,6 +237,8 @@ class UCTSearch:
                 self._edges()
                 self._evaluate()
                 self._backup()
+                if self.evaluator is not None:
+                    self._set_priors()
 
     def advance(self, actions, check=True):
         """Play actions[b] in tree b and re-root it (include/snac_hip.h, "Re-rooting after a move"): a tried action keeps its child's
@@ -209,6 +264,8 @@ class UCTSearch:
             self._adv_action.copy_(a.clamp(0, self.num_actions - 1))
             self._root_edges()
             self._reroot(reward, done)
+            if self.evaluator is not None:                           # the roots made from an untried action are unvisited: they get priors
+                self._prime_roots()
         return reward, done.view(torch.bool)
 
     # the two phases of advance() (tools/uct_advance_time.py times them one by one); the caller holds the env's device
@@ -228,16 +285,18 @@ class UCTSearch:
         return (self._iteration * (self.horizon + 1)) & 0xFFFFFFFF
 
     def _select(self):
-        fn = self._lib.snac_uct_select if self.paths == 1 else self._lib.snac_uct_select_paths
+        if self.evaluator is not None:
+            fn = self._lib.snac_uct_select_puct
+        else:
+            fn = self._lib.snac_uct_select if self.paths == 1 else self._lib.snac_uct_select_paths
         _lib.check(fn(*self._select_args, self.env._stream()))
 
     def _edges(self):
         env = self.env
         _lib.check(self._transition(C.byref(env._desc), C.byref(env._state), *self._edge_ptrs, self._t(), *self._step_ptrs, env._stream()))
 
-    def _evaluate(self):
-        env = self.env
-        if self.paths == 1:
+    def _first_reward(self):
+        if not self._multi:
             torch.where(self._expanded.view(torch.bool), self._reward, self._r_leaf, out=self._first)   # the new edge's reward or the stored one
         else:                                                        # the expander's edge reward (a fresh leaf: another slot's) or the stored
             torch.clamp(self._first_slot, min=0, out=self._first_idx)
@@ -245,13 +304,72 @@ class UCTSearch:
             torch.ge(self._first_slot, 0, out=self._first_has)
             torch.where(self._first_has, self._first_new, self._r_leaf, out=self._first)
         self._est.copy_(self._first)
+
+    def _evaluate(self):
+        env = self.env
+        self._first_reward()
+        if self.evaluator is not None:
+            self._evaluate_leaves()
+            return
         _lib.check(self._evaluate_fn(C.byref(env._desc), C.byref(env._state), *self._eval_ptrs, (self._t() + 1) & 0xFFFFFFFF, *self._est_ptrs,
                                      env._stream()))
 
     def _backup(self):
-        fn = self._lib.snac_uct_backup if self.paths == 1 else self._lib.snac_uct_backup_paths
+        fn = self._lib.snac_uct_backup_paths if self._multi else self._lib.snac_uct_backup
         _lib.check(fn(*self._backup_args, self.env._stream()))
         self._iteration += 1
+
+    # the PUCT phases (tools/uct_puct_time.py times them one by one); the caller holds the env's device
+    def _call(self, obs, rows):
+        """The evaluator on `rows` observation rows: (priors float32 [rows, A] as given, value float64 [rows])."""
+        priors, value = self.evaluator(obs)
+        if tuple(priors.shape) != (rows, self.num_actions) or int(value.numel()) != rows:
+            raise ValueError("the evaluator must return priors [%d, %d] and value [%d]" % (rows, self.num_actions, rows))
+        return priors.to(torch.float32), value.reshape(-1).to(torch.float64)
+
+    def _observe_leaves(self):
+        env = self.env
+        _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), *self._obs_ptrs, env._stream()))
+
+    def _evaluate_leaves(self):
+        """est = first reward + (the leaf terminal ? 0 : the evaluator's value); the leaf's priors wait for the backup."""
+        self._observe_leaves()
+        self._value_leaves()
+
+    def _value_leaves(self):
+        priors, value = self._call(self._obs, self.trees * self.paths)
+        self._priors.copy_(priors)
+        torch.index_select(self._done, 0, self._first_idx, out=self._term_new)       # the expander's done (a fresh leaf: another slot's)
+        torch.index_select(self.stats[:, 34], 0, self._leaf, out=self._term_old)     # else the stored node's terminal
+        torch.where(self._first_has, self._term_new != 0, self._term_old != 0, out=self._term)
+        torch.where(self._term, self._zero, value, out=self._value)
+        self._est.add_(self._value)
+
+    def _set_priors(self):
+        torch.where(self._expanded.view(torch.bool), self._leaf, self._none, out=self._prior_rows)
+        _lib.check(self._lib.snac_uct_set_priors(*self._prior_args, self.env._stream()))
+
+    def _prime_roots(self):
+        """Observe the B roots, call the evaluator, give the unvisited roots their priors (the value of this call is unused)."""
+        env = self.env
+        _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), *self._root_obs_ptrs, env._stream()))
+        priors, _ = self._call(self._root_obs, self.trees)
+        self._root_priors.copy_(priors)
+        _lib.check(self._lib.snac_uct_set_priors(self.num_actions, _ptr(self.stats), self.rows, self.trees, _ptr(self._root_rows),
+                                                 _ptr(self._root_priors), 1, env._stream()))
+
+    def set_root_priors(self, priors):
+        """Root b's priors <- priors[b] ([B, A], stored as float32), whether the root has been visited or not: where a caller mixes
+        exploration noise into the evaluator's root priors (root_priors())."""
+        if self.evaluator is None:
+            raise ValueError("priors belong to the PUCT search: give an evaluator")
+        p = torch.as_tensor(priors, device=self.env.device)
+        if tuple(p.shape) != (self.trees, self.num_actions):
+            raise ValueError("priors must be [%d, %d]" % (self.trees, self.num_actions))
+        with torch.cuda.device(self.env.device):
+            self._root_priors.copy_(p.to(torch.float32))
+            _lib.check(self._lib.snac_uct_set_priors(self.num_actions, _ptr(self.stats), self.rows, self.trees, _ptr(self._root_rows),
+                                                     _ptr(self._root_priors), 0, self.env._stream()))
 
     @property
     def iterations(self):
@@ -269,6 +387,10 @@ class UCTSearch:
         w = r[:, 16:32].contiguous().view(torch.float64)[:, :self.num_actions]
         q = w / r[:, 8:8 + self.num_actions].to(torch.float64)
         return torch.where(r[:, :self.num_actions] >= 0, q, torch.full_like(q, float("nan")))
+
+    def root_priors(self):
+        """[B, A] float32: the priors of each root (zero in a rollout search)."""
+        return self.stats[self._roots][:, 48:48 + self.num_actions].contiguous().view(torch.float32)
 
     def best_actions(self):
         """[B] int64: the most-visited root action, ties to the lowest."""
@@ -306,3 +428,8 @@ class UCTSearch:
     @property
     def reward(self):
         return self.stats[:, 38:39].view(torch.float32)[:, 0]
+
+    @property
+    def prior(self):
+        """[rows, A] float32: the PUCT priors (zero in a rollout search)."""
+        return self.stats[:, 48:48 + self.num_actions].view(torch.float32)

@@ -1,8 +1,9 @@
 #!/bin/sh
-# Compare the gfx950 instruction streams of k_uct_select / k_uct_backup / k_uct_advance between two k_uct objects (hipcc -c outputs).
+# Compare the gfx950 instruction streams of k_uct_select / k_uct_backup / k_uct_advance / k_uct_select_paths / k_uct_backup_paths between
+# two k_uct objects (hipcc -c outputs).
 #   tools/uct_isa_compare.sh OLD.o NEW.o
 # Each object's gfx950 code object is extracted, disassembled, and cut into one listing per kernel symbol with addresses, raw encodings and
-# branch-target comments dropped; the listings of the one-path kernels must be identical.
+# branch-target comments dropped; the listings of these five kernels must be identical.
 set -e
 ROCM=${ROCM_PATH:-/opt/rocm}
 T=$(mktemp -d)
@@ -12,7 +13,7 @@ for side in old new; do
     cp "$obj" "$T/$side.o"
     "$ROCM"/lib/llvm/bin/llvm-objdump --offloading "$T/$side.o" > /dev/null    # writes $side.o.0.hipv4-amdgcn-amd-amdhsa--gfx950
     "$ROCM"/lib/llvm/bin/llvm-objdump -d --no-show-raw-insn "$T/$side.o".*gfx950 |
-        awk '/^[0-9a-f]+ <.*>:$/ { keep = ($2 ~ /k_uct_(select|backup|advance)I/); if (keep) print $2; next }
+        awk '/^[0-9a-f]+ <.*>:$/ { keep = ($2 ~ /k_uct_(select|backup|advance|select_paths|backup_paths)I/); if (keep) print $2; next }
              keep { sub(/^[ \t]*/, ""); sub(/[ \t]*\/\/.*$/, ""); if ($0 != "" && $0 != "...") print }' > "$T/$side.txt"
 done
 n=$(grep -c '^<' "$T/old.txt")
