@@ -1,0 +1,67 @@
+"""AlphaZero-style self-play on the device, end to end: a small MLP guides a PUCT search (UCTSearch(evaluator=)), SelfPlay plays
+episodes with it and records (observation, visit distribution, return) per move, and the MLP is trained on minibatches of the ring --
+cross-entropy to the visit distribution, squared error to the discounted return.  An illustration of the interfaces, not a tuned
+trainer: nothing but the final printout crosses the bus.
+
+    python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20]
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from snac_amd import BatchedDMPEnv, SelfPlay, UCTSearch  # noqa: E402
+
+
+def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1):
+    """`steps` rounds of play(moves) -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the SelfPlay)."""
+    env = BatchedDMPEnv(kind, True, envs, seed=seed)
+    env.reset()
+    A = env.num_actions
+    torch.manual_seed(seed)
+    net = torch.nn.Sequential(torch.nn.Linear(env.obs_dim, hidden), torch.nn.ReLU(), torch.nn.Linear(hidden, A + 1)).to(env.device)
+    opt = torch.optim.Adam(net.parameters(), lr=1e-3)
+
+    @torch.no_grad()
+    def evaluator(obs):                                              # leaves' observation rows -> (priors, value)
+        y = net(obs.to(torch.float32))
+        return torch.softmax(y[:, :A], 1), y[:, A]
+
+    def noise(priors):                                               # exploration at the roots: the caller's (here: a uniform share)
+        return 0.75 * priors + 0.25 / A
+
+    search = UCTSearch(env, nodes, 0, 0.99, c=1.25, paths=paths, evaluator=evaluator, max_iterations=(env.total_step + 1) * iterations)
+    search.reset()
+    play = SelfPlay(search, capacity, sample_moves=8, root_noise=noise)
+    losses = []
+    for _ in range(steps):
+        play.play(moves, iterations)
+        play.targets()
+        b = play.sample(batch)
+        y = net(b["obs"])
+        policy_loss = -(b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1).mean()
+        value_loss = ((y[:, A] - b["z"]) ** 2).mean()
+        loss = policy_loss + value_loss
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+    return [float(x) for x in torch.stack(losses).cpu()], play
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", type=int, default=2)
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=20)
+    args = ap.parse_args()
+    losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps)
+    print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
+    print("loss: first %.4f, last %.4f" % (losses[0], losses[-1]))
+
+
+if __name__ == "__main__":
+    main()

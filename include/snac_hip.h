@@ -56,6 +56,9 @@
  *     and the step size as above.  The uniform table cdf[j] = ceil(65536 * (j+1) / A) draws exactly the actions of the
  *     multiply: floor(u * A / 65536) counts the j >= 1 with u * A >= 65536 * j, i.e. u >= ceil(65536 * j / A).
  *   stream 1 (per env, episode e):  plan_idx = (word * num_plans) >> 32
+ *   stream 2 (per plan row):        the plan generator (snac_make_plans with vertices NULL)
+ *   stream 3 (per env, move t):     the move a self-play search samples from its root's visits (snac_uct_pick_moves):
+ *                                   u = (word * total) >> 32, action = the lowest a with N_0 + ... + N_a > u
  *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.
  */
 #ifndef SNAC_HIP_H
@@ -670,7 +673,36 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *   only_unvisited != 0 a node whose visits != 0 is left alone; a rows[i] outside [0, stats_rows) is skipped (how a caller masks the
  *   slots that did not expand: the backup has already counted a visit on every leaf).  One 32-byte span per node; no other word
  *   changes.  Checks before any HIP call: num_actions 3, 5 or 8; stats non-null and 128-byte aligned; stats_rows >= 1; m >= 0; rows and
- *   priors non-null.  snac_uct_advance moves the priors of a kept node with it, bit for bit. */
+ *   priors non-null.  snac_uct_advance moves the priors of a kept node with it, bit for bit.
+ * Self-play: moves sampled from the visit counts, new episodes in finished trees, value targets (snac_uct_pick_moves / snac_uct_restart /
+ *   snac_uct_returns, k_uct_play.hip; snac_amd/selfplay.py: SelfPlay).  A move of every tree is
+ *     iterations -> snac_observe_nodes* (the B roots) -> snac_uct_pick_moves -> snac_transition_nodes* (the B root edges) -> snac_uct_advance
+ *                -> snac_reset of the finished trees' env rows -> snac_nodes*_pack into the scratch rows -> snac_uct_restart
+ *   on one stream, with no host synchronisation.  All three check every argument before any HIP call.
+ *   snac_uct_pick_moves: one move per tree from its root's statistics.  R = row b * cap, N_a = R.child_visits[a] for a < num_actions (zero
+ *     where untried; a negative word reads as zero), total = the sum of the N_a as an unsigned 64-bit integer.  Outputs, each may be NULL:
+ *       pi[b][a]  = total ? (float)((double)N_a / (double)total) : 0
+ *       value[b]  = R.visits ? (float)(R.value_sum / (double)R.visits) : 0
+ *       action[b] = 0 when total == 0;  the lowest a with the largest N_a when greedy is NULL or greedy[b] != 0;  otherwise proportional to
+ *                   the visits, in integers only: w = word(seed, 3, env_id_base + b, t) of the counter RNG above (desc supplies seed and
+ *                   env_id_base; t is the caller's move counter), u = ((uint64)w * total) >> 32 (in [0, total)), action = the lowest a
+ *                   with N_0 + ... + N_a > u.  An action with N_a = 0 is never drawn; action a is drawn for floor or ceil of
+ *                   2^32 * N_a / total of the 2^32 words.
+ *     No floating point enters the choice.  The statistics are READ ONLY.  With action, pi and value all NULL nothing is launched.
+ *     Checks: desc non-null; num_actions 3, 5 or 8; stats non-null and 128-byte aligned; B >= 1; cap >= 1; B * (cap + 1) within stats_rows
+ *     and int32.
+ *   snac_uct_restart: a new episode in the trees with mask[b] != 0.  The caller has just loaded each tree's new start state into its scratch
+ *     record B * cap + b (the convention of snac_uct_advance for an untried action).  For a masked tree that record goes to row b * cap byte
+ *     for byte; the root's statistics row is written whole (children -1, child visits and values 0, parent -1, action -1, terminal =
+ *     terminal[b] != 0 (terminal NULL: 0), visits 0, W 0, reward 0, every zero[] word 0, the priors included); used[b] = 1.  A tree with
+ *     mask[b] == 0 keeps every byte: statistics, records, used[b].  Rows [b * cap + 1, (b + 1) * cap) of a restarted tree hold unspecified
+ *     contents, as after snac_uct_advance.  Checks: those of snac_uct_advance for stats, records, record_bytes and record_rows; mask and
+ *     used non-null.
+ *   snac_uct_returns: value targets from a ring of cap_moves slots of [B] rewards and dones, for the `count` slots from `first` (the
+ *     oldest) on, modulo cap_moves.  Per tree, from the newest of them back to the oldest, in float64 with no contraction:
+ *       g = (double)bootstrap[b] (bootstrap NULL: 0);  at each slot  g = (double)reward + (done ? 0.0 : gamma * g),  z = (float)g.
+ *     Slots outside the count are not written.  Checks: B >= 1; cap_moves >= 1; B * cap_moves within int32; first in [0, cap_moves); count in
+ *     [0, cap_moves]; gamma finite; reward, done and z non-null.  count == 0: nothing is launched. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -711,6 +743,14 @@ int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stat
                          int32_t* first_slot, void* stream);
 int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
                         int32_t only_unvisited, void* stream);
+
+
+int snac_uct_pick_moves(const snac_env_desc* desc, int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap,
+                        const uint8_t* greedy, uint32_t t, int8_t* action, float* pi, float* value, void* stream);
+int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
+                     int32_t record_rows, const uint8_t* mask, const uint8_t* terminal, int32_t* used, void* stream);
+int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count, double gamma, const float* reward, const uint8_t* done,
+                     const float* bootstrap, float* z, void* stream);
 
 #ifdef __cplusplus
 }

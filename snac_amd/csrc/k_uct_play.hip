@@ -1,0 +1,208 @@
+// k_uct_play.hip -- self-play on the UCT trees of k_uct.hip: snac_uct_pick_moves (a move per tree from the root's visit counts, with the
+// visit distribution and the root value), snac_uct_restart (a new episode in some trees, the others untouched) and snac_uct_returns
+// (value targets from a ring of rewards).  include/snac_hip.h, "Self-play", has the semantics.
+#include <cmath>
+#include <cstddef>
+
+#include "snac_dev.h"
+
+// Three small, latency-bound kernels beside k_uct_advance.  pick and returns are lane = tree: a root is one 128-byte line (two when the
+// value is asked for) and a ring slot is one coalesced span over b.  restart is wave = tree: the record (8 or 56 pieces of 16 bytes) and
+// the statistics row (16 pieces) of a restarted tree leave as one piece per lane.
+namespace {
+
+static_assert(sizeof(snac_uct_node) == 256 && offsetof(snac_uct_node, child_visits) == 32 && offsetof(snac_uct_node, parent) == 128 &&
+                  offsetof(snac_uct_node, value_sum) == 144,
+              "the piece map below");
+
+constexpr int PIECES = 16;                                           // 16-byte pieces per statistics row
+constexpr int P_VISITS = 2, P_HDR = 8, P_OWN = 9;
+constexpr uint32_t PICK_STREAM = 3;                                  // the counter RNG's stream of the sampled moves
+
+struct UctPick {
+    const uint4* stats;
+    int32_t B, cap;
+    uint32_t key, t;
+    int64_t env_id_base;
+    const uint8_t* greedy;
+    int8_t* action;
+    float* pi;
+    float* value;
+};
+
+template <int A>
+__global__ __launch_bounds__(64) void k_uct_pick(const UctPick v) {
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= v.B) return;
+    const uint4* const rec = v.stats + (size_t)b * v.cap * PIECES;
+    const uint4 n0 = rec[P_VISITS], n1 = rec[P_VISITS + 1];
+    uint4 hdr = make_uint4(0u, 0u, 0u, 0u), own = hdr;
+    if (v.value) { hdr = rec[P_HDR]; own = rec[P_OWN]; }             // line 1 only when the value is asked for
+    const uint32_t raw[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    uint32_t n[A];
+    uint64_t total = 0;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        n[a] = (uint32_t)max((int)raw[a], 0);                        // a count is never negative in a tree the search built
+        total += n[a];
+    }
+    if (v.pi) {
+#pragma unroll
+        for (int a = 0; a < A; ++a) v.pi[(size_t)b * A + a] = total ? (float)((double)n[a] / (double)total) : 0.f;
+    }
+    if (v.value) {
+        const int visits = (int)hdr.w;
+        v.value[b] = visits ? (float)(__hiloint2double((int)own.y, (int)own.x) / (double)visits) : 0.f;
+    }
+    if (!v.action) return;
+    int act = 0;
+    if (total != 0) {
+        if (!v.greedy || v.greedy[b] != 0) {                         // the lowest a with the largest count
+            uint32_t best = n[0];
+#pragma unroll
+            for (int a = 1; a < A; ++a)
+                if (n[a] > best) { best = n[a]; act = a; }
+        } else {                                                     // proportional to the counts, in integers
+            const uint32_t w = rng_word(env_keys(v.key, (uint64_t)(v.env_id_base + b)), v.t);
+            // (w * total) >> 32 without leaving 64 bits (total < 2^35)
+            const uint64_t u = (uint64_t)w * (total >> 32) + (((uint64_t)w * (total & 0xFFFFFFFFull)) >> 32);
+            uint64_t cum = 0;
+            bool found = false;
+            act = A - 1;
+#pragma unroll
+            for (int a = 0; a < A; ++a) {                            // the lowest a whose running sum passes u (u < total: there is one)
+                cum += n[a];
+                if (!found && cum > u) { act = a; found = true; }
+            }
+        }
+    }
+    v.action[b] = (int8_t)act;
+}
+
+struct UctRestart {
+    uint4* stats;
+    uint4* records;
+    int32_t B, cap;
+    const uint8_t* mask;
+    const uint8_t* terminal;
+    int32_t* used;
+};
+
+constexpr int RESTART_WAVES = 4;                                     // trees per workgroup
+
+template <int RP>                                                    // 16-byte pieces of a node record (8: 1D / 2D, 56: 3D)
+__global__ __launch_bounds__(64 * RESTART_WAVES) void k_uct_restart(const UctRestart v) {
+    static_assert(RP <= 64, "a record is at most one piece per lane");
+    const int lane = (int)threadIdx.x & 63;
+    const int b = (int)blockIdx.x * RESTART_WAVES + ((int)threadIdx.x >> 6);
+    if (b >= v.B) return;
+    if (v.mask[b] == 0) return;                                      // the tree keeps every byte
+    const size_t root = (size_t)b * v.cap, scratch = (size_t)v.B * v.cap + b;
+    const bool term = v.terminal && v.terminal[b] != 0;
+    if (lane < RP) v.records[root * RP + lane] = v.records[scratch * RP + lane];
+    if (lane < PIECES) {
+        const uint4 none = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu), zero = make_uint4(0u, 0u, 0u, 0u);
+        v.stats[root * PIECES + lane] =
+            lane < P_VISITS ? none : lane == P_HDR ? make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, term ? 1u : 0u, 0u) : zero;
+    }
+    if (lane == 0) v.used[b] = 1;
+}
+
+struct UctReturns {
+    int32_t B, cap_moves, first, count;
+    double gamma;
+    const float* reward;
+    const uint8_t* done;
+    const float* bootstrap;
+    float* z;
+};
+
+__global__ __launch_bounds__(64) void k_uct_returns(const UctReturns v) {
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= v.B) return;
+    double g = v.bootstrap ? (double)v.bootstrap[b] : 0.0;
+    int slot = (int)(((long long)v.first + v.count - 1) % v.cap_moves);
+    for (int i = 0; i < v.count; ++i) {                              // the newest slot back to the oldest
+        const size_t at = (size_t)slot * v.B + b;
+        const double r = (double)v.reward[at];
+        const bool d = v.done[at] != 0;
+        {
+#pragma clang fp contract(off)                                      // no fma: product and sum each rounded, as a host restatement computes them
+            const double t = v.gamma * g;
+            g = r + (d ? 0.0 : t);
+        }
+        v.z[at] = (float)g;
+        slot = slot == 0 ? v.cap_moves - 1 : slot - 1;
+    }
+}
+
+int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
+    using namespace snac_detail;
+    if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
+    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
+    if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
+    if (cap < 1) return fail(SNAC_ERR_ARG, "cap must be >= 1");
+    const long long need = (long long)B * ((long long)cap + 1);
+    if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed int32");
+    if (need > rows) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed stats_rows");
+    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    return SNAC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int snac_uct_pick_moves(const snac_env_desc* desc, int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap,
+                        const uint8_t* greedy, uint32_t t, int8_t* action, float* pi, float* value, void* stream) {
+    using namespace snac_detail;
+    if (!desc) return fail(SNAC_ERR_ARG, "null desc");
+    if (int rc = play_check(num_actions, stats, stats_rows, B, cap)) return rc;
+    if (!action && !pi && !value) return SNAC_OK;                    // nothing asked for
+    const UctPick v{(const uint4*)stats, B, cap, stream_key(desc->seed, PICK_STREAM), t, desc->env_id_base, greedy, action, pi, value};
+    g_kernel = "k_uct_pick";
+    if (num_actions == 3) hipLaunchKernelGGL((k_uct_pick<3>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    else if (num_actions == 5) hipLaunchKernelGGL((k_uct_pick<5>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    else hipLaunchKernelGGL((k_uct_pick<8>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_pick_moves");
+}
+
+int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
+                     int32_t record_rows, const uint8_t* mask, const uint8_t* terminal, int32_t* used, void* stream) {
+    using namespace snac_detail;
+    if (int rc = play_check(num_actions, stats, stats_rows, B, cap)) return rc;
+    if (!records) return fail(SNAC_ERR_ARG, "null records");
+    if (((uintptr_t)records & 127) != 0) return fail(SNAC_ERR_ARG, "records must be 128-byte aligned");
+    if (record_bytes != 128 && record_bytes != 896) return fail(SNAC_ERR_ARG, "record_bytes must be 128 or 896");
+    if ((long long)B * ((long long)cap + 1) > record_rows) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed record_rows");
+    if (!mask) return fail(SNAC_ERR_ARG, "null mask");
+    if (!used) return fail(SNAC_ERR_ARG, "null used");
+    const UctRestart v{(uint4*)stats, (uint4*)records, B, cap, mask, terminal, used};
+    const dim3 grid((unsigned)((B + RESTART_WAVES - 1) / RESTART_WAVES)), block(64 * RESTART_WAVES);
+    g_kernel = "k_uct_restart";
+    if (record_bytes == 128) hipLaunchKernelGGL((k_uct_restart<8>), grid, block, 0, (hipStream_t)stream, v);
+    else hipLaunchKernelGGL((k_uct_restart<56>), grid, block, 0, (hipStream_t)stream, v);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_restart");
+}
+
+int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count, double gamma, const float* reward, const uint8_t* done,
+                     const float* bootstrap, float* z, void* stream) {
+    using namespace snac_detail;
+    if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
+    if (cap_moves < 1) return fail(SNAC_ERR_ARG, "cap_moves must be >= 1");
+    if ((long long)B * (long long)cap_moves > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * cap_moves entries exceed int32");
+    if (first < 0 || first >= cap_moves) return fail(SNAC_ERR_ARG, "first must be in [0, cap_moves)");
+    if (count < 0 || count > cap_moves) return fail(SNAC_ERR_ARG, "count must be in [0, cap_moves]");
+    if (!std::isfinite(gamma)) return fail(SNAC_ERR_ARG, "gamma must be finite");
+    if (!reward || !done || !z) return fail(SNAC_ERR_ARG, "null ring array (reward / done / z)");
+    if (count == 0) return SNAC_OK;                                  // no slot to fill
+    const UctReturns v{B, cap_moves, first, count, gamma, reward, done, bootstrap, z};
+    g_kernel = "k_uct_returns";
+    hipLaunchKernelGGL(k_uct_returns, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_returns");
+}
+
+}  // extern "C"

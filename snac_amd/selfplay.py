@@ -1,0 +1,149 @@
+"""Self-play on the device with a ring of training targets: the search side's counterpart of ReplayRing (snac_uct_pick_moves /
+snac_uct_restart / snac_uct_returns: include/snac_hip.h, "Self-play"; snac_amd/csrc/k_uct_play.hip).
+
+Tree b of a UCTSearch plays env row b.  play(moves, iterations) enqueues, per move and for all B trees at once: the search, the roots'
+observation rows, a move drawn from the root's visit counts (in proportion to them for the first `sample_moves` moves of an episode,
+the most-visited one after that), the re-rooting, and -- for the trees whose episode ended -- a reset of their env rows and a new
+root.  Everything lands in ring slot `head`; nothing crosses the bus and the host never waits:
+
+    env = BatchedDMPEnv(2, True, 64, seed=1); env.reset()
+    search = UCTSearch(env, 2048, 0, 0.99, c=1.25, paths=16, evaluator=fn, max_iterations=(env.total_step + 1) * 32)
+    search.reset()
+    play = SelfPlay(search, capacity_moves=512, sample_moves=10)
+    for step in range(steps):
+        play.play(16, iterations=32)
+        play.targets()                               # z: discounted returns to the end of each episode, bootstrapped at the ring's end
+        batch = play.sample(1024)                    # obs float32, pi, z, value, action, reward, done
+        loss = cross_entropy(policy(batch["obs"]), batch["pi"]) + mse(value(batch["obs"]), batch["z"]); ...
+
+The ring, over moves (slot = move % capacity_moves), every tensor on the env's device:
+    obs [cap, B, D] env.obs_dtype   pi [cap, B, A] float32   value [cap, B] float32   action [cap, B] int8
+    reward [cap, B] float32   done [cap, B] uint8   move [cap, B] int32 (the move's index inside its episode)   z [cap, B] float32
+"""
+import ctypes as C
+
+import torch
+
+from . import _lib
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class SelfPlay:
+    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None):
+        """search: a UCTSearch with one tree per env row (reset() by the caller); capacity_moves: ring slots; sample_moves: the moves of
+        an episode drawn in proportion to the visits (the rest: argmax); gamma: of the value targets (default: the search's);
+        root_noise: PUCT only, priors [B, A] -> priors [B, A], applied to the roots before every move's search (exploration noise is the
+        caller's)."""
+        self.cap, self.sample_moves = int(capacity_moves), int(sample_moves)
+        if self.cap < 1 or self.cap != capacity_moves:
+            raise ValueError("capacity_moves must be an integer >= 1")
+        if self.sample_moves < 0 or self.sample_moves != sample_moves:
+            raise ValueError("sample_moves must be an integer >= 0")
+        if root_noise is not None and not callable(root_noise):
+            raise ValueError("root_noise must be callable: priors [B, A] -> priors [B, A]")
+        if root_noise is not None and search.evaluator is None:
+            raise ValueError("root_noise belongs to the PUCT search: give the search an evaluator")
+        self.gamma = float(search.gamma if gamma is None else gamma)
+        if self.gamma != self.gamma or self.gamma in (float("inf"), float("-inf")):
+            raise ValueError("gamma must be finite")
+        env = search.env
+        if search.trees != env.num_envs:
+            raise ValueError("%d trees, %d env rows: self-play ties tree b to env row b" % (search.trees, env.num_envs))
+        self.search, self.env, self.root_noise = search, env, root_noise
+        B, A, dev = search.trees, search.num_actions, env.device
+        if B * self.cap > 0x7FFFFFFF:
+            raise ValueError("trees * capacity_moves entries exceed int32")
+        cap = self.cap
+        self.obs = torch.zeros((cap, B, env.obs_dim), dtype=env.obs_dtype, device=dev)
+        self.pi = torch.zeros((cap, B, A), dtype=torch.float32, device=dev)
+        self.value, self.reward, self.z = (torch.zeros((cap, B), dtype=torch.float32, device=dev) for _ in range(3))
+        self.action = torch.zeros((cap, B), dtype=torch.int8, device=dev)
+        self.done = torch.zeros((cap, B), dtype=torch.uint8, device=dev)
+        self.move = torch.zeros((cap, B), dtype=torch.int32, device=dev)
+        self.head, self.moves = 0, 0                                 # the next slot; moves played since construction
+        self._move = torch.zeros(B, dtype=torch.int32, device=dev)   # each tree's move inside its episode
+        self._next = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._zero = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._greedy = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self._boot = torch.zeros(B, dtype=torch.float32, device=dev)
+        self._observe = getattr(search._lib, search.pool.OBSERVE)
+        self._root_rows = search._adv_src                            # int32 [B]: row b * cap
+
+    def _check_budget(self, iterations):
+        s = self.search
+        need = (self.env.total_step + 1) * iterations
+        if s.max_iterations < need:
+            raise ValueError("max_iterations = %d is below (total_step + 1) * iterations = %d: a tree is restarted after at most "
+                             "total_step + 1 moves, and its visit counts must stay inside the search's tables" % (s.max_iterations, need))
+
+    def play(self, moves, iterations):
+        """Enqueue `moves` moves of every tree with `iterations` search iterations before each, into the ring; no host synchronisation."""
+        moves, n = int(moves), int(iterations)
+        if moves < 0 or n < 0:
+            raise ValueError("moves and iterations must be >= 0")
+        self._check_budget(n)
+        s, env, P = self.search, self.env, self.search.pool
+        B = s.trees
+        with torch.cuda.device(env.device):
+            for _ in range(moves):
+                h = self.head
+                if self.root_noise is not None:
+                    s.set_root_priors(self.root_noise(s.root_priors()))
+                s._run(n)
+                _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), _ptr(P.records), P.rows, B, _ptr(self._root_rows),
+                                         _ptr(self.obs[h]), env._stream()))
+                torch.ge(self._move, self.sample_moves, out=self._greedy.view(torch.bool))
+                s._pick(self._greedy, self.moves, self.action[h], self.pi[h], self.value[h])
+                s._advance_into(self.action[h], self.reward[h], self.done[h], prime=False)   # restart() primes every unvisited root
+                self.move[h].copy_(self._move)
+                env.reset(mask=self.done[h], want_obs=False)         # the finished trees' env rows: the next episode (and its plan)
+                s.restart(self.done[h])
+                torch.add(self._move, 1, out=self._next)
+                torch.where(self.done[h].view(torch.bool), self._zero, self._next, out=self._move)
+                self.head = (h + 1) % self.cap
+                self.moves += 1
+
+    # ---- the ring ---------------------------------------------------------------------------------------------------------
+    def valid_moves(self):
+        """Slots that hold a move."""
+        return min(self.moves, self.cap)
+
+    def __len__(self):
+        """Number of addressable samples (move, tree)."""
+        return self.valid_moves() * self.search.trees
+
+    def slots(self):
+        """Ring slots that hold a move, oldest first (int64 tensor on the device)."""
+        v = self.valid_moves()
+        return (torch.arange(v, device=self.env.device) + (self.head - v) % self.cap) % self.cap
+
+    def targets(self, bootstrap=True):
+        """Fill z for the valid slots (snac_uct_returns): per tree, from the newest move back, g = reward + (done ? 0 : gamma * g) in
+        float64, z = float32(g).  g starts as the value of the tree's current root (pick_moves' value: W / N, 0 before any iteration)
+        with bootstrap=True -- the episode goes on beyond the ring -- and as 0 with bootstrap=False.  No host synchronisation."""
+        s, env = self.search, self.env
+        v = self.valid_moves()
+        boot = None
+        if bootstrap and v:
+            s._pick(None, 0, None, None, self._boot)
+            boot = self._boot
+        with torch.cuda.device(env.device):
+            _lib.check(s._lib.snac_uct_returns(s.trees, self.cap, (self.head - v) % self.cap, v, self.gamma, _ptr(self.reward), _ptr(self.done),
+                                               _ptr(boot), _ptr(self.z), env._stream()))
+        return self.z
+
+    def sample(self, batch, generator=None):
+        """Uniform minibatch over the valid (move, tree) pairs -> dict on the device: obs float32 [n, D], pi [n, A], z, value, reward
+        float32 [n], action int64 [n], done bool [n].  One flat index and 1-D gathers (ReplayRing.gather has the measurement)."""
+        v = self.valid_moves()
+        if v == 0:
+            raise ValueError("the ring is empty")
+        B, dev = self.search.trees, self.env.device
+        i = torch.randint(0, v * B, (int(batch),), device=dev, generator=generator)
+        flat = (((self.head - v) % self.cap + i // B) % self.cap) * B + i % B
+        return dict(obs=self.obs.view(self.cap * B, -1)[flat].to(torch.float32), pi=self.pi.view(self.cap * B, -1)[flat],
+                    z=self.z.view(-1)[flat], value=self.value.view(-1)[flat], action=self.action.view(-1)[flat].long(),
+                    reward=self.reward.view(-1)[flat], done=self.done.view(-1)[flat].bool())

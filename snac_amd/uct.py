@@ -1,5 +1,6 @@
 """Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
-snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors: include/snac_hip.h; snac_amd/csrc/k_uct.hip).
+snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors, snac_uct_pick_moves / snac_uct_restart:
+include/snac_hip.h; snac_amd/csrc/k_uct.hip, k_uct_play.hip).
 
 B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
 stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
@@ -59,6 +60,18 @@ reset() and advance() call fn on the B roots for the priors of the new roots.
     search.reset()
     search.run(32)
     r, d = search.advance(search.best_actions())
+
+Self-play: pick_moves() draws a move per tree from the root's visit counts (argmax, or in proportion to them: counter-RNG stream 3) and
+gives the visit distribution and the root value, the training targets of the network above; restart(mask) starts a new episode in the
+finished trees and leaves the others alone.  Neither synchronises with the host.  snac_amd/selfplay.py (SelfPlay) is the loop with a
+ring of targets around them:
+
+    r, d = search.advance(search.pick_moves(greedy=False, t=move)[0], check=False)
+    env.reset(mask=d, want_obs=False)    # the finished trees' env rows: the next episode's start state (and plan)
+    search.restart(d)                    # tree b <- env row b where d[b]; every other tree keeps its subtree
+
+    play = SelfPlay(search, capacity_moves=256, sample_moves=10)
+    play.play(64, iterations=32); play.targets(); batch = play.sample(512)      # obs, pi, z, ...
 
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
 t0 = it * (H + 1) + 1, so no two iterations share a word (the slot index b * K + k keys the stream, so no two paths do either).  A
@@ -197,6 +210,15 @@ class UCTSearch:
         self._adv_step_ptrs = (_ptr(self._adv_action), None, None, _ptr(self._adv_reward), _ptr(self._adv_done))
         self._advance_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, _ptr(P.records), P.WORDS * 4, P.rows, _ptr(self._adv_action),
                               _ptr(self._adv_reward), _ptr(self._adv_done), _ptr(self._used), _ptr(self._work))
+        # pick_moves() / restart(): the roots' statistics; the B env rows into the scratch records, then the masked trees' new roots
+        self._pick_args = (C.byref(env._desc), self.num_actions, _ptr(self.stats), self.rows, B, cap)
+        self._sample_all = torch.zeros(B, dtype=torch.uint8, device=dev)     # greedy=False
+        self._rs_mask, self._rs_term = torch.zeros(B, dtype=torch.uint8, device=dev), torch.zeros(B, dtype=torch.uint8, device=dev)
+        self._rs_flags = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._rs_hdr = P.records[B * cap:B * cap + B, 0]             # word 0 of the scratch records: position and flags
+        self._pack = getattr(self._lib, P.PACK)
+        self._restart_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, _ptr(P.records), P.WORDS * 4, P.rows, _ptr(self._rs_mask),
+                              _ptr(self._rs_term), _ptr(self._used))
 
     # ---- the search ---------------------------------------------------------------------------------------------------
     def reset(self, rows=None):
@@ -231,6 +253,10 @@ class UCTSearch:
             raise ValueError("iterations must be >= 0")
         if self._iteration + n > self.max_iterations:
             raise ValueError("%d iterations after %d exceed max_iterations = %d" % (n, self._iteration, self.max_iterations))
+        self._run(n)
+
+    def _run(self, n):
+        """run() without the budget check, for a caller that bounds the visit counts itself (SelfPlay: per episode)."""
         with torch.cuda.device(self.env.device):
             for _ in range(n):
                 self._select()
@@ -260,13 +286,94 @@ class UCTSearch:
             raise ValueError("actions must be in [0, %d)" % self.num_actions)
         reward = torch.empty(B, dtype=torch.float32, device=env.device)
         done = torch.empty(B, dtype=torch.uint8, device=env.device)
-        with torch.cuda.device(env.device):
+        self._advance_into(a, reward, done)
+        return reward, done.view(torch.bool)
+
+    def _advance_into(self, a, reward, done, prime=True):
+        """advance(check=False) of the B integer actions `a` on the device into the caller's reward float32 [B] / done uint8 [B];
+        prime=False leaves the priors of the new roots to a priming that follows (restart())."""
+        with torch.cuda.device(self.env.device):
             self._adv_action.copy_(a.clamp(0, self.num_actions - 1))
             self._root_edges()
             self._reroot(reward, done)
-            if self.evaluator is not None:                           # the roots made from an untried action are unvisited: they get priors
+            if prime and self.evaluator is not None:                 # the roots made from an untried action are unvisited: they get priors
                 self._prime_roots()
-        return reward, done.view(torch.bool)
+
+    # ---- self-play: a move from the visit counts, a new episode in some trees ---------------------------------------------------
+    def pick_moves(self, greedy=None, t=0, out=None):
+        """One move per tree from its root's visit counts (snac_uct_pick_moves; include/snac_hip.h, "Self-play").  greedy: None or True
+        -- the most-visited action, ties to the lowest (best_actions()); False -- drawn in proportion to the visits with the counter
+        RNG's stream 3, keyed by (env_id_base + b, t); a [B] tensor -- per tree (non-zero: greedy).  t: the caller's move counter.  A
+        root without child visits (a terminal root; before any iteration) gives action 0 and pi 0.  out: (action int8 [B], pi float32
+        [B, A], value float32 [B]) contiguous on the env's device to write into.  Enqueued on the env's stream, no host synchronisation.
+        Returns (action, pi: the visit distribution N_a / sum N, value: the root's W / N)."""
+        B, A = self.trees, self.num_actions
+        g = None
+        if torch.is_tensor(greedy) or isinstance(greedy, (list, tuple)):
+            g = greedy if torch.is_tensor(greedy) else torch.as_tensor(greedy)
+            if int(g.numel()) != B:
+                raise ValueError("greedy must have %d entries" % B)
+        elif greedy is not None and not isinstance(greedy, (bool, int)):
+            raise ValueError("greedy must be None, a bool or a [%d] tensor" % B)
+        if out is not None:
+            if len(out) != 3:
+                raise ValueError("out must be (action, pi, value)")
+            for x, shape, dt in zip(out, ((B,), (B, A), (B,)), (torch.int8, torch.float32, torch.float32)):
+                if not torch.is_tensor(x) or tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous():
+                    raise ValueError("out must be contiguous action int8 [%d], pi float32 [%d, %d], value float32 [%d]" % (B, B, A, B))
+        dev = self.env.device
+        if out is None:
+            out = (torch.empty(B, dtype=torch.int8, device=dev), torch.empty((B, A), dtype=torch.float32, device=dev),
+                   torch.empty(B, dtype=torch.float32, device=dev))
+        elif any(x.device != dev for x in out):
+            raise ValueError("out must be on %s" % dev)
+        if g is not None:
+            g = g.to(dev).reshape(-1)
+            if g.dtype != torch.uint8 or not g.is_contiguous():
+                g = (g != 0).to(torch.uint8)
+        elif greedy is not None and not greedy:
+            g = self._sample_all
+        self._pick(g, t, *out)
+        return out
+
+    def _pick(self, greedy, t, action, pi, value):
+        """snac_uct_pick_moves on the env's stream; greedy uint8 [B] on the device or None, each output a tensor or None."""
+        env = self.env
+        with torch.cuda.device(env.device):
+            _lib.check(self._lib.snac_uct_pick_moves(*self._pick_args, None if greedy is None else _ptr(greedy), int(t) & 0xFFFFFFFF,
+                                                     *(None if x is None else _ptr(x) for x in (action, pi, value)), env._stream()))
+
+    def restart(self, mask, rows=None):
+        """A new episode in the trees with mask[b] != 0: env row rows[b] (None: row b) becomes their root exactly as reset() would make
+        it (fresh statistics, one node; a PUCT search primes the new roots with the evaluator's priors); every other tree keeps its
+        statistics, records and size bit for bit (a kept root that has been visited keeps its priors).  All B rows are loaded into the
+        trees' scratch records, then snac_uct_restart moves the masked ones: no host synchronisation, no data-dependent shape (row
+        indices are clamped on the device).  The iteration count is not reset, for advance()'s reasons."""
+        env, B = self.env, self.trees
+        m = mask if torch.is_tensor(mask) else torch.as_tensor(mask)
+        if int(m.numel()) != B:
+            raise ValueError("mask must have %d entries" % B)
+        if rows is None:
+            if B > env.num_envs:
+                raise ValueError("%d trees, %d env rows: give rows" % (B, env.num_envs))
+        else:
+            rows = rows if torch.is_tensor(rows) else torch.as_tensor(rows)
+            if int(rows.numel()) != B:
+                raise ValueError("rows must have %d entries" % B)
+            if rows.is_floating_point() or rows.is_complex() or rows.dtype == torch.bool:
+                raise ValueError("rows must be integers")
+            rows = rows.to(env.device).reshape(-1).to(torch.int32).contiguous()
+        P = self.pool
+        with torch.cuda.device(env.device):
+            torch.ne(m.to(env.device).reshape(-1), 0, out=self._rs_mask.view(torch.bool))
+            _lib.check(self._pack(C.byref(env._desc), C.byref(env._state), None if rows is None else _ptr(rows), B, _ptr(P.records), P.rows,
+                                  _ptr(self._adv_dst), env._stream()))
+            torch.bitwise_right_shift(self._rs_hdr, 16, out=self._rs_flags)          # the loaded records' NEED_RESET
+            self._rs_flags.bitwise_and_(_lib.FLAG_NEED_RESET)
+            self._rs_term.copy_(self._rs_flags)
+            _lib.check(self._lib.snac_uct_restart(*self._restart_args, env._stream()))
+            if self.evaluator is not None:
+                self._prime_roots()
 
     # the two phases of advance() (tools/uct_advance_time.py times them one by one); the caller holds the env's device
     def _root_edges(self):
