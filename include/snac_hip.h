@@ -59,7 +59,9 @@
  *   stream 2 (per plan row):        the plan generator (snac_make_plans with vertices NULL)
  *   stream 3 (per env, move t):     the move a self-play search samples from its root's visits (snac_uct_pick_moves):
  *                                   u = (word * total) >> 32, action = the lowest a with N_0 + ... + N_a > u
- *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.
+ *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.  The node-pool entry points key edge /
+ *   leaf i of a call by env_id_base + i; a search with K paths per tree hands them its B * K slots with env_id_base * K in the descriptor,
+ *   so that slot k of tree b draws with (env_id_base + b) * K + k, its slot in the search over all envs ("K paths per tree" below).
  */
 #ifndef SNAC_HIP_H
 #define SNAC_HIP_H
@@ -622,7 +624,11 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *   Slot s = b * K + k is path k of tree b.  Every per-slot array (src, dst, action, leaf, expanded, r_leaf, reward, done, est,
  *   first_slot) has B * K entries; used keeps B.  The scratch row of slot s is row B * cap + s, so the node pool and the statistics
  *   array need B * (cap + K) rows (snac_uct_advance keeps using scratch row B * cap + b, which lies inside that range; nothing reads a
- *   scratch row across calls).  An iteration is
+ *   scratch row across calls).  Counter words: the transition and evaluation launches of an iteration key slot s by the descriptor's
+ *   env_id_base + s.  The caller passes them a copy of the env's descriptor with env_id_base * K, so that path k of tree b draws with
+ *   (env_id_base + b) * K + k -- the slot of global tree env_id_base + b in one search over all envs -- and a shard of the trees searches
+ *   exactly as the whole does; env_id_base * K and (env_id_base + B) * K - 1 must fit int64.  Everything per tree (snac_uct_advance's
+ *   edge, snac_uct_pick_moves, the env's reset) keeps the env's own env_id_base.  An iteration is
  *     snac_uct_select_paths -> snac_transition_nodes* (B * K edges) -> est[s] = first_slot[s] >= 0 ? reward[first_slot[s]] : r_leaf[s]
  *                           -> snac_evaluate_nodes* (B * K leaves, several slots may name one row) -> snac_uct_backup_paths.
  *   Selection, per tree, paths k = 0 .. K - 1 strictly in that order.  u0 = used[b] on entry; a row >= b * cap + u0 is FRESH (made by

@@ -74,7 +74,12 @@ ring of targets around them:
     play.play(64, iterations=32); play.targets(); batch = play.sample(512)      # obs, pi, z, ...
 
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
-t0 = it * (H + 1) + 1, so no two iterations share a word (the slot index b * K + k keys the stream, so no two paths do either).  A
+t0 = it * (H + 1) + 1, so no two iterations share a word.  Path k of tree b draws both with the key (env_id_base + b) * K + k, its slot
+in the search over ALL envs, so no two paths share a word either and a shard of the trees (env_id_base = E: dist.py) searches exactly as
+the same trees do in one search over the whole batch; the transition and evaluation kernels key edge / leaf s of a call by the
+descriptor's base + s, so the per-iteration launches get a copy of the env's descriptor with env_id_base * K.  What is per tree keeps
+the env's own base: the move's edge of advance() (env_id_base + b, it * (H + 1)), pick_moves() (stream 3, env_id_base + b), restart()
+and env.reset() (stream 1).  A
 captured graph freezes these arguments: a graph of run(n), replayed after reset(), repeats run(n) exactly; a graph of one iteration
 replayed n times would draw iteration 0's words every time.
 """
@@ -137,6 +142,8 @@ class UCTSearch:
             raise ValueError("trees * (nodes_per_tree + %s) rows exceed int32" % ("1" if K == 1 else "paths"))
         if self.max_iterations * K + 1 > 0x7FFFFFFF:
             raise ValueError("max_iterations * paths visits exceed int32")
+        if K > 1 and not -(1 << 63) <= env.env_id_base * K <= (env.env_id_base + B) * K - 1 < 1 << 63:
+            raise ValueError("the slot keys (env_id_base + b) * paths + k exceed int64")
         self.num_actions = env.num_actions
         self.rows = B * (cap + K)                                    # the trees' rows, then a scratch row per slot b * K + k
         S = B * K
@@ -169,6 +176,7 @@ class UCTSearch:
         self._transition = getattr(self._lib, P.TRANSITION)
         self._evaluate_fn = getattr(self._lib, P.EVALUATE)
         self._multi = K > 1 or evaluator is not None                 # the rollout search with paths=1 keeps the one-path entry points
+        self._slot_desc = None if K == 1 else type(env._desc)()      # the per-iteration launches' descriptor (_slots())
         if self._multi:
             self._first_slot, self._first_idx = slot(torch.int32), slot(torch.int32)
             self._first_new, self._first_has = slot(torch.float32), slot(torch.bool)
@@ -398,9 +406,19 @@ class UCTSearch:
             fn = self._lib.snac_uct_select if self.paths == 1 else self._lib.snac_uct_select_paths
         _lib.check(fn(*self._select_args, self.env._stream()))
 
+    def _slots(self):
+        """The descriptor of the launches over the B * K slots: the env's as it is now (set_action_probs() may have changed it), with
+        env_id_base * K for K > 1, so that base + s is (env_id_base + b) * K + k (the module docstring, "Counter words")."""
+        env, d = self.env, self._slot_desc
+        if d is None:
+            return env._desc
+        C.memmove(C.byref(d), C.byref(env._desc), C.sizeof(d))
+        d.env_id_base = env.env_id_base * self.paths
+        return d
+
     def _edges(self):
         env = self.env
-        _lib.check(self._transition(C.byref(env._desc), C.byref(env._state), *self._edge_ptrs, self._t(), *self._step_ptrs, env._stream()))
+        _lib.check(self._transition(C.byref(self._slots()), C.byref(env._state), *self._edge_ptrs, self._t(), *self._step_ptrs, env._stream()))
 
     def _first_reward(self):
         if not self._multi:
@@ -418,7 +436,7 @@ class UCTSearch:
         if self.evaluator is not None:
             self._evaluate_leaves()
             return
-        _lib.check(self._evaluate_fn(C.byref(env._desc), C.byref(env._state), *self._eval_ptrs, (self._t() + 1) & 0xFFFFFFFF, *self._est_ptrs,
+        _lib.check(self._evaluate_fn(C.byref(self._slots()), C.byref(env._state), *self._eval_ptrs, (self._t() + 1) & 0xFFFFFFFF, *self._est_ptrs,
                                      env._stream()))
 
     def _backup(self):

@@ -13,6 +13,10 @@ pytestmark = pytest.mark.gpu
 
 KINDS = [(1, False), (1, True), (2, False), (2, True), (3, False), (3, True)]
 H = {1: 300, 2: 600, 3: 200}
+# a 2D env away from every default: a shard's base, a seed with a high word, the strict termination rules, a short time limit and the 2D
+# action mix of test_search_follows_the_action_distribution (the restatements read env.seed and env.env_id_base)
+NON_DEFAULT_SEED = (9 << 32) | 3
+NON_DEFAULT = dict(env_id_base=1000, brick_gt=True, time_gt=True, total_step=9, action_probs=[1, 3, 0, 2, 2])
 
 
 def _tag(kind, dyn):
@@ -297,3 +301,13 @@ def test_search_follows_the_action_distribution(kind, dyn, probs):
     B = 64
     env = _env(kind, dyn, B, 51 + kind, action_probs=probs)
     _pair(env, B, 32, H[kind] // 2, 48, None)
+
+
+@pytest.mark.parametrize("kind,dyn", [(2, True)])
+def test_search_on_a_non_default_env_equals_the_restatement_bit_for_bit(kind, dyn):
+    """env_id_base 1000, a 64-bit seed, brick_gt / time_gt, total_step 9 and an action distribution: rollouts run into the time limit."""
+    B = 64
+    env = _env(kind, dyn, B, NON_DEFAULT_SEED, **NON_DEFAULT)
+    assert env.env_id_base == 1000 and env.seed >> 32 == 9 and env.total_step == 9 and env.brick_gt and env.time_gt
+    search, ref = _pair(env, B, 32, H[kind] // 2, 48, None, chunks=(17, None))
+    assert (search.tree_sizes().cpu().numpy() > 1).all()

@@ -9,7 +9,7 @@ import pytest
 
 import helpers  # noqa: F401
 import rng_spec
-from test_gpu_uct import H, KINDS, Restatement, _env
+from test_gpu_uct import H, KINDS, NON_DEFAULT, NON_DEFAULT_SEED, Restatement, _env
 
 pytestmark = pytest.mark.gpu
 
@@ -166,6 +166,29 @@ def test_advance_equals_the_restatement_bit_for_bit(kind, dyn):
         tried += int((ch[np.arange(B), a] >= 0).sum())
         _advance(search, ref, a)
     assert untried and tried                                         # untried and tried actions both played
+    _run(search, ref, 25)
+    assert search.iterations == 75
+
+
+@pytest.mark.parametrize("kind,dyn", [(2, True)])
+def test_advance_on_a_non_default_env_equals_the_restatement_bit_for_bit(kind, dyn):
+    """env_id_base 1000, a 64-bit seed, brick_gt / time_gt, total_step 9 and an action distribution: the move's edge is keyed by
+    (1000 + b, it * (H + 1)); after three moves the episodes are a few steps from the time limit."""
+    rng = np.random.default_rng(7)
+    B, cap = 16, 24
+    env = _env(kind, dyn, B, NON_DEFAULT_SEED, **NON_DEFAULT)
+    assert env.env_id_base == 1000 and env.seed >> 32 == 9 and env.total_step == 9 and env.brick_gt and env.time_gt
+    search, ref = _pair(env, B, cap, 90)
+    _run(search, ref, 30)
+    _advance(search, ref, search.best_actions().cpu().numpy())
+    _run(search, ref, 20)
+    untried = tried = 0
+    for _ in range(2):
+        a, ch = _mixed(search, rng)
+        untried += int((ch[np.arange(B), a] < 0).sum())
+        tried += int((ch[np.arange(B), a] >= 0).sum())
+        _advance(search, ref, a)
+    assert untried and tried
     _run(search, ref, 25)
     assert search.iterations == 75
 

@@ -8,15 +8,18 @@ first_slot = the expander's slot, src = the root row), and compares
     Np = N_c + P_c;  q = (W_c - vl * P_c) / Np;  e = L[N(n) + P(n)] * R[Np];  u = q + c * e        (float64, ties to the lowest a);
 with its leaf found, P += 1 on every node of the path.  first_slot is s for an expanded slot and -1 for a stored leaf.  The leaf's
 first reward is reward[first_slot] where first_slot >= 0, else r_leaf; the edges draw counter word it * (H + 1), the leaves
-it * (H + 1) + 1.  Backup, per tree: every expanded row is written, then the walks run in slot order.
+it * (H + 1) + 1, both keyed by the slot of the unsharded search, (env_id_base + b) * K + k.  Backup, per tree: every expanded row is
+written, then the walks run in slot order.
 The restatement runs the same B * K-edge pool.transition and B * K-leaf pool.evaluate calls on a second pool of the same env.  Every
 statistic (W as raw float64 bytes), every tree size, every node and scratch record and the last launch's select outputs must be equal."""
+import contextlib
 import math
 
 import numpy as np
 import pytest
 
 import helpers
+from test_gpu_uct import NON_DEFAULT, NON_DEFAULT_SEED
 
 pytestmark = pytest.mark.gpu
 
@@ -67,6 +70,17 @@ class Restatement:
         self.it = 0
         self.last = None                                             # the last launch's select outputs
         self.fresh_hits = []                                         # per iteration: slots that stopped on a fresh row
+
+    @contextlib.contextmanager
+    def slot_keys(self):
+        """The pool calls key edge / leaf s of a call by env_id_base + s; an iteration's words are keyed by (env_id_base + b) * K + k, the
+        slot in the unsharded search, which is (env_id_base * K) + s: the calls inside run on the descriptor with that base."""
+        desc = self.env._desc
+        desc.env_id_base = self.env.env_id_base * self.K
+        try:
+            yield
+        finally:
+            desc.env_id_base = self.env.env_id_base
 
     def _select_tree(self, b):
         base, cap, K = b * self.cap, self.cap, self.K
@@ -126,10 +140,11 @@ class Restatement:
         self.fresh_hits.append((~exp) & (first >= 0))
         assert not np.isin(src, dst).any()                           # no edge's source is an edge's destination
         t = self.it * (self.H + 1)
-        _, rew, done = self.pool.transition(torch.as_tensor(act.astype(np.int8)), src=src, dst=dst, t=t, want_obs=False)
-        rew, done = rew.cpu().numpy(), done.cpu().numpy()
-        first_r = np.where(first >= 0, rew[np.maximum(first, 0)], rleaf.astype(np.float32)).astype(np.float64)
-        est, _ = self.pool.evaluate(torch.as_tensor(leaf), self.H, self.gamma, first_reward=torch.as_tensor(first_r), t0=t + 1)
+        with self.slot_keys():
+            _, rew, done = self.pool.transition(torch.as_tensor(act.astype(np.int8)), src=src, dst=dst, t=t, want_obs=False)
+            rew, done = rew.cpu().numpy(), done.cpu().numpy()
+            first_r = np.where(first >= 0, rew[np.maximum(first, 0)], rleaf.astype(np.float32)).astype(np.float64)
+            est, _ = self.pool.evaluate(torch.as_tensor(leaf), self.H, self.gamma, first_reward=torch.as_tensor(first_r), t0=t + 1)
         est = est.cpu().numpy()
         for s in np.nonzero(exp)[0]:                                 # first every expanded row, whole
             x = int(leaf[s])
@@ -534,3 +549,14 @@ def test_multi_path_search_follows_the_action_distribution(kind, dyn, probs):
     B = 16
     env = _env(kind, dyn, B, 51 + kind, action_probs=probs)
     _pair(env, B, 32, 4, VL, H[kind] // 4, 12)
+
+
+@pytest.mark.parametrize("kind,dyn,K", [(2, True, 4)])
+def test_multi_path_search_on_a_non_default_env_equals_the_restatement_bit_for_bit(kind, dyn, K):
+    """env_id_base 1000, a 64-bit seed, brick_gt / time_gt, total_step 9 and an action distribution: the slots' keys start at 1000 * K."""
+    B = 16
+    env = _env(kind, dyn, B, NON_DEFAULT_SEED, **NON_DEFAULT)
+    assert env.env_id_base == 1000 and env.seed >> 32 == 9 and env.total_step == 9 and env.brick_gt and env.time_gt
+    search, ref = _pair(env, B, 32, K, VL, H[kind] // 4, 12, chunks=(5, None))
+    assert (search.tree_sizes().cpu().numpy() > 1).all()
+    assert env._desc.env_id_base == 1000                             # the restatement left the descriptor as it was

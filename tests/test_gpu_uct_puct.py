@@ -16,6 +16,7 @@ import math
 import numpy as np
 import pytest
 
+from test_gpu_uct import NON_DEFAULT, NON_DEFAULT_SEED
 from test_gpu_uct_paths import H, KINDS, Restatement, _env, _outputs, _subtree
 
 pytestmark = pytest.mark.gpu
@@ -134,7 +135,8 @@ class PuctRestatement(Restatement):
         self.fresh_hits.append((~exp) & (first >= 0))
         assert not np.isin(src, dst).any()
         t = self.it * (self.H + 1)
-        _, rew, done = self.pool.transition(torch.as_tensor(act.astype(np.int8)), src=src, dst=dst, t=t, want_obs=False)
+        with self.slot_keys():
+            _, rew, done = self.pool.transition(torch.as_tensor(act.astype(np.int8)), src=src, dst=dst, t=t, want_obs=False)
         rew, done = rew.cpu().numpy(), done.cpu().numpy()
         first_r = np.where(first >= 0, rew[np.maximum(first, 0)], rleaf.astype(np.float32)).astype(np.float64)
         leaf_term = np.where(first >= 0, done[np.maximum(first, 0)], self.terminal[leaf])
@@ -546,3 +548,13 @@ def test_a_torch_network_guides_the_search(kind, dyn, K):
     assert (pr >= 0).all() and np.abs(pr.sum(1) - 1.0).max() <= 4 * A * 2.0 ** -24          # the float32 softmax's own rounding
     assert not search.stats[torch.as_tensor(live, device=env.device), 39:48].any()
     assert np.isfinite(search.value_sum.cpu().numpy()).all() and (sizes > 1).all()
+
+
+@pytest.mark.parametrize("kind,dyn,K", [(2, True, 5)])
+def test_puct_search_on_a_non_default_env_equals_the_restatement_bit_for_bit(kind, dyn, K):
+    """env_id_base 1000, a 64-bit seed, brick_gt / time_gt, total_step 9 and an action distribution: the slots' keys start at 1000 * K."""
+    B, cap, its = 12, 40, 10
+    env = _env(kind, dyn, B, NON_DEFAULT_SEED, **NON_DEFAULT)
+    assert env.env_id_base == 1000 and env.seed >> 32 == 9 and env.total_step == 9 and env.brick_gt and env.time_gt
+    search, ref = _pair(env, B, cap, K, VL, make_evaluator(env.num_actions, False), its, horizon=3, chunks=(its // 3, None))
+    assert (search.tree_sizes().cpu().numpy() > 1).all()

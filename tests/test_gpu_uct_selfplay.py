@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import rng_spec
+from test_gpu_uct import NON_DEFAULT, NON_DEFAULT_SEED
 from test_gpu_uct_paths import H, KINDS, Restatement, _env
 from test_gpu_uct_paths import _same as _same_rollout
 from test_gpu_uct_puct import C as CPUCT
@@ -83,12 +84,12 @@ def returns(reward, done, first, count, gamma, bootstrap, z):
     return z
 
 
-def _pair(kind, dyn, B, seed, cap, K, puct, budget, fpv=None, prep=None, twin=False):
+def _pair(kind, dyn, B, seed, cap, K, puct, budget, fpv=None, prep=None, twin=False, **env_kw):
     """(search, ref, env): a device search after reset() and its restatement; twin: the restatement on a second env made the same way
     (a whole play() resets env rows, and the restatement follows move by move afterwards)."""
     from snac_amd import UCTSearch
 
-    envs = [_env(kind, dyn, B, seed) for _ in range(2 if twin else 1)]
+    envs = [_env(kind, dyn, B, seed, **env_kw) for _ in range(2 if twin else 1)]
     for e in envs:
         if prep is not None:
             prep(e)
@@ -110,13 +111,14 @@ def _same(search, ref, live_only=False):
     (_same_puct if search.evaluator is not None else _same_rollout)(search, ref, live_only=live_only)
 
 
-def _near_the_end(kind, dyn, terminal_roots=False):
-    """count_step of rows 0::3 / 1::3 one / three steps before the time limit: their episodes end at the first / third move."""
+def _near_the_end(kind, dyn, terminal_roots=False, total_step=None):
+    """count_step of rows 0::3 / 1::3 one / three steps before the time limit (total_step: the env's own, where it is not the kind's):
+    their episodes end at the first / third move, one move later under time_gt."""
     import torch
 
     from snac_amd import _lib
 
-    ts = _lib.env_sizes(kind, dyn).total_step
+    ts = _lib.env_sizes(kind, dyn).total_step if total_step is None else total_step
 
     def prep(env):
         B = env.num_envs
@@ -251,16 +253,15 @@ def test_restart_with_a_mixed_mask(kind, dyn, K, puct):
 
 
 # ---- 3. the whole loop ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("puct", [False, True])
-@pytest.mark.parametrize("kind,dyn", [(1, False), (2, True), (3, True)])
-def test_play_equals_the_restatement_move_by_move(kind, dyn, puct):
+def _play_move_by_move(kind, dyn, puct, seed, **env_kw):
     import torch
 
     from snac_amd import SelfPlay, _lib
 
     B, cap, K, its, moves, slots, sample_moves = 12, 48, 3, 4, 7, 5, 2
     ts = _lib.env_sizes(kind, dyn).total_step
-    search, ref, env = _pair(kind, dyn, B, 37 + kind, cap, K, puct, (ts + 1) * its, prep=_near_the_end(kind, dyn), twin=True)
+    prep = _near_the_end(kind, dyn, total_step=env_kw.get("total_step"))
+    search, ref, env = _pair(kind, dyn, B, seed, cap, K, puct, (ts + 1) * its, prep=prep, twin=True, **env_kw)
     renv, A = ref.env, env.num_actions
     play = SelfPlay(search, slots, sample_moves=sample_moves)
     play.play(3, its)
@@ -305,6 +306,19 @@ def test_play_equals_the_restatement_move_by_move(kind, dyn, puct):
         plan = rng_spec.plan_of(rng_spec.words(env.seed, rng_spec.STREAM_PLAN, ids, episode.astype(np.uint64)), env.num_plans)
         got = search.pool.plan_idx[roots].cpu().numpy()
         assert np.array_equal(got[restarts > 0], plan[restarts > 0])
+
+
+@pytest.mark.parametrize("puct", [False, True])
+@pytest.mark.parametrize("kind,dyn", [(1, False), (2, True), (3, True)])
+def test_play_equals_the_restatement_move_by_move(kind, dyn, puct):
+    _play_move_by_move(kind, dyn, puct, 37 + kind)
+
+
+@pytest.mark.parametrize("kind,dyn,puct", [(2, True, True)])
+def test_play_on_a_non_default_env_equals_the_restatement_move_by_move(kind, dyn, puct):
+    """env_id_base 1000, a 64-bit seed, brick_gt / time_gt, total_step 9 and an action distribution: sampled moves and the restarted trees'
+    plans are keyed by 1000 + b, the slots of the K = 3 paths from 1000 * K."""
+    _play_move_by_move(kind, dyn, puct, NON_DEFAULT_SEED, **NON_DEFAULT)
 
 
 def test_play_with_root_noise_and_a_sample():

@@ -83,3 +83,30 @@ def test_uctsearch_rejects_bad_path_arguments_before_allocating(kw):
     args.update(kw)
     with pytest.raises(ValueError):
         UCTSearch(_NoDevice(), **args)
+
+
+class _Sharded(_NoDevice):
+    """_NoDevice with a shard's base: the one attribute the key check reads."""
+
+    def __init__(self, env_id_base):
+        self.env_id_base = env_id_base
+
+
+@pytest.mark.parametrize("base,K", [(1 << 62, 2), (1 << 61, 4), ((1 << 63) // 3, 3), ((1 << 62) - 3, 2), (-(1 << 62) - 1, 2), (-(1 << 61) - 1, 4)])
+def test_uctsearch_rejects_a_base_whose_slot_keys_leave_int64(base, K):
+    """Slot k of tree b draws with key (env_id_base + b) * K + k; with trees = 4 the keys span [base * K, (base + 4) * K)."""
+    from snac_amd import UCTSearch
+
+    assert not -(1 << 63) <= base * K <= (base + 4) * K - 1 < 1 << 63
+    with pytest.raises(ValueError, match="int64"):
+        UCTSearch(_Sharded(base), nodes_per_tree=16, horizon=10, gamma=0.9, paths=K)
+
+
+@pytest.mark.parametrize("base,K", [((1 << 62) - 4, 2), (-(1 << 62), 2), (1000, 16), ((1 << 63) - 5, 1)])
+def test_uctsearch_accepts_a_base_whose_slot_keys_fit_int64(base, K):
+    """The key check passes: the constructor goes on to the env's first real attribute, which _NoDevice answers with an AssertionError."""
+    from snac_amd import UCTSearch
+
+    assert K == 1 or -(1 << 63) <= base * K <= (base + 4) * K - 1 < 1 << 63
+    with pytest.raises(AssertionError, match="num_actions"):
+        UCTSearch(_Sharded(base), nodes_per_tree=16, horizon=10, gamma=0.9, paths=K)
