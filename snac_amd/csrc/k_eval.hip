@@ -1,7 +1,5 @@
 // k_eval.hip -- default-policy evaluation of tree leaves IN PLACE on node pools: snac_evaluate_nodes{1,2,3}d
-#include <cstddef>
-
-#include "snac_dev.h"
+#include "nodes_dev.h"
 
 // The "Evaluation" block of the vanilla MCTS procedure (script/MCTS/utils/mcts.py:100-110): from every new leaf, uniformly random steps
 // until `done` or the horizon, `estimate += reward * gamma**t`.  On batch rows that is BatchedDMPEnv.evaluate: a fork of the leaves
@@ -16,8 +14,6 @@
 //   epilogue  est and steps, one store each per leaf
 // The pool is read only: no record changes, no auto-reset, no episodic sums.
 namespace {
-
-constexpr int N1_PIECES = 8, N2_PIECES = 8, N3_PIECES = 56;           // 16-byte pieces per snac_node1d / snac_node2d / snac_node3d
 
 struct EvalArgs {
     const uint4* nodes;        // the pool's records
@@ -36,15 +32,15 @@ __device__ __forceinline__ void load_image(uint32_t* lds, const KArgs& a, const 
     constexpr int E = K::E;
     if constexpr (K::A == 3) {                                       // 1D: word e * 17 + j holds cells 2j - 2, 2j - 1 (frame: words 0, 16)
         if (!active) return;
-        uint4 c[4], p[4];
+        uint4 c[GRID_PIECES_1D], p[GRID_PIECES_1D];
         const uint4* const prow = (const uint4*)((const int16_t*)a.plans + (size_t)pidx * K::GE);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { c[q] = v.nodes[(size_t)row * N1_PIECES + 2 + q]; p[q] = prow[q]; }
+        for (int q = 0; q < GRID_PIECES_1D; ++q) { c[q] = v.nodes[(size_t)row * LINE_PIECES + REC_GRID_PIECE + q]; p[q] = prow[q]; }
         uint32_t* const h = lds + lane * (K::ES / 2);
         uint32_t* const pl = lds + K::P_OFF + lane * (K::ES / 2);
         h[0] = 0xFFFFFFFFu; h[16] = 0xFFFFFFFFu;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < GRID_PIECES_1D; ++q) {
             const uint32_t cw[4] = {c[q].x, c[q].y, c[q].z, c[q].w}, pw[4] = {p[q].x, p[q].y, p[q].z, p[q].w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -54,15 +50,15 @@ __device__ __forceinline__ void load_image(uint32_t* lds, const KArgs& a, const 
         }
     } else if constexpr (K::A == 5) {                                // 2D: C[(q + 3) * RS + e] = record row word q encoded, rows 0-2 / 23-25 frame
         if (!active) return;
-        uint4 b[5], p[5];
+        uint4 b[GRID_PIECES_2D], p[GRID_PIECES_2D];
         const uint4* const prow = (const uint4*)((const uint32_t*)a.plans + (size_t)pidx * K::GE);
 #pragma unroll
-        for (int q = 0; q < 5; ++q) { b[q] = v.nodes[(size_t)row * N2_PIECES + 2 + q]; p[q] = prow[q]; }
+        for (int q = 0; q < GRID_PIECES_2D; ++q) { b[q] = v.nodes[(size_t)row * LINE_PIECES + REC_GRID_PIECE + q]; p[q] = prow[q]; }
         uint64_t* const c = K::cells(lds) + lane;
 #pragma unroll
         for (int q = 0; q < 3; ++q) { c[q * K::RS] = 0x000FFFFFFFFFFFFFull; c[(23 + q) * K::RS] = 0x000FFFFFFFFFFFFFull; }
 #pragma unroll
-        for (int q = 0; q < 5; ++q) {
+        for (int q = 0; q < GRID_PIECES_2D; ++q) {
             const uint32_t bw[4] = {b[q].x, b[q].y, b[q].z, b[q].w}, pw[4] = {p[q].x, p[q].y, p[q].z, p[q].w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -74,14 +70,14 @@ __device__ __forceinline__ void load_image(uint32_t* lds, const KArgs& a, const 
         static_assert((E * K::ES / 2) % 4 == 0, "the image is whole 16-byte pieces");
         for (int i = lane; i < E * K::ES / 8; i += 64) ((uint4*)lds)[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
         int16_t* const h = K::hmap(lds);
-        constexpr int HP = K::GE / 8, R = 13;                        // 50 pieces of 8 cells per leaf; loads per lane per round
+        constexpr int HP = GRID_PIECES_3D, R = 13;                   // 50 pieces of 8 cells per leaf; loads per lane per round
         for (int i0 = 0; i0 < nleaf * HP; i0 += 64 * R) {
             uint4 w[R];
 #pragma unroll
             for (int u = 0; u < R; ++u) {
                 const int i = i0 + u * 64 + lane, e = min(i / HP, nleaf - 1), p = i - e * HP;
                 const int re = __shfl(row, e);
-                w[u] = i < nleaf * HP ? v.nodes[(size_t)re * N3_PIECES + 2 + p] : make_uint4(0u, 0u, 0u, 0u);
+                w[u] = i < nleaf * HP ? v.nodes[(size_t)re * REC3_PIECES + REC_GRID_PIECE + p] : make_uint4(0u, 0u, 0u, 0u);
             }
 #pragma unroll
             for (int u = 0; u < R; ++u) {
@@ -176,13 +172,13 @@ int evaluate_nodes(int kind, const char* name, const snac_env_desc* d, const sna
     g_kernel = "k_eval";
     if (kind == SNAC_ENV_1D) {
         const int E = tune(TN_EVAL_E);
-        dyn ? launch_kind<K1D, true, N1_PIECES>(E, a, v, s) : launch_kind<K1D, false, N1_PIECES>(E, a, v, s);
+        dyn ? launch_kind<K1D, true, LINE_PIECES>(E, a, v, s) : launch_kind<K1D, false, LINE_PIECES>(E, a, v, s);
     } else if (kind == SNAC_ENV_2D) {
         const int E = tune(TN_EVAL_E);
-        dyn ? launch_kind<K2D, true, N2_PIECES>(E, a, v, s) : launch_kind<K2D, false, N2_PIECES>(E, a, v, s);
+        dyn ? launch_kind<K2D, true, LINE_PIECES>(E, a, v, s) : launch_kind<K2D, false, LINE_PIECES>(E, a, v, s);
     } else {
         const int E = tune(TN_EVAL3D_E);
-        dyn ? launch_kind<K3D, true, N3_PIECES>(E, a, v, s) : launch_kind<K3D, false, N3_PIECES>(E, a, v, s);
+        dyn ? launch_kind<K3D, true, REC3_PIECES>(E, a, v, s) : launch_kind<K3D, false, REC3_PIECES>(E, a, v, s);
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, name);

@@ -16,8 +16,9 @@
 //   k_step3dq.hip   k_step3dq     the canonical 3D snac_step: 16 envs per wave, four lanes per env
 //   k_step1d.hip    k_step1d, k_edges1d   the 1D snac_step (canonical rows and the layout variants) and 1D tree edges
 //   k_reset.hip     k_reset, k_iou        whole-batch resets without reading the old state; snac_iou lane-per-env
-//   k_nodes2d.hip   k_edges2dp    2D tree edges on node pools of one 128-byte record per node
-//   k_nodes.hip     k_edges1dp, k_edges3dp   1D / 3D tree edges on node pools (one line / seven whole lines per node), k_nodes_copy
+//   k_nodes.hip     k_edges1dp / 2dp / 3dp   tree edges on node pools of one record per node (one 128-byte line, 3D: seven), k_nodes_copy
+//   k_nodes_obs.hip k_observe1dp / 2dp / 3dp   the observation rows of node records
+//                   (nodes_dev.h: the record's map, its trip through LDS and the window decoders, for these two and k_eval.hip)
 //   k_eval.hip      k_eval        default-policy evaluation of tree leaves in place on node pools: lane = leaf, the rollout and the sum fused
 //   k_mailbox.hip   k_mailbox     the resident stepper behind the drop-in classes (mailbox_host.h: the host half of its protocol)
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows

@@ -1,4 +1,4 @@
-"""2D tree-search node pools with ONE record per node (snac_node2d, include/snac_hip.h; snac_amd/csrc/k_nodes2d.hip).
+"""2D tree-search node pools with ONE record per node (snac_node2d, include/snac_hip.h; snac_amd/csrc/k_nodes.hip; the record's map: snac_amd/csrc/nodes_dev.h).
 
 `BatchedDMPEnv.transition()` uses the batch itself as the node pool: a tree edge then reads its parent's header, episode counter and
 board from three arrays at a random row -- three lines of memory for 100 bytes.  A NodePool2D keeps the three in one 128-byte record,

@@ -1,7 +1,7 @@
 """GPU: 1D and 3D node pools with one record per node (snac_nodes{1,3}d_pack / _unpack, snac_transition_nodes{1,3}d, snac_amd.NodePool1D /
 NodePool3D / NodePool) against the batch-layout path (snac_transition on a BatchedDMPEnv pool -- itself oracle-checked in
 tests/test_gpu_mcts.py) AND against the CPU oracle directly: search-shaped waves on all three, every wave's rows, rewards and done flags
-equal to the byte, the states equal afterwards."""
+equal to the byte, the states equal afterwards.  The head / tail seam of a wave is pinned for all three kinds (2D included)."""
 import ctypes as C
 
 import numpy as np
@@ -12,12 +12,12 @@ import helpers
 pytestmark = pytest.mark.gpu
 
 KINDS = [(1, False), (1, True), (3, False), (3, True)]
-GRID_BYTES = {1: 64, 3: 800}
-GRID_WORDS = {1: (8, 24), 3: (8, 208)}                              # the cells' int32 words in a record
+GRID_BYTES = {1: 64, 2: 80, 3: 800}
+GRID_WORDS = {1: (8, 24), 2: (8, 28), 3: (8, 208)}                  # the cells' int32 words in a record
 
 
 def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
+    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p1" if kind == 3 else "p0")
 
 
 def _pools(kind, dyn, pool, seed, dtype=None, oracle=True):
@@ -128,6 +128,35 @@ def test_edges_on_node_records_equal_the_batch_pool_and_the_oracle(kind, dyn, f3
     nodes.store()
     _same_state(env, orc)
     assert torch.equal(env._hdr, twin._hdr) and torch.equal(env._grid, twin._grid) and torch.equal(env.observe(), twin.observe())
+
+
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("dyn", [False, True])
+@pytest.mark.parametrize("kind", [1, 2, 3])
+def test_head_and_tail_launches_of_a_wave_equal_the_batch_pool(kind, dyn, f32):
+    """The seam between the head of a wave (m & ~3 edges, rows as 16-byte pieces) and its tail (the last one to three, value by value, a
+    launch of its own) for all three kinds: an empty head (3), an exact head (4), a head with a tail (7), a tail in the second wave
+    (67) and in the third (131) of the one block.  step_size=None: the step size comes from the counter RNG, keyed by the edge's index
+    in the CALL, so a tail launch that forgot its offset would draw other sizes.  The batch-row kernels are the reference: rows,
+    rewards, done flags and the written records equal to the byte."""
+    import torch
+
+    pool, used = 320, 100
+    env, twin, orc, nodes, torch = _pools(kind, dyn, pool, 17, torch.float32 if f32 else None, oracle=False)
+    rng = np.random.default_rng(40 + kind)
+    for t, m in enumerate((3, 4, 7, 67, 131), start=5):
+        src = rng.integers(0, used, m).astype(np.int32)
+        dst = (used + np.arange(m)).astype(np.int32)
+        acts = rng.integers(0, env.num_actions, m).astype(np.int8)
+        o1, r1, d1 = nodes.transition(acts, None, src=src, dst=dst, t=t)
+        assert env._lib.snac_last_kernel() == b"k_edges%ddp" % kind
+        o2, r2, d2 = twin.transition(torch.from_numpy(acts), None, src=src, dst=dst, t=t)
+        assert o1.dtype == o2.dtype and torch.equal(o1.contiguous().view(torch.uint8), o2.contiguous().view(torch.uint8)), (t, m)
+        assert torch.equal(r1, r2) and torch.equal(d1, d2), (t, m)
+        _same_records(nodes, twin, dst.astype(np.int64))
+        used += m
+    assert used <= pool
+    _same_records(nodes, twin)
 
 
 @pytest.mark.parametrize("kind,dyn", KINDS)

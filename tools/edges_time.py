@@ -66,8 +66,6 @@ def main():
     ms = a.elapsed_time(b) / reps
     rec = {1: 64, 2: 80, 3: 800}[kind] + 20
     per = 2 * rec + env.obs_dim * 8 + 5 + 9
-    if len(sys.argv) <= 5 or sys.argv[5] != "nodes" or True:
-        pass
     print("%dD %s: %d edges (%s) %.4f ms  %.3e edges/s  %.0f GB/s of %d B per edge = %.2f of 8 TB/s" % (
         kind, _lib.lib().snac_last_kernel().decode(), m, mode, ms, m / ms * 1e3, per * m / ms / 1e6, per, per * m / ms / 1e6 / 8000))
 

@@ -1,11 +1,12 @@
 #!/bin/sh
-# Compare the gfx950 instruction streams of k_uct_select / k_uct_backup / k_uct_advance / k_uct_select_paths / k_uct_backup_paths between
-# two k_uct objects (hipcc -c outputs).
-#   tools/uct_isa_compare.sh OLD.o NEW.o
+# Compare the gfx950 instruction streams of kernels between two objects (hipcc -c outputs): by default k_uct_select / k_uct_backup /
+# k_uct_advance / k_uct_select_paths / k_uct_backup_paths of two k_uct objects.
+#   tools/uct_isa_compare.sh OLD.o NEW.o [SYMBOL_REGEXP]
 # Each object's gfx950 code object is extracted, disassembled, and cut into one listing per kernel symbol with addresses, raw encodings and
-# branch-target comments dropped; the listings of these five kernels must be identical.
+# branch-target comments dropped; the listings of the kernels whose (mangled) symbol matches the awk regexp must be identical.
 set -e
 ROCM=${ROCM_PATH:-/opt/rocm}
+SYMS=${3:-'k_uct_(select|backup|advance|select_paths|backup_paths)I'}
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
 for side in old new; do
@@ -13,7 +14,7 @@ for side in old new; do
     cp "$obj" "$T/$side.o"
     "$ROCM"/lib/llvm/bin/llvm-objdump --offloading "$T/$side.o" > /dev/null    # writes $side.o.0.hipv4-amdgcn-amd-amdhsa--gfx950
     "$ROCM"/lib/llvm/bin/llvm-objdump -d --no-show-raw-insn "$T/$side.o".*gfx950 |
-        awk '/^[0-9a-f]+ <.*>:$/ { keep = ($2 ~ /k_uct_(select|backup|advance|select_paths|backup_paths)I/); if (keep) print $2; next }
+        awk -v syms="$SYMS" '/^[0-9a-f]+ <.*>:$/ { keep = ($2 ~ syms); if (keep) print $2; next }
              keep { sub(/^[ \t]*/, ""); sub(/[ \t]*\/\/.*$/, ""); if ($0 != "" && $0 != "...") print }' > "$T/$side.txt"
 done
 n=$(grep -c '^<' "$T/old.txt")
