@@ -708,7 +708,33 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *     oldest) on, modulo cap_moves.  Per tree, from the newest of them back to the oldest, in float64 with no contraction:
  *       g = (double)bootstrap[b] (bootstrap NULL: 0);  at each slot  g = (double)reward + (done ? 0.0 : gamma * g),  z = (float)g.
  *     Slots outside the count are not written.  Checks: B >= 1; cap_moves >= 1; B * cap_moves within int32; first in [0, cap_moves); count in
- *     [0, cap_moves]; gamma finite; reward, done and z non-null.  count == 0: nothing is launched. */
+ *     [0, cap_moves]; gamma finite; reward, done and z non-null.  count == 0: nothing is launched.
+ * Normalised q: per-tree min-max bounds of the mean values, so that U does not depend on the reward scale (snac_uct_select_paths_norm /
+ *   snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds; UCTSearch(q_normalise=True)).
+ *   The bounds array: caller-owned, 2 * B float64, 16-byte aligned; bounds[2 * b] = lo, bounds[2 * b + 1] = hi of tree b; the empty pair
+ *     is (+inf, -inf).  The bounds are not part of snac_uct_node: snac_uct_advance / snac_uct_restart do not know them.
+ *   Selection (snac_uct_select_paths_norm / snac_uct_select_puct_norm: the arguments of snac_uct_select_paths / snac_uct_select_puct and
+ *     `bounds`, read only).  Tree b's pair is read once when the launch starts.  Everything is as in the unnormalised entry point, except
+ *     that the q of a TRIED child, q = (W_a - virtual_loss * (double)P_a) / (double)Np as there, is normalised before it enters U, in
+ *     float64, no contraction, in this order:
+ *         if (hi > lo) q = (q - lo) / (hi - lo);      (hi - lo computed once per tree; otherwise q is unchanged)
+ *     No clamp: with virtual loss q may leave [0, 1].  An untried action's first_play_value is used as given: it is in normalised
+ *     units.  Ties, table clamping, expansion, fresh rows, in-flight counts and every output are unchanged; with the empty pair or
+ *     hi == lo the outputs equal the unnormalised entry point's bit for bit.  There is no _norm form of the one-path snac_uct_select:
+ *     snac_uct_select_paths_norm with paths = 1 is that search (every P = 0).
+ *   Backup (snac_uct_backup_paths_norm: snac_uct_backup_paths and `bounds`, read and written).  The walks are those of
+ *     snac_uct_backup_paths.  In addition, right after a node x with a parent (parent >= 0: not the root) has its new visits and
+ *     value_sum, m = value_sum / (double)visits enters the tree's pair:
+ *         lo = m < lo ? m : lo;   hi = m > hi ? m : hi;      (a NaN fails both comparisons and never enters)
+ *     in slot order, then walk order; the pair is written back once per launch.  The root stays out because no selection compares its
+ *     mean; the means below it are exactly the W_a / N_a that selection compares (the mirrors in the parents).
+ *   Bounds from a tree as it stands (snac_uct_bounds; mask NULL: every tree).  For every tree with mask[b] != 0: lo / hi = the smallest /
+ *     largest value_sum / (double)visits over rows b * cap + 1 .. b * cap + used[b] - 1 with visits > 0, by the comparisons above (used[b]
+ *     clamped into [1, cap]); no such row: the empty pair.  Every other tree keeps its pair bit for bit.  After snac_uct_advance a
+ *     kept subtree so gets the bounds of its own nodes, and a one-node tree (an untried action, snac_uct_restart) the empty pair.
+ *   Checks before any HIP call: the _norm forms run the checks of the entry point they extend, then bounds non-null and 16-byte aligned.
+ *     snac_uct_bounds: used non-null; stats non-null and 128-byte aligned; B >= 1; cap >= 1; B * (cap + 1) within stats_rows and int32;
+ *     bounds non-null and 16-byte aligned. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -757,6 +783,20 @@ int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
                      int32_t record_rows, const uint8_t* mask, const uint8_t* terminal, int32_t* used, void* stream);
 int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count, double gamma, const float* reward, const uint8_t* done,
                      const float* bootstrap, float* z, void* stream);
+
+int snac_uct_select_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                               double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
+                               int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                               int32_t* first_slot, const double* bounds, void* stream);
+int snac_uct_select_puct_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                              double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
+                              int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
+                              float* r_leaf, int32_t* first_slot, const double* bounds, void* stream);
+int snac_uct_backup_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
+                               const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
+                               const uint8_t* done, const double* est, double* bounds, void* stream);
+int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* used, const uint8_t* mask,
+                    double* bounds, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,13 @@
 // k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance, and the
 // K-paths-per-tree iteration snac_uct_select_paths / snac_uct_backup_paths, and PUCT: snac_uct_select_puct / snac_uct_set_priors
+// and their q_normalise forms snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm with snac_uct_bounds
 // (include/snac_hip.h has the semantics)
 #include <cmath>
 #include <cstddef>
+#include <type_traits>
 
 #include "snac_dev.h"
+#include "snac_tune.h"
 
 // lane = tree: both kernels are chains of dependent loads, one trip per tree level.  A node's record holds its children's rows, visits
 // and values (line 0) beside its own header (line 1), so a selection step reads one record: the pieces it compares and the node's own
@@ -342,13 +345,57 @@ struct UctBackPaths {
     int32_t K;
 };
 
-template <int A>
-__global__ __launch_bounds__(64) void k_uct_select_paths(const UctSelPaths w) {
+// Normalised q ("Normalised q" in include/snac_hip.h): the NORM forms take the same arguments and the bounds array, bounds[2 * b] = lo,
+// bounds[2 * b + 1] = hi of tree b.  A selection reads its tree's pair once, before the descent (one 16-byte load that no level waits
+// for), and a tried child's q becomes (q - lo) / (hi - lo) where hi > lo; the backup folds W / N of every node below the root into
+// the pair, which it keeps in registers over its K walks and stores once.  NORM = false is the code of the unnormalised kernels.
+struct UctSelPathsNorm {
+    UctSelPaths p;
+    const double* bounds;
+};
+
+struct UctBackPathsNorm {
+    UctBackPaths p;
+    double* bounds;
+};
+
+__device__ __forceinline__ const UctSelPaths& plain(const UctSelPaths& a) { return a; }
+__device__ __forceinline__ const UctSelPaths& plain(const UctSelPathsNorm& a) { return a.p; }
+__device__ __forceinline__ const UctBackPaths& plain(const UctBackPaths& a) { return a; }
+__device__ __forceinline__ const UctBackPaths& plain(const UctBackPathsNorm& a) { return a.p; }
+
+// tree b's pair as it enters U: on = hi > lo, lo and span = hi - lo (computed once per tree)
+struct QRange {
+    double lo, span;
+    bool on;
+};
+
+__device__ __forceinline__ QRange q_range(const double* bounds, int b) {
+    const double2 p = reinterpret_cast<const double2*>(bounds)[b];
+    QRange r{p.x, 0.0, p.y > p.x};
+    {
+#pragma clang fp contract(off)
+        r.span = p.y - p.x;
+    }
+    return r;
+}
+
+__device__ __forceinline__ double q_norm(double q, const QRange& r) {
+#pragma clang fp contract(off)
+    const double d = q - r.lo;
+    return r.on ? d / r.span : q;
+}
+
+template <int A, bool NORM>
+__global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_t<NORM, UctSelPathsNorm, UctSelPaths> arg) {
     constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
+    const UctSelPaths& w = plain(arg);
     const UctSel& v = w.s;
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
     const int base = b * v.cap, K = w.K;
+    QRange qr{0.0, 0.0, false};
+    if constexpr (NORM) qr = q_range(arg.bounds, b);
     const int used0 = v.used[b];
     const int fresh = base + used0;                                  // rows from here up are made by this launch
     int used = used0;
@@ -406,7 +453,8 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const UctSelPaths w) {
                 {
 #pragma clang fp contract(off)
                     const int np = cn[a] + cf[a];
-                    const double q = (cw[a] - w.vl * (double)cf[a]) / (double)np;
+                    double q = (cw[a] - w.vl * (double)cf[a]) / (double)np;
+                    if constexpr (NORM) q = q_norm(q, qr);
                     const double e = lg * v.rtab[min(max(np, 0), v.tlen - 1)];
                     u = q + v.c * e;
                 }
@@ -435,12 +483,15 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const UctSelPaths w) {
     v.used[b] = used;
 }
 
-template <int A>
-__global__ __launch_bounds__(64) void k_uct_backup_paths(const UctBackPaths w) {
+template <int A, bool NORM>
+__global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_t<NORM, UctBackPathsNorm, UctBackPaths> arg) {
+    const UctBackPaths& w = plain(arg);
     const UctBack& v = w.s;
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
     const int base = b * v.cap, K = w.K;
+    double2 range = make_double2(0.0, 0.0);                          // NORM: the tree's (lo, hi), in registers over the K walks
+    if constexpr (NORM) range = reinterpret_cast<const double2*>(arg.bounds)[b];
     for (int k = 0; k < K; ++k) {                                    // the new nodes' rows, whole, before any walk reads one
         const int s = b * K + k;
         if (!v.expanded[s]) continue;
@@ -482,6 +533,11 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const UctBackPaths w) {
             pw[8 + a] = visits;                                      // the mirror in the parent's line 0
             *reinterpret_cast<double*>(pw + 16 + 2 * a) = sum;
             pw[4 * P_FLY + a] = 0;                                   // the edge's in-flight count
+            if constexpr (NORM) {                                    // x is below the root: its mean is one that selection compares
+                const double m = sum / (double)visits;
+                range.x = m < range.x ? m : range.x;                 // a NaN fails both comparisons
+                range.y = m > range.y ? m : range.y;
+            }
             {
 #pragma clang fp contract(off)
                 const double t = v.gamma * g;
@@ -490,6 +546,7 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const UctBackPaths w) {
             x = p;
         }
     }
+    if constexpr (NORM) reinterpret_cast<double2*>(arg.bounds)[b] = range;
 }
 
 // ---- PUCT: a policy / value network in place of UCB1 and the rollout ----------------------------------------------------------------
@@ -506,14 +563,25 @@ struct UctSelPuct {
     double fpv;
 };
 
-template <int A>
-__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuct z) {
+struct UctSelPuctNorm {
+    UctSelPuct z;
+    const double* bounds;
+};
+
+__device__ __forceinline__ const UctSelPuct& plain(const UctSelPuct& a) { return a; }
+__device__ __forceinline__ const UctSelPuct& plain(const UctSelPuctNorm& a) { return a.z; }
+
+template <int A, bool NORM>                                          // NORM: a tried child's q normalised (first_play_value is used as given)
+__global__ __launch_bounds__(64) void k_uct_select_puct(const std::conditional_t<NORM, UctSelPuctNorm, UctSelPuct> arg) {
     constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
+    const UctSelPuct& z = plain(arg);
     const UctSelPaths& w = z.p;
     const UctSel& v = w.s;
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
     const int base = b * v.cap, K = w.K;
+    QRange qr{0.0, 0.0, false};
+    if constexpr (NORM) qr = q_range(arg.bounds, b);
     const int used0 = v.used[b];
     const int fresh = base + used0;                                  // rows from here up are made by this launch
     int used = used0;
@@ -551,7 +619,8 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuct z) {
 #pragma clang fp contract(off)                                      // no fma: U rounded step by step, as a host restatement computes it
                     const int np = has ? cn + cf : 0;
                     const double t = w.vl * (double)cf;
-                    const double q = has ? (cw - t) / (double)np : z.fpv;
+                    double q = has ? (cw - t) / (double)np : z.fpv;
+                    if constexpr (NORM) q = has ? q_norm(q, qr) : q;
                     const double e0 = (double)pr * sq;
                     const double e = e0 * v.rtab[min(max(np, 0), v.tlen - 1)];
                     const double ce = v.c * e;
@@ -617,9 +686,73 @@ __global__ __launch_bounds__(256) void k_uct_set_priors(uint4* stats, int32_t st
     rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
 }
 
+// ---- bounds from a tree as it stands ----------------------------------------------------------------------------------------------------
+// G lanes = tree, 64 / G trees per one-wave workgroup: the lanes stride over the tree's rows below `used`, each row one 32-byte read of
+// line 1 (P_HDR: visits, P_OWN: W), BOUNDS_ROWS rows in flight per lane; then min / max by < / > through the group's lanes (exact, so
+// the result does not depend on G) and one 16-byte store per tree.  A tree with mask[b] == 0 is neither read nor written.
+struct UctBounds {
+    const uint4* stats;
+    int32_t B, cap;
+    const int32_t* used;
+    const uint8_t* mask;
+    double* bounds;
+};
+
+constexpr int BOUNDS_ROWS = 8;
+
+template <int G>
+__global__ __launch_bounds__(64) void k_uct_bounds(const UctBounds v) {
+    const int lane = (int)threadIdx.x, g = lane % G;
+    const int b = (int)blockIdx.x * (64 / G) + lane / G;
+    const bool live = b < v.B && (!v.mask || v.mask[b] != 0);
+    double lo = INFINITY, hi = -INFINITY;
+    if (live) {
+        const int used = min(max(v.used[b], 1), v.cap);
+        const uint4* const tree = v.stats + (size_t)b * v.cap * PIECES;
+        for (int j0 = 1 + g; j0 < used; j0 += G * BOUNDS_ROWS) {
+            uint4 hdr[BOUNDS_ROWS], own[BOUNDS_ROWS];
+#pragma unroll
+            for (int i = 0; i < BOUNDS_ROWS; ++i) {                  // every load of the batch before the first is used
+                const int j = min(j0 + i * G, used - 1);
+                hdr[i] = tree[(size_t)j * PIECES + P_HDR];
+                own[i] = tree[(size_t)j * PIECES + P_OWN];
+            }
+#pragma unroll
+            for (int i = 0; i < BOUNDS_ROWS; ++i) {
+                const int n = (int)hdr[i].w;
+                if (j0 + i * G >= used || n <= 0) continue;
+                const double m = f64(own[i].x, own[i].y) / (double)n;
+                lo = m < lo ? m : lo;                                // a NaN fails both comparisons
+                hi = m > hi ? m : hi;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = G / 2; o > 0; o >>= 1) {                            // every lane of the wave takes part; a group's lanes are neighbours
+        const double l = __shfl_xor(lo, o), h = __shfl_xor(hi, o);
+        lo = l < lo ? l : lo;
+        hi = h > hi ? h : hi;
+    }
+    if (live && g == 0) reinterpret_cast<double2*>(v.bounds)[b] = make_double2(lo, hi);
+}
+
+// lanes per tree of k_uct_bounds: about four rows per lane for small trees, a whole wave from 129 rows on (SNAC_UCT_BOUNDS_WIDTH forces one)
+int bounds_width(int cap) {
+    const int forced = snac_detail::tune(snac_detail::TN_UCT_BOUNDS_WIDTH);
+    if (forced == 8 || forced == 16 || forced == 32 || forced == 64) return forced;
+    return cap > 128 ? 64 : cap > 64 ? 32 : cap > 32 ? 16 : 8;
+}
+
+int uct_check_rows(const void* stats, int32_t rows, int32_t B, int32_t cap);
+
 int uct_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     using namespace snac_detail;
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
+    return uct_check_rows(stats, rows, B, cap);
+}
+
+int uct_check_rows(const void* stats, int32_t rows, int32_t B, int32_t cap) {
+    using namespace snac_detail;
     if (!stats) return fail(SNAC_ERR_ARG, "null stats");
     if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
     if (cap < 1) return fail(SNAC_ERR_ARG, "cap must be >= 1");
@@ -643,6 +776,13 @@ int uct_check_paths(int A, const void* stats, int32_t rows, int32_t B, int32_t c
     if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * (cap + paths) rows exceed int32");
     if (need > rows) return fail(SNAC_ERR_ARG, "B * (cap + paths) rows exceed stats_rows");
     if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    return SNAC_OK;
+}
+
+int bounds_check(const void* bounds) {
+    using namespace snac_detail;
+    if (!bounds) return fail(SNAC_ERR_ARG, "null bounds");
+    if (((uintptr_t)bounds & 15) != 0) return fail(SNAC_ERR_ARG, "bounds must be 16-byte aligned (a tree's pair is one piece)");
     return SNAC_OK;
 }
 
@@ -714,10 +854,11 @@ int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_advance");
 }
 
-int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
-                          double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
-                          int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf, int32_t* first_slot,
-                          void* stream) {
+// the plain and the _norm entry points share their checks and launches: bounds == nullptr is the plain form
+static int select_paths(const char* name, int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths,
+                        double c, double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
+                        int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf, int32_t* first_slot,
+                        bool norm, const double* bounds, void* stream) {
     using namespace snac_detail;
     if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
     if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
@@ -725,36 +866,76 @@ int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t sta
     if (table_len < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
     if (!used || !src || !dst || !action || !leaf || !expanded || !r_leaf || !first_slot)
         return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
+    if (norm)
+        if (int rc = bounds_check(bounds)) return rc;
     const UctSelPaths v{{(uint4*)stats, B, cap, c, log_table, rsqrt_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
                         paths, virtual_loss, first_slot};
+    const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_select_paths";
     by_actions(num_actions, [&](auto k) {
-        hipLaunchKernelGGL((k_uct_select_paths<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+        constexpr int A = decltype(k)::value;
+        if (norm) hipLaunchKernelGGL((k_uct_select_paths<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPathsNorm{v, bounds});
+        else hipLaunchKernelGGL((k_uct_select_paths<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_select_paths");
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, name);
+}
+
+int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                          double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
+                          int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf, int32_t* first_slot,
+                          void* stream) {
+    return select_paths("snac_uct_select_paths", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, log_table, rsqrt_table, table_len,
+                        used, src, dst, action, leaf, expanded, r_leaf, first_slot, false, nullptr, stream);
+}
+
+int snac_uct_select_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                               double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,
+                               int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                               int32_t* first_slot, const double* bounds, void* stream) {
+    return select_paths("snac_uct_select_paths_norm", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, log_table, rsqrt_table,
+                        table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, stream);
+}
+
+static int backup_paths(const char* name, int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths,
+                        double gamma, const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
+                        const uint8_t* done, const double* est, bool norm, double* bounds, void* stream) {
+    using namespace snac_detail;
+    if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
+    if (!src || !action || !leaf || !expanded || !reward || !done || !est)
+        return fail(SNAC_ERR_ARG, "null per-slot array (src / action / leaf / expanded / reward / done / est)");
+    if (norm)
+        if (int rc = bounds_check(bounds)) return rc;
+    const UctBackPaths v{{(uint4*)stats, B, cap, gamma, src, action, leaf, expanded, reward, done, est}, paths};
+    const dim3 grid((unsigned)((B + 63) / 64));
+    g_kernel = "k_uct_backup_paths";
+    by_actions(num_actions, [&](auto k) {
+        constexpr int A = decltype(k)::value;
+        if (norm) hipLaunchKernelGGL((k_uct_backup_paths<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctBackPathsNorm{v, bounds});
+        else hipLaunchKernelGGL((k_uct_backup_paths<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, name);
 }
 
 int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
                           const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
                           const uint8_t* done, const double* est, void* stream) {
-    using namespace snac_detail;
-    if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
-    if (!src || !action || !leaf || !expanded || !reward || !done || !est)
-        return fail(SNAC_ERR_ARG, "null per-slot array (src / action / leaf / expanded / reward / done / est)");
-    const UctBackPaths v{{(uint4*)stats, B, cap, gamma, src, action, leaf, expanded, reward, done, est}, paths};
-    g_kernel = "k_uct_backup_paths";
-    by_actions(num_actions, [&](auto k) {
-        hipLaunchKernelGGL((k_uct_backup_paths<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
-    });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_backup_paths");
+    return backup_paths("snac_uct_backup_paths", num_actions, stats, stats_rows, B, cap, paths, gamma, src, action, leaf, expanded, reward, done,
+                        est, false, nullptr, stream);
 }
 
-int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
-                         double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table, int32_t table_len,
-                         int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
-                         int32_t* first_slot, void* stream) {
+int snac_uct_backup_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
+                               const int32_t* src, const int8_t* action, const int32_t* leaf, const uint8_t* expanded, const float* reward,
+                               const uint8_t* done, const double* est, double* bounds, void* stream) {
+    return backup_paths("snac_uct_backup_paths_norm", num_actions, stats, stats_rows, B, cap, paths, gamma, src, action, leaf, expanded, reward,
+                        done, est, true, bounds, stream);
+}
+
+static int select_puct(const char* name, int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths,
+                       double c, double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
+                       int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
+                       float* r_leaf, int32_t* first_slot, bool norm, const double* bounds, void* stream) {
     using namespace snac_detail;
     if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
     if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
@@ -763,15 +944,36 @@ int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stat
     if (table_len < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
     if (!used || !src || !dst || !action || !leaf || !expanded || !r_leaf || !first_slot)
         return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
+    if (norm)
+        if (int rc = bounds_check(bounds)) return rc;
     const UctSelPuct v{{{(uint4*)stats, B, cap, c, sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
                         paths, virtual_loss, first_slot},
                        first_play_value};
+    const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_select_puct";
     by_actions(num_actions, [&](auto k) {
-        hipLaunchKernelGGL((k_uct_select_puct<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+        constexpr int A = decltype(k)::value;
+        if (norm) hipLaunchKernelGGL((k_uct_select_puct<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPuctNorm{v, bounds});
+        else hipLaunchKernelGGL((k_uct_select_puct<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_select_puct");
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, name);
+}
+
+int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                         double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table, int32_t table_len,
+                         int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                         int32_t* first_slot, void* stream) {
+    return select_puct("snac_uct_select_puct", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, false, nullptr, stream);
+}
+
+int snac_uct_select_puct_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                              double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
+                              int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
+                              float* r_leaf, int32_t* first_slot, const double* bounds, void* stream) {
+    return select_puct("snac_uct_select_puct_norm", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, stream);
 }
 
 int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
@@ -791,6 +993,24 @@ int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats
     });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_set_priors");
+}
+
+int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* used, const uint8_t* mask,
+                    double* bounds, void* stream) {
+    using namespace snac_detail;
+    if (!used) return fail(SNAC_ERR_ARG, "null used");
+    if (int rc = uct_check_rows(stats, stats_rows, B, cap)) return rc;
+    if (int rc = bounds_check(bounds)) return rc;
+    const UctBounds v{(const uint4*)stats, B, cap, used, mask, bounds};
+    const int G = bounds_width(cap), per = 64 / G;
+    const dim3 grid((unsigned)((B + per - 1) / per));
+    g_kernel = "k_uct_bounds";
+    if (G == 8) hipLaunchKernelGGL((k_uct_bounds<8>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else if (G == 16) hipLaunchKernelGGL((k_uct_bounds<16>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else if (G == 32) hipLaunchKernelGGL((k_uct_bounds<32>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else hipLaunchKernelGGL((k_uct_bounds<64>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_bounds");
 }
 
 }  // extern "C"

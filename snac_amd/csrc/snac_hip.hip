@@ -196,6 +196,7 @@ const Knob KNOBS[TN_COUNT] = {
     /* TN_AUX_STEP        */ {"SNAC_AUX_STEP", 1, "snac_reset with a mask and snac_observe (canonical layout, N % 4 == 0, aligned obs, from 256 envs) on the step kernels' AUX forms (k_step1d / k_step2d / k_step3dq without a step); 0 = the tile kernel k_aux"},
     /* TN_EVAL_E          */ {"SNAC_EVAL_E", 64, "leaves per wave of k_eval for 1D / 2D leaves (snac_evaluate_nodes1d / 2d; 16 / 32 / 64): 2D, 65 536 leaves, H = 600: 0.320 against 0.359 ms per call with 32, 4096 leaves level (0.275 / 0.274); 1D, 65 536 leaves, H = 300: 0.172 / 0.194 (r08_eval.txt)"},
     /* TN_EVAL3D_E        */ {"SNAC_EVAL3D_E", 16, "leaves per wave of k_eval for 3D leaves (16 / 32 / 64: 22 / 44 / 88 KB of LDS per wave): 65 536 leaves, H = 200: 0.219 ms per call against 0.262 with 32 and 0.355 with 64; 4096 leaves: 0.142 / 0.166 / 0.160 (r08_eval.txt)"},
+    /* TN_UCT_BOUNDS_WIDTH */ {"SNAC_UCT_BOUNDS_WIDTH", 0, "lanes per tree of k_uct_bounds (snac_uct_bounds; 8 / 16 / 32 / 64): 0 = from cap, 8 lanes up to 32 nodes per tree, 16 up to 64, 32 up to 128, a wave above (r15_uct_norm.txt)"},
 };
 
 int tune(int id) {

@@ -16,6 +16,9 @@ root.  Everything lands in ring slot `head`; nothing crosses the bus and the hos
         batch = play.sample(1024)                    # obs float32, pi, z, value, action, reward, done
         loss = cross_entropy(policy(batch["obs"]), batch["pi"]) + mse(value(batch["obs"]), batch["z"]); ...
 
+A search built with q_normalise=True plays the same way: advance() and restart() keep its q bounds (snac_amd/uct.py), nothing here
+knows them.
+
 The ring, over moves (slot = move % capacity_moves), every tensor on the env's device:
     obs [cap, B, D] env.obs_dtype   pi [cap, B, A] float32   value [cap, B] float32   action [cap, B] int8
     reward [cap, B] float32   done [cap, B] uint8   move [cap, B] int32 (the move's index inside its episode)   z [cap, B] float32

@@ -1,6 +1,7 @@
 """Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
-snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors, snac_uct_pick_moves / snac_uct_restart:
-include/snac_hip.h; snac_amd/csrc/k_uct.hip, k_uct_play.hip).
+snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors, snac_uct_pick_moves / snac_uct_restart,
+snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds: include/snac_hip.h;
+snac_amd/csrc/k_uct.hip, k_uct_play.hip).
 
 B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
 stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
@@ -73,6 +74,17 @@ ring of targets around them:
     play = SelfPlay(search, capacity_moves=256, sample_moves=10)
     play.play(64, iterations=32); play.targets(); batch = play.sample(512)      # obs, pi, z, ...
 
+Rewards of any scale: q_normalise=True keeps, per tree, the smallest and the largest mean value W / N of its nodes below the root
+(q_bounds, [B, 2] float64: lo, hi; empty: +inf, -inf) and compares (q - lo) / (hi - lo) in place of a tried child's q ("Normalised q" in
+include/snac_hip.h), in the rollout search and in PUCT, for every paths >= 1.  This environment pays 5 or 10 per brick and -100 for a
+boxed-in 3D episode, so raw returns run from tens to hundreds and drown an exploration term of order 1; normalised, c keeps its textbook
+meaning at every move of an episode.  first_play_value is then in normalised units: 0.0 rates an untried action like the worst child
+seen so far, 1.0 like the best.  Until a tree has seen two different means its q is left as it is.  The backup folds the new means into
+the bounds; advance() and restart() recompute them from the tree they leave (a kept subtree: the bounds of its own nodes, since the
+return still to collect shrinks along an episode; a one-node tree: empty), all on the env's stream with no host synchronisation.
+
+    search = UCTSearch(env, nodes_per_tree=512, horizon=0, gamma=0.99, c=1.25, paths=16, evaluator=fn, q_normalise=True)
+
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
 t0 = it * (H + 1) + 1, so no two iterations share a word.  Path k of tree b draws both with the key (env_id_base + b) * K + k, its slot
 in the search over ALL envs, so no two paths share a word either and a shard of the trees (env_id_base = E: dist.py) searches exactly as
@@ -113,9 +125,12 @@ class UCTSearch:
     path ("K paths per tree and iteration" there).  Everything is allocated here; run() only enqueues work."""
 
     def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None, paths=1, virtual_loss=0.0,
-                 evaluator=None, first_play_value=None):
+                 evaluator=None, first_play_value=None, q_normalise=False):
         """evaluator: None (the rollout search) or a callable obs [S, obs_dim] -> (priors [S, A], value [S]) that guides a PUCT search
-        (the module docstring); first_play_value (PUCT only, default 0.0): the q of an untried action."""
+        (the module docstring); first_play_value (PUCT only, default 0.0): the q of an untried action.  q_normalise (a bool): compare
+        q normalised by the tree's min-max bounds (the module docstring); q_bounds is then a [B, 2] float64 tensor, else None."""
+        if not isinstance(q_normalise, bool):
+            raise ValueError("q_normalise must be a bool")
         if evaluator is not None and not callable(evaluator):
             raise ValueError("evaluator must be callable: obs [S, obs_dim] -> (priors [S, A], value [S])")
         if first_play_value is not None and evaluator is None:
@@ -123,7 +138,7 @@ class UCTSearch:
         fpv = 0.0 if first_play_value is None else float(first_play_value)
         if not math.isfinite(fpv):
             raise ValueError("first_play_value must be finite")
-        self.evaluator, self.first_play_value = evaluator, fpv
+        self.evaluator, self.first_play_value, self.q_normalise = evaluator, fpv, q_normalise
         self.env = env
         self.trees = int(env.num_envs if trees is None else trees)
         self.nodes_per_tree, self.horizon, self.gamma, self.c = int(nodes_per_tree), int(horizon), float(gamma), float(c)
@@ -175,7 +190,8 @@ class UCTSearch:
                              _ptr(self._leaf), _ptr(self._expanded), _ptr(self._reward), _ptr(self._done), _ptr(self._est))
         self._transition = getattr(self._lib, P.TRANSITION)
         self._evaluate_fn = getattr(self._lib, P.EVALUATE)
-        self._multi = K > 1 or evaluator is not None                 # the rollout search with paths=1 keeps the one-path entry points
+        # the rollout search with paths=1 keeps the one-path entry points, unless it normalises q: there is no one-path _norm form
+        self._multi = K > 1 or evaluator is not None or q_normalise
         self._slot_desc = None if K == 1 else type(env._desc)()      # the per-iteration launches' descriptor (_slots())
         if self._multi:
             self._first_slot, self._first_idx = slot(torch.int32), slot(torch.int32)
@@ -204,6 +220,15 @@ class UCTSearch:
             self._obs_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), _ptr(self._obs))
             self._root_obs_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._root_rows), _ptr(self._root_obs))
             self._prior_args = (A, _ptr(self.stats), self.rows, S, _ptr(self._prior_rows), _ptr(self._priors), 0)
+        self.q_bounds = None
+        if q_normalise:                                              # the _norm entry points: the same arguments, then the bounds
+            self.q_bounds = torch.empty((B, 2), dtype=torch.float64, device=dev)
+            assert self.q_bounds.data_ptr() % 16 == 0
+            self._no_bounds = torch.tensor([math.inf, -math.inf], dtype=torch.float64, device=dev)
+            self.q_bounds.copy_(self._no_bounds.expand(B, 2))
+            self._select_args += (_ptr(self.q_bounds),)
+            self._backup_args += (_ptr(self.q_bounds),)
+            self._bounds_args = (_ptr(self.stats), self.rows, B, cap, _ptr(self._used))
         self._edge_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._src), _ptr(self._dst))
         self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
         self._eval_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), self.horizon)
@@ -249,6 +274,8 @@ class UCTSearch:
         self.stats[roots, 34] = self.pool.need_reset[roots].to(torch.int32)
         self._used.fill_(1)
         self._iteration = 0
+        if self.q_normalise:
+            self.q_bounds.copy_(self._no_bounds.expand(B, 2))
         if self.evaluator is not None:
             with torch.cuda.device(env.device):
                 self._prime_roots()
@@ -304,6 +331,8 @@ class UCTSearch:
             self._adv_action.copy_(a.clamp(0, self.num_actions - 1))
             self._root_edges()
             self._reroot(reward, done)
+            if self.q_normalise:                                     # every tree: the bounds of the subtree it kept
+                self._rebound(None)
             if prime and self.evaluator is not None:                 # the roots made from an untried action are unvisited: they get priors
                 self._prime_roots()
 
@@ -380,6 +409,8 @@ class UCTSearch:
             self._rs_flags.bitwise_and_(_lib.FLAG_NEED_RESET)
             self._rs_term.copy_(self._rs_flags)
             _lib.check(self._lib.snac_uct_restart(*self._restart_args, env._stream()))
+            if self.q_normalise:                                     # the restarted trees have one node: empty bounds; the others keep theirs
+                self._rebound(self._rs_mask)
             if self.evaluator is not None:
                 self._prime_roots()
 
@@ -391,6 +422,10 @@ class UCTSearch:
     def _reroot(self, reward, done):
         _lib.check(self._lib.snac_uct_advance(*self._advance_args, _ptr(reward), _ptr(done), self.env._stream()))
 
+    def _rebound(self, mask):
+        """q_bounds of the trees with mask[b] != 0 (uint8 [B] on the device; None: all) <- the bounds of their nodes as they stand."""
+        _lib.check(self._lib.snac_uct_bounds(*self._bounds_args, None if mask is None else _ptr(mask), _ptr(self.q_bounds), self.env._stream()))
+
     def store_roots(self, rows=None):
         """Env row rows[b] <- the record of root b (None: row b), so that observe() / iou() read the played states."""
         self.pool.store(node_rows=self._roots, rows=rows)
@@ -400,10 +435,13 @@ class UCTSearch:
         return (self._iteration * (self.horizon + 1)) & 0xFFFFFFFF
 
     def _select(self):
+        L = self._lib
         if self.evaluator is not None:
-            fn = self._lib.snac_uct_select_puct
+            fn = L.snac_uct_select_puct_norm if self.q_normalise else L.snac_uct_select_puct
+        elif self.q_normalise:
+            fn = L.snac_uct_select_paths_norm
         else:
-            fn = self._lib.snac_uct_select if self.paths == 1 else self._lib.snac_uct_select_paths
+            fn = L.snac_uct_select if self.paths == 1 else L.snac_uct_select_paths
         _lib.check(fn(*self._select_args, self.env._stream()))
 
     def _slots(self):
@@ -440,7 +478,8 @@ class UCTSearch:
                                      env._stream()))
 
     def _backup(self):
-        fn = self._lib.snac_uct_backup_paths if self._multi else self._lib.snac_uct_backup
+        L = self._lib
+        fn = L.snac_uct_backup_paths_norm if self.q_normalise else L.snac_uct_backup_paths if self._multi else L.snac_uct_backup
         _lib.check(fn(*self._backup_args, self.env._stream()))
         self._iteration += 1
 
@@ -520,6 +559,12 @@ class UCTSearch:
     def best_actions(self):
         """[B] int64: the most-visited root action, ties to the lowest."""
         return torch.argmax(self.root_visits(), dim=1)
+
+    def q_bounds_of_trees(self):
+        """[B, 2] float64: (lo, hi) of each tree's mean values below the root, (+inf, -inf) while there is none (q_normalise=True only)."""
+        if not self.q_normalise:
+            raise ValueError("bounds belong to a search with q_normalise=True")
+        return self.q_bounds.clone()
 
     def tree_sizes(self):
         """[B] int32: nodes used by each tree (the root counts)."""

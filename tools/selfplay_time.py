@@ -13,9 +13,10 @@ with HIP events on the env's stream.
               records loaded row by row (pool.load), the root statistics rows written with torch indexing.  It keeps the unfinished trees'
               subtrees, like restart(); reset() of every tree whenever one finishes would throw them away and is not the same search.
   ended       episodes that ended in the phase pass (its two warm-up moves included) / in the timed moves of the host-driven loop.
+  --normalise adds a row with q_normalise=True under each row: its advance and restart phases include snac_uct_bounds.
   Each (shape, search) runs in a child process of its own under a time limit; the first one that fails ends the run.
 
-    python tools/selfplay_time.py [--moves 24] [--iterations 32]
+    python tools/selfplay_time.py [--moves 24] [--iterations 32] [--normalise]
 """
 import argparse
 import ctypes as C
@@ -50,7 +51,7 @@ def mlp(env, hidden=128):
     return fn
 
 
-def make(B, cap, K, n, puct):
+def make(B, cap, K, n, puct, norm=False):
     env = BatchedDMPEnv(2, True, B, seed=1)
     env.reset()
     cs = env._hdr.view(torch.int16).view(B, 8)[:, 3]
@@ -59,14 +60,16 @@ def make(B, cap, K, n, puct):
     kw = dict(paths=K) if K > 1 else {}
     if puct:
         kw["evaluator"] = mlp(env)
+    if norm:
+        kw["q_normalise"] = True
     search = UCTSearch(env, cap, 0 if puct else H, 0.99, max_iterations=(env.total_step + 1) * n, **kw)
     search.reset()
     return env, search
 
 
-def phases(B, cap, K, n, puct, moves):
+def phases(B, cap, K, n, puct, moves, norm=False):
     """Device ms per move and phase: play()'s own sequence, with an event between the phases."""
-    env, s = make(B, cap, K, n, puct)
+    env, s = make(B, cap, K, n, puct, norm)
     play = SelfPlay(s, moves + 2, sample_moves=4)
     play.play(2, n)                                                  # warm-up: every kernel and torch op of the timed window
     torch.cuda.synchronize()
@@ -106,9 +109,9 @@ def phases(B, cap, K, n, puct, moves):
     return ms, int(play.done[:play.valid_moves()].sum())
 
 
-def whole(B, cap, K, n, puct, moves):
+def whole(B, cap, K, n, puct, moves, norm=False):
     """Wall ms per move of play(moves, n)."""
-    env, s = make(B, cap, K, n, puct)
+    env, s = make(B, cap, K, n, puct, norm)
     play = SelfPlay(s, moves + 2, sample_moves=4)
     play.play(2, n)
     torch.cuda.synchronize()
@@ -130,15 +133,17 @@ def host_move(env, s, fresh_row):
         s.pool.load(rows=idx, node_rows=B * cap + idx)
         s.stats[idx * cap] = fresh_row
         s._used[idx] = 1
+        if s.q_normalise:
+            s.q_bounds[idx] = s._no_bounds                           # a one-node tree: empty bounds
         if s.evaluator is not None:
             with torch.cuda.device(env.device):
                 s._prime_roots()
     return r, d
 
 
-def host(B, cap, K, n, puct, moves):
+def host(B, cap, K, n, puct, moves, norm=False):
     """Wall ms per move of the host-driven loop."""
-    env, s = make(B, cap, K, n, puct)
+    env, s = make(B, cap, K, n, puct, norm)
     fresh = torch.zeros(64, dtype=torch.int32, device=env.device)
     fresh[0:8] = -1
     fresh[32:34] = -1
@@ -156,10 +161,10 @@ def host(B, cap, K, n, puct, moves):
 
 
 def worker(cfg):
-    B, cap, K, n, puct, moves = cfg
-    ph, ended = phases(B, cap, K, n, puct, moves)
-    w, _ = whole(B, cap, K, n, puct, moves)
-    h, h_ended = host(B, cap, K, n, puct, moves)
+    B, cap, K, n, puct, moves, norm = cfg
+    ph, ended = phases(B, cap, K, n, puct, moves, norm)
+    w, _ = whole(B, cap, K, n, puct, moves, norm)
+    h, h_ended = host(B, cap, K, n, puct, moves, norm)
     print(json.dumps(dict(phases=ph, ended=ended, whole=w, host=h, host_ended=h_ended)))
 
 
@@ -167,6 +172,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--moves", type=int, default=24)
     ap.add_argument("--iterations", type=int, default=32)
+    ap.add_argument("--normalise", action="store_true", help="a q_normalise=True row under each row")
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -178,15 +184,17 @@ def main():
     print("2D dynamic, %d iterations per move, %d timed moves; device ms per move by phase (HIP events), then wall ms per move" % (n, moves))
     print("  %-34s" % "" + "".join("%10s" % p for p in PHASES) + "  |%10s%10s%10s%9s" % ("additions", "play()", "host move", "ended"))
     for B, cap, K in SHAPES:
-        for puct in (False, True):
-            cfg = [B, cap, K, n, puct, moves]
+        for puct, norm in ((False, False), (False, True), (True, False), (True, True)):
+            if norm and not args.normalise:
+                continue
+            cfg = [B, cap, K, n, puct, moves, norm]
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", json.dumps(cfg)], capture_output=True, text=True,
                                  timeout=LIMIT)
             if out.returncode != 0:                                  # nothing more is started on the device after a failure
                 sys.stderr.write(out.stderr[-4000:])
                 raise SystemExit("the worker for %r ended with status %d" % (cfg, out.returncode))
             m = json.loads(out.stdout.strip().splitlines()[-1])
-            label = "B = %d x %d nodes, paths=%d, %s" % (B, cap, K, "PUCT" if puct else "rollout")
+            label = "  q_normalise=True" if norm else "B = %d x %d nodes, paths=%d, %s" % (B, cap, K, "PUCT" if puct else "rollout")
             print("  %-34s" % label + "".join("%10.3f" % x for x in m["phases"]) + "  |%10.3f%10.3f%10.3f%5d/%d"
                   % (sum(m["phases"][1:]), m["whole"], m["host"], m["ended"], m["host_ended"]), flush=True)
 

@@ -10,10 +10,15 @@
               the estimate; the rollout rows: the rollout), backup + priors; mean tree size, mean depth of the allocated nodes, and
               levels = the summed depth of the iterations' leaves, wave levels = the same with each wave of 64 trees counted as its
               deepest lane, select us per wave level = select ms / wave levels (a pass of its own).
+              --normalise adds a row with q_normalise=True (k_uct_select_paths / k_uct_select_puct / k_uct_backup_paths in their NORM
+              forms) under each of this build's rows.
   part 2      snac_observe_nodes2d beside snac_transition_nodes2d at m = 524 288 random records of a 2^20-record pool (the shape of
               bench.py's transition_2d_nodes_524288_edges): ms and bytes per second by lines read + lines / rows written.
+  part 3      snac_uct_bounds alone on full trees (every row visited) at B = 64 x 8192 nodes and B = 4096 x 512 nodes: ms per call and
+              bytes read per second (32 bytes per row: pieces P_HDR and P_OWN), with the lanes per tree the library picks from cap and
+              with each forced width (SNAC_UCT_BOUNDS_WIDTH), every width in a child process of its own.
 
-    python tools/uct_puct_time.py [--repeat 5] [--reference-root DIR] [--parts 1,2]
+    python tools/uct_puct_time.py [--repeat 5] [--reference-root DIR] [--parts 1,2] [--normalise]
 """
 import argparse
 import ctypes as C
@@ -56,10 +61,12 @@ def mlp(env, hidden=128):
     return fn
 
 
-def make(B, cap, K, n, mode):
+def make(B, cap, K, n, mode, norm=False):
     env = BatchedDMPEnv(2, True, B, seed=1)
     env.reset()
     kw = {} if K == 1 else dict(paths=K)
+    if norm:
+        kw["q_normalise"] = True
     if mode != "rollout":
         kw["evaluator"] = constant(env.num_actions) if mode == "const" else mlp(env)
     return UCTSearch(env, cap, H, 0.99, max_iterations=n, **kw)
@@ -145,8 +152,8 @@ def shape(search):
     return float(used.mean()), float(d[rows].mean())
 
 
-def measure(B, cap, K, n, mode, R):
-    search = make(B, cap, K, n, mode)
+def measure(B, cap, K, n, mode, R, norm=False):
+    search = make(B, cap, K, n, mode, norm)
     search.reset()
     search.run(min(n, 8))                                            # warm-up: every kernel and torch op of the timed window
     torch.cuda.synchronize()
@@ -167,7 +174,7 @@ def reference(root, cfg, R):
     return json.loads(out.strip().splitlines()[-1])
 
 
-def part1(R, ref_root):
+def part1(R, ref_root, norm=False):
     print("part 1: 2D dynamic; the rollout rows with H = %d; device ms (HIP events); us/wavelvl = 1000 x select ms / wave levels" % H)
     for B, cap, K, n in SHAPES:
         print("  B = %d trees x %d nodes, %d iterations x paths=%d" % (B, cap, n, K))
@@ -176,9 +183,10 @@ def part1(R, ref_root):
         cfg = [B, cap, K, n]
         if ref_root:
             row("reference rollout", reference(ref_root, cfg, R))
-        row("this build, rollout", measure(B, cap, K, n, "rollout", R))
-        row("PUCT, constant evaluator", measure(B, cap, K, n, "const", R))
-        row("PUCT, two-layer MLP", measure(B, cap, K, n, "mlp", R))
+        for label, mode in (("this build, rollout", "rollout"), ("PUCT, constant evaluator", "const"), ("PUCT, two-layer MLP", "mlp")):
+            row(label, measure(B, cap, K, n, mode, R))
+            if norm:
+                row("  q_normalise=True", measure(B, cap, K, n, mode, R, norm=True))
         if ref_root:
             row("reference rollout (again)", reference(ref_root, cfg, R))
 
@@ -230,6 +238,46 @@ def part2():
               % (best, nbytes, nbytes * m / (best * 1e-3) / 1e9), flush=True)
 
 
+BOUNDS_SHAPES = ((64, 8192), (4096, 512))
+
+
+def bounds_worker():
+    """ms per snac_uct_bounds call on full trees at BOUNDS_SHAPES, one JSON line."""
+    out = []
+    for B, cap in BOUNDS_SHAPES:
+        env = BatchedDMPEnv(2, True, B, seed=1)
+        env.reset()
+        s = UCTSearch(env, cap, 0, 0.99, max_iterations=4, q_normalise=True)
+        s.reset()
+        g = torch.Generator(device=env.device).manual_seed(1)
+        s.stats[:, 35] = torch.randint(1, 6, (s.rows,), generator=g, device=env.device, dtype=torch.int32)
+        s.value_sum.copy_(300.0 * torch.randn(s.rows, generator=g, device=env.device, dtype=torch.float64))
+        s._used.fill_(cap)
+        with torch.cuda.device(env.device):
+            out.append(timed(lambda: s._rebound(None), 20))
+        lo_hi = s.q_bounds_of_trees()
+        means = (s.value_sum / s.visits.double())[:B * cap].view(B, cap)[:, 1:]
+        assert torch.equal(lo_hi[:, 0], means.min(1).values) and torch.equal(lo_hi[:, 1], means.max(1).values)
+    print(json.dumps(out))
+
+
+def part3():
+    print("\npart 3: snac_uct_bounds on full trees; five windows of 20 calls, ms per call; bytes = 32 per row below the root")
+    for width in ("", "8", "16", "32", "64"):
+        env = dict(os.environ)
+        env.pop("SNAC_UCT_BOUNDS_WIDTH", None)
+        if width:
+            env["SNAC_UCT_BOUNDS_WIDTH"] = width
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--bounds-worker"], env=env, capture_output=True, text=True, timeout=300)
+        if r.returncode != 0:                                        # nothing more is started on the device after a failure
+            sys.stderr.write(r.stderr[-4000:])
+            raise SystemExit("the bounds worker (width %s) ended with status %d" % (width or "from cap", r.returncode))
+        for (B, cap), t in zip(BOUNDS_SHAPES, json.loads(r.stdout.strip().splitlines()[-1])):
+            best = min(t)
+            print("  %-22s B = %4d x %4d nodes" % ("lanes per tree: " + (width or "from cap"), B, cap) + "".join("%9.4f" % x for x in t)
+                  + "   best %.4f ms: %.0f GB/s" % (best, 32 * B * (cap - 1) / (best * 1e-3) / 1e9), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="1,2")
@@ -237,6 +285,8 @@ def main():
     ap.add_argument("--reference-root", default=None)
     ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--worker", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--normalise", action="store_true", help="part 1: a q_normalise=True row under each of this build's rows")
+    ap.add_argument("--bounds-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("no GPU: nothing is measured")
@@ -244,11 +294,16 @@ def main():
         B, cap, K, n = json.loads(args.worker)
         print(json.dumps(measure(B, cap, K, n, "rollout", args.repeat)))
         return
+    if args.bounds_worker:
+        bounds_worker()
+        return
     parts = [int(p) for p in args.parts.split(",")]
     if 1 in parts:
-        part1(args.repeat, args.reference_root)
+        part1(args.repeat, args.reference_root, args.normalise)
     if 2 in parts:
         part2()
+    if 3 in parts:
+        part3()
 
 
 if __name__ == "__main__":
