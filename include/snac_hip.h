@@ -734,7 +734,39 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *     kept subtree so gets the bounds of its own nodes, and a one-node tree (an untried action, snac_uct_restart) the empty pair.
  *   Checks before any HIP call: the _norm forms run the checks of the entry point they extend, then bounds non-null and 16-byte aligned.
  *     snac_uct_bounds: used non-null; stats non-null and 128-byte aligned; B >= 1; cap >= 1; B * (cap + 1) within stats_rows and int32;
- *     bounds non-null and 16-byte aligned. */
+ *     bounds non-null and 16-byte aligned.
+ * Gumbel root: sequential halving over sampled root actions in place of PUCT at the root (Danihelka et al. 2022, Gumbel AlphaZero;
+ *   snac_uct_select_gumbel, k_uct.hip; snac_uct_gumbel_candidates, k_uct_play.hip; UCTSearch(gumbel=m), SelfPlay(gumbel=True)).  A move is
+ *     BEGIN -> per phase: [HALVE ->] iterations of (snac_uct_select_gumbel -> edges -> evaluator -> snac_uct_backup_paths_norm ->
+ *     snac_uct_set_priors) -> PICK
+ *   on one stream, with no host synchronisation.  The candidate array: caller-owned, B int32; bit a of cand[b] = root action a of tree b is
+ *   a candidate; only bits below num_actions count.  It is not part of snac_uct_node: the caller zeroes it when a tree gets a new root.
+ *   Selection (snac_uct_select_gumbel: the arguments of snac_uct_select_puct_norm, then `cand`, read only, and `offset`).  cand[b] is read
+ *     once when the launch starts, beside the bounds pair; no level waits for that load.  cand[b] == 0 (below num_actions): tree b is
+ *     selected exactly as by snac_uct_select_puct_norm, every output and statistics word bit for bit.  Otherwise let c_0 < ... < c_{M-1}
+ *     be the candidates: path k of the launch takes the root action a = c[(offset + k) mod M] (integers only; no U is computed at the
+ *     root).  A terminal root stops as before.  a tried: the path descends to it.  a untried and used < cap: a is expanded exactly as
+ *     snac_uct_select_puct expands its best action.  a untried and the budget spent: the path stops at the root (leaf = src = the root,
+ *     not expanded, first_slot = -1, r_leaf = the root's reward).  The root rule ignores the in-flight counts but counts them as before;
+ *     slots, scratch rows, fresh rows, first_slot and every output are those of snac_uct_select_puct.  Below the root (depth >= 1) the
+ *     rule is snac_uct_select_puct_norm's, unchanged.  Checks before any HIP call: those of snac_uct_select_puct_norm, then cand non-null,
+ *     offset >= 0, offset + paths within int32.
+ *   Candidates (snac_uct_gumbel_candidates): lane = tree, the statistics READ ONLY.  scores[b * A + a] (A = num_actions) is the caller's
+ *     g(a) + logit(a) in float32; a NaN reads as -inf.  "The n largest of a set by x" below means: n times, take the member with the
+ *     largest x among those not yet taken, by strict > scanning a upward (ties to the lowest a).
+ *       mode 0, BEGIN:  cand[b] = 0 at a terminal root, else the min(m, A) largest of all actions by score.  Of the statistics only the
+ *                       root's terminal word is read.
+ *       mode 1, HALVE:  with M = popcount(cand[b]) (bits below A), cand[b] = the (M + 1) / 2 largest of the candidates by RANK.
+ *       mode 2, PICK:   action[b] = the largest of the candidates by RANK; cand is not written.  cand[b] == 0: the lowest a with the
+ *                       largest child_visits[a] (a negative word reads as zero), 0 when there are none -- the greedy snac_uct_pick_moves.
+ *     RANK of action a at the root R, in float64, no contraction, in this order (lo, hi: the tree's pair of `bounds`):
+ *         maxN = the largest max(R.child_visits[a'], 0) over a' < A with R.child[a'] >= 0 (none: 0)
+ *         visited = R.child[a] >= 0 && R.child_visits[a] > 0
+ *         q = visited ? R.child_value[a] / (double)R.child_visits[a] : first_play_value;   if (visited && hi > lo) q = (q - lo) / (hi - lo)
+ *         s1 = c_visit + (double)maxN;  s2 = s1 * c_scale;  sig = s2 * q;  rank = (double)score + sig;  a NaN rank reads as -inf
+ *     Checks before any HIP call: num_actions, stats, B, cap and rows as snac_uct_pick_moves; mode in 0 .. 2; m >= 1 for BEGIN; scores
+ *     non-null; c_visit, c_scale and first_play_value finite; bounds non-null and 16-byte aligned for HALVE and PICK; cand non-null;
+ *     action non-null for PICK. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -797,6 +829,14 @@ int snac_uct_backup_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_
                                const uint8_t* done, const double* est, double* bounds, void* stream);
 int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* used, const uint8_t* mask,
                     double* bounds, void* stream);
+
+int snac_uct_select_gumbel(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                           double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table, int32_t table_len,
+                           int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                           int32_t* first_slot, const double* bounds, const int32_t* cand, int32_t offset, void* stream);
+int snac_uct_gumbel_candidates(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t mode, int32_t m,
+                               const float* scores, double c_visit, double c_scale, double first_play_value, const double* bounds, int32_t* cand,
+                               int8_t* action, void* stream);
 
 #ifdef __cplusplus
 }

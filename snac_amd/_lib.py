@@ -32,7 +32,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist", "snac_uct_select", "snac_uct_backup",
            "snac_uct_advance", "snac_uct_select_paths", "snac_uct_backup_paths", "snac_observe_nodes1d", "snac_observe_nodes2d",
            "snac_observe_nodes3d", "snac_uct_select_puct", "snac_uct_set_priors", "snac_uct_pick_moves", "snac_uct_restart",
-           "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds")
+           "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds",
+           "snac_uct_select_gumbel", "snac_uct_gumbel_candidates")
 
 
 class Sizes(C.Structure):
@@ -174,6 +175,9 @@ def lib():
         for n in ("snac_uct_select_paths", "snac_uct_select_puct", "snac_uct_backup_paths"):       # the arguments, bounds, the stream
             getattr(L, n + "_norm").argtypes = getattr(L, n).argtypes[:-1] + [vp, vp]
         L.snac_uct_bounds.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+        L.snac_uct_select_gumbel.argtypes = L.snac_uct_select_puct_norm.argtypes[:-1] + [vp, C.c_int32, vp]     # cand, offset, the stream
+        L.snac_uct_gumbel_candidates.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double, C.c_double,
+                                                 C.c_double, vp, vp, vp, vp]
         for k in ("1d", "2d", "3d"):
             getattr(L, "snac_observe_nodes%s" % k).argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, vp, vp]
         L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]

@@ -1,6 +1,7 @@
 // k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance, and the
 // K-paths-per-tree iteration snac_uct_select_paths / snac_uct_backup_paths, and PUCT: snac_uct_select_puct / snac_uct_set_priors
-// and their q_normalise forms snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm with snac_uct_bounds
+// and their q_normalise forms snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm with snac_uct_bounds,
+// and the Gumbel root rule on top of the normalised PUCT selection, snac_uct_select_gumbel
 // (include/snac_hip.h has the semantics)
 #include <cmath>
 #include <cstddef>
@@ -568,11 +569,29 @@ struct UctSelPuctNorm {
     const double* bounds;
 };
 
+// Gumbel root ("Gumbel root" in include/snac_hip.h): the GUMBEL form is the NORM form with another rule at the ROOT of a tree whose
+// candidate mask cand[b] is not zero: path k takes the ((offset + k) mod M)-th of the M candidates, in integers, and no U is computed
+// there.  The mask is one 4-byte load beside the bounds pair, before the descent.  A tree with cand[b] == 0, and every level below a
+// root, runs the NORM code.
+struct UctSelGumbel {
+    UctSelPuctNorm n;
+    const int32_t* cand;
+    int32_t offset;
+};
+
 __device__ __forceinline__ const UctSelPuct& plain(const UctSelPuct& a) { return a; }
 __device__ __forceinline__ const UctSelPuct& plain(const UctSelPuctNorm& a) { return a.z; }
+__device__ __forceinline__ const UctSelPuct& plain(const UctSelGumbel& a) { return a.n.z; }
+__device__ __forceinline__ const double* bounds_of(const UctSelPuctNorm& a) { return a.bounds; }
+__device__ __forceinline__ const double* bounds_of(const UctSelGumbel& a) { return a.n.bounds; }
 
-template <int A, bool NORM>                                          // NORM: a tried child's q normalised (first_play_value is used as given)
-__global__ __launch_bounds__(64) void k_uct_select_puct(const std::conditional_t<NORM, UctSelPuctNorm, UctSelPuct> arg) {
+template <bool NORM, bool GUMBEL>
+using UctSelPuctArg = std::conditional_t<GUMBEL, UctSelGumbel, std::conditional_t<NORM, UctSelPuctNorm, UctSelPuct>>;
+
+// NORM: a tried child's q normalised (first_play_value is used as given); GUMBEL (with NORM): the candidates' turn at the root
+template <int A, bool NORM, bool GUMBEL = false>
+__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM, GUMBEL> arg) {
+    static_assert(NORM || !GUMBEL, "the Gumbel form extends the normalised one");
     constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
     const UctSelPuct& z = plain(arg);
     const UctSelPaths& w = z.p;
@@ -581,7 +600,12 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const std::conditional_t
     if (b >= v.B) return;
     const int base = b * v.cap, K = w.K;
     QRange qr{0.0, 0.0, false};
-    if constexpr (NORM) qr = q_range(arg.bounds, b);
+    if constexpr (NORM) qr = q_range(bounds_of(arg), b);
+    [[maybe_unused]] int cmask = 0, cnum = 1;                        // GUMBEL: the tree's candidates and their number
+    if constexpr (GUMBEL) {
+        cmask = arg.cand[b] & ((1 << A) - 1);
+        cnum = max(__popc((unsigned)cmask), 1);
+    }
     const int used0 = v.used[b];
     const int fresh = base + used0;                                  // rows from here up are made by this launch
     int used = used0;
@@ -604,6 +628,14 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const std::conditional_t
             const double sq = v.ltab[min(max((int)hdr.w + fly, 0), v.tlen - 1)];
             int best = -1, bf = 0, tried = -1, tf = 0, bchild = -1, tchild = -1;
             double bu = 0.0, tu = 0.0;
+            [[maybe_unused]] int turn = -1;                          // GUMBEL, a root with candidates: the action whose turn it is
+            if constexpr (GUMBEL) {
+                if (depth == 0 && cmask != 0) {
+                    int skip = (arg.offset + k) % cnum;
+#pragma unroll
+                    for (int a = A - 1; a >= 0; --a) turn = (cmask >> a & 1) && __popc((unsigned)cmask & ((1u << a) - 1u)) == skip ? a : turn;
+                }
+            }
 #pragma unroll
             for (int a = 0; a < A; ++a) {
                 const uint4 c4 = pc[a / 4], n4 = pn[a / 4], f4 = pf[a / 4], p4 = pp[a / 4], w2 = pw[a / 2];
@@ -611,6 +643,12 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const std::conditional_t
                 const int child = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
                 const int cn = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
                 const int cf = (int)(j == 0 ? f4.x : j == 1 ? f4.y : j == 2 ? f4.z : f4.w);
+                if constexpr (GUMBEL) {
+                    if (turn >= 0) {                                 // no U: the action is given; untried with the budget spent stops here
+                        if (a == turn) { best = a; bf = cf; bchild = child; }
+                        continue;
+                    }
+                }
                 const float pr = __uint_as_float(j == 0 ? p4.x : j == 1 ? p4.y : j == 2 ? p4.z : p4.w);
                 const double cw = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
                 const bool has = child >= 0;
@@ -935,7 +973,8 @@ int snac_uct_backup_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_
 static int select_puct(const char* name, int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths,
                        double c, double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
                        int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
-                       float* r_leaf, int32_t* first_slot, bool norm, const double* bounds, void* stream) {
+                       float* r_leaf, int32_t* first_slot, bool norm, const double* bounds, bool gumbel, const int32_t* cand, int32_t offset,
+                       void* stream) {
     using namespace snac_detail;
     if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
     if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
@@ -946,6 +985,11 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
         return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
     if (norm)
         if (int rc = bounds_check(bounds)) return rc;
+    if (gumbel) {
+        if (!cand) return fail(SNAC_ERR_ARG, "null cand");
+        if (offset < 0) return fail(SNAC_ERR_ARG, "offset must be >= 0");
+        if ((long long)offset + (long long)paths > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "offset + paths exceeds int32");
+    }
     const UctSelPuct v{{{(uint4*)stats, B, cap, c, sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
                         paths, virtual_loss, first_slot},
                        first_play_value};
@@ -953,7 +997,8 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
     g_kernel = "k_uct_select_puct";
     by_actions(num_actions, [&](auto k) {
         constexpr int A = decltype(k)::value;
-        if (norm) hipLaunchKernelGGL((k_uct_select_puct<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPuctNorm{v, bounds});
+        if (cand) hipLaunchKernelGGL((k_uct_select_puct<A, true, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelGumbel{{v, bounds}, cand, offset});
+        else if (norm) hipLaunchKernelGGL((k_uct_select_puct<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPuctNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_select_puct<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
     const hipError_t e = hipGetLastError();
@@ -965,7 +1010,7 @@ int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stat
                          int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
                          int32_t* first_slot, void* stream) {
     return select_puct("snac_uct_select_puct", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
-                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, false, nullptr, stream);
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, false, nullptr, false, nullptr, 0, stream);
 }
 
 int snac_uct_select_puct_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -973,7 +1018,15 @@ int snac_uct_select_puct_norm(int32_t num_actions, snac_uct_node* stats, int32_t
                               int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
                               float* r_leaf, int32_t* first_slot, const double* bounds, void* stream) {
     return select_puct("snac_uct_select_puct_norm", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
-                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, stream);
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, false, nullptr, 0, stream);
+}
+
+int snac_uct_select_gumbel(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                           double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table, int32_t table_len,
+                           int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
+                           int32_t* first_slot, const double* bounds, const int32_t* cand, int32_t offset, void* stream) {
+    return select_puct("snac_uct_select_gumbel", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, true, cand, offset, stream);
 }
 
 int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,

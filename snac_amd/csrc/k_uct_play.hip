@@ -1,6 +1,7 @@
 // k_uct_play.hip -- self-play on the UCT trees of k_uct.hip: snac_uct_pick_moves (a move per tree from the root's visit counts, with the
-// visit distribution and the root value), snac_uct_restart (a new episode in some trees, the others untouched) and snac_uct_returns
-// (value targets from a ring of rewards).  include/snac_hip.h, "Self-play", has the semantics.
+// visit distribution and the root value), snac_uct_restart (a new episode in some trees, the others untouched), snac_uct_returns
+// (value targets from a ring of rewards) and snac_uct_gumbel_candidates (the candidate sets and the move of the Gumbel root search).
+// include/snac_hip.h, "Self-play" and "Gumbel root", has the semantics.
 #include <cmath>
 #include <cstddef>
 
@@ -136,6 +137,109 @@ __global__ __launch_bounds__(64) void k_uct_returns(const UctReturns v) {
     }
 }
 
+// ---- Gumbel root: candidate sets and the final move --------------------------------------------------------------------------------------
+// lane = tree, as k_uct_pick: the root's line 0 (children, child visits, child values), its header's terminal word, the tree's A scores
+// and its bounds pair are all issued before the first is used; the choice is A rounds of "the largest remaining by strict >, scanning a
+// upward" over at most 8 ranks held in registers.
+constexpr int P_CHILD = 0, P_VALUE = 4;
+constexpr int GUMBEL_BEGIN = 0, GUMBEL_HALVE = 1, GUMBEL_PICK = 2;
+
+struct UctGumbel {
+    const uint4* stats;
+    int32_t B, cap, mode, m;
+    const float* scores;
+    double c_visit, c_scale, fpv;
+    const double* bounds;
+    int32_t* cand;
+    int8_t* action;
+};
+
+// the `keep` members of `from` (a mask over a < A) with the largest rank: one at a time, the largest remaining by strict >, a upward
+template <int A>
+__device__ __forceinline__ int top_ranks(const double (&rank)[A], int from, int keep) {
+    int out = 0;
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        if (i >= keep) break;
+        int best = -1;
+        double br = 0.0;
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+            const bool open = (from >> a & 1) != 0 && (out >> a & 1) == 0;
+            if (open && (best < 0 || rank[a] > br)) { best = a; br = rank[a]; }
+        }
+        if (best >= 0) out |= 1 << best;
+    }
+    return out;
+}
+
+template <int A>
+__global__ __launch_bounds__(64) void k_uct_gumbel(const UctGumbel v) {
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b >= v.B) return;
+    const uint4* const rec = v.stats + (size_t)b * v.cap * PIECES;
+    const bool begin = v.mode == GUMBEL_BEGIN;
+    const uint4 hdr = rec[P_HDR];
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+    uint4 c0 = zero4, c1 = zero4, n0 = zero4, n1 = zero4, w[4] = {zero4, zero4, zero4, zero4};
+    double2 pair = make_double2(0.0, 0.0);
+    int from = (1 << A) - 1;
+    if (!begin) {                                                    // BEGIN reads no statistics but the root's terminal word
+        c0 = rec[P_CHILD]; c1 = rec[P_CHILD + 1];
+        n0 = rec[P_VISITS]; n1 = rec[P_VISITS + 1];
+#pragma unroll
+        for (int q = 0; q < (A + 1) / 2; ++q) w[q] = rec[P_VALUE + q];
+        pair = reinterpret_cast<const double2*>(v.bounds)[b];
+        from &= v.cand[b];
+    }
+    float score[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) score[a] = v.scores[(size_t)b * A + a];
+    const uint32_t ch[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w}, nn[8] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+    int maxn = 0;
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+        if ((int)ch[a] >= 0) maxn = max(maxn, max((int)nn[a], 0));
+    double rank[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+#pragma clang fp contract(off)                                      // no fma: the rank rounded step by step, as a host restatement computes it
+        double x = (double)score[a];
+        if (!begin) {
+            const uint4 w2 = w[a / 2];
+            const double wa = (a % 2 == 0) ? __hiloint2double((int)w2.y, (int)w2.x) : __hiloint2double((int)w2.w, (int)w2.z);
+            const bool visited = (int)ch[a] >= 0 && (int)nn[a] > 0;
+            double q = visited ? wa / (double)(int)nn[a] : v.fpv;
+            if (visited && pair.y > pair.x) {
+                const double d = q - pair.x, span = pair.y - pair.x;
+                q = d / span;
+            }
+            const double s1 = v.c_visit + (double)maxn;
+            const double s2 = s1 * v.c_scale;
+            const double sig = s2 * q;
+            x = x + sig;
+        }
+        rank[a] = x != x ? -INFINITY : x;
+    }
+    if (begin) {
+        v.cand[b] = hdr.z != 0u ? 0 : top_ranks<A>(rank, from, min(v.m, A));
+    } else if (v.mode == GUMBEL_HALVE) {
+        v.cand[b] = top_ranks<A>(rank, from, (__popc((unsigned)from) + 1) / 2);
+    } else {
+        int act = 0;
+        if (from != 0) {
+            const int one = top_ranks<A>(rank, from, 1);
+            act = __ffs(one) - 1;
+        } else {                                                     // no candidates: the lowest a with the most child visits
+            int best = max((int)nn[0], 0);
+#pragma unroll
+            for (int a = 1; a < A; ++a)
+                if (max((int)nn[a], 0) > best) { best = max((int)nn[a], 0); act = a; }
+        }
+        v.action[b] = (int8_t)act;
+    }
+}
+
 int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     using namespace snac_detail;
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
@@ -203,6 +307,32 @@ int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count,
     hipLaunchKernelGGL(k_uct_returns, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_returns");
+}
+
+int snac_uct_gumbel_candidates(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t mode, int32_t m,
+                               const float* scores, double c_visit, double c_scale, double first_play_value, const double* bounds, int32_t* cand,
+                               int8_t* action, void* stream) {
+    using namespace snac_detail;
+    if (int rc = play_check(num_actions, stats, stats_rows, B, cap)) return rc;
+    if (mode < GUMBEL_BEGIN || mode > GUMBEL_PICK) return fail(SNAC_ERR_ARG, "mode must be 0 (begin), 1 (halve) or 2 (pick)");
+    if (mode == GUMBEL_BEGIN && m < 1) return fail(SNAC_ERR_ARG, "m must be >= 1");
+    if (!scores) return fail(SNAC_ERR_ARG, "null scores");
+    if (!std::isfinite(c_visit) || !std::isfinite(c_scale)) return fail(SNAC_ERR_ARG, "c_visit and c_scale must be finite");
+    if (!std::isfinite(first_play_value)) return fail(SNAC_ERR_ARG, "first_play_value must be finite");
+    if (mode != GUMBEL_BEGIN) {
+        if (!bounds) return fail(SNAC_ERR_ARG, "null bounds");
+        if (((uintptr_t)bounds & 15) != 0) return fail(SNAC_ERR_ARG, "bounds must be 16-byte aligned (a tree's pair is one piece)");
+    }
+    if (!cand) return fail(SNAC_ERR_ARG, "null cand");
+    if (mode == GUMBEL_PICK && !action) return fail(SNAC_ERR_ARG, "null action");
+    const UctGumbel v{(const uint4*)stats, B, cap, mode, m, scores, c_visit, c_scale, first_play_value, bounds, cand, action};
+    const dim3 grid((unsigned)((B + 63) / 64));
+    g_kernel = "k_uct_gumbel";
+    if (num_actions == 3) hipLaunchKernelGGL((k_uct_gumbel<3>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else if (num_actions == 5) hipLaunchKernelGGL((k_uct_gumbel<5>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else hipLaunchKernelGGL((k_uct_gumbel<8>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_gumbel_candidates");
 }
 
 }  // extern "C"

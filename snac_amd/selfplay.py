@@ -19,6 +19,11 @@ root.  Everything lands in ring slot `head`; nothing crosses the bus and the hos
 A search built with q_normalise=True plays the same way: advance() and restart() keep its q bounds (snac_amd/uct.py), nothing here
 knows them.
 
+SelfPlay(search, ..., gumbel=True) on a UCTSearch(gumbel=m) plays by the Gumbel root search ("Gumbel root" in include/snac_hip.h) in place
+of PUCT at the root and the visit counts: per move gumbel_begin() on log-priors with Gumbel noise (for the first `sample_moves` moves
+of an episode; without noise after that), gumbel_run(iterations), action = gumbel_actions(), pi = improved_policy(); value, reward, done
+and the re-rooting are as above.  Exploration comes from the Gumbel noise: there is no root_noise hook in this mode.
+
 The ring, over moves (slot = move % capacity_moves), every tensor on the env's device:
     obs [cap, B, D] env.obs_dtype   pi [cap, B, A] float32   value [cap, B] float32   action [cap, B] int8
     reward [cap, B] float32   done [cap, B] uint8   move [cap, B] int32 (the move's index inside its episode)   z [cap, B] float32
@@ -35,11 +40,22 @@ def _ptr(t):
 
 
 class SelfPlay:
-    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None):
+    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None, gumbel=False, generator=None):
         """search: a UCTSearch with one tree per env row (reset() by the caller); capacity_moves: ring slots; sample_moves: the moves of
         an episode drawn in proportion to the visits (the rest: argmax); gamma: of the value targets (default: the search's);
         root_noise: PUCT only, priors [B, A] -> priors [B, A], applied to the roots before every move's search (exploration noise is the
-        caller's)."""
+        caller's).  gumbel=True (a UCTSearch(gumbel=m), root_noise None): the moves and policy targets of the Gumbel root search, with
+        Gumbel noise in the first sample_moves moves of an episode drawn from `generator` (a torch.Generator of the env's device; None:
+        the default one)."""
+        if not isinstance(gumbel, bool):
+            raise ValueError("gumbel must be a bool")
+        if gumbel and getattr(search, "gumbel", None) is None:
+            raise ValueError("gumbel=True needs a Gumbel search: UCTSearch(gumbel=m)")
+        if gumbel and root_noise is not None:
+            raise ValueError("root_noise does not go with gumbel=True: the Gumbel noise explores")
+        if generator is not None and not gumbel:
+            raise ValueError("generator belongs to gumbel=True")
+        self.gumbel, self.generator = gumbel, generator
         self.cap, self.sample_moves = int(capacity_moves), int(sample_moves)
         if self.cap < 1 or self.cap != capacity_moves:
             raise ValueError("capacity_moves must be an integer >= 1")
@@ -71,6 +87,7 @@ class SelfPlay:
         self._next = torch.zeros(B, dtype=torch.int32, device=dev)
         self._zero = torch.zeros(B, dtype=torch.int32, device=dev)
         self._greedy = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self._noisy = torch.zeros((B, 1), dtype=torch.bool, device=dev)
         self._boot = torch.zeros(B, dtype=torch.float32, device=dev)
         self._observe = getattr(search._lib, search.pool.OBSERVE)
         self._root_rows = search._adv_src                            # int32 [B]: row b * cap
@@ -93,13 +110,21 @@ class SelfPlay:
         with torch.cuda.device(env.device):
             for _ in range(moves):
                 h = self.head
-                if self.root_noise is not None:
-                    s.set_root_priors(self.root_noise(s.root_priors()))
-                s._run(n)
+                if self.gumbel:
+                    self._gumbel_search(n)
+                else:
+                    if self.root_noise is not None:
+                        s.set_root_priors(self.root_noise(s.root_priors()))
+                    s._run(n)
                 _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), _ptr(P.records), P.rows, B, _ptr(self._root_rows),
                                          _ptr(self.obs[h]), env._stream()))
-                torch.ge(self._move, self.sample_moves, out=self._greedy.view(torch.bool))
-                s._pick(self._greedy, self.moves, self.action[h], self.pi[h], self.value[h])
+                if self.gumbel:
+                    s.gumbel_actions(out=self.action[h])
+                    self.pi[h].copy_(s.improved_policy())
+                    s._pick(None, 0, None, None, self.value[h])      # the root's W / N
+                else:
+                    torch.ge(self._move, self.sample_moves, out=self._greedy.view(torch.bool))
+                    s._pick(self._greedy, self.moves, self.action[h], self.pi[h], self.value[h])
                 s._advance_into(self.action[h], self.reward[h], self.done[h], prime=False)   # restart() primes every unvisited root
                 self.move[h].copy_(self._move)
                 env.reset(mask=self.done[h], want_obs=False)         # the finished trees' env rows: the next episode (and its plan)
@@ -108,6 +133,14 @@ class SelfPlay:
                 torch.where(self.done[h].view(torch.bool), self._zero, self._next, out=self._move)
                 self.head = (h + 1) % self.cap
                 self.moves += 1
+
+    def _gumbel_search(self, n):
+        """A move's Gumbel root search: candidates from noisy scores in the first sample_moves moves of a tree's episode, from the
+        log-priors alone after that (one torch.where of the two), then the sequential-halving iterations."""
+        s = self.search
+        torch.lt(self._move.view(-1, 1), self.sample_moves, out=self._noisy)
+        s.gumbel_begin(torch.where(self._noisy, s.gumbel_scores(True, self.generator), s.gumbel_scores(False)))
+        s._gumbel_run(n)
 
     # ---- the ring ---------------------------------------------------------------------------------------------------------
     def valid_moves(self):

@@ -1,7 +1,7 @@
 """Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
 snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors, snac_uct_pick_moves / snac_uct_restart,
-snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds: include/snac_hip.h;
-snac_amd/csrc/k_uct.hip, k_uct_play.hip).
+snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds, snac_uct_select_gumbel /
+snac_uct_gumbel_candidates: include/snac_hip.h; snac_amd/csrc/k_uct.hip, k_uct_play.hip).
 
 B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
 stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
@@ -85,6 +85,20 @@ return still to collect shrinks along an episode; a one-node tree: empty), all o
 
     search = UCTSearch(env, nodes_per_tree=512, horizon=0, gamma=0.99, c=1.25, paths=16, evaluator=fn, q_normalise=True)
 
+Small budgets: gumbel=m (with an evaluator and q_normalise=True) adds the Gumbel root search of Gumbel AlphaZero / MuZero (Danihelka et
+al. 2022; "Gumbel root" in include/snac_hip.h).  At a few dozen iterations per move PUCT's visit counts are a poor policy target and an
+unvisited action gets target 0; instead m root actions are sampled without replacement by Gumbel-top-k, the budget is spent on them by
+sequential halving, the survivor is played and the target is an improved policy built from completed q-values.  Below the root the
+search is the normalised PUCT search.  `cand` (int32 [B], a bit per root action) holds the candidates; reset(), advance() and restart()
+zero it, and with cand all zero run(n) is the PUCT search.
+
+    search = UCTSearch(env, 512, 0, 0.99, c=1.25, paths=4, evaluator=fn, q_normalise=True, gumbel=4)
+    search.reset()
+    search.gumbel_begin(search.gumbel_scores())          # log-priors + Gumbel noise -> the 4 candidates of every tree
+    search.gumbel_run(32)                                # gumbel_schedule(32, 4): two phases of 16 iterations, a halving between them
+    a, pi = search.gumbel_actions(), search.improved_policy()
+    r, d = search.advance(a)
+
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
 t0 = it * (H + 1) + 1, so no two iterations share a word.  Path k of tree b draws both with the key (env_id_base + b) * K + k, its slot
 in the search over ALL envs, so no two paths share a word either and a shard of the trees (env_id_base = E: dist.py) searches exactly as
@@ -119,18 +133,46 @@ def uct_tables(n):
     return lt, rt
 
 
+def gumbel_schedule(n, m):
+    """The sequential-halving plan of n iterations over m candidates: max(1, ceil(log2 m)) phases of n // phases iterations each, the
+    last phase taking the remainder.  Returns [(halve, i)] per iteration: halve -- the candidates are halved before it (the first
+    iteration of every phase but the first); i -- its index inside its phase.  The candidates then run m -> ceil(m / 2) -> ... -> 2."""
+    n, m = int(n), int(m)
+    if m < 1:
+        raise ValueError("m must be >= 1")
+    phases = max(1, (m - 1).bit_length())
+    if n < phases:
+        raise ValueError("%d iterations cannot cover the %d halving phases of %d candidates" % (n, phases, m))
+    L = n // phases
+    plan = []
+    for p in range(phases):
+        length = L if p < phases - 1 else n - L * (phases - 1)
+        plan += [(p > 0 and i == 0, i) for i in range(length)]
+    return plan
+
+
 class UCTSearch:
     """UCT over `trees` independent trees of `nodes_per_tree` nodes each on one NodePool of env's kind (include/snac_hip.h, "UCT tree
     search", has the exact selection and backup rules).  paths=K > 1: K paths per tree and iteration with `virtual_loss` per in-flight
     path ("K paths per tree and iteration" there).  Everything is allocated here; run() only enqueues work."""
 
     def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None, paths=1, virtual_loss=0.0,
-                 evaluator=None, first_play_value=None, q_normalise=False):
+                 evaluator=None, first_play_value=None, q_normalise=False, gumbel=None, gumbel_c_visit=50.0, gumbel_c_scale=1.0):
         """evaluator: None (the rollout search) or a callable obs [S, obs_dim] -> (priors [S, A], value [S]) that guides a PUCT search
         (the module docstring); first_play_value (PUCT only, default 0.0): the q of an untried action.  q_normalise (a bool): compare
-        q normalised by the tree's min-max bounds (the module docstring); q_bounds is then a [B, 2] float64 tensor, else None."""
+        q normalised by the tree's min-max bounds (the module docstring); q_bounds is then a [B, 2] float64 tensor, else None.
+        gumbel (None or m >= 1; needs an evaluator and q_normalise=True): the Gumbel root search over m sampled root actions (the module
+        docstring, "Gumbel root"), with sigma(q) = (gumbel_c_visit + max_a N_a) * gumbel_c_scale * q."""
         if not isinstance(q_normalise, bool):
             raise ValueError("q_normalise must be a bool")
+        if gumbel is not None:
+            if isinstance(gumbel, bool) or not isinstance(gumbel, int) or gumbel < 1:
+                raise ValueError("gumbel must be an integer >= 1")
+            if evaluator is None or not q_normalise:
+                raise ValueError("the Gumbel root search needs an evaluator and q_normalise=True")
+            if not (math.isfinite(float(gumbel_c_visit)) and math.isfinite(float(gumbel_c_scale))):
+                raise ValueError("gumbel_c_visit and gumbel_c_scale must be finite")
+        self.gumbel, self.gumbel_c_visit, self.gumbel_c_scale = gumbel, float(gumbel_c_visit), float(gumbel_c_scale)
         if evaluator is not None and not callable(evaluator):
             raise ValueError("evaluator must be callable: obs [S, obs_dim] -> (priors [S, A], value [S])")
         if first_play_value is not None and evaluator is None:
@@ -229,6 +271,15 @@ class UCTSearch:
             self._select_args += (_ptr(self.q_bounds),)
             self._backup_args += (_ptr(self.q_bounds),)
             self._bounds_args = (_ptr(self.stats), self.rows, B, cap, _ptr(self._used))
+        self.cand = None
+        if gumbel is not None:                                       # snac_uct_select_gumbel: the _norm arguments, then cand and the offset
+            self.cand = torch.zeros(B, dtype=torch.int32, device=dev)
+            self._gumbel_begun = False
+            self._gscores = torch.zeros((B, self.num_actions), dtype=torch.float32, device=dev)
+            self._select_args += (_ptr(self.cand),)
+            self._cand_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap)
+            self._cand_tail = (_ptr(self._gscores), self.gumbel_c_visit, self.gumbel_c_scale, self.first_play_value, _ptr(self.q_bounds),
+                               _ptr(self.cand))
         self._edge_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._src), _ptr(self._dst))
         self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
         self._eval_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), self.horizon)
@@ -276,6 +327,7 @@ class UCTSearch:
         self._iteration = 0
         if self.q_normalise:
             self.q_bounds.copy_(self._no_bounds.expand(B, 2))
+        self._no_candidates()
         if self.evaluator is not None:
             with torch.cuda.device(env.device):
                 self._prime_roots()
@@ -329,6 +381,7 @@ class UCTSearch:
         prime=False leaves the priors of the new roots to a priming that follows (restart())."""
         with torch.cuda.device(self.env.device):
             self._adv_action.copy_(a.clamp(0, self.num_actions - 1))
+            self._no_candidates()
             self._root_edges()
             self._reroot(reward, done)
             if self.q_normalise:                                     # every tree: the bounds of the subtree it kept
@@ -403,6 +456,7 @@ class UCTSearch:
         P = self.pool
         with torch.cuda.device(env.device):
             torch.ne(m.to(env.device).reshape(-1), 0, out=self._rs_mask.view(torch.bool))
+            self._no_candidates()
             _lib.check(self._pack(C.byref(env._desc), C.byref(env._state), None if rows is None else _ptr(rows), B, _ptr(P.records), P.rows,
                                   _ptr(self._adv_dst), env._stream()))
             torch.bitwise_right_shift(self._rs_hdr, 16, out=self._rs_flags)          # the loaded records' NEED_RESET
@@ -434,8 +488,11 @@ class UCTSearch:
     def _t(self):
         return (self._iteration * (self.horizon + 1)) & 0xFFFFFFFF
 
-    def _select(self):
+    def _select(self, offset=0):
         L = self._lib
+        if self.gumbel is not None:                                  # cand all zero: snac_uct_select_puct_norm's search
+            _lib.check(L.snac_uct_select_gumbel(*self._select_args, offset, self.env._stream()))
+            return
         if self.evaluator is not None:
             fn = L.snac_uct_select_puct_norm if self.q_normalise else L.snac_uct_select_puct
         elif self.q_normalise:
@@ -539,6 +596,116 @@ class UCTSearch:
     def iterations(self):
         """Iterations enqueued since reset()."""
         return self._iteration
+
+    # ---- the Gumbel root search (include/snac_hip.h, "Gumbel root") ---------------------------------------------------------------
+    def _no_candidates(self):
+        """A new root: no candidate set steers it (one torch op, no host synchronisation)."""
+        if self.gumbel is not None:
+            self.cand.zero_()
+            self._gumbel_begun = False
+
+    def _need_gumbel(self):
+        if self.gumbel is None:
+            raise ValueError("not a Gumbel search: give UCTSearch gumbel=m")
+
+    def _candidates(self, mode, action=None):
+        _lib.check(self._lib.snac_uct_gumbel_candidates(*self._cand_args, mode, self.gumbel, *self._cand_tail,
+                                                        None if action is None else _ptr(action), self.env._stream()))
+
+    def gumbel_scores(self, noise=True, generator=None):
+        """[B, A] float32: log(root_priors()), plus a Gumbel(0, 1) sample -log(-log(U)) per entry with noise=True, U from torch.rand on the
+        env's device (generator: a torch.Generator of that device).  A prior of 0 gives -inf: the action is never a candidate before
+        one with a positive prior."""
+        self._need_gumbel()
+        logits = torch.log(self.root_priors())
+        if not noise:
+            return logits
+        u = torch.rand(logits.shape, dtype=torch.float32, device=self.env.device, generator=generator)
+        return logits - torch.log(-torch.log(u))
+
+    def gumbel_begin(self, scores):
+        """Candidate sets for this move: cand[b] <- the min(m, A) root actions of tree b with the largest scores[b] ([B, A], stored as
+        float32: g(a) + logit(a), gumbel_scores(); ties to the lowest a, NaN as -inf), none at a terminal root (snac_uct_gumbel_candidates,
+        BEGIN).  The scores stay with the search for the halvings and the final move."""
+        self._need_gumbel()
+        s = torch.as_tensor(scores, device=self.env.device)
+        if tuple(s.shape) != (self.trees, self.num_actions):
+            raise ValueError("scores must be [%d, %d]" % (self.trees, self.num_actions))
+        with torch.cuda.device(self.env.device):
+            self._gscores.copy_(s)
+            self._candidates(0)
+        self._gumbel_begun = True
+
+    def gumbel_run(self, iterations):
+        """Enqueue `iterations` iterations split by gumbel_schedule(iterations, min(m, A)) into sequential-halving phases: the phase's
+        candidates are visited in turn (iteration i of a phase sends its K paths to candidates i * K, i * K + 1, ... modulo their
+        number), and before every phase but the first the candidates are halved by g + logit + sigma(q) (snac_uct_gumbel_candidates,
+        HALVE).  Needs gumbel_begin() since the last reset() / advance() / restart().  No host synchronisation."""
+        n = int(iterations)
+        if self._iteration + n > self.max_iterations:
+            raise ValueError("%d iterations after %d exceed max_iterations = %d" % (n, self._iteration, self.max_iterations))
+        self._gumbel_run(n)
+
+    def _gumbel_run(self, n):
+        """gumbel_run() without the budget check (SelfPlay bounds the visit counts per episode)."""
+        self._need_gumbel()
+        if not self._gumbel_begun:
+            raise ValueError("gumbel_run() needs gumbel_begin() since the last reset(), advance() or restart()")
+        plan = gumbel_schedule(n, min(self.gumbel, self.num_actions))
+        K = self.paths
+        with torch.cuda.device(self.env.device):
+            for halve, i in plan:
+                if halve:
+                    self._candidates(1)
+                self._select(i * K)
+                self._edges()
+                self._evaluate()
+                self._backup()
+                self._set_priors()
+
+    def gumbel_actions(self, out=None):
+        """[B] int8: the move of the Gumbel search, the remaining candidate with the largest g + logit + sigma(q) (ties to the lowest; a
+        tree without candidates: the most-visited action as best_actions(), 0 without visits): snac_uct_gumbel_candidates, PICK.
+        out: a contiguous int8 [B] tensor on the env's device to write into."""
+        self._need_gumbel()
+        dev = self.env.device
+        if out is None:
+            out = torch.empty(self.trees, dtype=torch.int8, device=dev)
+        elif (not torch.is_tensor(out) or tuple(out.shape) != (self.trees,) or out.dtype != torch.int8 or not out.is_contiguous()
+              or out.device != dev):
+            raise ValueError("out must be a contiguous int8 [%d] tensor on %s" % (self.trees, dev))
+        with torch.cuda.device(dev):
+            self._candidates(2, out)
+        return out
+
+    def improved_policy(self):
+        """[B, A] float32: the policy target of the Gumbel search, softmax(logits + sigma(completed q)) in float64 torch ops.  logits =
+        log(root priors); q of a visited root child (N_a > 0) is its normalised W_a / N_a, q of every other action the normalised
+        sum W_visited / sum N_visited; sigma(q) = (c_visit + max_a N_a) * c_scale * q.  A root without a visited child gives its
+        normalised priors.  The value given to unvisited actions simplifies the paper's v_mix (Danihelka et al. 2022, eq. 33), which
+        also mixes in the root's network value weighted by the priors: that value is not stored in the tree, so the visit-weighted
+        mean of the visited children's q stands in for it.  No host synchronisation."""
+        self._need_gumbel()
+        A = self.num_actions
+        r = self.stats[self._roots]
+        child, N = r[:, :A], r[:, 8:8 + A]
+        W = r[:, 16:32].contiguous().view(torch.float64)[:, :A]
+        visited = (child >= 0) & (N > 0)
+        zero = torch.zeros_like(W)
+        n = torch.where(visited, N.to(torch.float64), zero)
+        w = torch.where(visited, W, zero)
+        sum_n = n.sum(1, keepdim=True)
+        any_visit = sum_n > 0
+        one = torch.ones_like(sum_n)
+        mixed = w.sum(1, keepdim=True) / torch.where(any_visit, sum_n, one)      # every unvisited action's q
+        q = torch.where(visited, w / torch.where(visited, n, one), mixed)
+        lo, hi = self.q_bounds[:, 0:1], self.q_bounds[:, 1:2]
+        on = hi > lo
+        q = torch.where(on, (q - lo) / torch.where(on, hi - lo, one), q)
+        sig = (self.gumbel_c_visit + n.max(1, keepdim=True).values) * self.gumbel_c_scale * q
+        sig = torch.where(any_visit, sig, zero)
+        logits = torch.log(self.root_priors().to(torch.float64))
+        return torch.softmax(logits + sig, 1).to(torch.float32)
 
     # ---- readers ----------------------------------------------------------------------------------------------------------
     def root_visits(self):
