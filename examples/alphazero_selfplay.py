@@ -3,13 +3,15 @@ episodes with it and records (observation, visit distribution, return) per move,
 cross-entropy to the visit distribution, squared error to the discounted return.  An illustration of the interfaces, not a tuned
 trainer: nothing but the final printout crosses the bus.
 
-    python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20] [--normalise] [--gumbel M]
+    python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20] [--normalise] [--gumbel M [--gumbel-interior]]
 
 --normalise: the search compares q normalised by each tree's min-max bounds (UCTSearch(q_normalise=True)), so that c = 1.25 weighs
 the priors against returns of any scale (a brick pays 5 here).
 --gumbel M: the Gumbel root search (UCTSearch(gumbel=M), SelfPlay(gumbel=True); it normalises q): M root actions sampled by Gumbel noise
 share the 8 iterations of a move by sequential halving, and the policy target is the improved policy, which is above zero for
 actions the search never visited.
+--gumbel-interior (with --gumbel M): the Gumbel rule below the root too (UCTSearch(gumbel_interior=True)): every node keeps its network
+value, selection follows the node's improved policy in place of PUCT, and the policy target uses the full v_mix.
 """
 import argparse
 import os
@@ -23,7 +25,7 @@ from snac_amd import BatchedDMPEnv, SelfPlay, UCTSearch  # noqa: E402
 
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
-          gumbel=None):
+          gumbel=None, gumbel_interior=False):
     """`steps` rounds of play(moves) -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the SelfPlay)."""
     env = BatchedDMPEnv(kind, True, envs, seed=seed)
     env.reset()
@@ -41,7 +43,8 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
         return 0.75 * priors + 0.25 / A
 
     search = UCTSearch(env, nodes, 0, 0.99, c=1.25, paths=paths, evaluator=evaluator, max_iterations=(env.total_step + 1) * iterations,
-                       q_normalise=bool(normalise) or gumbel is not None, gumbel=gumbel)
+                       q_normalise=bool(normalise) or gumbel is not None, gumbel=gumbel,
+                       gumbel_interior=bool(gumbel_interior))
     search.reset()
     if gumbel is None:
         play = SelfPlay(search, capacity, sample_moves=8, root_noise=noise)
@@ -70,8 +73,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--normalise", action="store_true")
     ap.add_argument("--gumbel", type=int, default=None, metavar="M")
+    ap.add_argument("--gumbel-interior", action="store_true")
     args = ap.parse_args()
-    losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps, normalise=args.normalise, gumbel=args.gumbel)
+    if args.gumbel_interior and args.gumbel is None:
+        ap.error("--gumbel-interior needs --gumbel M")
+    losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps, normalise=args.normalise, gumbel=args.gumbel,
+                         gumbel_interior=args.gumbel_interior)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     print("loss: first %.4f, last %.4f" % (losses[0], losses[-1]))
 

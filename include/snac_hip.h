@@ -766,7 +766,47 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *         s1 = c_visit + (double)maxN;  s2 = s1 * c_scale;  sig = s2 * q;  rank = (double)score + sig;  a NaN rank reads as -inf
  *     Checks before any HIP call: num_actions, stats, B, cap and rows as snac_uct_pick_moves; mode in 0 .. 2; m >= 1 for BEGIN; scores
  *     non-null; c_visit, c_scale and first_play_value finite; bounds non-null and 16-byte aligned for HALVE and PICK; cand non-null;
- *     action non-null for PICK. */
+ *     action non-null for PICK.
+ * Gumbel interior: the Gumbel rule below the root as well, and the improved policy with the full v_mix (Danihelka et al. 2022, Gumbel
+ *   MuZero, section 5 and appendix D; snac_uct_set_priors_value / snac_uct_select_gumbel_interior / snac_uct_improved_policy, k_uct.hip;
+ *   UCTSearch(gumbel=m, gumbel_interior=True)).  An iteration is that of "Gumbel root" with snac_uct_select_gumbel_interior in place of
+ *   snac_uct_select_gumbel and snac_uct_set_priors_value in place of snac_uct_set_priors.
+ *   The network value: words 56-57 of a node (net_value, float64) hold the value the evaluator gave for the node's state, 0 for a terminal
+ *     node.  snac_uct_set_priors_value (the arguments of snac_uct_set_priors, and `value`, m float64, before only_unvisited) is
+ *     snac_uct_set_priors and, for the same rows under the same skip rules, net_value <- value[i] (one 8-byte store; no other word
+ *     changes).  snac_uct_advance moves the words with a kept node bit for bit; the backups and snac_uct_restart, which write an expanded
+ *     or restarted row whole, zero them; no other entry point reads or writes them.  Checks before any HIP call: those of
+ *     snac_uct_set_priors, then value non-null.
+ *   The improved policy pi' of a non-terminal node n, in float64, no contraction, in this order (lo, hi: the tree's pair of `bounds`;
+ *     P_a: the in-flight count of child[a], every P_a = 0 in snac_uct_improved_policy; v = n.net_value; p_a = (double)prior_n[a]):
+ *         has_a = child[a] >= 0;  N_a = has_a ? max(child_visits[a], 0) : 0;  P_a = has_a ? in-flight : 0;  vis_a = has_a && N_a > 0
+ *         sumN = sum N_a;  sumP = sum P_a;  maxN = max N_a        (int32, a ascending: the caller keeps sumN + sumP within int32)
+ *         q_a  = W_a / (double)N_a                                  (vis_a only)
+ *         sp = sum_{vis} p_a;  spq = sum_{vis} p_a * q_a;  sW = sum_{vis} W_a        (a ascending, from 0.0)
+ *         vmix = sumN == 0 ? v : (v + (double)sumN * (sp > 0 ? spq / sp : sW / (double)sumN)) * inv_table[sumN]
+ *         qh_a = vis_a ? q_a : vmix;      if (hi > lo) qh_a = (qh_a - lo) / (hi - lo)      (hi - lo computed once per tree)
+ *         s1 = c_visit + (double)maxN;  s2 = s1 * c_scale;  sig_a = s2 * qh_a
+ *         smax = -inf;  for a ascending: if (sig_a > smax) smax = sig_a                    (a NaN never wins)
+ *         e_a = p_a * uct_exp(sig_a - smax);   Z = sum e_a (a ascending, from 0.0);   pi_a = Z > 0 ? e_a / Z : 0
+ *     This is softmax(log p + sig) without a logarithm.  inv_table[i] = 1 / (1 + i) is PUCT's table, its index clamped as there;
+ *     snac_uct_improved_policy takes no table and computes 1.0 / (1.0 + (double)sumN), the table's entry wherever sumN < table_len.
+ *     uct_exp(x), made of float64 + - *, floor and ldexp alone so that a host restatement reproduces it bit for bit (within 1 ulp of exp
+ *     on [-700, 0]): a NaN x or x < -700.0 gives 0.0; x > 0 reads as 0; k = floor(x * LOG2E + 0.5); r = (x - k * LN2_HI) - k * LN2_LO with
+ *     LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42fee00000p-1, LN2_LO = 0x1.a39ef35793c76p-33; p = the Horner sum of r^i / i! from
+ *     i = 13 down to 0 (p = 1.0 / 13!; p = p * r + 1.0 / i!, the coefficients the float64 quotients 1.0 / i!); the result is ldexp(p, k).
+ *   Selection (snac_uct_select_gumbel_interior: the arguments of snac_uct_select_gumbel, then c_visit and c_scale).  A root with
+ *     candidates (cand[b] != 0) takes its turn action; slots, scratch rows, fresh rows, first_slot, in-flight counts, every output, the
+ *     stop at a terminal node and the stop on a fresh row are those of snac_uct_select_gumbel.  At every other non-terminal node -- every
+ *     depth >= 1, and a root with cand[b] == 0 -- no U is computed (c, virtual_loss, first_play_value and sqrt_table are checked but not
+ *     used): with pi' as above,
+ *         score_a = pi_a - (double)(N_a + P_a) * inv_table[sumN + sumP]                    (index clamped)
+ *     best = the largest score by strict >, ties to the lowest a, and the code continues as after PUCT's U: best untried and
+ *     used[b] < cap: expand it; best untried and the budget spent: the best of the tried children by score, none: stop; best tried:
+ *     descend, P += 1.  Checks before any HIP call: those of snac_uct_select_gumbel, then c_visit and c_scale finite.
+ *   snac_uct_improved_policy: for i in [0, m), pi[i * A + a] = (float)pi_a of node rows[i], the bounds those of tree rows[i] / cap; a row
+ *     outside [0, B * cap) or a terminal node gives zeros.  The statistics are READ ONLY.  Checks before any HIP call: num_actions 3, 5 or
+ *     8; stats non-null and 128-byte aligned; B >= 1; cap >= 1; B * (cap + 1) within stats_rows and int32; m >= 0; rows non-null; c_visit
+ *     and c_scale finite; bounds non-null and 16-byte aligned; pi non-null.  m == 0: nothing is launched. */
 typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all that selection compares, line 1 the node's own header */
     int32_t child[8];           /* row of the child through action a, -1 = untried (a >= num_actions: always -1) */
     int32_t child_visits[8];    /* N of child[a] */
@@ -780,9 +820,13 @@ typedef struct snac_uct_node {  /* 256 bytes, 128-byte aligned: line 0 is all th
     int32_t zero[25];           /* zero[0 .. 8]: in-flight counts during a multi-path iteration (zero[1 + a]: of child[a]; zero[0]: a fresh
                                    row's expander slot), zero outside one.  zero[9 + a] (words 48-55 of the record, pieces 12 and 13): the
                                    PUCT prior of action a as a float32 bit pattern (snac_uct_set_priors; a >= num_actions: 0); the
-                                   rollout search never writes these words: zero there.  zero[17 .. 24]: zero */
+                                   rollout search never writes these words: zero there.  zero[17 .. 18] (words 56-57, byte 224, the first
+                                   half of piece 14): net_value, the float64 value the evaluator gave for this node's state, 0 for a
+                                   terminal node (snac_uct_set_priors_value; zero in every search that does not call it).
+                                   zero[19 .. 24]: zero */
 } snac_uct_node;
 #define SNAC_UCT_PRIOR_WORD 48  /* int32 word of prior[0] in a snac_uct_node: ((const float*)node)[SNAC_UCT_PRIOR_WORD + a] */
+#define SNAC_UCT_NET_VALUE_WORD 56  /* int32 word of net_value in a snac_uct_node: *(const double*)((const int32_t*)node + 56) */
 int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double c, const double* log_table,
                     const double* rsqrt_table, int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf,
                     uint8_t* expanded, float* r_leaf, void* stream);
@@ -837,6 +881,16 @@ int snac_uct_select_gumbel(int32_t num_actions, snac_uct_node* stats, int32_t st
 int snac_uct_gumbel_candidates(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t mode, int32_t m,
                                const float* scores, double c_visit, double c_scale, double first_play_value, const double* bounds, int32_t* cand,
                                int8_t* action, void* stream);
+
+int snac_uct_set_priors_value(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                              const double* value, int32_t only_unvisited, void* stream);
+int snac_uct_select_gumbel_interior(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                                    double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
+                                    int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf,
+                                    uint8_t* expanded, float* r_leaf, int32_t* first_slot, const double* bounds, const int32_t* cand,
+                                    int32_t offset, double c_visit, double c_scale, void* stream);
+int snac_uct_improved_policy(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t m,
+                             const int32_t* rows, double c_visit, double c_scale, const double* bounds, float* pi, void* stream);
 
 #ifdef __cplusplus
 }

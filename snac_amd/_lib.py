@@ -33,7 +33,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_uct_advance", "snac_uct_select_paths", "snac_uct_backup_paths", "snac_observe_nodes1d", "snac_observe_nodes2d",
            "snac_observe_nodes3d", "snac_uct_select_puct", "snac_uct_set_priors", "snac_uct_pick_moves", "snac_uct_restart",
            "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds",
-           "snac_uct_select_gumbel", "snac_uct_gumbel_candidates")
+           "snac_uct_select_gumbel", "snac_uct_gumbel_candidates", "snac_uct_set_priors_value", "snac_uct_select_gumbel_interior",
+           "snac_uct_improved_policy")
 
 
 class Sizes(C.Structure):
@@ -178,6 +179,9 @@ def lib():
         L.snac_uct_select_gumbel.argtypes = L.snac_uct_select_puct_norm.argtypes[:-1] + [vp, C.c_int32, vp]     # cand, offset, the stream
         L.snac_uct_gumbel_candidates.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double, C.c_double,
                                                  C.c_double, vp, vp, vp, vp]
+        L.snac_uct_set_priors_value.argtypes = L.snac_uct_set_priors.argtypes[:-2] + [vp, C.c_int32, vp]        # value, only_unvisited, the stream
+        L.snac_uct_select_gumbel_interior.argtypes = L.snac_uct_select_gumbel.argtypes[:-1] + [C.c_double, C.c_double, vp]  # c_visit, c_scale
+        L.snac_uct_improved_policy.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double, C.c_double, vp, vp, vp]
         for k in ("1d", "2d", "3d"):
             getattr(L, "snac_observe_nodes%s" % k).argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, vp, vp]
         L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]

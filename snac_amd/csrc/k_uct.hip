@@ -1,7 +1,8 @@
 // k_uct.hip -- UCT selection, backup and re-rooting over node pools: snac_uct_select / snac_uct_backup / snac_uct_advance, and the
 // K-paths-per-tree iteration snac_uct_select_paths / snac_uct_backup_paths, and PUCT: snac_uct_select_puct / snac_uct_set_priors
 // and their q_normalise forms snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm with snac_uct_bounds,
-// and the Gumbel root rule on top of the normalised PUCT selection, snac_uct_select_gumbel
+// and the Gumbel root rule on top of the normalised PUCT selection, snac_uct_select_gumbel, with the Gumbel rule below the root as well,
+// snac_uct_select_gumbel_interior / snac_uct_set_priors_value / snac_uct_improved_policy
 // (include/snac_hip.h has the semantics)
 #include <cmath>
 #include <cstddef>
@@ -579,19 +580,152 @@ struct UctSelGumbel {
     int32_t offset;
 };
 
+// Gumbel interior ("Gumbel interior" in include/snac_hip.h): the INTERIOR form is the GUMBEL form with another rule at every node that
+// is not a root taking a candidate's turn: the action with the largest pi'(a) - (N_a + P_a) / (1 + sum N + sum P), pi' the improved policy
+// of the node (gumbel_policy below).  No U is computed in this form.  The node's network value is words 56-57 of its record, the first
+// half of piece P_NETV: one more piece of line 1, issued with the others before the first is used.
+struct UctSelGumbelInterior {
+    UctSelGumbel g;
+    double c_visit, c_scale;
+};
+
+constexpr int P_NETV = 14;
+
+static_assert(4 * SNAC_UCT_NET_VALUE_WORD == 16 * P_NETV && offsetof(snac_uct_node, zero) + 17 * 4 == 16 * P_NETV, "net_value's piece");
+
 __device__ __forceinline__ const UctSelPuct& plain(const UctSelPuct& a) { return a; }
 __device__ __forceinline__ const UctSelPuct& plain(const UctSelPuctNorm& a) { return a.z; }
 __device__ __forceinline__ const UctSelPuct& plain(const UctSelGumbel& a) { return a.n.z; }
+__device__ __forceinline__ const UctSelPuct& plain(const UctSelGumbelInterior& a) { return a.g.n.z; }
 __device__ __forceinline__ const double* bounds_of(const UctSelPuctNorm& a) { return a.bounds; }
 __device__ __forceinline__ const double* bounds_of(const UctSelGumbel& a) { return a.n.bounds; }
+__device__ __forceinline__ const double* bounds_of(const UctSelGumbelInterior& a) { return a.g.n.bounds; }
+__device__ __forceinline__ const UctSelGumbel& gumbel_of(const UctSelGumbel& a) { return a; }
+__device__ __forceinline__ const UctSelGumbel& gumbel_of(const UctSelGumbelInterior& a) { return a.g; }
 
-template <bool NORM, bool GUMBEL>
-using UctSelPuctArg = std::conditional_t<GUMBEL, UctSelGumbel, std::conditional_t<NORM, UctSelPuctNorm, UctSelPuct>>;
+template <bool NORM, bool GUMBEL, bool INTERIOR>
+using UctSelPuctArg = std::conditional_t<INTERIOR, UctSelGumbelInterior,
+                                         std::conditional_t<GUMBEL, UctSelGumbel, std::conditional_t<NORM, UctSelPuctNorm, UctSelPuct>>>;
 
-// NORM: a tried child's q normalised (first_play_value is used as given); GUMBEL (with NORM): the candidates' turn at the root
-template <int A, bool NORM, bool GUMBEL = false>
-__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM, GUMBEL> arg) {
+// exp(x) for x <= 0 from float64 + - *, floor and ldexp alone, so that python floats reproduce it bit for bit: 0 for a NaN and below
+// -700, x > 0 reads as 0; x = k ln 2 + r with k = floor(x log2(e) + 0.5) and ln 2 split in two so that k * LN2_HI is exact; the
+// Taylor sum of exp(r) to r^13 / 13! (|r| <= 0.35: the remainder is below 4e-18) by Horner's rule; ldexp(sum, k).  Within 1 ulp of exp.
+constexpr double UCT_EXP_LOG2E = 0x1.71547652b82fep+0, UCT_EXP_LN2_HI = 0x1.62e42fee00000p-1, UCT_EXP_LN2_LO = 0x1.a39ef35793c76p-33;
+constexpr int UCT_EXP_TERMS = 14;
+__device__ constexpr double UCT_EXP_COEF[UCT_EXP_TERMS] = {1.0 / 1.0,        1.0 / 1.0,         1.0 / 2.0,          1.0 / 6.0,         1.0 / 24.0,
+                                                           1.0 / 120.0,      1.0 / 720.0,       1.0 / 5040.0,       1.0 / 40320.0,     1.0 / 362880.0,
+                                                           1.0 / 3628800.0,  1.0 / 39916800.0,  1.0 / 479001600.0,  1.0 / 6227020800.0};
+
+__device__ __forceinline__ double uct_exp(double x) {
+#pragma clang fp contract(off)
+    if (!(x >= -700.0)) return 0.0;                                  // a NaN too
+    x = x > 0.0 ? 0.0 : x;
+    const double t = x * UCT_EXP_LOG2E;
+    const double k = floor(t + 0.5);
+    const double hi = k * UCT_EXP_LN2_HI, lo = k * UCT_EXP_LN2_LO;
+    const double r = (x - hi) - lo;
+    double p = UCT_EXP_COEF[UCT_EXP_TERMS - 1];
+#pragma unroll
+    for (int i = UCT_EXP_TERMS - 2; i >= 0; --i) {
+        const double pr = p * r;
+        p = pr + UCT_EXP_COEF[i];
+    }
+    return ldexp(p, (int)k);
+}
+
+// a node's line-0 words and priors out of their pieces (pf: the in-flight counts' pieces, or nullptr: every P = 0)
+template <int A>
+__device__ __forceinline__ void node_actions(const uint4* pc, const uint4* pn, const uint4* pf, const uint4* pp, const uint4* pw, int (&child)[A],
+                                             int (&cn)[A], int (&cf)[A], float (&pr)[A], double (&cw)[A]) {
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const uint4 c4 = pc[a / 4], n4 = pn[a / 4], p4 = pp[a / 4], w2 = pw[a / 2];
+        const int j = a % 4;
+        child[a] = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
+        cn[a] = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
+        cf[a] = 0;
+        if (pf) {
+            const uint4 f4 = pf[a / 4];
+            cf[a] = (int)(j == 0 ? f4.x : j == 1 ? f4.y : j == 2 ? f4.z : f4.w);
+        }
+        pr[a] = __uint_as_float(j == 0 ? p4.x : j == 1 ? p4.y : j == 2 ? p4.z : p4.w);
+        cw[a] = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
+    }
+}
+
+// The improved policy pi' of a node ("Gumbel interior" in include/snac_hip.h, whose order of operations this is): softmax of log prior +
+// sigma(completed q), the q of an action without a visited child completed by v_mix, which mixes the node's network value `netv` with
+// the prior-weighted mean of the visited children's q.  np[a] = N_a + P_a and total = sum N + sum P are what selection subtracts.
+// TABLE: 1 / (1 + sum N) from inv_table (index clamped), else computed -- the same float64 wherever the index is inside the table.
+template <int A, bool TABLE>
+__device__ __forceinline__ void gumbel_policy(const int (&child)[A], const int (&cn)[A], const int (&cf)[A], const float (&pr)[A],
+                                              const double (&cw)[A], double netv, const QRange& qr, double c_visit, double c_scale,
+                                              const double* itab, int tlen, double (&pi)[A], int (&np)[A], int& total) {
+#pragma clang fp contract(off)
+    int N[A], sum_n = 0, sum_p = 0, max_n = 0;
+    bool vis[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const bool has = child[a] >= 0;
+        const int P = has ? cf[a] : 0;
+        N[a] = has ? max(cn[a], 0) : 0;
+        vis[a] = has && N[a] > 0;
+        sum_n += N[a];
+        sum_p += P;
+        max_n = max(max_n, N[a]);
+        np[a] = N[a] + P;
+    }
+    total = sum_n + sum_p;
+    double q[A], sp = 0.0, spq = 0.0, sw = 0.0;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        q[a] = 0.0;
+        if (vis[a]) {
+            const double p = (double)pr[a];
+            q[a] = cw[a] / (double)N[a];
+            const double pq = p * q[a];
+            sp = sp + p;
+            spq = spq + pq;
+            sw = sw + cw[a];
+        }
+    }
+    double vmix = netv;
+    if (sum_n != 0) {
+        const double n = (double)sum_n;
+        const double mean = sp > 0.0 ? spq / sp : sw / n;
+        const double nm = n * mean;
+        const double num = netv + nm;
+        double inv;
+        if constexpr (TABLE) inv = itab[min(max(sum_n, 0), tlen - 1)];
+        else inv = 1.0 / (1.0 + n);
+        vmix = num * inv;
+    }
+    const double s1 = c_visit + (double)max_n;
+    const double s2 = s1 * c_scale;
+    double sig[A], smax = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const double qh = q_norm(vis[a] ? q[a] : vmix, qr);
+        sig[a] = s2 * qh;
+        smax = sig[a] > smax ? sig[a] : smax;                        // a NaN never wins
+    }
+    double e[A], z = 0.0;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        const double d = sig[a] - smax;
+        e[a] = (double)pr[a] * uct_exp(d);
+        z = z + e[a];
+    }
+#pragma unroll
+    for (int a = 0; a < A; ++a) pi[a] = z > 0.0 ? e[a] / z : 0.0;
+}
+
+// NORM: a tried child's q normalised (first_play_value is used as given); GUMBEL (with NORM): the candidates' turn at the root;
+// INTERIOR (with GUMBEL): the improved policy's rule in place of U everywhere else
+template <int A, bool NORM, bool GUMBEL = false, bool INTERIOR = false>
+__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM, GUMBEL, INTERIOR> arg) {
     static_assert(NORM || !GUMBEL, "the Gumbel form extends the normalised one");
+    static_assert(GUMBEL || !INTERIOR, "the interior form extends the Gumbel one");
     constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
     const UctSelPuct& z = plain(arg);
     const UctSelPaths& w = z.p;
@@ -603,7 +737,7 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
     if constexpr (NORM) qr = q_range(bounds_of(arg), b);
     [[maybe_unused]] int cmask = 0, cnum = 1;                        // GUMBEL: the tree's candidates and their number
     if constexpr (GUMBEL) {
-        cmask = arg.cand[b] & ((1 << A) - 1);
+        cmask = gumbel_of(arg).cand[b] & ((1 << A) - 1);
         cnum = max(__popc((unsigned)cmask), 1);
     }
     const int used0 = v.used[b];
@@ -622,18 +756,40 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
 #pragma unroll
             for (int q = 0; q < CW; ++q) pw[q] = rec[P_VALUE + q];
             const uint4 hdr = rec[P_HDR], own = rec[P_OWN];
+            [[maybe_unused]] uint4 pv = make_uint4(0u, 0u, 0u, 0u);  // INTERIOR: the node's network value
+            if constexpr (INTERIOR) pv = rec[P_NETV];
             leaf = src = n;
             r = __uint_as_float(own.z);
             if (hdr.z != 0u) break;                                  // terminal
-            const double sq = v.ltab[min(max((int)hdr.w + fly, 0), v.tlen - 1)];
+            [[maybe_unused]] const double sq = INTERIOR ? 0.0 : v.ltab[min(max((int)hdr.w + fly, 0), v.tlen - 1)];
             int best = -1, bf = 0, tried = -1, tf = 0, bchild = -1, tchild = -1;
             double bu = 0.0, tu = 0.0;
             [[maybe_unused]] int turn = -1;                          // GUMBEL, a root with candidates: the action whose turn it is
             if constexpr (GUMBEL) {
                 if (depth == 0 && cmask != 0) {
-                    int skip = (arg.offset + k) % cnum;
+                    int skip = (gumbel_of(arg).offset + k) % cnum;
 #pragma unroll
                     for (int a = A - 1; a >= 0; --a) turn = (cmask >> a & 1) && __popc((unsigned)cmask & ((1u << a) - 1u)) == skip ? a : turn;
+                }
+            }
+            [[maybe_unused]] double score[A] = {};                   // INTERIOR: pi'(a) - (N_a + P_a) / (1 + sum N + sum P), in place of U
+            // The rule needs sums over every action before any score, so INTERIOR unpacks the pieces here (node_actions) and the shared loop
+            // below unpacks child / visits / in-flight once more, with pr and cw it does not use: deliberate.  The loop stays the one the
+            // other forms compile (their instruction streams are unchanged), and the compiler folds the repeated selects of the same registers.
+            if constexpr (INTERIOR) {
+                if (turn < 0) {
+                    int ch[A], cn[A], cf[A], np[A], total;
+                    float pr[A];
+                    double cw[A], pi[A];
+                    node_actions<A>(pc, pn, pf, pp, pw, ch, cn, cf, pr, cw);
+                    gumbel_policy<A, true>(ch, cn, cf, pr, cw, f64(pv.x, pv.y), qr, arg.c_visit, arg.c_scale, v.rtab, v.tlen, pi, np, total);
+                    const double inv = v.rtab[min(max(total, 0), v.tlen - 1)];
+#pragma unroll
+                    for (int a = 0; a < A; ++a) {
+#pragma clang fp contract(off)
+                        const double t = (double)np[a] * inv;
+                        score[a] = pi[a] - t;
+                    }
                 }
             }
 #pragma unroll
@@ -653,7 +809,9 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
                 const double cw = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
                 const bool has = child >= 0;
                 double u;
-                {
+                if constexpr (INTERIOR) {
+                    u = score[a];
+                } else {
 #pragma clang fp contract(off)                                      // no fma: U rounded step by step, as a host restatement computes it
                     const int np = has ? cn + cf : 0;
                     const double t = w.vl * (double)cf;
@@ -722,6 +880,68 @@ __global__ __launch_bounds__(256) void k_uct_set_priors(uint4* stats, int32_t st
     for (int a = 0; a < 8; ++a) p[a] = a < A ? __float_as_uint(priors[(size_t)i * A + a]) : 0u;
     rec[P_PRIOR] = make_uint4(p[0], p[1], p[2], p[3]);
     rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
+}
+
+// priors and the network value into nodes: k_uct_set_priors, and the node's net_value (words 56-57) as one 8-byte store
+template <int A>
+__global__ __launch_bounds__(256) void k_uct_set_priors_value(uint4* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                                                              const double* value, int only_unvisited) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= m) return;
+    const int row = rows[i];
+    if (row < 0 || row >= stats_rows) return;
+    uint4* const rec = stats + (size_t)row * PIECES;
+    if (only_unvisited && rec[P_HDR].w != 0u) return;
+    uint32_t p[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) p[a] = a < A ? __float_as_uint(priors[(size_t)i * A + a]) : 0u;
+    const double nv = value[i];
+    rec[P_PRIOR] = make_uint4(p[0], p[1], p[2], p[3]);
+    rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
+    *reinterpret_cast<double*>(rec + P_NETV) = nv;
+}
+
+// the improved policy of m nodes: thread = node, the statistics read only; the node's six kinds of pieces are all issued before the
+// first is used; gumbel_policy with every P = 0; a row outside the trees or a terminal node gives zeros
+struct UctImproved {
+    const uint4* stats;
+    int32_t B, cap, m;
+    const int32_t* rows;
+    double c_visit, c_scale;
+    const double* bounds;
+    float* pi;
+};
+
+template <int A>
+__global__ __launch_bounds__(64) void k_uct_improved_policy(const UctImproved v) {
+    constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i >= v.m) return;
+    const int row = v.rows[i];
+    float out[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) out[a] = 0.f;
+    if (row >= 0 && row < v.B * v.cap) {
+        const uint4* const rec = v.stats + (size_t)row * PIECES;
+        uint4 pc[CI], pn[CI], pp[CI], pw[CW];
+#pragma unroll
+        for (int q = 0; q < CI; ++q) { pc[q] = rec[P_CHILD + q]; pn[q] = rec[P_VISITS + q]; pp[q] = rec[P_PRIOR + q]; }
+#pragma unroll
+        for (int q = 0; q < CW; ++q) pw[q] = rec[P_VALUE + q];
+        const uint4 hdr = rec[P_HDR], pv = rec[P_NETV];
+        const QRange qr = q_range(v.bounds, row / v.cap);
+        if (hdr.z == 0u) {
+            int ch[A], cn[A], cf[A], np[A], total;
+            float pr[A];
+            double cw[A], pi[A];
+            node_actions<A>(pc, pn, nullptr, pp, pw, ch, cn, cf, pr, cw);
+            gumbel_policy<A, false>(ch, cn, cf, pr, cw, f64(pv.x, pv.y), qr, v.c_visit, v.c_scale, nullptr, 0, pi, np, total);
+#pragma unroll
+            for (int a = 0; a < A; ++a) out[a] = (float)pi[a];
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < A; ++a) v.pi[(size_t)i * A + a] = out[a];
 }
 
 // ---- bounds from a tree as it stands ----------------------------------------------------------------------------------------------------
@@ -974,7 +1194,7 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
                        double c, double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
                        int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
                        float* r_leaf, int32_t* first_slot, bool norm, const double* bounds, bool gumbel, const int32_t* cand, int32_t offset,
-                       void* stream) {
+                       bool interior, double c_visit, double c_scale, void* stream) {
     using namespace snac_detail;
     if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
     if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
@@ -990,6 +1210,7 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
         if (offset < 0) return fail(SNAC_ERR_ARG, "offset must be >= 0");
         if ((long long)offset + (long long)paths > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "offset + paths exceeds int32");
     }
+    if (interior && (!std::isfinite(c_visit) || !std::isfinite(c_scale))) return fail(SNAC_ERR_ARG, "c_visit and c_scale must be finite");
     const UctSelPuct v{{{(uint4*)stats, B, cap, c, sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
                         paths, virtual_loss, first_slot},
                        first_play_value};
@@ -997,7 +1218,10 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
     g_kernel = "k_uct_select_puct";
     by_actions(num_actions, [&](auto k) {
         constexpr int A = decltype(k)::value;
-        if (cand) hipLaunchKernelGGL((k_uct_select_puct<A, true, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelGumbel{{v, bounds}, cand, offset});
+        if (interior)
+            hipLaunchKernelGGL((k_uct_select_puct<A, true, true, true>), grid, dim3(64), 0, (hipStream_t)stream,
+                               UctSelGumbelInterior{{{v, bounds}, cand, offset}, c_visit, c_scale});
+        else if (cand) hipLaunchKernelGGL((k_uct_select_puct<A, true, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelGumbel{{v, bounds}, cand, offset});
         else if (norm) hipLaunchKernelGGL((k_uct_select_puct<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPuctNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_select_puct<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
@@ -1010,7 +1234,8 @@ int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stat
                          int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
                          int32_t* first_slot, void* stream) {
     return select_puct("snac_uct_select_puct", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
-                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, false, nullptr, false, nullptr, 0, stream);
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, false, nullptr, false, nullptr, 0, false, 0.0, 0.0,
+                       stream);
 }
 
 int snac_uct_select_puct_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -1018,7 +1243,8 @@ int snac_uct_select_puct_norm(int32_t num_actions, snac_uct_node* stats, int32_t
                               int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded,
                               float* r_leaf, int32_t* first_slot, const double* bounds, void* stream) {
     return select_puct("snac_uct_select_puct_norm", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
-                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, false, nullptr, 0, stream);
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, false, nullptr, 0, false, 0.0, 0.0,
+                       stream);
 }
 
 int snac_uct_select_gumbel(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -1026,7 +1252,18 @@ int snac_uct_select_gumbel(int32_t num_actions, snac_uct_node* stats, int32_t st
                            int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf, uint8_t* expanded, float* r_leaf,
                            int32_t* first_slot, const double* bounds, const int32_t* cand, int32_t offset, void* stream) {
     return select_puct("snac_uct_select_gumbel", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value, sqrt_table,
-                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, true, cand, offset, stream);
+                       inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, true, cand, offset, false, 0.0, 0.0,
+                       stream);
+}
+
+int snac_uct_select_gumbel_interior(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
+                                    double virtual_loss, double first_play_value, const double* sqrt_table, const double* inv_table,
+                                    int32_t table_len, int32_t* used, int32_t* src, int32_t* dst, int8_t* action, int32_t* leaf,
+                                    uint8_t* expanded, float* r_leaf, int32_t* first_slot, const double* bounds, const int32_t* cand,
+                                    int32_t offset, double c_visit, double c_scale, void* stream) {
+    return select_puct("snac_uct_select_gumbel_interior", num_actions, stats, stats_rows, B, cap, paths, c, virtual_loss, first_play_value,
+                       sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf, first_slot, true, bounds, true, cand,
+                       offset, true, c_visit, c_scale, stream);
 }
 
 int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
@@ -1046,6 +1283,45 @@ int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats
     });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_set_priors");
+}
+
+int snac_uct_set_priors_value(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                              const double* value, int32_t only_unvisited, void* stream) {
+    using namespace snac_detail;
+    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
+    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
+    if (stats_rows < 1) return fail(SNAC_ERR_ARG, "stats_rows must be >= 1");
+    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
+    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    if (!rows || !priors) return fail(SNAC_ERR_ARG, "null rows / priors");
+    if (!value) return fail(SNAC_ERR_ARG, "null value");
+    if (m == 0) return SNAC_OK;
+    g_kernel = "k_uct_set_priors_value";
+    by_actions(num_actions, [&](auto k) {
+        hipLaunchKernelGGL((k_uct_set_priors_value<decltype(k)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           (uint4*)stats, stats_rows, m, rows, priors, value, only_unvisited != 0 ? 1 : 0);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_set_priors_value");
+}
+
+int snac_uct_improved_policy(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t m,
+                             const int32_t* rows, double c_visit, double c_scale, const double* bounds, float* pi, void* stream) {
+    using namespace snac_detail;
+    if (int rc = uct_check(num_actions, stats, stats_rows, B, cap)) return rc;
+    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
+    if (!rows) return fail(SNAC_ERR_ARG, "null rows");
+    if (!std::isfinite(c_visit) || !std::isfinite(c_scale)) return fail(SNAC_ERR_ARG, "c_visit and c_scale must be finite");
+    if (int rc = bounds_check(bounds)) return rc;
+    if (!pi) return fail(SNAC_ERR_ARG, "null pi");
+    if (m == 0) return SNAC_OK;
+    const UctImproved v{(const uint4*)stats, B, cap, m, rows, c_visit, c_scale, bounds, pi};
+    g_kernel = "k_uct_improved_policy";
+    by_actions(num_actions, [&](auto k) {
+        hipLaunchKernelGGL((k_uct_improved_policy<decltype(k)::value>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_improved_policy");
 }
 
 int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* used, const uint8_t* mask,

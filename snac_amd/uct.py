@@ -1,7 +1,8 @@
 """Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
 snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors, snac_uct_pick_moves / snac_uct_restart,
 snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds, snac_uct_select_gumbel /
-snac_uct_gumbel_candidates: include/snac_hip.h; snac_amd/csrc/k_uct.hip, k_uct_play.hip).
+snac_uct_gumbel_candidates, snac_uct_set_priors_value / snac_uct_select_gumbel_interior / snac_uct_improved_policy: include/snac_hip.h;
+snac_amd/csrc/k_uct.hip, k_uct_play.hip).
 
 B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
 stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
@@ -99,6 +100,16 @@ zero it, and with cand all zero run(n) is the PUCT search.
     a, pi = search.gumbel_actions(), search.improved_policy()
     r, d = search.advance(a)
 
+gumbel_interior=True finishes the method ("Gumbel interior" in include/snac_hip.h): every node keeps the value the evaluator gave for
+its state (net_values), and every node that is not a root taking a candidate's turn -- every level below the root, and the root in
+run(n) -- selects, deterministically, the action with the largest pi'(a) - N(a) / (1 + sum N), where pi' is the node's improved policy:
+softmax(log prior + sigma(completed q)), an unvisited action's q completed by v_mix, the mix of the node's network value and the
+prior-weighted mean of its visited children's q.  c, virtual_loss and first_play_value then play no part in selection (first_play_value
+still rates an unvisited candidate in the halvings and the final move), and improved_policy() is computed on the device by the function
+that selects, with the paper's v_mix.
+
+    search = UCTSearch(env, 512, 0, 0.99, paths=4, evaluator=fn, q_normalise=True, gumbel=4, gumbel_interior=True)
+
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
 t0 = it * (H + 1) + 1, so no two iterations share a word.  Path k of tree b draws both with the key (env_id_base + b) * K + k, its slot
 in the search over ALL envs, so no two paths share a word either and a shard of the trees (env_id_base = E: dist.py) searches exactly as
@@ -157,12 +168,18 @@ class UCTSearch:
     path ("K paths per tree and iteration" there).  Everything is allocated here; run() only enqueues work."""
 
     def __init__(self, env, nodes_per_tree, horizon, gamma, c=math.sqrt(2), max_iterations=1024, trees=None, paths=1, virtual_loss=0.0,
-                 evaluator=None, first_play_value=None, q_normalise=False, gumbel=None, gumbel_c_visit=50.0, gumbel_c_scale=1.0):
+                 evaluator=None, first_play_value=None, q_normalise=False, gumbel=None, gumbel_c_visit=50.0, gumbel_c_scale=1.0,
+                 gumbel_interior=False):
         """evaluator: None (the rollout search) or a callable obs [S, obs_dim] -> (priors [S, A], value [S]) that guides a PUCT search
         (the module docstring); first_play_value (PUCT only, default 0.0): the q of an untried action.  q_normalise (a bool): compare
         q normalised by the tree's min-max bounds (the module docstring); q_bounds is then a [B, 2] float64 tensor, else None.
         gumbel (None or m >= 1; needs an evaluator and q_normalise=True): the Gumbel root search over m sampled root actions (the module
-        docstring, "Gumbel root"), with sigma(q) = (gumbel_c_visit + max_a N_a) * gumbel_c_scale * q."""
+        docstring, "Gumbel root"), with sigma(q) = (gumbel_c_visit + max_a N_a) * gumbel_c_scale * q.  gumbel_interior (a bool; True
+        needs gumbel): the Gumbel rule below the root too, the network values kept in the nodes, improved_policy() with the full v_mix."""
+        if not isinstance(gumbel_interior, bool):
+            raise ValueError("gumbel_interior must be a bool")
+        if gumbel_interior and gumbel is None:
+            raise ValueError("gumbel_interior=True extends the Gumbel root search: give gumbel=m")
         if not isinstance(q_normalise, bool):
             raise ValueError("q_normalise must be a bool")
         if gumbel is not None:
@@ -173,6 +190,7 @@ class UCTSearch:
             if not (math.isfinite(float(gumbel_c_visit)) and math.isfinite(float(gumbel_c_scale))):
                 raise ValueError("gumbel_c_visit and gumbel_c_scale must be finite")
         self.gumbel, self.gumbel_c_visit, self.gumbel_c_scale = gumbel, float(gumbel_c_visit), float(gumbel_c_scale)
+        self.gumbel_interior = gumbel_interior
         if evaluator is not None and not callable(evaluator):
             raise ValueError("evaluator must be callable: obs [S, obs_dim] -> (priors [S, A], value [S])")
         if first_play_value is not None and evaluator is None:
@@ -280,6 +298,11 @@ class UCTSearch:
             self._cand_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap)
             self._cand_tail = (_ptr(self._gscores), self.gumbel_c_visit, self.gumbel_c_scale, self.first_play_value, _ptr(self.q_bounds),
                                _ptr(self.cand))
+            if gumbel_interior:                                      # the network value of every node; the roots' improved policies
+                self._root_value, self._root_term = torch.zeros(B, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
+                self._root_zero = torch.zeros(B, dtype=torch.float64, device=dev)
+                self._policy_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, B, _ptr(self._root_rows), self.gumbel_c_visit,
+                                     self.gumbel_c_scale, _ptr(self.q_bounds))
         self._edge_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._src), _ptr(self._dst))
         self._step_ptrs = (_ptr(self._action), None, None, _ptr(self._reward), _ptr(self._done))
         self._eval_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), self.horizon)
@@ -490,6 +513,10 @@ class UCTSearch:
 
     def _select(self, offset=0):
         L = self._lib
+        if self.gumbel is not None and self.gumbel_interior:         # the improved policy's rule wherever no candidate has its turn
+            _lib.check(L.snac_uct_select_gumbel_interior(*self._select_args, offset, self.gumbel_c_visit, self.gumbel_c_scale,
+                                                         self.env._stream()))
+            return
         if self.gumbel is not None:                                  # cand all zero: snac_uct_select_puct_norm's search
             _lib.check(L.snac_uct_select_gumbel(*self._select_args, offset, self.env._stream()))
             return
@@ -568,14 +595,24 @@ class UCTSearch:
 
     def _set_priors(self):
         torch.where(self._expanded.view(torch.bool), self._leaf, self._none, out=self._prior_rows)
+        if self.gumbel_interior:                                     # and the leaves' values: 0 where terminal (_value_leaves())
+            _lib.check(self._lib.snac_uct_set_priors_value(*self._prior_args[:-1], _ptr(self._value), 0, self.env._stream()))
+            return
         _lib.check(self._lib.snac_uct_set_priors(*self._prior_args, self.env._stream()))
 
     def _prime_roots(self):
-        """Observe the B roots, call the evaluator, give the unvisited roots their priors (the value of this call is unused)."""
+        """Observe the B roots, call the evaluator, give the unvisited roots their priors (the value of this call is unused, except by a
+        gumbel_interior search: the unvisited roots keep it as their network value, 0 where the root is terminal)."""
         env = self.env
         _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), *self._root_obs_ptrs, env._stream()))
-        priors, _ = self._call(self._root_obs, self.trees)
+        priors, value = self._call(self._root_obs, self.trees)
         self._root_priors.copy_(priors)
+        if self.gumbel_interior:
+            torch.index_select(self.stats[:, 34], 0, self._roots, out=self._root_term)
+            torch.where(self._root_term != 0, self._root_zero, value, out=self._root_value)
+            _lib.check(self._lib.snac_uct_set_priors_value(self.num_actions, _ptr(self.stats), self.rows, self.trees, _ptr(self._root_rows),
+                                                           _ptr(self._root_priors), _ptr(self._root_value), 1, env._stream()))
+            return
         _lib.check(self._lib.snac_uct_set_priors(self.num_actions, _ptr(self.stats), self.rows, self.trees, _ptr(self._root_rows),
                                                  _ptr(self._root_priors), 1, env._stream()))
 
@@ -684,9 +721,16 @@ class UCTSearch:
         sum W_visited / sum N_visited; sigma(q) = (c_visit + max_a N_a) * c_scale * q.  A root without a visited child gives its
         normalised priors.  The value given to unvisited actions simplifies the paper's v_mix (Danihelka et al. 2022, eq. 33), which
         also mixes in the root's network value weighted by the priors: that value is not stored in the tree, so the visit-weighted
-        mean of the visited children's q stands in for it.  No host synchronisation."""
+        mean of the visited children's q stands in for it.  A gumbel_interior search keeps that value, and returns instead the
+        improved policy of snac_uct_improved_policy for the roots, the one its selection uses, with the paper's v_mix ("Gumbel
+        interior" in include/snac_hip.h; a terminal root: zeros).  No host synchronisation."""
         self._need_gumbel()
         A = self.num_actions
+        if self.gumbel_interior:
+            pi = torch.empty((self.trees, A), dtype=torch.float32, device=self.env.device)
+            with torch.cuda.device(self.env.device):
+                _lib.check(self._lib.snac_uct_improved_policy(*self._policy_args, _ptr(pi), self.env._stream()))
+            return pi
         r = self.stats[self._roots]
         child, N = r[:, :A], r[:, 8:8 + A]
         W = r[:, 16:32].contiguous().view(torch.float64)[:, :A]
@@ -770,3 +814,9 @@ class UCTSearch:
     def prior(self):
         """[rows, A] float32: the PUCT priors (zero in a rollout search)."""
         return self.stats[:, 48:48 + self.num_actions].view(torch.float32)
+
+    @property
+    def net_values(self):
+        """[rows] float64: the value the evaluator gave for each node's state, 0 at a terminal node (a gumbel_interior search; zero in
+        every other)."""
+        return self.stats[:, 56:58].view(torch.float64)[:, 0]
