@@ -4,6 +4,7 @@ cross-entropy to the visit distribution, squared error to the discounted return.
 trainer: nothing but the final printout crosses the bus.
 
     python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20] [--normalise] [--gumbel M [--gumbel-interior]]
+                                          [--reanalyse R] [--td-steps N]
 
 --normalise: the search compares q normalised by each tree's min-max bounds (UCTSearch(q_normalise=True)), so that c = 1.25 weighs
 the priors against returns of any scale (a brick pays 5 here).
@@ -12,6 +13,11 @@ share the 8 iterations of a move by sequential halving, and the policy target is
 actions the search never visited.
 --gumbel-interior (with --gumbel M): the Gumbel rule below the root too (UCTSearch(gumbel_interior=True)): every node keeps its network
 value, selection follows the node's improved policy in place of PUCT, and the policy target uses the full v_mix.
+--reanalyse R: the ring keeps every move's root record (SelfPlay(keep_states=True)) and, once per training step, R stored positions drawn
+on the device are searched again by a second search of R trees that shares the network, which overwrites their pi and value
+(SelfPlay.reanalyse()).
+--td-steps N: the value target is the N-step return that bootstraps from the ring's values (targets(td_steps=N)), so that refreshed
+values reach z, in place of the return to the end of the episode.
 """
 import argparse
 import os
@@ -25,8 +31,9 @@ from snac_amd import BatchedDMPEnv, SelfPlay, UCTSearch  # noqa: E402
 
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
-          gumbel=None, gumbel_interior=False):
-    """`steps` rounds of play(moves) -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the SelfPlay)."""
+          gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None):
+    """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
+    SelfPlay)."""
     env = BatchedDMPEnv(kind, True, envs, seed=seed)
     env.reset()
     A = env.num_actions
@@ -46,14 +53,21 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
                        q_normalise=bool(normalise) or gumbel is not None, gumbel=gumbel,
                        gumbel_interior=bool(gumbel_interior))
     search.reset()
+    keep = dict(keep_states=True) if reanalyse else {}
     if gumbel is None:
-        play = SelfPlay(search, capacity, sample_moves=8, root_noise=noise)
+        play = SelfPlay(search, capacity, sample_moves=8, root_noise=noise, **keep)
     else:                                                            # the Gumbel noise of the first moves explores
-        play = SelfPlay(search, capacity, sample_moves=8, gumbel=True)
+        play = SelfPlay(search, capacity, sample_moves=8, gumbel=True, **keep)
+    again = None
+    if reanalyse:                                                    # a second search over the same env and network: R trees
+        again = UCTSearch(env, nodes, 0, 0.99, c=1.25, paths=paths, evaluator=evaluator, max_iterations=iterations, trees=reanalyse,
+                          q_normalise=search.q_normalise, gumbel=gumbel, gumbel_interior=bool(gumbel_interior))
     losses = []
     for _ in range(steps):
         play.play(moves, iterations)
-        play.targets()
+        if again is not None:
+            play.reanalyse(again, iterations)
+        play.targets(td_steps=td_steps)
         b = play.sample(batch)
         y = net(b["obs"])
         policy_loss = -(b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1).mean()
@@ -74,12 +88,16 @@ def main():
     ap.add_argument("--normalise", action="store_true")
     ap.add_argument("--gumbel", type=int, default=None, metavar="M")
     ap.add_argument("--gumbel-interior", action="store_true")
+    ap.add_argument("--reanalyse", type=int, default=0, metavar="R", help="stored positions searched again per training step (default: none)")
+    ap.add_argument("--td-steps", type=int, default=None, metavar="N", help="the N-step value target (default: the return to the episode's end)")
     args = ap.parse_args()
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
     losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps, normalise=args.normalise, gumbel=args.gumbel,
-                         gumbel_interior=args.gumbel_interior)
+                         gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
+    if args.reanalyse:
+        print("entries reanalysed: %d" % int(play.refreshed.sum()))
     print("loss: first %.4f, last %.4f" % (losses[0], losses[-1]))
 
 

@@ -709,6 +709,39 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *       g = (double)bootstrap[b] (bootstrap NULL: 0);  at each slot  g = (double)reward + (done ? 0.0 : gamma * g),  z = (float)g.
  *     Slots outside the count are not written.  Checks: B >= 1; cap_moves >= 1; B * cap_moves within int32; first in [0, cap_moves); count in
  *     [0, cap_moves]; gamma finite; reward, done and z non-null.  count == 0: nothing is launched.
+ * Reanalyse: stored positions searched again, n-step value targets (snac_uct_save_roots / snac_uct_load_roots / snac_uct_store_targets /
+ *   snac_uct_returns_nstep, k_uct_reanalyse.hip; UCTSearch.load_roots(), SelfPlay(keep_states=True).reanalyse() / targets(td_steps=n)).  A
+ *   node record is a complete state (header with the plan row, episode counter, grid; the plan table stays in the env), so a ring that
+ *   keeps each move's root record can be searched again after the env rows have moved on:
+ *     play:      ... iterations -> snac_uct_save_roots (into the ring slot) -> snac_uct_pick_moves -> ... as "Self-play"
+ *     reanalyse: snac_uct_load_roots (R trees of a second search <- R ring entries) -> iterations -> snac_uct_store_targets
+ *   on one stream, with no host synchronisation.  All four check every argument before any HIP call and never wait for the device.
+ *   snac_uct_save_roots: out[b] <- the record of row b * cap, byte for byte, for b in [0, B): B records of record_bytes, one run.  The
+ *     records are READ ONLY.  Checks: B >= 1; cap >= 1; B * (cap + 1) within int32 and record_rows; records non-null and 128-byte aligned;
+ *     record_bytes 128 or 896; out non-null and 128-byte aligned.
+ *   snac_uct_load_roots: tree b starts over from a stored record.  s = index ? clamp(index[b], 0, src_rows - 1) : b.  Record src[s] goes,
+ *     byte for byte, to row b * cap and to the tree's scratch row B * cap + b; the root's statistics row is written whole exactly as
+ *     snac_uct_restart writes it, with terminal = (word 0 of the record >> 16) & SNAC_FLAG_NEED_RESET (the header's flags byte); used[b] = 1.
+ *     Every tree is loaded; several trees may name one s.  Rows [b * cap + 1, (b + 1) * cap) hold unspecified contents afterwards, as
+ *     after snac_uct_restart.  src is READ ONLY and must not overlap records: an overlap of [src, src + src_rows * record_bytes) with
+ *     [records, records + record_rows * record_bytes) is rejected.  Checks: those of snac_uct_restart for num_actions, stats, B, cap,
+ *     records, record_bytes, record_rows and used; src non-null and 128-byte aligned; src_rows >= 1; src_rows >= B when index is NULL.
+ *   snac_uct_store_targets: tree b writes ring entry e = index[b]; an e outside [0, entries) is skipped.  With R = row b * cap:
+ *       pi[e][a]  = policy ? policy[b * num_actions + a] : (total ? (float)((double)N_a / (double)total) : 0)     (snac_uct_pick_moves' pi)
+ *       value[e]  = R.visits ? (float)(R.value_sum / (double)R.visits) : 0                                        (snac_uct_pick_moves' value)
+ *       refreshed[e] += 1                                                                                        (int32)
+ *     The statistics are READ ONLY.  The entries must be distinct: where two trees name one e, which of them wins, and whether refreshed
+ *     counts one or both, is unspecified.  Checks: num_actions, stats, B, cap and rows as snac_uct_pick_moves; index non-null; entries >= 0;
+ *     pi, value and refreshed non-null.  entries == 0: nothing is launched.
+ *   snac_uct_returns_nstep: MuZero's n-step value target z_t = sum_{k<n} gamma^k r_{t+k} + gamma^n v_{t+n} over the ring of snac_uct_returns,
+ *     for the `count` slots from `first` on (modulo cap_moves); slot i below is ring slot (first + i) % cap_moves, i = 0 the oldest.  Per
+ *     tree b and slot i, in float64 with no contraction:
+ *       e = min(i + n, count);   g = e < count ? (double)value[slot e][b] : (bootstrap ? (double)bootstrap[b] : 0.0)
+ *       for j = e - 1 down to i:   g = (double)reward[slot j][b] + (done[slot j][b] ? 0.0 : gamma * g)
+ *       z[slot i][b] = (float)g
+ *     Hence n >= count gives snac_uct_returns bit for bit, and a window that crosses the end of an episode stops there.  Slots outside the
+ *     count are not written; z must not alias value.  Checks: those of snac_uct_returns; n >= 1; value non-null.  count == 0: nothing is
+ *     launched.
  * Normalised q: per-tree min-max bounds of the mean values, so that U does not depend on the reward scale (snac_uct_select_paths_norm /
  *   snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds; UCTSearch(q_normalise=True)).
  *   The bounds array: caller-owned, 2 * B float64, 16-byte aligned; bounds[2 * b] = lo, bounds[2 * b + 1] = hi of tree b; the empty pair
@@ -859,6 +892,14 @@ int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
                      int32_t record_rows, const uint8_t* mask, const uint8_t* terminal, int32_t* used, void* stream);
 int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count, double gamma, const float* reward, const uint8_t* done,
                      const float* bootstrap, float* z, void* stream);
+
+int snac_uct_save_roots(int32_t B, int32_t cap, const void* records, int32_t record_bytes, int32_t record_rows, void* out, void* stream);
+int snac_uct_load_roots(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
+                        int32_t record_rows, const void* src, int32_t src_rows, const int32_t* index, int32_t* used, void* stream);
+int snac_uct_store_targets(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* index,
+                           int32_t entries, const float* policy, float* pi, float* value, int32_t* refreshed, void* stream);
+int snac_uct_returns_nstep(int32_t B, int32_t cap_moves, int32_t first, int32_t count, int32_t n, double gamma, const float* reward,
+                           const uint8_t* done, const float* value, const float* bootstrap, float* z, void* stream);
 
 int snac_uct_select_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
                                double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,

@@ -240,8 +240,11 @@ __global__ __launch_bounds__(64) void k_uct_gumbel(const UctGumbel v) {
     }
 }
 
+}  // namespace
+
+namespace snac_detail {
+// declared in snac_dev.h: k_uct_reanalyse.hip runs the same checks
 int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
-    using namespace snac_detail;
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
     if (!stats) return fail(SNAC_ERR_ARG, "null stats");
     if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
@@ -252,8 +255,7 @@ int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
     return SNAC_OK;
 }
-
-}  // namespace
+}  // namespace snac_detail
 
 extern "C" {
 

@@ -109,6 +109,8 @@ int check_common(const snac_env_desc* d, const snac_state* st);
 KArgs make_args(const snac_env_desc* d, const snac_state* st);
 // the checks of the node-pool entry points (kind: the record's kind), defined in k_nodes.hip
 int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m);
+// the checks the self-play and Reanalyse entry points share (num_actions, stats, B, cap, B * (cap + 1) rows), defined in k_uct_play.hip
+int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap);
 int launch(Op op, const snac_env_desc* d, const KArgs& a, void* stream);
 
 // ---- the launch functions of the kernel families (each defined beside its kernels; the dispatch decides, they only launch)

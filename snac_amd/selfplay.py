@@ -1,5 +1,6 @@
 """Self-play on the device with a ring of training targets: the search side's counterpart of ReplayRing (snac_uct_pick_moves /
-snac_uct_restart / snac_uct_returns: include/snac_hip.h, "Self-play"; snac_amd/csrc/k_uct_play.hip).
+snac_uct_restart / snac_uct_returns: include/snac_hip.h, "Self-play"; snac_amd/csrc/k_uct_play.hip; snac_uct_save_roots /
+snac_uct_store_targets / snac_uct_returns_nstep: "Reanalyse"; snac_amd/csrc/k_uct_reanalyse.hip).
 
 Tree b of a UCTSearch plays env row b.  play(moves, iterations) enqueues, per move and for all B trees at once: the search, the roots'
 observation rows, a move drawn from the root's visit counts (in proportion to them for the first `sample_moves` moves of an episode,
@@ -24,9 +25,24 @@ of PUCT at the root and the visit counts: per move gumbel_begin() on log-priors 
 of an episode; without noise after that), gumbel_run(iterations), action = gumbel_actions(), pi = improved_policy(); value, reward, done
 and the re-rooting are as above.  Exploration comes from the Gumbel noise: there is no root_noise hook in this mode.
 
+Reanalyse: a position's pi and value come from a search guided by the network as it was when the move was played, and at a few dozen
+iterations per move they age quickly, while replaying costs far more than searching again.  SelfPlay(..., keep_states=True) also keeps
+each move's root record, a complete state (`state`: 128 bytes per ring entry for 1D and 2D, 896 for 3D), and reanalyse(search, iterations)
+searches R stored positions again with a second UCTSearch over the same env -- any trees = R, its own evaluator: the latest network --
+and overwrites their pi and value (`refreshed` counts how often).  targets(td_steps=n) then builds MuZero's n-step value target
+z_t = sum_{k<n} gamma^k r_{t+k} + gamma^n v_{t+n} from the ring's values, so that fresh root values reach z:
+
+    play = SelfPlay(search, capacity_moves=512, sample_moves=10, keep_states=True)
+    again = UCTSearch(env, 512, 0, 0.99, c=1.25, paths=4, evaluator=latest, trees=256, max_iterations=32)
+    for step in range(steps):
+        play.play(16, iterations=32)
+        play.reanalyse(again, 32)                    # 256 entries drawn without replacement on the device; no host synchronisation
+        play.targets(td_steps=5)
+
 The ring, over moves (slot = move % capacity_moves), every tensor on the env's device:
     obs [cap, B, D] env.obs_dtype   pi [cap, B, A] float32   value [cap, B] float32   action [cap, B] int8
     reward [cap, B] float32   done [cap, B] uint8   move [cap, B] int32 (the move's index inside its episode)   z [cap, B] float32
+    keep_states=True:   state [cap, B, record_bytes] uint8 (the root's record when the move was chosen)   refreshed [cap, B] int32
 """
 import ctypes as C
 
@@ -40,13 +56,18 @@ def _ptr(t):
 
 
 class SelfPlay:
-    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None, gumbel=False, generator=None):
+    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None, gumbel=False, generator=None, keep_states=False):
         """search: a UCTSearch with one tree per env row (reset() by the caller); capacity_moves: ring slots; sample_moves: the moves of
         an episode drawn in proportion to the visits (the rest: argmax); gamma: of the value targets (default: the search's);
         root_noise: PUCT only, priors [B, A] -> priors [B, A], applied to the roots before every move's search (exploration noise is the
         caller's).  gumbel=True (a UCTSearch(gumbel=m), root_noise None): the moves and policy targets of the Gumbel root search, with
         Gumbel noise in the first sample_moves moves of an episode drawn from `generator` (a torch.Generator of the env's device; None:
-        the default one)."""
+        the default one).  keep_states=True: the ring also keeps every move's root record (`state`: 128 bytes per entry for 1D and 2D,
+        896 for 3D, capacity_moves * trees entries) and a count of its reanalyses (`refreshed`), which reanalyse() needs; one more
+        launch per move."""
+        if not isinstance(keep_states, bool):
+            raise ValueError("keep_states must be a bool")
+        self.keep_states = keep_states
         if not isinstance(gumbel, bool):
             raise ValueError("gumbel must be a bool")
         if gumbel and getattr(search, "gumbel", None) is None:
@@ -91,6 +112,13 @@ class SelfPlay:
         self._boot = torch.zeros(B, dtype=torch.float32, device=dev)
         self._observe = getattr(search._lib, search.pool.OBSERVE)
         self._root_rows = search._adv_src                            # int32 [B]: row b * cap
+        self.state = self.refreshed = None
+        if keep_states:
+            P = search.pool
+            self.state = torch.zeros((cap, B, P.WORDS * 4), dtype=torch.uint8, device=dev)
+            self.refreshed = torch.zeros((cap, B), dtype=torch.int32, device=dev)
+            assert self.state.data_ptr() % 128 == 0
+            self._save_args = (B, search.nodes_per_tree, _ptr(P.records), P.WORDS * 4, P.rows)
 
     def _check_budget(self, iterations):
         s = self.search
@@ -118,6 +146,9 @@ class SelfPlay:
                     s._run(n)
                 _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), _ptr(P.records), P.rows, B, _ptr(self._root_rows),
                                          _ptr(self.obs[h]), env._stream()))
+                if self.keep_states:                                 # the roots' records, before the advance moves them on
+                    _lib.check(s._lib.snac_uct_save_roots(*self._save_args, _ptr(self.state[h]), env._stream()))
+                    self.refreshed[h].zero_()
                 if self.gumbel:
                     s.gumbel_actions(out=self.action[h])
                     self.pi[h].copy_(s.improved_policy())
@@ -156,30 +187,100 @@ class SelfPlay:
         v = self.valid_moves()
         return (torch.arange(v, device=self.env.device) + (self.head - v) % self.cap) % self.cap
 
-    def targets(self, bootstrap=True):
+    def targets(self, bootstrap=True, td_steps=None):
         """Fill z for the valid slots (snac_uct_returns): per tree, from the newest move back, g = reward + (done ? 0 : gamma * g) in
         float64, z = float32(g).  g starts as the value of the tree's current root (pick_moves' value: W / N, 0 before any iteration)
-        with bootstrap=True -- the episode goes on beyond the ring -- and as 0 with bootstrap=False.  No host synchronisation."""
+        with bootstrap=True -- the episode goes on beyond the ring -- and as 0 with bootstrap=False.  td_steps=n >= 1: the n-step target
+        instead (snac_uct_returns_nstep): the same recurrence over the n moves from each slot on, started from the ring's `value` n
+        moves later (what reanalyse() refreshes), or from the bootstrap where the ring ends first; n >= valid_moves() is the default's
+        z bit for bit.  No host synchronisation."""
+        if td_steps is not None and (isinstance(td_steps, bool) or td_steps != int(td_steps) or int(td_steps) < 1):
+            raise ValueError("td_steps must be None or an integer >= 1")
         s, env = self.search, self.env
         v = self.valid_moves()
         boot = None
         if bootstrap and v:
             s._pick(None, 0, None, None, self._boot)
             boot = self._boot
+        ring = (s.trees, self.cap, (self.head - v) % self.cap, v)
         with torch.cuda.device(env.device):
-            _lib.check(s._lib.snac_uct_returns(s.trees, self.cap, (self.head - v) % self.cap, v, self.gamma, _ptr(self.reward), _ptr(self.done),
-                                               _ptr(boot), _ptr(self.z), env._stream()))
+            if td_steps is None:
+                _lib.check(s._lib.snac_uct_returns(*ring, self.gamma, _ptr(self.reward), _ptr(self.done), _ptr(boot), _ptr(self.z), env._stream()))
+            else:
+                _lib.check(s._lib.snac_uct_returns_nstep(*ring, min(int(td_steps), 0x7FFFFFFF), self.gamma, _ptr(self.reward), _ptr(self.done),
+                                                         _ptr(self.value), _ptr(boot), _ptr(self.z), env._stream()))
         return self.z
+
+    def reanalyse(self, search, iterations, index=None, generator=None, check=True):
+        """Search R = search.trees stored positions again and overwrite their targets (include/snac_hip.h, "Reanalyse").  search: a second
+        UCTSearch over the same env with an evaluator -- the latest network -- and the same actions; any trees = R <= len(self),
+        nodes_per_tree and paths; iterations <= its max_iterations.  index: R distinct flat entries slot * trees + b in valid slots
+        (an integer tensor; check=True validates it with a host read), or None: drawn without replacement on the device from
+        `generator` (a torch.Generator of the env's device; None: the default one).  Enqueues search.load_roots() of the entries'
+        stored records, the search (a gumbel=m search: gumbel_begin() on the log-priors without noise and the halving schedule; any
+        other: the PUCT iterations) and snac_uct_store_targets: pi <- the improved policy or the visit distribution, value <- the
+        root's W / N, refreshed += 1, at the indexed entries only.  With check=False or index=None there is no host synchronisation.
+        Returns the index (int64 [R], on the device)."""
+        if not self.keep_states:
+            raise ValueError("reanalyse() needs the stored root records: SelfPlay(..., keep_states=True)")
+        if search is self.search:
+            raise ValueError("reanalyse() needs a second UCTSearch over the same env: the playing search keeps its trees")
+        if search.env is not self.env:
+            raise ValueError("the reanalysing search must be built on the env of the playing search (its plan table and rules)")
+        if search.evaluator is None:
+            raise ValueError("the reanalysing search needs an evaluator")
+        if search.num_actions != self.search.num_actions:
+            raise ValueError("the reanalysing search must have %d actions" % self.search.num_actions)
+        R, n = search.trees, int(iterations)
+        if R > len(self):
+            raise ValueError("%d trees to reanalyse, %d entries in the ring" % (R, len(self)))
+        if n < 0 or n != iterations or n > search.max_iterations:
+            raise ValueError("iterations must be an integer in [0, max_iterations = %d]" % search.max_iterations)
+        B, cap, dev = self.search.trees, self.cap, self.env.device
+        v = self.valid_moves()
+        first = (self.head - v) % cap
+        if index is None:                                            # the R largest of v * B uniform draws: distinct entries
+            i = torch.topk(torch.rand(v * B, device=dev, generator=generator), R).indices
+            flat = ((first + i // B) % cap) * B + i % B
+        else:
+            if not torch.is_tensor(index) or int(index.numel()) != R:
+                raise ValueError("index must be a tensor of %d entries" % R)
+            if index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+                raise ValueError("index must be integers")
+            flat = index.to(dev).reshape(-1).to(torch.int64)
+            if check:
+                if int(flat.min()) < 0 or int(flat.max()) >= cap * B or int(((flat // B - first) % cap).max()) >= v:
+                    raise ValueError("index must name entries slot * %d + b of valid slots" % B)
+                if int(torch.unique(flat).numel()) != R:
+                    raise ValueError("index must name distinct entries")
+        idx = flat.to(torch.int32)
+        search.load_roots(self.state.view(cap * B, -1), idx)
+        policy = None
+        if search.gumbel is not None:
+            search.gumbel_begin(search.gumbel_scores(False))
+            search._gumbel_run(n)
+            policy = search.improved_policy()
+        else:
+            search._run(n)
+        with torch.cuda.device(dev):
+            _lib.check(search._lib.snac_uct_store_targets(search.num_actions, _ptr(search.stats), search.rows, R, search.nodes_per_tree, _ptr(idx),
+                                                          cap * B, _ptr(policy), _ptr(self.pi), _ptr(self.value), _ptr(self.refreshed),
+                                                          self.env._stream()))
+        return flat
 
     def sample(self, batch, generator=None):
         """Uniform minibatch over the valid (move, tree) pairs -> dict on the device: obs float32 [n, D], pi [n, A], z, value, reward
-        float32 [n], action int64 [n], done bool [n].  One flat index and 1-D gathers (ReplayRing.gather has the measurement)."""
+        float32 [n], action int64 [n], done bool [n]; with keep_states=True also refreshed int32 [n].  One flat index and 1-D gathers
+        (ReplayRing.gather has the measurement)."""
         v = self.valid_moves()
         if v == 0:
             raise ValueError("the ring is empty")
         B, dev = self.search.trees, self.env.device
         i = torch.randint(0, v * B, (int(batch),), device=dev, generator=generator)
         flat = (((self.head - v) % self.cap + i // B) % self.cap) * B + i % B
-        return dict(obs=self.obs.view(self.cap * B, -1)[flat].to(torch.float32), pi=self.pi.view(self.cap * B, -1)[flat],
-                    z=self.z.view(-1)[flat], value=self.value.view(-1)[flat], action=self.action.view(-1)[flat].long(),
-                    reward=self.reward.view(-1)[flat], done=self.done.view(-1)[flat].bool())
+        out = dict(obs=self.obs.view(self.cap * B, -1)[flat].to(torch.float32), pi=self.pi.view(self.cap * B, -1)[flat],
+                   z=self.z.view(-1)[flat], value=self.value.view(-1)[flat], action=self.action.view(-1)[flat].long(),
+                   reward=self.reward.view(-1)[flat], done=self.done.view(-1)[flat].bool())
+        if self.keep_states:
+            out["refreshed"] = self.refreshed.view(-1)[flat]
+        return out

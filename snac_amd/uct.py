@@ -1,8 +1,8 @@
 """Batched UCT tree search on the device over node pools (snac_uct_node, snac_uct_select / snac_uct_backup / snac_uct_advance and
 snac_uct_select_paths / snac_uct_backup_paths, snac_uct_select_puct / snac_uct_set_priors, snac_uct_pick_moves / snac_uct_restart,
 snac_uct_select_paths_norm / snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds, snac_uct_select_gumbel /
-snac_uct_gumbel_candidates, snac_uct_set_priors_value / snac_uct_select_gumbel_interior / snac_uct_improved_policy: include/snac_hip.h;
-snac_amd/csrc/k_uct.hip, k_uct_play.hip).
+snac_uct_gumbel_candidates, snac_uct_set_priors_value / snac_uct_select_gumbel_interior / snac_uct_improved_policy, snac_uct_load_roots:
+include/snac_hip.h; snac_amd/csrc/k_uct.hip, k_uct_play.hip, k_uct_reanalyse.hip).
 
 B independent trees, one path per tree per iteration (paths=1) or K of them (paths=K, below).  An iteration is enqueued on the env's
 stream with no host synchronisation: selection (k_uct_select), the B tree edges (snac_transition_nodes*: edge b belongs to tree b),
@@ -109,6 +109,16 @@ still rates an unvisited candidate in the halvings and the final move), and impr
 that selects, with the paper's v_mix.
 
     search = UCTSearch(env, 512, 0, 0.99, paths=4, evaluator=fn, q_normalise=True, gumbel=4, gumbel_interior=True)
+
+Stored positions: load_roots(records, index) is reset() from node records instead of env rows ("Reanalyse" in include/snac_hip.h).  A
+record is a complete state -- header with the plan row, episode counter, grid; the plan table stays in the env -- so a position can be
+searched again long after its env row has moved on: tree b starts over from records[index[b]] (one launch, no host synchronisation).
+SelfPlay(keep_states=True) keeps each move's root record in its ring and reanalyse() re-searches them with a second search over the same
+env, typically one with the latest network as its evaluator:
+
+    again = UCTSearch(env, 512, 0, 0.99, c=1.25, paths=4, evaluator=latest, trees=256, max_iterations=32)
+    again.load_roots(play.state.view(-1, play.state.shape[-1]), index)       # index: [256] flat ring entries
+    again.run(32)
 
 Counter words: iteration `it` (counted from reset()) steps its edges with t = it * (H + 1) and rolls its leaves out from
 t0 = it * (H + 1) + 1, so no two iterations share a word.  Path k of tree b draws both with the key (env_id_base + b) * K + k, its slot
@@ -326,6 +336,7 @@ class UCTSearch:
         self._pack = getattr(self._lib, P.PACK)
         self._restart_args = (self.num_actions, _ptr(self.stats), self.rows, B, cap, _ptr(P.records), P.WORDS * 4, P.rows, _ptr(self._rs_mask),
                               _ptr(self._rs_term), _ptr(self._used))
+        self._load_args = self._restart_args[:8]                     # load_roots(): then src, src_rows, index, used
 
     # ---- the search ---------------------------------------------------------------------------------------------------
     def reset(self, rows=None):
@@ -353,6 +364,42 @@ class UCTSearch:
         self._no_candidates()
         if self.evaluator is not None:
             with torch.cuda.device(env.device):
+                self._prime_roots()
+
+    def load_roots(self, records, index=None):
+        """reset() from stored node records instead of env rows (snac_uct_load_roots; include/snac_hip.h, "Reanalyse"): root b <-
+        records[index[b]] (None: records[b]), also copied into the tree's scratch record; fresh root statistics, terminal where the
+        record's header carries NEED_RESET; the iteration count, the q bounds and the candidates start over and a PUCT search primes the
+        new roots.  records: a contiguous uint8 [n, record_bytes] tensor of the pool's kind on the env's device, 128-byte aligned and
+        apart from the pool's own records (SelfPlay.state, NodePool.records viewed as bytes); index: an integer tensor [trees], clamped
+        into [0, n) on the device.  One launch on the env's stream, no host synchronisation.  Unlike reset(), only the roots'
+        statistics rows are written: the other rows are outside every tree (tree_sizes() == 1), as after restart()."""
+        B, rb = self.trees, self.pool.WORDS * 4
+        if not torch.is_tensor(records) or records.dtype != torch.uint8 or records.dim() != 2 or int(records.shape[1]) != rb:
+            raise ValueError("records must be a uint8 [n, %d] tensor: the node records of a %dD pool" % (rb, self.pool.KIND))
+        n = int(records.shape[0])
+        if n < 1 or (index is None and n < B):
+            raise ValueError("%d records for %d trees: give an index" % (n, B) if n else "records is empty")
+        if index is not None:
+            if not torch.is_tensor(index) or int(index.numel()) != B:
+                raise ValueError("index must be a tensor of %d entries" % B)
+            if index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+                raise ValueError("index must be integers")
+        env = self.env
+        if records.device != env.device or (index is not None and index.device != env.device):
+            raise ValueError("records and index must be on %s" % env.device)
+        if not records.is_contiguous() or records.data_ptr() % 128 != 0:
+            raise ValueError("records must be contiguous and 128-byte aligned")
+        if index is not None:
+            index = index.reshape(-1).to(torch.int32).contiguous()
+        with torch.cuda.device(env.device):
+            _lib.check(self._lib.snac_uct_load_roots(*self._load_args, _ptr(records), n, None if index is None else _ptr(index),
+                                                     _ptr(self._used), env._stream()))
+            self._iteration = 0
+            if self.q_normalise:
+                self.q_bounds.copy_(self._no_bounds.expand(B, 2))
+            self._no_candidates()
+            if self.evaluator is not None:
                 self._prime_roots()
 
     def run(self, iterations):
