@@ -10,6 +10,7 @@
 
 #include "snac_dev.h"
 #include "snac_tune.h"
+#include "uct_dev.h"
 
 // lane = tree: both kernels are chains of dependent loads, one trip per tree level.  A node's record holds its children's rows, visits
 // and values (line 0) beside its own header (line 1), so a selection step reads one record: the pieces it compares and the node's own
@@ -17,14 +18,6 @@
 // their mirror in the parent.  The kernels depend on A (num_actions) only, not on the env kind.  Spreading the trees thinner (8, 16 or
 // 64 lanes per wave with one working) measured no faster: a level costs a dependent trip whatever the wave holds (profiles/r10_uct.txt).
 namespace {
-
-static_assert(sizeof(snac_uct_node) == 256, "snac_uct_node is two lines");
-static_assert(offsetof(snac_uct_node, child_value) == 64 && offsetof(snac_uct_node, parent) == 128 && offsetof(snac_uct_node, value_sum) == 144 &&
-                  offsetof(snac_uct_node, reward) == 152,
-              "the piece map below");
-
-constexpr int PIECES = 16;                                           // 16-byte pieces per record
-constexpr int P_CHILD = 0, P_VISITS = 2, P_VALUE = 4, P_HDR = 8, P_OWN = 9;
 
 struct UctSel {
     uint4* stats;
@@ -55,13 +48,8 @@ struct UctBack {
     const double* est;
 };
 
-__device__ __forceinline__ double f64(uint32_t lo, uint32_t hi) { return __hiloint2double((int)hi, (int)lo); }
-
-__device__ __forceinline__ int clamp_row(int r, int base, int cap) { return min(max(r, base), base + cap - 1); }
-
 template <int A>
 __global__ __launch_bounds__(64) void k_uct_select(const UctSel v) {
-    constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;                // pieces of child / child_visits, of child_value
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
     const int base = b * v.cap;
@@ -70,24 +58,19 @@ __global__ __launch_bounds__(64) void k_uct_select(const UctSel v) {
     bool expanded = false;
     float r = 0.f;
     for (int depth = 0; depth < v.cap; ++depth) {                    // bounded: a corrupted tree cannot keep the wave spinning
-        const uint4* const rec = v.stats + (size_t)n * PIECES;
-        uint4 pc[CI], pn[CI], pw[CW];
-#pragma unroll
-        for (int q = 0; q < CI; ++q) { pc[q] = rec[P_CHILD + q]; pn[q] = rec[P_VISITS + q]; }
-#pragma unroll
-        for (int q = 0; q < CW; ++q) pw[q] = rec[P_VALUE + q];
-        const uint4 hdr = rec[P_HDR], own = rec[P_OWN];
+        NodePieces<A, false> p;
+        p.load(v.stats + (size_t)n * PIECES);
         leaf = n;
-        r = __uint_as_float(own.z);
-        if (hdr.z != 0u) break;                                      // terminal
+        r = __uint_as_float(p.own.z);
+        if (p.hdr.z != 0u) break;                                    // terminal
         int child[A], cn[A];
         double cw[A];
 #pragma unroll
         for (int a = 0; a < A; ++a) {
-            const uint4 c4 = pc[a / 4], n4 = pn[a / 4], w2 = pw[a / 2];
+            const uint4 c4 = p.pc[a / 4], n4 = p.pn[a / 4], w2 = p.pw[a / 2];
             const int j = a % 4;
-            child[a] = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
-            cn[a] = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
+            child[a] = (int)word_of(c4, j);
+            cn[a] = (int)word_of(n4, j);
             cw[a] = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
         }
         int untried = -1;
@@ -104,7 +87,7 @@ __global__ __launch_bounds__(64) void k_uct_select(const UctSel v) {
             expanded = true;
             break;
         }
-        const double lg = v.ltab[min(max((int)hdr.w, 0), v.tlen - 1)];
+        const double lg = v.ltab[min(max((int)p.hdr.w, 0), v.tlen - 1)];
         int best = -1;
         double bu = 0.0;
 #pragma unroll
@@ -170,16 +153,16 @@ __global__ __launch_bounds__(64) void k_uct_backup(const UctBack v) {
 #pragma clang fp contract(off)
             w = w + g;
         }
-        own[35] = visits;                                            // snac_uct_node.visits, .value_sum
-        *reinterpret_cast<double*>(own + 36) = w;
+        own[W_VISITS] = visits;
+        *reinterpret_cast<double*>(own + W_VALUE_SUM) = w;
         if (parent < 0) break;
         const int p = clamp_row(parent, base, v.cap);
         const int a = min(max(action, 0), A - 1);
         uint4* const prec = v.stats + (size_t)p * PIECES;
         const uint4 hdr = prec[P_HDR], pown = prec[P_OWN];
         int32_t* const pw = reinterpret_cast<int32_t*>(prec);
-        pw[8 + a] = visits;                                          // the mirror in the parent's line 0
-        *reinterpret_cast<double*>(pw + 16 + 2 * a) = w;
+        pw[W_CHILD_VISITS + a] = visits;                             // the mirror in the parent's line 0
+        *reinterpret_cast<double*>(pw + W_CHILD_VALUE + 2 * a) = w;
         {
 #pragma clang fp contract(off)
             const double t = v.gamma * g;
@@ -269,7 +252,7 @@ __global__ __launch_bounds__(256) void k_uct_advance(const UctAdv v) {
         if (i < end) {
             int x = i;
             for (int d = 0; d < cap && x >= s && x > c; ++d)         // bounded, as select and backup
-                x = clamp_row(reinterpret_cast<const int32_t*>(v.stats + (size_t)x * PIECES)[32], base, cap);
+                x = clamp_row(reinterpret_cast<const int32_t*>(v.stats + (size_t)x * PIECES)[W_PARENT], base, cap);
             keep = x == c || (x > c && x < s && o2n[x - base] >= 0);
         }
         const unsigned long long m = __ballot(keep);
@@ -332,18 +315,16 @@ __global__ __launch_bounds__(256) void k_uct_advance(const UctAdv v) {
 // every word a path reads back was stored by the same lane.  The in-flight count P of child a of node n is n's zero[1 + a] (pieces
 // P_FLY, P_FLY + 1), incremented on the way down and cleared by the backup; a node's own count is that entry of its parent, carried
 // down in a register, and the root's is the path index k.  A fresh row (>= base + used on entry) has no record and no header yet; its
-// word 39 (zero[0]) holds the slot that expanded it until the backup writes the row whole.
-constexpr int P_FLY = 10;
-
-struct UctSelPaths {
-    UctSel s;
+// word W_SLOT (zero[0]) holds the slot that expanded it until the backup writes the row whole.
+// The argument blocks: each form's is the one before it plus its own members (single inheritance: no base here has tail padding that a
+// member could move into, so every kernarg layout is the one the nested structs had; static_asserts below pin them).
+struct UctSelPaths : UctSel {
     int32_t K;
     double vl;
     int32_t* first_slot;
 };
 
-struct UctBackPaths {
-    UctBack s;
+struct UctBackPaths : UctBack {
     int32_t K;
 };
 
@@ -351,20 +332,13 @@ struct UctBackPaths {
 // bounds[2 * b + 1] = hi of tree b.  A selection reads its tree's pair once, before the descent (one 16-byte load that no level waits
 // for), and a tried child's q becomes (q - lo) / (hi - lo) where hi > lo; the backup folds W / N of every node below the root into
 // the pair, which it keeps in registers over its K walks and stores once.  NORM = false is the code of the unnormalised kernels.
-struct UctSelPathsNorm {
-    UctSelPaths p;
+struct UctSelPathsNorm : UctSelPaths {
     const double* bounds;
 };
 
-struct UctBackPathsNorm {
-    UctBackPaths p;
+struct UctBackPathsNorm : UctBackPaths {
     double* bounds;
 };
-
-__device__ __forceinline__ const UctSelPaths& plain(const UctSelPaths& a) { return a; }
-__device__ __forceinline__ const UctSelPaths& plain(const UctSelPathsNorm& a) { return a.p; }
-__device__ __forceinline__ const UctBackPaths& plain(const UctBackPaths& a) { return a; }
-__device__ __forceinline__ const UctBackPaths& plain(const UctBackPathsNorm& a) { return a.p; }
 
 // tree b's pair as it enters U: on = hi > lo, lo and span = hi - lo (computed once per tree)
 struct QRange {
@@ -389,15 +363,12 @@ __device__ __forceinline__ double q_norm(double q, const QRange& r) {
 }
 
 template <int A, bool NORM>
-__global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_t<NORM, UctSelPathsNorm, UctSelPaths> arg) {
-    constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
-    const UctSelPaths& w = plain(arg);
-    const UctSel& v = w.s;
+__global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_t<NORM, UctSelPathsNorm, UctSelPaths> v) {
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
-    const int base = b * v.cap, K = w.K;
+    const int base = b * v.cap, K = v.K;
     QRange qr{0.0, 0.0, false};
-    if constexpr (NORM) qr = q_range(arg.bounds, b);
+    if constexpr (NORM) qr = q_range(v.bounds, b);
     const int used0 = v.used[b];
     const int fresh = base + used0;                                  // rows from here up are made by this launch
     int used = used0;
@@ -407,25 +378,20 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_
         bool expanded = false;
         float r = 0.f;
         for (int depth = 0; depth < v.cap; ++depth) {
-            const uint4* const rec = v.stats + (size_t)n * PIECES;
-            uint4 pc[CI], pn[CI], pf[CI], pw[CW];
-#pragma unroll
-            for (int q = 0; q < CI; ++q) { pc[q] = rec[P_CHILD + q]; pn[q] = rec[P_VISITS + q]; pf[q] = rec[P_FLY + q]; }
-#pragma unroll
-            for (int q = 0; q < CW; ++q) pw[q] = rec[P_VALUE + q];
-            const uint4 hdr = rec[P_HDR], own = rec[P_OWN];
+            NodePieces<A, true> p;
+            p.load(v.stats + (size_t)n * PIECES);
             leaf = src = n;
-            r = __uint_as_float(own.z);
-            if (hdr.z != 0u) break;                                  // terminal
+            r = __uint_as_float(p.own.z);
+            if (p.hdr.z != 0u) break;                                // terminal
             int child[A], cn[A], cf[A];
             double cw[A];
 #pragma unroll
             for (int a = 0; a < A; ++a) {
-                const uint4 c4 = pc[a / 4], n4 = pn[a / 4], f4 = pf[a / 4], w2 = pw[a / 2];
+                const uint4 c4 = p.pc[a / 4], n4 = p.pn[a / 4], f4 = p.pf[a / 4], w2 = p.pw[a / 2];
                 const int j = a % 4;
-                child[a] = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
-                cn[a] = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
-                cf[a] = (int)(j == 0 ? f4.x : j == 1 ? f4.y : j == 2 ? f4.z : f4.w);
+                child[a] = (int)word_of(c4, j);
+                cn[a] = (int)word_of(n4, j);
+                cf[a] = (int)word_of(f4, j);
                 cw[a] = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
             }
             int untried = -1;
@@ -434,18 +400,13 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_
                 if (child[a] < 0) untried = a;
             int32_t* const words = reinterpret_cast<int32_t*>(v.stats + (size_t)n * PIECES);
             if (untried >= 0 && used < v.cap) {                      // expand the lowest untried action into the tree's next row
-                const int row = base + used;
-                used += 1;
-                words[untried] = row;
-                words[4 * P_FLY + untried] = 1;
-                reinterpret_cast<int32_t*>(v.stats + (size_t)row * PIECES)[39] = s;
-                leaf = row;
+                leaf = expand_path(words, v.stats, untried, base, used, s);
                 act = untried;
                 expanded = true;
                 first = s;
                 break;
             }
-            const double lg = v.ltab[min(max((int)hdr.w + fly, 0), v.tlen - 1)];
+            const double lg = v.ltab[min(max((int)p.hdr.w + fly, 0), v.tlen - 1)];
             int best = -1, bf = 0;
             double bu = 0.0;
 #pragma unroll
@@ -455,7 +416,7 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_
                 {
 #pragma clang fp contract(off)
                     const int np = cn[a] + cf[a];
-                    double q = (cw[a] - w.vl * (double)cf[a]) / (double)np;
+                    double q = (cw[a] - v.vl * (double)cf[a]) / (double)np;
                     if constexpr (NORM) q = q_norm(q, qr);
                     const double e = lg * v.rtab[min(max(np, 0), v.tlen - 1)];
                     u = q + v.c * e;
@@ -463,14 +424,14 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_
                 if (best < 0 || u > bu) { best = a; bu = u; bf = cf[a]; }
             }
             if (best < 0) break;                                     // no children and the budget spent
-            words[4 * P_FLY + best] = bf + 1;
+            words[W_FLY + best] = bf + 1;
             fly = bf;
             n = clamp_row(child[best], base, v.cap);
             if (n >= fresh) {                                        // made by an earlier path of this launch: stop on it
                 leaf = n;
                 src = base;                                          // the row is another edge's destination: step the root instead
                 r = 0.f;
-                first = reinterpret_cast<const int32_t*>(v.stats + (size_t)n * PIECES)[39];
+                first = fresh_row_slot(v.stats, n);
                 break;
             }
         }
@@ -480,20 +441,18 @@ __global__ __launch_bounds__(64) void k_uct_select_paths(const std::conditional_
         v.leaf[s] = leaf;
         v.expanded[s] = expanded ? 1 : 0;
         v.r_leaf[s] = expanded ? 0.f : r;
-        w.first_slot[s] = first;
+        v.first_slot[s] = first;
     }
     v.used[b] = used;
 }
 
 template <int A, bool NORM>
-__global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_t<NORM, UctBackPathsNorm, UctBackPaths> arg) {
-    const UctBackPaths& w = plain(arg);
-    const UctBack& v = w.s;
+__global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_t<NORM, UctBackPathsNorm, UctBackPaths> v) {
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
-    const int base = b * v.cap, K = w.K;
+    const int base = b * v.cap, K = v.K;
     double2 range = make_double2(0.0, 0.0);                          // NORM: the tree's (lo, hi), in registers over the K walks
-    if constexpr (NORM) range = reinterpret_cast<const double2*>(arg.bounds)[b];
+    if constexpr (NORM) range = reinterpret_cast<const double2*>(v.bounds)[b];
     for (int k = 0; k < K; ++k) {                                    // the new nodes' rows, whole, before any walk reads one
         const int s = b * K + k;
         if (!v.expanded[s]) continue;
@@ -522,8 +481,8 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_
 #pragma clang fp contract(off)
                 sum = f64(own.x, own.y) + g;
             }
-            me[35] = visits;
-            *reinterpret_cast<double*>(me + 36) = sum;
+            me[W_VISITS] = visits;
+            *reinterpret_cast<double*>(me + W_VALUE_SUM) = sum;
             const int parent = (int)hdr.x;
             if (parent < 0) break;
             const int p = clamp_row(parent, base, v.cap);
@@ -532,9 +491,9 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_
             hdr = prec[P_HDR];
             own = prec[P_OWN];
             int32_t* const pw = reinterpret_cast<int32_t*>(prec);
-            pw[8 + a] = visits;                                      // the mirror in the parent's line 0
-            *reinterpret_cast<double*>(pw + 16 + 2 * a) = sum;
-            pw[4 * P_FLY + a] = 0;                                   // the edge's in-flight count
+            pw[W_CHILD_VISITS + a] = visits;                         // the mirror in the parent's line 0
+            *reinterpret_cast<double*>(pw + W_CHILD_VALUE + 2 * a) = sum;
+            pw[W_FLY + a] = 0;                                   // the edge's in-flight count
             if constexpr (NORM) {                                    // x is below the root: its mean is one that selection compares
                 const double m = sum / (double)visits;
                 range.x = m < range.x ? m : range.x;                 // a NaN fails both comparisons
@@ -548,7 +507,7 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_
             x = p;
         }
     }
-    if constexpr (NORM) reinterpret_cast<double2*>(arg.bounds)[b] = range;
+    if constexpr (NORM) reinterpret_cast<double2*>(v.bounds)[b] = range;
 }
 
 // ---- PUCT: a policy / value network in place of UCB1 and the rollout ----------------------------------------------------------------
@@ -556,17 +515,11 @@ __global__ __launch_bounds__(64) void k_uct_backup_paths(const std::conditional_
 //     U = q + c * ((prior[a] * sqrt_table[N(n) + P(n)]) * inv_table[Np]),   q = (W_a - vl * P_a) / Np tried, first_play_value untried,
 // and the best one is expanded or descended.  The priors are words 48-55 of the record (pieces P_PRIOR ..): two more pieces of line 1,
 // issued with the others before the first is used; the chain of dependent loads per level is the one of k_uct_select_paths.
-constexpr int P_PRIOR = 12;
-
-static_assert(4 * SNAC_UCT_PRIOR_WORD == 16 * P_PRIOR && offsetof(snac_uct_node, zero) + 9 * 4 == 16 * P_PRIOR, "the priors' pieces");
-
-struct UctSelPuct {
-    UctSelPaths p;                                                   // p.s.ltab / p.s.rtab: sqrt_table / inv_table
+struct UctSelPuct : UctSelPaths {                                    // ltab / rtab: sqrt_table / inv_table
     double fpv;
 };
 
-struct UctSelPuctNorm {
-    UctSelPuct z;
+struct UctSelPuctNorm : UctSelPuct {
     const double* bounds;
 };
 
@@ -574,8 +527,7 @@ struct UctSelPuctNorm {
 // candidate mask cand[b] is not zero: path k takes the ((offset + k) mod M)-th of the M candidates, in integers, and no U is computed
 // there.  The mask is one 4-byte load beside the bounds pair, before the descent.  A tree with cand[b] == 0, and every level below a
 // root, runs the NORM code.
-struct UctSelGumbel {
-    UctSelPuctNorm n;
+struct UctSelGumbel : UctSelPuctNorm {
     const int32_t* cand;
     int32_t offset;
 };
@@ -584,24 +536,25 @@ struct UctSelGumbel {
 // is not a root taking a candidate's turn: the action with the largest pi'(a) - (N_a + P_a) / (1 + sum N + sum P), pi' the improved policy
 // of the node (gumbel_policy below).  No U is computed in this form.  The node's network value is words 56-57 of its record, the first
 // half of piece P_NETV: one more piece of line 1, issued with the others before the first is used.
-struct UctSelGumbelInterior {
-    UctSelGumbel g;
+struct UctSelGumbelInterior : UctSelGumbel {
     double c_visit, c_scale;
 };
 
-constexpr int P_NETV = 14;
-
-static_assert(4 * SNAC_UCT_NET_VALUE_WORD == 16 * P_NETV && offsetof(snac_uct_node, zero) + 17 * 4 == 16 * P_NETV, "net_value's piece");
-
-__device__ __forceinline__ const UctSelPuct& plain(const UctSelPuct& a) { return a; }
-__device__ __forceinline__ const UctSelPuct& plain(const UctSelPuctNorm& a) { return a.z; }
-__device__ __forceinline__ const UctSelPuct& plain(const UctSelGumbel& a) { return a.n.z; }
-__device__ __forceinline__ const UctSelPuct& plain(const UctSelGumbelInterior& a) { return a.g.n.z; }
-__device__ __forceinline__ const double* bounds_of(const UctSelPuctNorm& a) { return a.bounds; }
-__device__ __forceinline__ const double* bounds_of(const UctSelGumbel& a) { return a.n.bounds; }
-__device__ __forceinline__ const double* bounds_of(const UctSelGumbelInterior& a) { return a.g.n.bounds; }
-__device__ __forceinline__ const UctSelGumbel& gumbel_of(const UctSelGumbel& a) { return a; }
-__device__ __forceinline__ const UctSelGumbel& gumbel_of(const UctSelGumbelInterior& a) { return a.g; }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"                // a derived struct is not standard-layout; its offsets are what is pinned
+static_assert(sizeof(UctSel) == 104 && offsetof(UctSelPaths, K) == 104 && offsetof(UctSelPaths, vl) == 112 &&
+                  offsetof(UctSelPaths, first_slot) == 120 && sizeof(UctSelPaths) == 128 && offsetof(UctSelPathsNorm, bounds) == 128 &&
+                  sizeof(UctSelPathsNorm) == 136,
+              "the kernarg layouts of the selections");
+static_assert(offsetof(UctSelPuct, fpv) == 128 && sizeof(UctSelPuct) == 136 && offsetof(UctSelPuctNorm, bounds) == 136 &&
+                  sizeof(UctSelPuctNorm) == 144 && offsetof(UctSelGumbel, cand) == 144 && offsetof(UctSelGumbel, offset) == 152 &&
+                  sizeof(UctSelGumbel) == 160 && offsetof(UctSelGumbelInterior, c_visit) == 160 &&
+                  offsetof(UctSelGumbelInterior, c_scale) == 168 && sizeof(UctSelGumbelInterior) == 176,
+              "the kernarg layouts of the PUCT selections");
+static_assert(sizeof(UctBack) == 80 && offsetof(UctBackPaths, K) == 80 && sizeof(UctBackPaths) == 88 &&
+                  offsetof(UctBackPathsNorm, bounds) == 88 && sizeof(UctBackPathsNorm) == 96,
+              "the kernarg layouts of the backups");
+#pragma clang diagnostic pop
 
 template <bool NORM, bool GUMBEL, bool INTERIOR>
 using UctSelPuctArg = std::conditional_t<INTERIOR, UctSelGumbelInterior,
@@ -641,14 +594,14 @@ __device__ __forceinline__ void node_actions(const uint4* pc, const uint4* pn, c
     for (int a = 0; a < A; ++a) {
         const uint4 c4 = pc[a / 4], n4 = pn[a / 4], p4 = pp[a / 4], w2 = pw[a / 2];
         const int j = a % 4;
-        child[a] = (int)(j == 0 ? c4.x : j == 1 ? c4.y : j == 2 ? c4.z : c4.w);
-        cn[a] = (int)(j == 0 ? n4.x : j == 1 ? n4.y : j == 2 ? n4.z : n4.w);
+        child[a] = (int)word_of(c4, j);
+        cn[a] = (int)word_of(n4, j);
         cf[a] = 0;
         if (pf) {
             const uint4 f4 = pf[a / 4];
-            cf[a] = (int)(j == 0 ? f4.x : j == 1 ? f4.y : j == 2 ? f4.z : f4.w);
+            cf[a] = (int)word_of(f4, j);
         }
-        pr[a] = __uint_as_float(j == 0 ? p4.x : j == 1 ? p4.y : j == 2 ? p4.z : p4.w);
+        pr[a] = __uint_as_float(word_of(p4, j));
         cw[a] = (a % 2 == 0) ? f64(w2.x, w2.y) : f64(w2.z, w2.w);
     }
 }
@@ -723,21 +676,18 @@ __device__ __forceinline__ void gumbel_policy(const int (&child)[A], const int (
 // NORM: a tried child's q normalised (first_play_value is used as given); GUMBEL (with NORM): the candidates' turn at the root;
 // INTERIOR (with GUMBEL): the improved policy's rule in place of U everywhere else
 template <int A, bool NORM, bool GUMBEL = false, bool INTERIOR = false>
-__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM, GUMBEL, INTERIOR> arg) {
+__global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM, GUMBEL, INTERIOR> v) {
     static_assert(NORM || !GUMBEL, "the Gumbel form extends the normalised one");
     static_assert(GUMBEL || !INTERIOR, "the interior form extends the Gumbel one");
     constexpr int CI = (A + 3) / 4, CW = (A + 1) / 2;
-    const UctSelPuct& z = plain(arg);
-    const UctSelPaths& w = z.p;
-    const UctSel& v = w.s;
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
-    const int base = b * v.cap, K = w.K;
+    const int base = b * v.cap, K = v.K;
     QRange qr{0.0, 0.0, false};
-    if constexpr (NORM) qr = q_range(bounds_of(arg), b);
+    if constexpr (NORM) qr = q_range(v.bounds, b);
     [[maybe_unused]] int cmask = 0, cnum = 1;                        // GUMBEL: the tree's candidates and their number
     if constexpr (GUMBEL) {
-        cmask = gumbel_of(arg).cand[b] & ((1 << A) - 1);
+        cmask = v.cand[b] & ((1 << A) - 1);
         cnum = max(__popc((unsigned)cmask), 1);
     }
     const int used0 = v.used[b];
@@ -767,7 +717,7 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
             [[maybe_unused]] int turn = -1;                          // GUMBEL, a root with candidates: the action whose turn it is
             if constexpr (GUMBEL) {
                 if (depth == 0 && cmask != 0) {
-                    int skip = (gumbel_of(arg).offset + k) % cnum;
+                    int skip = (v.offset + k) % cnum;
 #pragma unroll
                     for (int a = A - 1; a >= 0; --a) turn = (cmask >> a & 1) && __popc((unsigned)cmask & ((1u << a) - 1u)) == skip ? a : turn;
                 }
@@ -776,13 +726,14 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
             // The rule needs sums over every action before any score, so INTERIOR unpacks the pieces here (node_actions) and the shared loop
             // below unpacks child / visits / in-flight once more, with pr and cw it does not use: deliberate.  The loop stays the one the
             // other forms compile (their instruction streams are unchanged), and the compiler folds the repeated selects of the same registers.
+            // Its selects are spelled out, and this kernel loads its own pieces: with word_of or NodePieces (uct_dev.h) several forms' listings move.
             if constexpr (INTERIOR) {
                 if (turn < 0) {
                     int ch[A], cn[A], cf[A], np[A], total;
                     float pr[A];
                     double cw[A], pi[A];
                     node_actions<A>(pc, pn, pf, pp, pw, ch, cn, cf, pr, cw);
-                    gumbel_policy<A, true>(ch, cn, cf, pr, cw, f64(pv.x, pv.y), qr, arg.c_visit, arg.c_scale, v.rtab, v.tlen, pi, np, total);
+                    gumbel_policy<A, true>(ch, cn, cf, pr, cw, f64(pv.x, pv.y), qr, v.c_visit, v.c_scale, v.rtab, v.tlen, pi, np, total);
                     const double inv = v.rtab[min(max(total, 0), v.tlen - 1)];
 #pragma unroll
                     for (int a = 0; a < A; ++a) {
@@ -814,8 +765,8 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
                 } else {
 #pragma clang fp contract(off)                                      // no fma: U rounded step by step, as a host restatement computes it
                     const int np = has ? cn + cf : 0;
-                    const double t = w.vl * (double)cf;
-                    double q = has ? (cw - t) / (double)np : z.fpv;
+                    const double t = v.vl * (double)cf;
+                    double q = has ? (cw - t) / (double)np : v.fpv;
                     if constexpr (NORM) q = has ? q_norm(q, qr) : q;
                     const double e0 = (double)pr * sq;
                     const double e = e0 * v.rtab[min(max(np, 0), v.tlen - 1)];
@@ -828,12 +779,7 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
             int32_t* const words = reinterpret_cast<int32_t*>(v.stats + (size_t)n * PIECES);
             if (bchild < 0) {                                        // the best action is untried
                 if (used < v.cap) {                                  // expand it into the tree's next row
-                    const int row = base + used;
-                    used += 1;
-                    words[best] = row;
-                    words[4 * P_FLY + best] = 1;
-                    reinterpret_cast<int32_t*>(v.stats + (size_t)row * PIECES)[39] = s;
-                    leaf = row;
+                    leaf = expand_path(words, v.stats, best, base, used, s);
                     act = best;
                     expanded = true;
                     first = s;
@@ -842,14 +788,14 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
                 if (tried < 0) break;                                // no children and the budget spent
                 best = tried; bf = tf; bchild = tchild;              // the budget spent: the best of the tried children
             }
-            words[4 * P_FLY + best] = bf + 1;
+            words[W_FLY + best] = bf + 1;
             fly = bf;
             n = clamp_row(bchild, base, v.cap);
             if (n >= fresh) {                                        // made by an earlier path of this launch: stop on it
                 leaf = n;
                 src = base;                                          // the row is another edge's destination: step the root instead
                 r = 0.f;
-                first = reinterpret_cast<const int32_t*>(v.stats + (size_t)n * PIECES)[39];
+                first = fresh_row_slot(v.stats, n);
                 break;
             }
         }
@@ -859,46 +805,42 @@ __global__ __launch_bounds__(64) void k_uct_select_puct(const UctSelPuctArg<NORM
         v.leaf[s] = leaf;
         v.expanded[s] = expanded ? 1 : 0;
         v.r_leaf[s] = expanded ? 0.f : r;
-        w.first_slot[s] = first;
+        v.first_slot[s] = first;
     }
     v.used[b] = used;
 }
 
 // priors into nodes: thread = node, the node's 32-byte span (pieces P_PRIOR, P_PRIOR + 1) as two 16-byte stores; a row outside the
-// array is skipped
+// array is skipped.  VALUE: the node's net_value (words 56-57) too, as one 8-byte store, loaded before the first store.
+template <int A, bool VALUE>
+__device__ __forceinline__ void set_priors(uint4* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
+                                           const double* value, int only_unvisited) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= m) return;
+    const int row = rows[i];
+    if (row < 0 || row >= stats_rows) return;
+    uint4* const rec = stats + (size_t)row * PIECES;
+    if (only_unvisited && rec[P_HDR].w != 0u) return;
+    uint32_t p[8];
+#pragma unroll
+    for (int a = 0; a < 8; ++a) p[a] = a < A ? __float_as_uint(priors[(size_t)i * A + a]) : 0u;
+    [[maybe_unused]] double nv = 0.0;
+    if constexpr (VALUE) nv = value[i];
+    rec[P_PRIOR] = make_uint4(p[0], p[1], p[2], p[3]);
+    rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
+    if constexpr (VALUE) *reinterpret_cast<double*>(rec + P_NETV) = nv;
+}
+
 template <int A>
 __global__ __launch_bounds__(256) void k_uct_set_priors(uint4* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
                                                         int only_unvisited) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= m) return;
-    const int row = rows[i];
-    if (row < 0 || row >= stats_rows) return;
-    uint4* const rec = stats + (size_t)row * PIECES;
-    if (only_unvisited && rec[P_HDR].w != 0u) return;
-    uint32_t p[8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a) p[a] = a < A ? __float_as_uint(priors[(size_t)i * A + a]) : 0u;
-    rec[P_PRIOR] = make_uint4(p[0], p[1], p[2], p[3]);
-    rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
+    set_priors<A, false>(stats, stats_rows, m, rows, priors, nullptr, only_unvisited);
 }
 
-// priors and the network value into nodes: k_uct_set_priors, and the node's net_value (words 56-57) as one 8-byte store
 template <int A>
 __global__ __launch_bounds__(256) void k_uct_set_priors_value(uint4* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
                                                               const double* value, int only_unvisited) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= m) return;
-    const int row = rows[i];
-    if (row < 0 || row >= stats_rows) return;
-    uint4* const rec = stats + (size_t)row * PIECES;
-    if (only_unvisited && rec[P_HDR].w != 0u) return;
-    uint32_t p[8];
-#pragma unroll
-    for (int a = 0; a < 8; ++a) p[a] = a < A ? __float_as_uint(priors[(size_t)i * A + a]) : 0u;
-    const double nv = value[i];
-    rec[P_PRIOR] = make_uint4(p[0], p[1], p[2], p[3]);
-    rec[P_PRIOR + 1] = make_uint4(p[4], p[5], p[6], p[7]);
-    *reinterpret_cast<double*>(rec + P_NETV) = nv;
+    set_priors<A, true>(stats, stats_rows, m, rows, priors, value, only_unvisited);
 }
 
 // the improved policy of m nodes: thread = node, the statistics read only; the node's six kinds of pieces are all issued before the
@@ -1001,46 +943,61 @@ int bounds_width(int cap) {
     return cap > 128 ? 64 : cap > 64 ? 32 : cap > 32 ? 16 : 8;
 }
 
-int uct_check_rows(const void* stats, int32_t rows, int32_t B, int32_t cap);
+int actions_check(int A) { return A != 3 && A != 5 && A != 8 ? fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8") : SNAC_OK; }
+
+// the statistics array against B trees of cap rows: one slot and one scratch row per tree, or with `paths` (K paths per tree) B * K
+// slots and B * (cap + K) rows
+int uct_check_rows(const void* stats, int32_t rows, int32_t B, int32_t cap, const int32_t* paths = nullptr) {
+    using namespace snac_detail;
+    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
+    if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
+    if (cap < 1) return fail(SNAC_ERR_ARG, "cap must be >= 1");
+    if (paths && *paths < 1) return fail(SNAC_ERR_ARG, "paths must be >= 1");
+    if (paths && (long long)B * (long long)*paths > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * paths slots exceed int32");
+    const long long need = (long long)B * ((long long)cap + (paths ? (long long)*paths : 1));
+    if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, paths ? "B * (cap + paths) rows exceed int32" : "B * (cap + 1) rows exceed int32");
+    if (need > rows) return fail(SNAC_ERR_ARG, paths ? "B * (cap + paths) rows exceed stats_rows" : "B * (cap + 1) rows exceed stats_rows");
+    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    return SNAC_OK;
+}
 
 int uct_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
-    using namespace snac_detail;
-    if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
+    if (int rc = actions_check(A)) return rc;
     return uct_check_rows(stats, rows, B, cap);
 }
 
-int uct_check_rows(const void* stats, int32_t rows, int32_t B, int32_t cap) {
-    using namespace snac_detail;
-    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
-    if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
-    if (cap < 1) return fail(SNAC_ERR_ARG, "cap must be >= 1");
-    const long long need = (long long)B * ((long long)cap + 1);
-    if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed int32");
-    if (need > rows) return fail(SNAC_ERR_ARG, "B * (cap + 1) rows exceed stats_rows");
-    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
-    return SNAC_OK;
-}
-
-// the checks of uct_check for K paths per tree: B * K slots, B * (cap + K) rows
 int uct_check_paths(int A, const void* stats, int32_t rows, int32_t B, int32_t cap, int32_t K) {
-    using namespace snac_detail;
-    if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
-    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
-    if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
-    if (cap < 1) return fail(SNAC_ERR_ARG, "cap must be >= 1");
-    if (K < 1) return fail(SNAC_ERR_ARG, "paths must be >= 1");
-    if ((long long)B * (long long)K > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * paths slots exceed int32");
-    const long long need = (long long)B * ((long long)cap + (long long)K);
-    if (need > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "B * (cap + paths) rows exceed int32");
-    if (need > rows) return fail(SNAC_ERR_ARG, "B * (cap + paths) rows exceed stats_rows");
-    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
-    return SNAC_OK;
+    if (int rc = actions_check(A)) return rc;
+    return uct_check_rows(stats, rows, B, cap, &K);
 }
 
 int bounds_check(const void* bounds) {
     using namespace snac_detail;
     if (!bounds) return fail(SNAC_ERR_ARG, "null bounds");
     if (((uintptr_t)bounds & 15) != 0) return fail(SNAC_ERR_ARG, "bounds must be 16-byte aligned (a tree's pair is one piece)");
+    return SNAC_OK;
+}
+
+// what the K-paths selections check after their scalars: the two tables (null_tables: the message that names them), the per-slot
+// arrays, and with `norm` the bounds
+int select_check(const UctSelPaths& v, const char* null_tables, bool norm, const double* bounds) {
+    using namespace snac_detail;
+    if (!v.ltab || !v.rtab) return fail(SNAC_ERR_ARG, null_tables);
+    if (v.tlen < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
+    if (!v.used || !v.src || !v.dst || !v.action || !v.leaf || !v.expanded || !v.r_leaf || !v.first_slot)
+        return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
+    return norm ? bounds_check(bounds) : SNAC_OK;
+}
+
+// what snac_uct_set_priors and snac_uct_set_priors_value check alike
+int set_priors_check(int A, const void* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors) {
+    using namespace snac_detail;
+    if (int rc = actions_check(A)) return rc;
+    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
+    if (stats_rows < 1) return fail(SNAC_ERR_ARG, "stats_rows must be >= 1");
+    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
+    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
+    if (!rows || !priors) return fail(SNAC_ERR_ARG, "null rows / priors");
     return SNAC_OK;
 }
 
@@ -1069,8 +1026,7 @@ int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
     by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_select<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_select");
+    return launched("snac_uct_select");
 }
 
 int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double gamma, const int32_t* src,
@@ -1085,8 +1041,7 @@ int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
     by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_backup<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_backup");
+    return launched("snac_uct_backup");
 }
 
 int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
@@ -1108,8 +1063,7 @@ int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
         if (record_bytes == 128) hipLaunchKernelGGL((k_uct_advance<A, 8>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, v);
         else hipLaunchKernelGGL((k_uct_advance<A, 56>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_advance");
+    return launched("snac_uct_advance");
 }
 
 // the plain and the _norm entry points share their checks and launches: bounds == nullptr is the plain form
@@ -1120,14 +1074,9 @@ static int select_paths(const char* name, int32_t num_actions, snac_uct_node* st
     using namespace snac_detail;
     if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
     if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
-    if (!log_table || !rsqrt_table) return fail(SNAC_ERR_ARG, "null log_table / rsqrt_table");
-    if (table_len < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
-    if (!used || !src || !dst || !action || !leaf || !expanded || !r_leaf || !first_slot)
-        return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
-    if (norm)
-        if (int rc = bounds_check(bounds)) return rc;
     const UctSelPaths v{{(uint4*)stats, B, cap, c, log_table, rsqrt_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
                         paths, virtual_loss, first_slot};
+    if (int rc = select_check(v, "null log_table / rsqrt_table", norm, bounds)) return rc;
     const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_select_paths";
     by_actions(num_actions, [&](auto k) {
@@ -1135,8 +1084,7 @@ static int select_paths(const char* name, int32_t num_actions, snac_uct_node* st
         if (norm) hipLaunchKernelGGL((k_uct_select_paths<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPathsNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_select_paths<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, name);
+    return launched(name);
 }
 
 int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -1172,8 +1120,7 @@ static int backup_paths(const char* name, int32_t num_actions, snac_uct_node* st
         if (norm) hipLaunchKernelGGL((k_uct_backup_paths<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctBackPathsNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_backup_paths<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, name);
+    return launched(name);
 }
 
 int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
@@ -1199,21 +1146,16 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
     if (int rc = uct_check_paths(num_actions, stats, stats_rows, B, cap, paths)) return rc;
     if (!std::isfinite(virtual_loss)) return fail(SNAC_ERR_ARG, "virtual_loss must be finite");
     if (!std::isfinite(first_play_value)) return fail(SNAC_ERR_ARG, "first_play_value must be finite");
-    if (!sqrt_table || !inv_table) return fail(SNAC_ERR_ARG, "null sqrt_table / inv_table");
-    if (table_len < 2) return fail(SNAC_ERR_ARG, "table_len must be >= 2");
-    if (!used || !src || !dst || !action || !leaf || !expanded || !r_leaf || !first_slot)
-        return fail(SNAC_ERR_ARG, "null per-slot array (used / src / dst / action / leaf / expanded / r_leaf / first_slot)");
-    if (norm)
-        if (int rc = bounds_check(bounds)) return rc;
+    const UctSelPuct v{{{(uint4*)stats, B, cap, c, sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
+                        paths, virtual_loss, first_slot},
+                       first_play_value};
+    if (int rc = select_check(v, "null sqrt_table / inv_table", norm, bounds)) return rc;
     if (gumbel) {
         if (!cand) return fail(SNAC_ERR_ARG, "null cand");
         if (offset < 0) return fail(SNAC_ERR_ARG, "offset must be >= 0");
         if ((long long)offset + (long long)paths > 0x7FFFFFFFll) return fail(SNAC_ERR_ARG, "offset + paths exceeds int32");
     }
     if (interior && (!std::isfinite(c_visit) || !std::isfinite(c_scale))) return fail(SNAC_ERR_ARG, "c_visit and c_scale must be finite");
-    const UctSelPuct v{{{(uint4*)stats, B, cap, c, sqrt_table, inv_table, table_len, used, src, dst, action, leaf, expanded, r_leaf},
-                        paths, virtual_loss, first_slot},
-                       first_play_value};
     const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_select_puct";
     by_actions(num_actions, [&](auto k) {
@@ -1225,8 +1167,7 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
         else if (norm) hipLaunchKernelGGL((k_uct_select_puct<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPuctNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_select_puct<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, name);
+    return launched(name);
 }
 
 int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -1269,31 +1210,20 @@ int snac_uct_select_gumbel_interior(int32_t num_actions, snac_uct_node* stats, i
 int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
                         int32_t only_unvisited, void* stream) {
     using namespace snac_detail;
-    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
-    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
-    if (stats_rows < 1) return fail(SNAC_ERR_ARG, "stats_rows must be >= 1");
-    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
-    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
-    if (!rows || !priors) return fail(SNAC_ERR_ARG, "null rows / priors");
+    if (int rc = set_priors_check(num_actions, stats, stats_rows, m, rows, priors)) return rc;
     if (m == 0) return SNAC_OK;
     g_kernel = "k_uct_set_priors";
     by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_set_priors<decltype(k)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint4*)stats,
                            stats_rows, m, rows, priors, only_unvisited != 0 ? 1 : 0);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_set_priors");
+    return launched("snac_uct_set_priors");
 }
 
 int snac_uct_set_priors_value(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
                               const double* value, int32_t only_unvisited, void* stream) {
     using namespace snac_detail;
-    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
-    if (!stats) return fail(SNAC_ERR_ARG, "null stats");
-    if (stats_rows < 1) return fail(SNAC_ERR_ARG, "stats_rows must be >= 1");
-    if (m < 0) return fail(SNAC_ERR_ARG, "m must be >= 0");
-    if (((uintptr_t)stats & 127) != 0) return fail(SNAC_ERR_ARG, "stats must be 128-byte aligned (records of whole lines)");
-    if (!rows || !priors) return fail(SNAC_ERR_ARG, "null rows / priors");
+    if (int rc = set_priors_check(num_actions, stats, stats_rows, m, rows, priors)) return rc;
     if (!value) return fail(SNAC_ERR_ARG, "null value");
     if (m == 0) return SNAC_OK;
     g_kernel = "k_uct_set_priors_value";
@@ -1301,8 +1231,7 @@ int snac_uct_set_priors_value(int32_t num_actions, snac_uct_node* stats, int32_t
         hipLaunchKernelGGL((k_uct_set_priors_value<decltype(k)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            (uint4*)stats, stats_rows, m, rows, priors, value, only_unvisited != 0 ? 1 : 0);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_set_priors_value");
+    return launched("snac_uct_set_priors_value");
 }
 
 int snac_uct_improved_policy(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t m,
@@ -1320,8 +1249,7 @@ int snac_uct_improved_policy(int32_t num_actions, const snac_uct_node* stats, in
     by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_improved_policy<decltype(k)::value>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_improved_policy");
+    return launched("snac_uct_improved_policy");
 }
 
 int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* used, const uint8_t* mask,
@@ -1338,8 +1266,7 @@ int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, i
     else if (G == 16) hipLaunchKernelGGL((k_uct_bounds<16>), grid, dim3(64), 0, (hipStream_t)stream, v);
     else if (G == 32) hipLaunchKernelGGL((k_uct_bounds<32>), grid, dim3(64), 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_bounds<64>), grid, dim3(64), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_bounds");
+    return launched("snac_uct_bounds");
 }
 
 }  // extern "C"

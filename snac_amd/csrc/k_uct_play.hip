@@ -6,18 +6,13 @@
 #include <cstddef>
 
 #include "snac_dev.h"
+#include "uct_dev.h"
 
 // Three small, latency-bound kernels beside k_uct_advance.  pick and returns are lane = tree: a root is one 128-byte line (two when the
 // value is asked for) and a ring slot is one coalesced span over b.  restart is wave = tree: the record (8 or 56 pieces of 16 bytes) and
 // the statistics row (16 pieces) of a restarted tree leave as one piece per lane.
 namespace {
 
-static_assert(sizeof(snac_uct_node) == 256 && offsetof(snac_uct_node, child_visits) == 32 && offsetof(snac_uct_node, parent) == 128 &&
-                  offsetof(snac_uct_node, value_sum) == 144,
-              "the piece map below");
-
-constexpr int PIECES = 16;                                           // 16-byte pieces per statistics row
-constexpr int P_VISITS = 2, P_HDR = 8, P_OWN = 9;
 constexpr uint32_t PICK_STREAM = 3;                                  // the counter RNG's stream of the sampled moves
 
 struct UctPick {
@@ -141,7 +136,6 @@ __global__ __launch_bounds__(64) void k_uct_returns(const UctReturns v) {
 // lane = tree, as k_uct_pick: the root's line 0 (children, child visits, child values), its header's terminal word, the tree's A scores
 // and its bounds pair are all issued before the first is used; the choice is A rounds of "the largest remaining by strict >, scanning a
 // upward" over at most 8 ranks held in registers.
-constexpr int P_CHILD = 0, P_VALUE = 4;
 constexpr int GUMBEL_BEGIN = 0, GUMBEL_HALVE = 1, GUMBEL_PICK = 2;
 
 struct UctGumbel {
@@ -270,8 +264,7 @@ int snac_uct_pick_moves(const snac_env_desc* desc, int32_t num_actions, const sn
     if (num_actions == 3) hipLaunchKernelGGL((k_uct_pick<3>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     else if (num_actions == 5) hipLaunchKernelGGL((k_uct_pick<5>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_pick<8>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_pick_moves");
+    return launched("snac_uct_pick_moves");
 }
 
 int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
@@ -289,8 +282,7 @@ int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
     g_kernel = "k_uct_restart";
     if (record_bytes == 128) hipLaunchKernelGGL((k_uct_restart<8>), grid, block, 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_restart<56>), grid, block, 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_restart");
+    return launched("snac_uct_restart");
 }
 
 int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count, double gamma, const float* reward, const uint8_t* done,
@@ -307,8 +299,7 @@ int snac_uct_returns(int32_t B, int32_t cap_moves, int32_t first, int32_t count,
     const UctReturns v{B, cap_moves, first, count, gamma, reward, done, bootstrap, z};
     g_kernel = "k_uct_returns";
     hipLaunchKernelGGL(k_uct_returns, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_returns");
+    return launched("snac_uct_returns");
 }
 
 int snac_uct_gumbel_candidates(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t mode, int32_t m,
@@ -333,8 +324,7 @@ int snac_uct_gumbel_candidates(int32_t num_actions, const snac_uct_node* stats, 
     if (num_actions == 3) hipLaunchKernelGGL((k_uct_gumbel<3>), grid, dim3(64), 0, (hipStream_t)stream, v);
     else if (num_actions == 5) hipLaunchKernelGGL((k_uct_gumbel<5>), grid, dim3(64), 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_gumbel<8>), grid, dim3(64), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_gumbel_candidates");
+    return launched("snac_uct_gumbel_candidates");
 }
 
 }  // extern "C"

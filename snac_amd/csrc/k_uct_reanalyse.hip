@@ -6,18 +6,12 @@
 #include <cstddef>
 
 #include "snac_dev.h"
+#include "uct_dev.h"
 
 // Four small, latency-bound kernels beside those of k_uct_play.hip, with its shapes.  save is lane = piece: the B root records leave as
 // one run of 16-byte pieces.  load is wave = tree, as k_uct_restart: the record (8 or 56 pieces) is read once and stored twice, the
 // statistics row (16 pieces) is written whole, one piece per lane.  store and returns are lane = tree, as k_uct_pick and k_uct_returns.
 namespace {
-
-static_assert(sizeof(snac_uct_node) == 256 && offsetof(snac_uct_node, child_visits) == 32 && offsetof(snac_uct_node, parent) == 128 &&
-                  offsetof(snac_uct_node, value_sum) == 144,
-              "the piece map below");
-
-constexpr int PIECES = 16;                                           // 16-byte pieces per statistics row
-constexpr int P_VISITS = 2, P_HDR = 8, P_OWN = 9;
 
 struct UctSave {
     const uint4* records;
@@ -175,8 +169,7 @@ int snac_uct_save_roots(int32_t B, int32_t cap, const void* records, int32_t rec
     g_kernel = "k_uct_save_roots";
     if (record_bytes == 128) hipLaunchKernelGGL((k_uct_save_roots<8>), grid, dim3(256), 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_save_roots<56>), grid, dim3(256), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_save_roots");
+    return launched("snac_uct_save_roots");
 }
 
 int snac_uct_load_roots(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
@@ -197,8 +190,7 @@ int snac_uct_load_roots(int32_t num_actions, snac_uct_node* stats, int32_t stats
     g_kernel = "k_uct_load_roots";
     if (record_bytes == 128) hipLaunchKernelGGL((k_uct_load_roots<8>), grid, block, 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_load_roots<56>), grid, block, 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_load_roots");
+    return launched("snac_uct_load_roots");
 }
 
 int snac_uct_store_targets(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* index,
@@ -215,8 +207,7 @@ int snac_uct_store_targets(int32_t num_actions, const snac_uct_node* stats, int3
     if (num_actions == 3) hipLaunchKernelGGL((k_uct_store_targets<3>), grid, dim3(64), 0, (hipStream_t)stream, v);
     else if (num_actions == 5) hipLaunchKernelGGL((k_uct_store_targets<5>), grid, dim3(64), 0, (hipStream_t)stream, v);
     else hipLaunchKernelGGL((k_uct_store_targets<8>), grid, dim3(64), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_store_targets");
+    return launched("snac_uct_store_targets");
 }
 
 int snac_uct_returns_nstep(int32_t B, int32_t cap_moves, int32_t first, int32_t count, int32_t n, double gamma, const float* reward,
@@ -235,8 +226,7 @@ int snac_uct_returns_nstep(int32_t B, int32_t cap_moves, int32_t first, int32_t 
     const UctNstep v{B, cap_moves, first, count, n, gamma, reward, done, value, bootstrap, z};
     g_kernel = "k_uct_returns_nstep";
     hipLaunchKernelGGL(k_uct_returns_nstep, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SNAC_OK : fail_hip(e, "snac_uct_returns_nstep");
+    return launched("snac_uct_returns_nstep");
 }
 
 }  // extern "C"

@@ -20,6 +20,9 @@
 //   k_nodes_obs.hip k_observe1dp / 2dp / 3dp   the observation rows of node records
 //                   (nodes_dev.h: the record's map, its trip through LDS and the window decoders, for these two and k_eval.hip)
 //   k_eval.hip      k_eval        default-policy evaluation of tree leaves in place on node pools: lane = leaf, the rollout and the sum fused
+//   k_uct.hip       k_uct_select / backup / advance and their K-paths, PUCT, normalised and Gumbel forms: tree search over node pools
+//   k_uct_play.hip, k_uct_reanalyse.hip   self-play and Reanalyse on those trees
+//                   (uct_dev.h: the map of a statistics row in pieces and words, for these three)
 //   k_mailbox.hip   k_mailbox     the resident stepper behind the drop-in classes (mailbox_host.h: the host half of its protocol)
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows
 //   k_tile{1,2,3}d.hip  the tile kernels k_rollout / k_transition / k_aux (rounds 1-2) behind all of them (templates: k_tile.inc)
