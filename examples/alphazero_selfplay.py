@@ -4,7 +4,7 @@ cross-entropy to the visit distribution, squared error to the discounted return.
 trainer: nothing but the final printout crosses the bus.
 
     python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20] [--normalise] [--gumbel M [--gumbel-interior]]
-                                          [--reanalyse R] [--td-steps N]
+                                          [--reanalyse R] [--td-steps N] [--prioritized [--per-alpha A] [--per-beta B]]
 
 --normalise: the search compares q normalised by each tree's min-max bounds (UCTSearch(q_normalise=True)), so that c = 1.25 weighs
 the priors against returns of any scale (a brick pays 5 here).
@@ -18,6 +18,9 @@ on the device are searched again by a second search of R trees that shares the n
 (SelfPlay.reanalyse()).
 --td-steps N: the value target is the N-step return that bootstraps from the ring's values (targets(td_steps=N)), so that refreshed
 values reach z, in place of the return to the end of the episode.
+--prioritized: MuZero's prioritised replay (SelfPlay(prioritized=True)): minibatches -- and the positions of --reanalyse -- are drawn in
+proportion to |value - z| ** A from a sum tree on the device, the loss is weighted by the importance weights (exponent B), and the
+sampled entries get their new priorities after every step (update_priorities()).
 """
 import argparse
 import os
@@ -31,7 +34,7 @@ from snac_amd import BatchedDMPEnv, SelfPlay, UCTSearch  # noqa: E402
 
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
-          gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None):
+          gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4):
     """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
     SelfPlay)."""
     env = BatchedDMPEnv(kind, True, envs, seed=seed)
@@ -54,6 +57,8 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
                        gumbel_interior=bool(gumbel_interior))
     search.reset()
     keep = dict(keep_states=True) if reanalyse else {}
+    if prioritized:
+        keep["prioritized"] = True
     if gumbel is None:
         play = SelfPlay(search, capacity, sample_moves=8, root_noise=noise, **keep)
     else:                                                            # the Gumbel noise of the first moves explores
@@ -66,12 +71,17 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
     for _ in range(steps):
         play.play(moves, iterations)
         if again is not None:
-            play.reanalyse(again, iterations)
+            play.reanalyse(again, iterations, **(dict(prioritized=True) if prioritized else {}))
         play.targets(td_steps=td_steps)
-        b = play.sample(batch)
+        b = play.sample(batch, **(dict(prioritized=True, beta=per_beta) if prioritized else {}))
         y = net(b["obs"])
-        policy_loss = -(b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1).mean()
-        value_loss = ((y[:, A] - b["z"]) ** 2).mean()
+        if prioritized:                                              # the importance weights undo the sampling bias
+            policy_loss = -(b["weight"] * (b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1)).mean()
+            value_loss = (b["weight"] * (y[:, A] - b["z"]) ** 2).mean()
+            play.update_priorities(b["index"], (y[:, A].detach() - b["z"]).abs() ** per_alpha)
+        else:
+            policy_loss = -(b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1).mean()
+            value_loss = ((y[:, A] - b["z"]) ** 2).mean()
         loss = policy_loss + value_loss
         opt.zero_grad()
         loss.backward()
@@ -90,11 +100,15 @@ def main():
     ap.add_argument("--gumbel-interior", action="store_true")
     ap.add_argument("--reanalyse", type=int, default=0, metavar="R", help="stored positions searched again per training step (default: none)")
     ap.add_argument("--td-steps", type=int, default=None, metavar="N", help="the N-step value target (default: the return to the episode's end)")
+    ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample and reanalyse in proportion to |value - z| ** alpha")
+    ap.add_argument("--per-alpha", type=float, default=1.0, metavar="A", help="the priority exponent (default 1, MuZero's)")
+    ap.add_argument("--per-beta", type=float, default=0.4, metavar="B", help="the exponent of the importance weights (default 0.4)")
     args = ap.parse_args()
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
     losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps, normalise=args.normalise, gumbel=args.gumbel,
-                         gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps)
+                         gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps,
+                         prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     if args.reanalyse:
         print("entries reanalysed: %d" % int(play.refreshed.sum()))

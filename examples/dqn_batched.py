@@ -4,7 +4,11 @@ are appended with ReplayRing.append), minibatches come from snac_replay_gather. 
 reference's 2D dynamic DQN (script/DQN/2d/DQN_2d_dynamic.py: observation 51 + plan 400 -> 5 Q values, target network,
 replace every `replace` steps); this file is an illustration of the API, not part of the parity surface.
 
-    python examples/dqn_batched.py --envs 4096 --ticks 200
+    python examples/dqn_batched.py --envs 4096 --ticks 200 [--prioritized]
+
+--prioritized: prioritised replay as in the reference's script/Rainbow, with the sum tree on the device (ReplayRing(prioritized=True)):
+minibatches are drawn in proportion to |td|, the loss is weighted by the importance weights, and the sampled transitions get their new
+priorities after every step.
 """
 import argparse
 import os
@@ -29,12 +33,12 @@ class QNet(nn.Module):
         return self.body(torch.cat([obs, plan.flatten(1)], dim=1))
 
 
-def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print):
+def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4):
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev = env.device
     obs = env.reset()
-    ring = ReplayRing(env, capacity_ticks=max(2 * prefill, 128))
+    ring = ReplayRing(env, capacity_ticks=max(2 * prefill, 128), **(dict(prioritized=True) if prioritized else {}))
     ring.collect(prefill)                                          # random policy, one fused launch
     obs = env.observe()
     plan = env.input_plan().float()
@@ -51,12 +55,17 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
         ring.append(actions)                                       # one env tick, recorded in the ring (auto-reset)
         obs = env.observe()
         plan = env.input_plan().float()                            # resets change plans
-        mb = ring.sample(batch)
+        mb = ring.sample(batch, **(dict(prioritized=True, beta=beta) if prioritized else {}))
         with torch.no_grad():
             q_next = target(mb["s_next"], mb["plan"]).max(dim=1).values
             y = mb["reward"] + gamma * q_next * (~mb["done"]).float()
         q = net(mb["s"], mb["plan"]).gather(1, mb["action"][:, None]).squeeze(1)
-        loss = nn.functional.mse_loss(q, y)
+        if prioritized:
+            td = q - y
+            loss = (mb["weight"] * td ** 2).mean()
+            ring.update_priorities(mb["index"], td.detach().abs())
+        else:
+            loss = nn.functional.mse_loss(q, y)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -76,5 +85,6 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--batch", type=int, default=2048)
+    ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample in proportion to |td|")
     a = ap.parse_args()
-    run(a.envs, a.ticks, a.batch)
+    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized)

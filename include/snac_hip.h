@@ -59,6 +59,8 @@
  *   stream 2 (per plan row):        the plan generator (snac_make_plans with vertices NULL)
  *   stream 3 (per env, move t):     the move a self-play search samples from its root's visits (snac_uct_pick_moves):
  *                                   u = (word * total) >> 32, action = the lowest a with N_0 + ... + N_a > u
+ *   stream 4 (per sample, draw d):  the entry a prioritised-replay tree draws (snac_prio_sample; "Prioritised replay" below):
+ *                                   r = (word(.., 2 * d) << 32) | word(.., 2 * d + 1), keyed by sampler_id + j for sample j of a call
  *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.  The node-pool entry points key edge /
  *   leaf i of a call by env_id_base + i; a search with K paths per tree hands them its B * K slots with env_id_base * K in the descriptor,
  *   so that slot k of tree b draws with (env_id_base + b) * K + k, its slot in the search over all envs ("K paths per tree" below).
@@ -742,6 +744,46 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *     Hence n >= count gives snac_uct_returns bit for bit, and a window that crosses the end of an episode stops there.  Slots outside the
  *     count are not written; z must not alias value.  Checks: those of snac_uct_returns; n >= 1; value non-null.  count == 0: nothing is
  *     launched.
+ * Prioritised replay: a 64-ary sum tree of integer weights in device memory, updated and sampled in O(log64 entries) per item with no
+ *   host synchronisation (snac_prio_layout / snac_prio_init / snac_prio_update / snac_prio_fill / snac_prio_sample, k_prio.hip;
+ *   snac_amd/priority.py PriorityTree, SelfPlay(prioritized=True), ReplayRing(prioritized=True)).
+ *   Weights.  An entry's weight is a uint32; every sum is a uint64, hence exact and independent of the order of its terms.  A float
+ *     priority p becomes a weight by quant(p, s), s = scale_log2 in 0 .. 31:
+ *         p == 0 -> 0 (the entry cannot be drawn);   NaN or p < 0 -> 1;   otherwise min(max(rint((double)p * 2^s), 1), 2^32 - 1)
+ *     (the multiply by a power of two is exact in float64; rint rounds half to even).
+ *   The buffer: caller-owned, 128-byte aligned, snac_prio_layout's `bytes` long, uint64 words:
+ *         head     128 bytes: word 0 = max_weight, the largest weight any snac_prio_update has stored (2^s, priority 1.0, after
+ *                  snac_prio_init); word 1 = entries; word 2 = the number of sum levels; words 3 .. 15 = 0
+ *         leaves   uint32[E64], E64 = entries rounded up to a multiple of 64               (level_offset[0] = 128)
+ *         level 1  uint64[n_1 rounded up to a multiple of 64], n_1 = E64 / 64: value g = the sum of leaves 64 g .. 64 g + 63
+ *         level l+1  uint64[n_{l+1} rounded up to a multiple of 64], n_{l+1} = ceil(n_l / 64): value g = the sum of level l's
+ *                  values 64 g .. 64 g + 63;  the last level has n = 1: its value 0 is the total T
+ *     Every level starts 128-byte aligned and all padding is zero.  entries is in [1, 2^31 - 64], so T < 2^63 and there are at most 6
+ *     sum levels.  The entry points take `entries` (and scale_log2) by value and derive the layout from it: the head is for readers.
+ *   snac_prio_layout (host only, no HIP call): bytes, levels (sum levels), level_offset[8] = bytes from the buffer's start of the
+ *     leaves ([0]) and of sum level l ([l], l = 1 .. levels); the unused offsets are 0.
+ *   snac_prio_init: writes the head and zeroes everything else (one launch).
+ *   snac_prio_update: for j < n with i = index[j] in [0, entries) (any other index is skipped): leaf i <- quant(priority[j], s); where
+ *     an index occurs more than once in a call the largest weight wins; max_weight <- max(max_weight, the weights stored).  Then every
+ *     sum above a touched leaf is recomputed from its 64 children.  Launches, in stream order: the indexed leaves <- 0; atomic max of
+ *     the weights into the leaves (and one atomic max per wavefront into max_weight); then one launch per sum level, one wavefront per
+ *     parent (lane = child, a wave reduction, one lane stores): the parent of each index, or, where the level has no more values
+ *     than n, all of them.  Duplicate parents do identical work.
+ *   snac_prio_fill: entries [first, first + count) <- one weight: priority < 0: the head's max_weight as it stands on the device (new
+ *     transitions get the largest priority seen); priority == 0: 0; otherwise quant(priority, s).  Then the sums above them, a
+ *     contiguous range of each level, one launch per level; count = entries rebuilds the tree.  max_weight is not changed; the span does
+ *     not wrap.
+ *   snac_prio_sample: sample j < n draws with r as under "Counter RNG", stream 4.  With T the total, q = T / n and rem = T % n:
+ *         stratified != 0 and q >= 1:  lo = j * q + min(j, rem);  len = q + (j < rem);  u = lo + mulhi64(r, len)
+ *         otherwise:                   u = mulhi64(r, T)                        (mulhi64: the high 64 bits of the 128-bit product)
+ *     index[j] = the lowest i with w_0 + ... + w_i > u, found from the top group down: at each level the lowest child whose inclusive
+ *     prefix sum within its group of 64 exceeds u, then u less that child's exclusive prefix.  prob[j] = (float)((double)w_i / (double)T);
+ *     weight[j] = w_i (weight may be NULL).  T == 0: index -1, prob 0, weight 0.  An entry of weight 0 is never drawn.  The tree is
+ *     READ ONLY.  Sums that do not match their children (a buffer written by other means) give index -1, never an index out of range.
+ *   Checks before any HIP call: tree non-null and 128-byte aligned; entries in [1, 2^31 - 64]; scale_log2 in 0 .. 31 (init, update,
+ *     fill); n >= 0, index and priority non-null (update); first in [0, entries), count in [0, entries - first], priority not NaN
+ *     (fill); draw in [0, 2^31), n >= 0, index and prob non-null (sample); the outputs non-null (layout).  n == 0 / count == 0: nothing
+ *     is launched.
  * Normalised q: per-tree min-max bounds of the mean values, so that U does not depend on the reward scale (snac_uct_select_paths_norm /
  *   snac_uct_select_puct_norm / snac_uct_backup_paths_norm / snac_uct_bounds; UCTSearch(q_normalise=True)).
  *   The bounds array: caller-owned, 2 * B float64, 16-byte aligned; bounds[2 * b] = lo, bounds[2 * b + 1] = hi of tree b; the empty pair
@@ -900,6 +942,13 @@ int snac_uct_store_targets(int32_t num_actions, const snac_uct_node* stats, int3
                            int32_t entries, const float* policy, float* pi, float* value, int32_t* refreshed, void* stream);
 int snac_uct_returns_nstep(int32_t B, int32_t cap_moves, int32_t first, int32_t count, int32_t n, double gamma, const float* reward,
                            const uint8_t* done, const float* value, const float* bootstrap, float* z, void* stream);
+
+int snac_prio_layout(int32_t entries, int64_t* bytes, int32_t* levels, int64_t* level_offset);
+int snac_prio_init(void* tree, int32_t entries, int32_t scale_log2, void* stream);
+int snac_prio_update(void* tree, int32_t entries, int32_t scale_log2, const int32_t* index, const float* priority, int32_t n, void* stream);
+int snac_prio_fill(void* tree, int32_t entries, int32_t scale_log2, int32_t first, int32_t count, double priority, void* stream);
+int snac_prio_sample(const void* tree, int32_t entries, uint64_t seed, int64_t sampler_id, int32_t draw, int32_t n, int32_t stratified,
+                     int32_t* index, float* prob, uint32_t* weight, void* stream);
 
 int snac_uct_select_paths_norm(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
                                double virtual_loss, const double* log_table, const double* rsqrt_table, int32_t table_len, int32_t* used,

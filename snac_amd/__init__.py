@@ -6,7 +6,7 @@ implementation.  See DESIGN.md / INTEGRATION.md.
 from ._lib import SnacError, build  # noqa: F401
 from . import plans  # noqa: F401
 
-__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "UCTSearch", "SelfPlay", "SnacError", "build", "plans"]
+__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "UCTSearch", "SelfPlay", "PriorityTree", "SnacError", "build", "plans"]
 
 
 def __getattr__(name):  # torch is imported lazily so that `import snac_amd` stays cheap
@@ -30,6 +30,10 @@ def __getattr__(name):  # torch is imported lazily so that `import snac_amd` sta
         from .selfplay import SelfPlay
 
         return SelfPlay
+    if name == "PriorityTree":
+        from .priority import PriorityTree
+
+        return PriorityTree
     if name == "VectorizedEnvWrapper":
         from .vector import VectorizedEnvWrapper
 

@@ -34,7 +34,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_observe_nodes3d", "snac_uct_select_puct", "snac_uct_set_priors", "snac_uct_pick_moves", "snac_uct_restart",
            "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds",
            "snac_uct_select_gumbel", "snac_uct_gumbel_candidates", "snac_uct_set_priors_value", "snac_uct_select_gumbel_interior",
-           "snac_uct_improved_policy", "snac_uct_save_roots", "snac_uct_load_roots", "snac_uct_store_targets", "snac_uct_returns_nstep")
+           "snac_uct_improved_policy", "snac_uct_save_roots", "snac_uct_load_roots", "snac_uct_store_targets", "snac_uct_returns_nstep",
+           "snac_prio_layout", "snac_prio_init", "snac_prio_update", "snac_prio_fill", "snac_prio_sample")
 
 
 class Sizes(C.Structure):
@@ -177,6 +178,11 @@ def lib():
         L.snac_uct_load_roots.argtypes = L.snac_uct_restart.argtypes[:8] + [vp, C.c_int32, vp, vp, vp]      # src, src_rows, index, used, the stream
         L.snac_uct_store_targets.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         L.snac_uct_returns_nstep.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
+        L.snac_prio_layout.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64 * 8)]
+        L.snac_prio_init.argtypes = [vp, C.c_int32, C.c_int32, vp]
+        L.snac_prio_update.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
+        L.snac_prio_fill.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp]
+        L.snac_prio_sample.argtypes = [vp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
         for n in ("snac_uct_select_paths", "snac_uct_select_puct", "snac_uct_backup_paths"):       # the arguments, bounds, the stream
             getattr(L, n + "_norm").argtypes = getattr(L, n).argtypes[:-1] + [vp, vp]
         L.snac_uct_bounds.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]

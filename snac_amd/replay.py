@@ -9,6 +9,12 @@ Here the fused rollout writes its outputs straight into a ring over ticks,
 and a transition is addressed by (slot, env): s' = obs[slot, env]; s = obs[slot - 1, env], or the reset observation
 when first[slot, env] (the reference takes prev_state from env.reset() there); plan = the plan row in effect.  Nothing
 is stored twice and nothing crosses PCIe; sample() gathers float32 minibatches with snac_replay_gather.
+
+Prioritised replay (the reference's script/Rainbow keeps a segment tree on the host): ReplayRing(..., prioritized=True) keeps a
+PriorityTree (snac_amd/priority.py; include/snac_hip.h, "Prioritised replay") over the cap * N entries, flat = slot * N + env.
+collect() gives every transition it writes the largest priority seen so far; sample(batch, prioritized=True, beta=...) draws in
+proportion to the priorities and adds slot, env, index, prob and the importance weights `weight`; update_priorities(index, |td|)
+stores new ones.
 """
 import ctypes as C
 
@@ -22,7 +28,7 @@ def _ptr(t):
 
 
 class ReplayRing:
-    def __init__(self, env, capacity_ticks, layout="ticks", place_candidates=0, memory="malloc"):
+    def __init__(self, env, capacity_ticks, layout="ticks", place_candidates=0, memory="malloc", prioritized=False, priority_scale_log2=16):
         """env: BatchedDMPEnv (already reset); capacity_ticks: ring length in vector steps (>= 2).
         layout "ticks": obs[cap, N, D]; "tiled": obs[ceil(N / 64), cap, 64, D] -- a tile of 64 envs streams through its own
         contiguous region of the ring (SNAC_OBS_TILED: the faster layout to collect into); row(slot, env) and
@@ -30,7 +36,13 @@ class ReplayRing:
         over chunks from two 32 GiB slices of physical memory: MI355X writes it 15-20 % faster; building it
         holds up to half of the free device memory for about a second and freeing it waits for the device, so it is opt-in),
         "malloc" (default): torch.empty, "auto": "vmm" from 1 GiB up.  place_candidates > 1: the ring is placed by env.alloc_trajectory (that many
-        candidate blocks timed with the rollout itself, the fastest kept: where the driver puts a block's runs still matters)."""
+        candidate blocks timed with the rollout itself, the fastest kept: where the driver puts a block's runs still matters).
+        prioritized=True: a PriorityTree over the cap * N entries (flat = slot * N + env), seeded from the env's seed, with
+        priority_scale_log2 as its scale_log2."""
+        if not isinstance(prioritized, bool):
+            raise ValueError("prioritized must be a bool")
+        if isinstance(priority_scale_log2, bool) or not isinstance(priority_scale_log2, int) or not 0 <= priority_scale_log2 <= 31:
+            raise ValueError("priority_scale_log2 must be an integer in [0, 31]")
         if capacity_ticks < 2:
             raise ValueError("capacity_ticks must be >= 2")
         if layout not in ("ticks", "tiled"):
@@ -68,6 +80,13 @@ class ReplayRing:
         # transitions have their `s` also when the ring is attached to envs in mid-episode (first[0, i] == 0)
         self._put(self.cap - 1, env.observe())
         self._env_t = env.t    # the env may only advance through the ring: s' / s are paired by slot
+        self.tree = None
+        if prioritized:
+            from .priority import MAX_ENTRIES, PriorityTree
+
+            if self.cap * N > MAX_ENTRIES:
+                raise ValueError("capacity_ticks * num_envs entries exceed what a PriorityTree holds (2^31 - 64)")
+            self.tree = PriorityTree(self.cap * N, dev, scale_log2=priority_scale_log2, seed=env.seed, sampler_id=env.env_id_base * self.cap)
 
     def _put(self, slot, rows):
         """rows [N, D] -> the ring's slot (either layout)"""
@@ -125,9 +144,13 @@ class ReplayRing:
             else:
                 self.env.rollout(n, actions=a, step_size=k, obs="all", out=self.obs[sl], reward_out=self.reward[sl],
                                  done_out=self.done[sl], record=rec)
+            if self.tree is not None:                                # the span just written: the largest priority seen so far
+                self.tree.fill(self.head * self.env.num_envs, n * self.env.num_envs)
             self.head = (self.head + n) % self.cap
             self.ticks += n
             done_ticks += n
+        if self.tree is not None and T and self.ticks >= self.cap:   # wrapped: slot `head` survives only as a predecessor
+            self.tree.fill(self.head * self.env.num_envs, self.env.num_envs, 0.0)
         self._env_t = self.env.t
 
     def append(self, actions, step_size=None):
@@ -164,16 +187,52 @@ class ReplayRing:
             out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
         return out
 
-    def sample(self, batch, generator=None, with_plan=True):
-        """Uniform minibatch over the addressable transitions (random.sample in the reference, :144)."""
+    def sample(self, batch, generator=None, with_plan=True, prioritized=False, beta=0.4, stratified=True):
+        """Uniform minibatch over the addressable transitions (random.sample in the reference, :144).  prioritized=True (a
+        ReplayRing(prioritized=True); generator None): the transitions are drawn from the priority tree, with replacement, stratified
+        over the total unless stratified=False, and the gather() dict gains slot, env and index = slot * N + env (int64 [n]; what
+        update_priorities() takes), prob float32 [n] and the importance weights weight = (len(self) * prob) ** -beta / their largest
+        over the batch (beta = 0: all ones)."""
+        if not isinstance(prioritized, bool):
+            raise ValueError("prioritized must be a bool")
+        if prioritized and self.tree is None:
+            raise ValueError("prioritized=True needs the priority tree: ReplayRing(..., prioritized=True)")
+        if prioritized and generator is not None:
+            raise ValueError("generator does not go with prioritized=True: the tree draws with the counter RNG")
+        if prioritized:
+            beta = float(beta)
+            if beta != beta or beta < 0 or beta == float("inf"):
+                raise ValueError("beta must be a finite number >= 0")
         v = self.valid_ticks()
         if v == 0:
             raise ValueError("the ring is empty")
         dev = self.env.device
+        if prioritized:
+            N = self.env.num_envs
+            flat, prob = self.tree.sample(int(batch), stratified)
+            slot, env_index = flat // N, flat % N
+            out = self.gather(slot, env_index, with_plan=with_plan)
+            w = (prob * float(len(self))) ** -beta
+            out.update(slot=slot, env=env_index, index=flat, prob=prob, weight=w / w.max())
+            return out
         age = torch.randint(0, v, (batch,), device=dev, generator=generator)
         slot = (self.head - 1 - age) % self.cap
         env_index = torch.randint(0, self.env.num_envs, (batch,), device=dev, generator=generator)
         return self.gather(slot, env_index, with_plan=with_plan)
+
+    def update_priorities(self, index, priority):
+        """New priorities for sampled transitions (PriorityTree.update): index [n], the `index` of sample(prioritized=True);
+        priority [n], floats >= 0, e.g. |td| (the caller applies alpha).  Where an index repeats, the largest priority wins.  A
+        transition that collect() overwrote between sample() and update_priorities() receives the stale priority: the usual behaviour
+        of prioritised replay; the next update of that entry corrects it.  Indices in the slot kept only as a predecessor are skipped,
+        so that it stays undrawable.  No host synchronisation."""
+        if self.tree is None:
+            raise ValueError("update_priorities() needs the priority tree: ReplayRing(..., prioritized=True)")
+        if not torch.is_tensor(index) or index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+            raise ValueError("index must be an integer tensor")
+        if self.ticks >= self.cap:
+            index = index.masked_fill(index // self.env.num_envs == self.head, -1)
+        self.tree.update(index, priority)
 
     def sample_sequences(self, batch, time_step, generator=None, with_plan=True, oversample=4):
         """DRQN-style minibatch (Memory.get_batch of script/DRQN/2d/DRQN_2D_dynamic_training.py:131-143): `batch` windows of

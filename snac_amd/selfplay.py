@@ -43,6 +43,12 @@ The ring, over moves (slot = move % capacity_moves), every tensor on the env's d
     obs [cap, B, D] env.obs_dtype   pi [cap, B, A] float32   value [cap, B] float32   action [cap, B] int8
     reward [cap, B] float32   done [cap, B] uint8   move [cap, B] int32 (the move's index inside its episode)   z [cap, B] float32
     keep_states=True:   state [cap, B, record_bytes] uint8 (the root's record when the move was chosen)   refreshed [cap, B] int32
+
+Prioritised replay: SelfPlay(..., prioritized=True) keeps a PriorityTree (snac_amd/priority.py; include/snac_hip.h, "Prioritised
+replay") over the capacity_moves * trees entries, flat = slot * trees + b.  Every move written gets the largest priority seen so far
+(one more small entry point per move); sample(batch, prioritized=True, beta=...) draws in proportion to the priorities and returns
+`index`, `prob` and the importance weights `weight`; update_priorities(index, priority) stores new ones, e.g. MuZero's
+(value - z).abs() ** alpha; reanalyse(..., prioritized=True) draws its entries from the same distribution.
 """
 import ctypes as C
 
@@ -56,7 +62,8 @@ def _ptr(t):
 
 
 class SelfPlay:
-    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None, gumbel=False, generator=None, keep_states=False):
+    def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None, gumbel=False, generator=None, keep_states=False,
+                 prioritized=False, priority_scale_log2=16):
         """search: a UCTSearch with one tree per env row (reset() by the caller); capacity_moves: ring slots; sample_moves: the moves of
         an episode drawn in proportion to the visits (the rest: argmax); gamma: of the value targets (default: the search's);
         root_noise: PUCT only, priors [B, A] -> priors [B, A], applied to the roots before every move's search (exploration noise is the
@@ -64,9 +71,14 @@ class SelfPlay:
         Gumbel noise in the first sample_moves moves of an episode drawn from `generator` (a torch.Generator of the env's device; None:
         the default one).  keep_states=True: the ring also keeps every move's root record (`state`: 128 bytes per entry for 1D and 2D,
         896 for 3D, capacity_moves * trees entries) and a count of its reanalyses (`refreshed`), which reanalyse() needs; one more
-        launch per move."""
+        launch per move.  prioritized=True: a PriorityTree over the capacity_moves * trees entries (flat = slot * trees + b), seeded from
+        the env's seed, with priority_scale_log2 as its scale_log2; every move played gets the largest priority seen so far."""
         if not isinstance(keep_states, bool):
             raise ValueError("keep_states must be a bool")
+        if not isinstance(prioritized, bool):
+            raise ValueError("prioritized must be a bool")
+        if isinstance(priority_scale_log2, bool) or not isinstance(priority_scale_log2, int) or not 0 <= priority_scale_log2 <= 31:
+            raise ValueError("priority_scale_log2 must be an integer in [0, 31]")
         self.keep_states = keep_states
         if not isinstance(gumbel, bool):
             raise ValueError("gumbel must be a bool")
@@ -119,6 +131,13 @@ class SelfPlay:
             self.refreshed = torch.zeros((cap, B), dtype=torch.int32, device=dev)
             assert self.state.data_ptr() % 128 == 0
             self._save_args = (B, search.nodes_per_tree, _ptr(P.records), P.WORDS * 4, P.rows)
+        self.tree = None
+        if prioritized:
+            from .priority import MAX_ENTRIES, PriorityTree
+
+            if B * cap > MAX_ENTRIES:
+                raise ValueError("trees * capacity_moves entries exceed what a PriorityTree holds (2^31 - 64)")
+            self.tree = PriorityTree(B * cap, dev, scale_log2=priority_scale_log2, seed=env.seed, sampler_id=env.env_id_base * cap)
 
     def _check_budget(self, iterations):
         s = self.search
@@ -162,6 +181,8 @@ class SelfPlay:
                 s.restart(self.done[h])
                 torch.add(self._move, 1, out=self._next)
                 torch.where(self.done[h].view(torch.bool), self._zero, self._next, out=self._move)
+                if self.tree is not None:                            # the slot's new positions: the largest priority seen so far
+                    self.tree.fill(h * B, B)
                 self.head = (h + 1) % self.cap
                 self.moves += 1
 
@@ -211,7 +232,7 @@ class SelfPlay:
                                                          _ptr(self.value), _ptr(boot), _ptr(self.z), env._stream()))
         return self.z
 
-    def reanalyse(self, search, iterations, index=None, generator=None, check=True):
+    def reanalyse(self, search, iterations, index=None, generator=None, check=True, prioritized=False):
         """Search R = search.trees stored positions again and overwrite their targets (include/snac_hip.h, "Reanalyse").  search: a second
         UCTSearch over the same env with an evaluator -- the latest network -- and the same actions; any trees = R <= len(self),
         nodes_per_tree and paths; iterations <= its max_iterations.  index: R distinct flat entries slot * trees + b in valid slots
@@ -220,7 +241,17 @@ class SelfPlay:
         stored records, the search (a gumbel=m search: gumbel_begin() on the log-priors without noise and the halving schedule; any
         other: the PUCT iterations) and snac_uct_store_targets: pi <- the improved policy or the visit distribution, value <- the
         root's W / N, refreshed += 1, at the indexed entries only.  With check=False or index=None there is no host synchronisation.
-        Returns the index (int64 [R], on the device)."""
+        prioritized=True (a SelfPlay(prioritized=True), index None): the R entries are drawn from the priority tree instead, MuZero's
+        Reanalyse distribution.  The tree draws with replacement and snac_uct_store_targets needs distinct entries, so the draws are
+        sorted on the device and every repeat is marked -1: its tree searches entry 0 and stores nothing, and fewer than R entries
+        are refreshed.  An empty tree (every priority 0) refreshes nothing.
+        Returns the index (int64 [R], on the device; -1 at a marked repeat)."""
+        if not isinstance(prioritized, bool):
+            raise ValueError("prioritized must be a bool")
+        if prioritized and self.tree is None:
+            raise ValueError("prioritized=True needs the priority tree: SelfPlay(..., prioritized=True)")
+        if prioritized and index is not None:
+            raise ValueError("prioritized=True draws the entries itself: index must be None")
         if not self.keep_states:
             raise ValueError("reanalyse() needs the stored root records: SelfPlay(..., keep_states=True)")
         if search is self.search:
@@ -239,7 +270,10 @@ class SelfPlay:
         B, cap, dev = self.search.trees, self.cap, self.env.device
         v = self.valid_moves()
         first = (self.head - v) % cap
-        if index is None:                                            # the R largest of v * B uniform draws: distinct entries
+        if prioritized:
+            flat = torch.sort(self.tree.sample(R)[0]).values
+            flat[1:].masked_fill_(flat[1:] == flat[:-1], -1)
+        elif index is None:                                          # the R largest of v * B uniform draws: distinct entries
             i = torch.topk(torch.rand(v * B, device=dev, generator=generator), R).indices
             flat = ((first + i // B) % cap) * B + i % B
         else:
@@ -268,19 +302,46 @@ class SelfPlay:
                                                           self.env._stream()))
         return flat
 
-    def sample(self, batch, generator=None):
+    def sample(self, batch, generator=None, prioritized=False, beta=0.4, stratified=True):
         """Uniform minibatch over the valid (move, tree) pairs -> dict on the device: obs float32 [n, D], pi [n, A], z, value, reward
         float32 [n], action int64 [n], done bool [n]; with keep_states=True also refreshed int32 [n].  One flat index and 1-D gathers
-        (ReplayRing.gather has the measurement)."""
+        (ReplayRing.gather has the measurement).  prioritized=True (a SelfPlay(prioritized=True); generator None): the entries are
+        drawn from the priority tree, with replacement, stratified over the total unless stratified=False, and three keys are added:
+        index int64 [n] (flat = slot * trees + b, what update_priorities() takes), prob float32 [n] and the importance weights
+        weight = (len(self) * prob) ** -beta / their largest over the batch (beta = 0: all ones)."""
         v = self.valid_moves()
         if v == 0:
             raise ValueError("the ring is empty")
-        B, dev = self.search.trees, self.env.device
-        i = torch.randint(0, v * B, (int(batch),), device=dev, generator=generator)
-        flat = (((self.head - v) % self.cap + i // B) % self.cap) * B + i % B
+        if not isinstance(prioritized, bool):
+            raise ValueError("prioritized must be a bool")
+        B = self.search.trees
+        if prioritized:
+            if self.tree is None:
+                raise ValueError("prioritized=True needs the priority tree: SelfPlay(..., prioritized=True)")
+            if generator is not None:
+                raise ValueError("generator does not go with prioritized=True: the tree draws with the counter RNG")
+            beta = float(beta)
+            if beta != beta or beta < 0 or beta == float("inf"):
+                raise ValueError("beta must be a finite number >= 0")
+            flat, prob = self.tree.sample(int(batch), stratified)
+        else:
+            i = torch.randint(0, v * B, (int(batch),), device=self.env.device, generator=generator)
+            flat = (((self.head - v) % self.cap + i // B) % self.cap) * B + i % B
         out = dict(obs=self.obs.view(self.cap * B, -1)[flat].to(torch.float32), pi=self.pi.view(self.cap * B, -1)[flat],
                    z=self.z.view(-1)[flat], value=self.value.view(-1)[flat], action=self.action.view(-1)[flat].long(),
                    reward=self.reward.view(-1)[flat], done=self.done.view(-1)[flat].bool())
         if self.keep_states:
             out["refreshed"] = self.refreshed.view(-1)[flat]
+        if prioritized:
+            w = (prob * float(len(self))) ** -beta
+            out["index"], out["prob"], out["weight"] = flat, prob, w / w.max()
         return out
+
+    def update_priorities(self, index, priority):
+        """New priorities for sampled entries (PriorityTree.update): index [n], the `index` of sample(prioritized=True); priority [n],
+        floats >= 0 -- the caller applies alpha, e.g. (value - z).abs() ** alpha.  Where an index repeats, the largest priority wins.
+        An entry that play() overwrote between sample() and update_priorities() receives the stale priority: the usual behaviour of
+        prioritised replay, harmless because the next update of that entry corrects it.  No host synchronisation."""
+        if self.tree is None:
+            raise ValueError("update_priorities() needs the priority tree: SelfPlay(..., prioritized=True)")
+        self.tree.update(index, priority)
