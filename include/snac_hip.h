@@ -406,6 +406,17 @@ int snac_observe(const snac_env_desc* desc, const snac_state* st, void* obs, voi
  * caller-side boolean IoU of the 2D scripts (script/DQN/2d/DQN_2d_dynamic.py:63-71).  out: double[N] */
 int snac_iou(const snac_env_desc* desc, const snac_state* st, double* out, void* stream);
 
+/* the batch's three episodic sums in ONE launch: out3[0 .. 2] = the sums over all N envs of st->stat_episodes, stat_return and
+ * stat_iou_fx (int64, modulo 2^64: exactly what adding the arrays up in any order gives).  out3: int64[3] on the device, written by
+ * the launch (nothing is read from it).  scratch: int64[SNAC_SUMS_SCRATCH_WORDS] on the device, OWNED BY THE CALLER: zeroed once when
+ * it is created and never touched by anyone else; every call leaves it zeroed where it has to be (the launch's last block takes the
+ * partial sums out and sets its ticket back to 0), so no call is preceded by a fill.  Calls that may run at the same time -- two
+ * batches on two streams -- need a scratch each; calls on one stream may share one.  The per-env arrays stay the only record of the
+ * sums: nothing is kept between calls.  Pointers 8-byte aligned.  Arguments are checked before any HIP call; the call does not
+ * change what snac_last_kernel() names. */
+#define SNAC_SUMS_SCRATCH_WORDS (3 * 64 + 1)
+int snac_episodic_sums(const snac_env_desc* desc, const snac_state* st, int64_t* out3, int64_t* scratch, void* stream);
+
 /* environment_memory as the reference holds it: out is double[N][env_height][env_width] with the -1 frame */
 int snac_export_grid(const snac_env_desc* desc, const snac_state* st, double* out, void* stream);
 

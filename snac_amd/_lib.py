@@ -20,6 +20,7 @@ FLAG_NEED_RESET = 1
 RULE_BRICK_GT, RULE_TIME_GT = 1, 2
 SCALARS_DEFAULT, SCALARS_RAW, SCALARS_NORM = 0, 1, 2
 TAIL_POSITION, TAIL_PLAN, TAIL_RECORD = 1, 2, 4
+SUMS_SCRATCH_WORDS = 3 * 64 + 1   # SNAC_SUMS_SCRATCH_WORDS: the scratch of snac_episodic_sums, int64 words
 
 EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", "snac_reset", "snac_reset_scalar", "snac_step",
            "snac_step_scalar", "snac_rollout",
@@ -35,7 +36,7 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds",
            "snac_uct_select_gumbel", "snac_uct_gumbel_candidates", "snac_uct_set_priors_value", "snac_uct_select_gumbel_interior",
            "snac_uct_improved_policy", "snac_uct_save_roots", "snac_uct_load_roots", "snac_uct_store_targets", "snac_uct_returns_nstep",
-           "snac_prio_layout", "snac_prio_init", "snac_prio_update", "snac_prio_fill", "snac_prio_sample")
+           "snac_prio_layout", "snac_prio_init", "snac_prio_update", "snac_prio_fill", "snac_prio_sample", "snac_episodic_sums")
 
 
 class Sizes(C.Structure):
@@ -134,6 +135,7 @@ def lib():
         L.snac_make_plans.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, vp, vp, vp]
         L.snac_observe.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
         L.snac_iou.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
+        L.snac_episodic_sums.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp, vp]
         L.snac_export_grid.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
         L.snac_transition.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
         L.snac_nodes2d_pack.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, vp, C.c_int32, vp, vp]

@@ -124,6 +124,7 @@ class BatchedDMPEnv:
         self._episode = torch.full((N,), -1, dtype=torch.int32, device=dev)
         self._grid = torch.zeros((N, sz.grid_elems), dtype=_GRID_DTYPE[self.kind], device=dev)
         self._stats = torch.zeros((3, N), dtype=torch.int64, device=dev)
+        self._sums_scratch = torch.zeros((_lib.SUMS_SCRATCH_WORDS,), dtype=torch.int64, device=dev)   # snac_episodic_sums: this batch's own, zeroed once
         self._desc = _lib.EnvDesc(self.kind, int(self.dynamic), N, self.num_plans,
                                   _lib.OBS_F64 if obs_dtype == torch.float64 else _lib.OBS_F32, int(static_plan),
                                   self.seed & 0xFFFFFFFFFFFFFFFF, self.env_id_base, self.total_step,
@@ -179,6 +180,9 @@ class BatchedDMPEnv:
         if self._mb is not None:
             self._settle()
             self._mb_dirty = True                                    # whoever asks for the stream launches: the resident stepper reloads the records
+        return self._current_stream()
+
+    def _current_stream(self):
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # the handle without building a Stream object (2 us)
         if raw is not None:
             return C.c_void_p(raw(self.device.index))
@@ -991,14 +995,19 @@ class BatchedDMPEnv:
 
     def episodic_stats(self):
         """Local sums over finished episodes: dict(episodes, return_sum, iou_fx_sum) of python ints (iou in 2^-40 units)."""
-        self._settle()
-        s = self._stats.sum(dim=1).tolist()
+        s = self.stats_tensor().tolist()
         return dict(episodes=int(s[0]), return_sum=int(s[1]), iou_fx_sum=int(s[2]))
 
     def stats_tensor(self, out=None):
         """int64 [3] on device: [episodes, return_sum, iou_fx_sum]; what snac_amd.dist all-reduces.  out: a preallocated int64 [3]
-        tensor on this device that receives the sums (one kernel instead of sum + copy)."""
-        self._settle()
-        if out is None:
-            return self._stats.sum(dim=1)
-        return torch.sum(self._stats, dim=1, out=out)
+        tensor on this device that receives the sums.  One launch (snac_episodic_sums) that adds the per-env arrays up as they are
+        at that point of the stream: nothing is kept between calls."""
+        if out is not None and (out.dtype != torch.int64 or out.device != self._stats.device or tuple(out.shape) != (3,)):
+            raise ValueError("out must be an int64 tensor of shape (3,) on %s" % (self._stats.device,))
+        dst = out if (out is not None and out.is_contiguous()) else torch.empty((3,), dtype=torch.int64, device=self._stats.device)
+        self._settle()                                               # (a reader: the resident stepper keeps its records)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.snac_episodic_sums(self._desc_ref, self._state_ref, _ptr(dst), _ptr(self._sums_scratch), self._current_stream()))
+        if out is None or dst is out:
+            return dst
+        return out.copy_(dst)

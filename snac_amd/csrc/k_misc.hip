@@ -1,4 +1,4 @@
-// k_misc.hip -- environment_memory export, state import, observation equality, plan generators, replay gather: kernels and entry points
+// k_misc.hip -- environment_memory export, state import, observation equality, plan generators, replay gather, the episodic sums: kernels and entry points
 #include "snac_dev.h"
 
 using namespace snac_detail;
@@ -437,9 +437,97 @@ __global__ __launch_bounds__(256) void k_plans_from_grids(const FArgs g) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the three episodic sums of a batch (snac_episodic_sums): what torch.sum(stats[3][N], dim = 1) gave in two launches -- a zeroing fill
+// and the reduction -- as one, written where the caller keeps the sums.  G <= 64 blocks each sum a slice of the three arrays with
+// 16-byte loads and leave three partials in the caller's scratch; the block that draws the last ticket adds the G x 3 partials, lane =
+// block, by the same butterfly every time, writes out3 and sets the ticket back to 0: the next call finds the scratch as this one did,
+// and nothing is ever zeroed by a launch.  The XCDs' L2s are not coherent for plain accesses, so partials and ticket are written and
+// read by agent-scope atomic operations only, with a release before the ticket and an acquire behind it.  Integer sums (mod 2^64):
+// the result does not depend on the order and equals stats.sum(dim = 1) exactly.
+constexpr int SUMS_BLOCKS = SNAC_SUMS_SCRATCH_WORDS / 3;             // 64: a lane per partial in the last block's wave
+struct SumArgs {
+    int32_t n, blocks;
+    const int64_t* src[3];
+    int64_t* out3;
+    unsigned long long* scratch;   // [3 * 64] partials, [3 * 64] the ticket
+};
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_episodic_sums(const SumArgs g) {
+    __shared__ unsigned long long part[4][3];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, b = (int)blockIdx.x, G = g.blocks;
+    unsigned long long acc[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int64_t* const p = g.src[k];
+        const int head = (int)(((uintptr_t)p >> 3) & 1);             // an array that starts in the middle of a 16-byte piece (odd N)
+        const int pairs = (g.n - head) >> 1, per = (pairs + G - 1) / G;
+        const ulonglong2* const q = (const ulonglong2*)(p + head);
+        const int lo = b * per, hi = min(lo + per, pairs);
+        unsigned long long s = 0;
+        for (int i = lo + tid; i < hi; i += 256) { const ulonglong2 v = q[i]; s += v.x + v.y; }
+        if (b == 0 && tid == 0) {                                    // the elements outside the pairs: at most one at either end
+            if (head) s += (unsigned long long)p[0];
+            if ((g.n - head) & 1) s += (unsigned long long)p[g.n - 1];
+        }
+        acc[k] = wave_sum(s);
+    }
+    if (lane == 0) { part[wv][0] = acc[0]; part[wv][1] = acc[1]; part[wv][2] = acc[2]; }
+    __syncthreads();
+    if (wv != 0) return;
+    unsigned long long* const ticket_word = g.scratch + 3 * SUMS_BLOCKS;
+    unsigned long long ticket = 0;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            __hip_atomic_store(g.scratch + 3 * b + k, part[0][k] + part[1][k] + part[2][k] + part[3][k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the partials have left before the ticket is drawn
+        ticket = __hip_atomic_fetch_add(ticket_word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    ticket = __shfl(ticket, 0);
+    if (ticket != (unsigned long long)(G - 1)) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unsigned long long tot[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const unsigned long long v = lane < G ? __hip_atomic_load(g.scratch + 3 * lane + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+        tot[k] = wave_sum(v);
+    }
+    if (lane == 0) {
+        g.out3[0] = (int64_t)tot[0]; g.out3[1] = (int64_t)tot[1]; g.out3[2] = (int64_t)tot[2];
+        __hip_atomic_store(ticket_word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+// (snac_last_kernel() keeps naming the launch before: the sums are bookkeeping beside a rollout, not a kernel the dispatch chose)
+int snac_episodic_sums(const snac_env_desc* d, const snac_state* st, int64_t* out3, int64_t* scratch, void* stream) {
+    if (!d || !st) return fail(SNAC_ERR_ARG, "null desc/state");
+    if (d->num_envs < 1) return fail(SNAC_ERR_ARG, "num_envs must be positive");
+    if (!out3 || !scratch) return fail(SNAC_ERR_ARG, "null out3 / scratch");
+    if (!st->stat_episodes || !st->stat_return || !st->stat_iou_fx) return fail(SNAC_ERR_ARG, "null pointer in snac_state");
+    if (((uintptr_t)st->stat_episodes | (uintptr_t)st->stat_return | (uintptr_t)st->stat_iou_fx | (uintptr_t)out3 | (uintptr_t)scratch) & 7)
+        return fail(SNAC_ERR_ARG, "the sums, out3 and scratch must be 8-byte aligned");
+    SumArgs g;
+    g.n = d->num_envs;
+    g.blocks = std::min(SUMS_BLOCKS, (d->num_envs + 1023) / 1024);   // two 16-byte loads per lane and array before another block pays
+    g.src[0] = st->stat_episodes; g.src[1] = st->stat_return; g.src[2] = st->stat_iou_fx;
+    g.out3 = out3; g.scratch = (unsigned long long*)scratch;
+    hipLaunchKernelGGL(k_episodic_sums, dim3((unsigned)g.blocks), dim3(256), 0, (hipStream_t)stream, g);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip(e, "episodic sums launch");
+    return SNAC_OK;
+}
 
 static int replay_gather(const snac_env_desc* d, const snac_state* st, int32_t cap, const void* obs_ring,
                          const uint8_t* first_ring, const int16_t* plan_idx_ring, const int32_t* tick_idx,

@@ -1,5 +1,10 @@
 // k_roll2d.hip -- k_rollout2d: the headline kernel
 #include "snac_dev.h"
+#include "tile_order.h"
+
+using snac_detail::tile_order_block;
+using snac_detail::tile_order_grid;
+using snac_detail::tune;
 
 namespace {
 
@@ -33,7 +38,7 @@ namespace {
 
 
 template <bool DYN, typename OT, int WPB, bool EXPL, bool VAR>
-__global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a) {
+__global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a, const int xcd) {
     using K = K2D<DYN, 64>;
     constexpr int E = 64, D = K::D, RS = K::RS, GE = K::GE;
     constexpr int IMG_WORDS = 26 * RS * 2;                           // the bordered two-bit image: 26 rows x 65 x 8 B
@@ -44,7 +49,8 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a) {
     static_assert(IMG_WORDS % 4 == 0 && WAVE_WORDS % 4 == 0, "16-byte aligned staging tiles");
     __shared__ __attribute__((aligned(16))) uint32_t lds_all[WPB * WAVE_WORDS];
     const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6);
-    const int tile = (int)blockIdx.x * WPB + wv;
+    // SNAC_2D_STAGE_XCD: the block of 256 envs by launch order, or each XCD a contiguous eighth of the env range (tile_order.h)
+    const int tile = tile_order_block((int)blockIdx.x, (int)gridDim.x, xcd != 0) * WPB + wv;
     const int env0 = __builtin_amdgcn_readfirstlane(tile * E);
     if (env0 >= a.n) return;
     const int nenv = min(E, a.n - env0);
@@ -57,17 +63,45 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a) {
     Lane s;
     s.clear();
     s.r = 3; s.c = 3;                                                // idle lanes keep an in-range position and plan row 0
+    // The launch's state comes in TWO trips instead of one per array: everything that depends on nothing but the env's index is asked
+    // for before the first wait -- the header, the episode counter, the env's three episodic sums (kept in registers until the launch
+    // ends: nothing else writes a batch's sums during its launch, and the epilogue then STORES sum + delta instead of a
+    // read-modify-write that would return only behind every row of the last tick: vmcnt retires in order) and the tile's grid words,
+    // which are one run of nenv x 20 words, word lane + 64 j in register j.  The plan rows need the header's plan_idx: the second trip.
     int episode = 0;
-    if (active) { s.unpack(a.hdr[env]); episode = a.episode[env]; }
-    K::load_grid(lds, a, env0, nenv, lane);
+    int4 h = make_int4(0, 0, 0, 0);
+    long long st_eps = 0, st_ret = 0, st_iou = 0;
+    if (active) {
+        h = a.hdr[env]; episode = a.episode[env];
+        st_eps = a.stat_episodes[env]; st_ret = a.stat_return[env]; st_iou = a.stat_iou_fx[env];
+    }
+    uint32_t gw[GE];
+    {
+        const uint32_t* const src = (const uint32_t*)a.grid + (size_t)env0 * GE;
+#pragma unroll
+        for (int j = 0; j < GE; ++j) { const int i = lane + 64 * j; gw[j] = i < nenv * GE ? src[i] : 0u; }
+    }
+    for (int i = lane; i < 3 * RS; i += 64) { cells[i] = 0x000FFFFFFFFFFFFFull; cells[23 * RS + i] = 0x000FFFFFFFFFFFFFull; }   // the frame rows (K2D::load_grid)
+    if (active) s.unpack(h);
+    uint32_t pw[GE];
+    {
+        const uint32_t* const prow = (const uint32_t*)a.plans + (size_t)s.pidx * GE;   // (idle lanes: row 0)
+#pragma unroll
+        for (int q = 0; q < GE; ++q) pw[q] = prow[q];
+    }
+#pragma unroll
+    for (int j = 0; j < GE; ++j) {
+        const int i = lane + 64 * j, e = i / GE, row = i - e * GE;
+        if (i < nenv * GE) cells[(row + 3) * RS + e] = K::encode_row(gw[j]);
+    }
     const uint64_t gid = (uint64_t)(a.env_id_base + env);
     const EnvKeys sk = env_keys(a.key_step, gid), pk = env_keys(a.key_plan, gid);
     // |P|, |G|, |P and G| of the lane's env as the launch finds them
     int pcnt = 0, gcnt = 0, inter = 0;
     {
-        const uint32_t* const prow = (const uint32_t*)a.plans + (size_t)s.pidx * GE;   // (idle lanes: row 0)
+#pragma unroll
         for (int q = 0; q < GE; ++q) {
-            const uint32_t p = prow[q];
+            const uint32_t p = pw[q];
             pl[q * 65 + lane] = p; pcnt += __popc(p);
             const uint32_t g = active ? K::decode_row(cells[(q + 3) * RS + lane]) : 0u;
             gcnt += __popc(g); inter += __popc(g & p);
@@ -195,10 +229,10 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a) {
     if (active) {
         a.hdr[env] = s.pack();
         a.episode[env] = episode;
-        if (d_eps) {
-            a.stat_episodes[env] += d_eps;
-            a.stat_return[env] += d_ret;
-            a.stat_iou_fx[env] += d_iou;
+        if (d_eps) {                                                 // stores only: the sums as the launch found them + its own episodes
+            a.stat_episodes[env] = st_eps + d_eps;
+            a.stat_return[env] = st_ret + d_ret;
+            a.stat_iou_fx[env] = st_iou + d_iou;
         }
     }
 }
@@ -207,15 +241,19 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout2d(const KArgs a) {
 template <bool DYN, typename OT>
 void launch_roll2d_w(const KArgs& a, hipStream_t s) {
     const int tiles = (a.n + 63) / 64;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
+    // 2 (the default): the XCD-contiguous order where the grid needs no padding for it; padded, whole blocks end up behind the first
+    // round of workgroups where launch order leaves the ragged one (65 540 envs: 3.82 against 3.17 ms, profiles/pass_ends.txt)
+    const int blocks = (tiles + 3) / 4, knob = tune(snac_detail::TN_2D_STAGE_XCD);
+    const int xcd = (knob == 1 || (knob == 2 && (blocks & 7) == 0)) ? 1 : 0;
+    const dim3 grid((unsigned)tile_order_grid(blocks, xcd != 0)), block(256);   // (padded: workgroups past the last tile leave)
     // the layout variants (a.variant: frame value, scalar form, row tail) are their own instantiations
     const bool expl = a.actions || a.step_size;
     if (a.variant) {
-        if (expl) hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, true, true>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, false, true>), grid, block, 0, s, a);
+        if (expl) hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, true, true>), grid, block, 0, s, a, xcd);
+        else hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, false, true>), grid, block, 0, s, a, xcd);
     } else {
-        if (expl) hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, true, false>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, false, false>), grid, block, 0, s, a);
+        if (expl) hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, true, false>), grid, block, 0, s, a, xcd);
+        else hipLaunchKernelGGL((k_rollout2d<DYN, OT, 4, false, false>), grid, block, 0, s, a, xcd);
     }
 }
 

@@ -197,6 +197,7 @@ const Knob KNOBS[TN_COUNT] = {
     /* TN_EVAL_E          */ {"SNAC_EVAL_E", 64, "leaves per wave of k_eval for 1D / 2D leaves (snac_evaluate_nodes1d / 2d; 16 / 32 / 64): 2D, 65 536 leaves, H = 600: 0.320 against 0.359 ms per call with 32, 4096 leaves level (0.275 / 0.274); 1D, 65 536 leaves, H = 300: 0.172 / 0.194 (r08_eval.txt)"},
     /* TN_EVAL3D_E        */ {"SNAC_EVAL3D_E", 16, "leaves per wave of k_eval for 3D leaves (16 / 32 / 64: 22 / 44 / 88 KB of LDS per wave): 65 536 leaves, H = 200: 0.219 ms per call against 0.262 with 32 and 0.355 with 64; 4096 leaves: 0.142 / 0.166 / 0.160 (r08_eval.txt)"},
     /* TN_UCT_BOUNDS_WIDTH */ {"SNAC_UCT_BOUNDS_WIDTH", 0, "lanes per tree of k_uct_bounds (snac_uct_bounds; 8 / 16 / 32 / 64): 0 = from cap, 8 lanes up to 32 nodes per tree, 16 up to 64, 32 up to 128, a wave above (r15_uct_norm.txt)"},
+    /* TN_2D_STAGE_XCD    */ {"SNAC_2D_STAGE_XCD", 2, "k_rollout2d gives each XCD a contiguous eighth of the env range (tile_order.h) instead of every 8th block of 256 envs: 0 never, 1 always (grid padded to a multiple of 8), 2 where the number of blocks is a multiple of 8 (headline, 8 fresh processes per arm alternating: 2.3025 against 2.3122 ms per pass, and 2.3091 against 2.3183 with the launch's old ends; 49 152 envs 1.75 against 1.77, 131 072 x 300 ticks 2.285 against 2.30, float32 / PPO / tile-major rows level; padded, 65 540 envs 3.82 against 3.17; profiles/pass_ends.txt)"},
 };
 
 int tune(int id) {
