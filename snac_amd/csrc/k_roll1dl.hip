@@ -169,7 +169,7 @@ __global__ __launch_bounds__(WPB * 64) void k_rollout1dl(const KArgs a) {
 }
 
 template <bool DYN, typename OT, bool EXPL, bool REC>
-void launch_roll1dl_x(const KArgs& a, hipStream_t s) {
+void launch_roll1dl_x(const KArgs& a, bool nts, hipStream_t s) {
     const int tiles = (a.n + 63) / 64;
     if (a.variant) {                                                 // the staging tile sized for rows of 16 / 38 / 46 values (k_rollout1dt's classes)
         const dim3 g4((unsigned)((tiles + 3) / 4)), b4(256), g2((unsigned)((tiles + 1) / 2)), b2(128);
@@ -179,25 +179,24 @@ void launch_roll1dl_x(const KArgs& a, hipStream_t s) {
         return;
     }
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (snac_detail::tune(snac_detail::TN_1D_LANE_NT) != 0) hipLaunchKernelGGL((k_rollout1dl<DYN, OT, 4, EXPL, true, REC>), grid, block, 0, s, a);
+    if (nts) hipLaunchKernelGGL((k_rollout1dl<DYN, OT, 4, EXPL, true, REC>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((k_rollout1dl<DYN, OT, 4, EXPL, false, REC>), grid, block, 0, s, a);
-}
-template <bool DYN, typename OT>
-void launch_roll1dl_w(const KArgs& a, hipStream_t s) {
-    const bool expl = a.actions || a.step_size;
-    const bool rec = a.actions_out || a.step_size_out || a.plan_idx_out || a.first_out;   // snac_rollout_rec: the per-step record outputs
-    if (expl) rec ? launch_roll1dl_x<DYN, OT, true, true>(a, s) : launch_roll1dl_x<DYN, OT, true, false>(a, s);
-    else rec ? launch_roll1dl_x<DYN, OT, false, true>(a, s) : launch_roll1dl_x<DYN, OT, false, false>(a, s);
 }
 
 }  // namespace
 
 namespace snac_detail {
 
-void launch_roll1dl(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_roll1dl_w<true, float>(a, s) : launch_roll1dl_w<true, double>(a, s);
-    else f32 ? launch_roll1dl_w<false, float>(a, s) : launch_roll1dl_w<false, double>(a, s);
+void launch_roll1dl(const snac_env_desc* d, const KArgs& a, int form, hipStream_t s) {   // form bit 1: the canonical rows leave as non-temporal stores
+    const bool expl = a.actions || a.step_size;
+    const bool rec = a.actions_out || a.step_size_out || a.plan_idx_out || a.first_out;   // snac_rollout_rec: the per-step record outputs
+    const bool nts = (form & 2) != 0;
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (expl) rec ? launch_roll1dl_x<DYN, OT, true, true>(a, nts, s) : launch_roll1dl_x<DYN, OT, true, false>(a, nts, s);
+        else rec ? launch_roll1dl_x<DYN, OT, false, true>(a, nts, s) : launch_roll1dl_x<DYN, OT, false, false>(a, nts, s);
+    });
 }
 
 }  // namespace snac_detail

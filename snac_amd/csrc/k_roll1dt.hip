@@ -277,43 +277,29 @@ __global__ __launch_bounds__(EB * 64, VLD ? 1 : 16 / EB) void k_rollout1dt(const
 }
 
 
-template <bool DYN, typename OT, int EB>
+template <bool DYN, typename OT, int EB, int LD = 0>
 void launch_roll1dt_e(const KArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.n + EB - 1) / EB)), block(EB * 64);
-    if (a.actions || a.step_size) hipLaunchKernelGGL((k_rollout1dt<DYN, OT, EB, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_rollout1dt<DYN, OT, EB, false>), grid, block, 0, s, a);
-}
-template <bool DYN, typename OT>
-void launch_roll1dt_w(const KArgs& a, hipStream_t s) {
-    if (a.variant) {
-        const dim3 grid((unsigned)((a.n + 3) / 4)), block(256);
-        const bool expl = a.actions || a.step_size;
-        if (a.ld <= 16) {                                            // the smaller the staging tile, the more blocks share a CU
-            if (expl) hipLaunchKernelGGL((k_rollout1dt<DYN, OT, 4, true, 16>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((k_rollout1dt<DYN, OT, 4, false, 16>), grid, block, 0, s, a);
-        } else if (a.ld <= 38) {
-            if (expl) hipLaunchKernelGGL((k_rollout1dt<DYN, OT, 4, true, 38>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((k_rollout1dt<DYN, OT, 4, false, 38>), grid, block, 0, s, a);
-        } else {
-            if (expl) hipLaunchKernelGGL((k_rollout1dt<DYN, OT, 4, true, 46>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((k_rollout1dt<DYN, OT, 4, false, 46>), grid, block, 0, s, a);
-        }
-        return;
-    }
-    const int emin = snac_detail::tune(snac_detail::TN_1D_TP_EB16), e8lo = snac_detail::tune(snac_detail::TN_1D_TP_EB8_MIN), e8hi = snac_detail::tune(snac_detail::TN_1D_TP_EB8_MAX);
-    if (a.n >= e8lo && a.n <= e8hi) launch_roll1dt_e<DYN, OT, 8>(a, s);   // 8 envs per block: two blocks share a CU where 16-env blocks number one per CU
-    else if (a.n >= emin) launch_roll1dt_e<DYN, OT, 16>(a, s); // 16 envs per block: runs of 896 / 448 bytes per tick (3072 envs: 0.048 against 0.041 ms; 3584: level)
-    else launch_roll1dt_e<DYN, OT, 4>(a, s);                        // small batches: more blocks than CUs first
+    if (a.actions || a.step_size) hipLaunchKernelGGL((k_rollout1dt<DYN, OT, EB, true, LD>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_rollout1dt<DYN, OT, EB, false, LD>), grid, block, 0, s, a);
 }
 
 }  // namespace
 
 namespace snac_detail {
 
-void launch_roll1dt(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_roll1dt_w<true, float>(a, s) : launch_roll1dt_w<true, double>(a, s);
-    else f32 ? launch_roll1dt_w<false, float>(a, s) : launch_roll1dt_w<false, double>(a, s);
+void launch_roll1dt(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s) {   // E envs per block (canonical rows: 4 / 8 / 16)
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (a.variant) {                                             // blocks of four envs; the smaller the staging tile, the more blocks share a CU
+            if (a.ld <= 16) launch_roll1dt_e<DYN, OT, 4, 16>(a, s);
+            else if (a.ld <= 38) launch_roll1dt_e<DYN, OT, 4, 38>(a, s);
+            else launch_roll1dt_e<DYN, OT, 4, 46>(a, s);
+        } else if (E == 8) launch_roll1dt_e<DYN, OT, 8>(a, s);
+        else if (E == 16) launch_roll1dt_e<DYN, OT, 16>(a, s);
+        else launch_roll1dt_e<DYN, OT, 4>(a, s);
+    });
 }
 
 }  // namespace snac_detail

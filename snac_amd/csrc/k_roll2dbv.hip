@@ -3,10 +3,8 @@
 
 namespace snac_detail {
 
-void launch_roll2dbv(const snac_env_desc* d, const KArgs& a, int steppers, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_roll2db_n<true, float, true>(a, steppers, s) : launch_roll2db_n<true, double, true>(a, steppers, s);
-    else f32 ? launch_roll2db_n<false, float, true>(a, steppers, s) : launch_roll2db_n<false, double, true>(a, steppers, s);
+void launch_roll2dbv(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s) {   // E envs per block: 64 per stepper wave
+    by_rows(d, [&](auto dyn, auto ot) { launch_roll2db_n<decltype(dyn)::value, decltype(ot), true>(a, E / 64, s); });
 }
 
 }  // namespace snac_detail

@@ -475,37 +475,33 @@ __global__ __launch_bounds__((EB + WR) * 64) void k_rollout2dt(const KArgs a) {
     }
 }
 
-template <bool DYN, typename OT, int EB>
-void launch_roll2dt_e(const KArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)((a.n + EB - 1) / EB)), block(2 * EB * 64);   // EB stepper waves + EB writer waves
-    if (a.actions || a.step_size) hipLaunchKernelGGL((k_rollout2dt<DYN, OT, EB, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_rollout2dt<DYN, OT, EB, false>), grid, block, 0, s, a);
-}
-template <bool DYN, typename OT>
-void launch_roll2dt_var(const KArgs& a, hipStream_t s) {
-    // 4 steppers and 12 writers per block: the rows are what takes the time (with 4 writers in blocks of 8 waves: 5.7 instead of 6.0 TB/s
-    // at 1024 envs and half the rate at 256)
-    constexpr int EB = 4, WR = 12;
-    const dim3 grid((unsigned)((a.n + EB - 1) / EB)), block((EB + WR) * 64);
-    if (a.actions || a.step_size) hipLaunchKernelGGL((k_rollout2dt<DYN, OT, EB, true, true, WR>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_rollout2dt<DYN, OT, EB, false, true, WR>), grid, block, 0, s, a);
-}
-template <bool DYN, typename OT>
-void launch_roll2dt_w(const KArgs& a, hipStream_t s) {
-    if (a.variant) { launch_roll2dt_var<DYN, OT>(a, s); return; }
-    const int emin = snac_detail::tune(snac_detail::TN_2D_TP_EB8);
-    if (a.n >= emin) launch_roll2dt_e<DYN, OT, 8>(a, s);       // 8 envs per block: runs of 3264 / 1632 bytes per tick
-    else launch_roll2dt_e<DYN, OT, 4>(a, s);                        // up to 1024 envs: a block per CU first (1536 envs: 0.097 against 0.086 ms)
-}
-
 }  // namespace
 
 namespace snac_detail {
 
-void launch_roll2dt(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_roll2dt_w<true, float>(a, s) : launch_roll2dt_w<true, double>(a, s);
-    else f32 ? launch_roll2dt_w<false, float>(a, s) : launch_roll2dt_w<false, double>(a, s);
+void launch_roll2dt(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s) {   // E envs per block (canonical rows: 4 / 8)
+    const bool expl = a.actions || a.step_size;
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (a.variant) {
+            // 4 steppers and 12 writers per block: the rows are what takes the time (with 4 writers in blocks of 8 waves: 5.7 instead of 6.0 TB/s
+            // at 1024 envs and half the rate at 256)
+            constexpr int EB = 4, WR = 12;
+            const dim3 grid((unsigned)((a.n + EB - 1) / EB)), block((EB + WR) * 64);
+            if (expl) hipLaunchKernelGGL((k_rollout2dt<DYN, OT, EB, true, true, WR>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_rollout2dt<DYN, OT, EB, false, true, WR>), grid, block, 0, s, a);
+            return;
+        }
+        const dim3 grid((unsigned)((a.n + E - 1) / E)), block(2 * E * 64);   // E stepper waves + E writer waves
+        if (E == 8) {
+            if (expl) hipLaunchKernelGGL((k_rollout2dt<DYN, OT, 8, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_rollout2dt<DYN, OT, 8, false>), grid, block, 0, s, a);
+        } else {
+            if (expl) hipLaunchKernelGGL((k_rollout2dt<DYN, OT, 4, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_rollout2dt<DYN, OT, 4, false>), grid, block, 0, s, a);
+        }
+    });
 }
 
 }  // namespace snac_detail

@@ -550,64 +550,34 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(3, 3))
 namespace snac_detail {
 
 void launch_aux2d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {   // masked reset / observe: the canonical layout, plain loads and rows
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    const int tiles = (a.n + 63) / 64;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (dyn) { if (f32) hipLaunchKernelGGL((k_step2d<true, float, 4, false, 64, false, false, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<true, double, 4, false, 64, false, false, true>), grid, block, 0, s, a); }
-    else { if (f32) hipLaunchKernelGGL((k_step2d<false, float, 4, false, 64, false, false, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<false, double, 4, false, 64, false, false, true>), grid, block, 0, s, a); }
+    const dim3 grid((unsigned)(((a.n + 63) / 64 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) { hipLaunchKernelGGL((k_step2d<decltype(dyn)::value, decltype(ot), 4, false, 64, false, false, true>), grid, block, 0, s, a); });
 }
 
-void launch_step2d(const snac_env_desc* d, const KArgs& a, bool half, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    const int tiles = (a.n + 63) / 64;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (a.variant && half) {                                     // half-filled tiles: 32 envs per wave on twice the waves
-        const dim3 grid2((unsigned)(((a.n + 31) / 32 + 3) / 4));
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_step2d<true, float, 4, true, 32>), grid2, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<true, double, 4, true, 32>), grid2, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_step2d<false, float, 4, true, 32>), grid2, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<false, double, 4, true, 32>), grid2, block, 0, s, a); }
-    } else if (a.variant) {
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_step2d<true, float, 4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<true, double, 4, true>), grid, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_step2d<false, float, 4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<false, double, 4, true>), grid, block, 0, s, a); }
-    } else {
-        // canonical rows: four forms (bit 0: the records by non-temporal loads, bit 1: the rows by non-temporal stores), picked by what fits
-        // the Infinity Cache at this batch size (profiles/r06_step_loads.txt); SNAC_STEP2D_FORM forces one
-        int form = tune(TN_STEP2D_FORM);
-        if (form < 0) {
-            if (a.n < tune(TN_STEP2D_PLAIN_LO)) form = 1;            // small batches: round 5's form
-            else if (a.n <= tune(TN_STEP2D_RES_HI)) form = 2;        // "resident": plain loads keep the state cached, non-temporal rows stay out of it
-            else if (a.n <= tune(TN_STEP2D_PLAIN_HI)) form = 0;      // plain loads, plain rows
-            else if (a.n < tune(TN_STEP2D_HUGE_MIN)) form = 1;       // the state streams
-            else form = tune(TN_STEP2D_HUGE_FORM);                   // the rows of one tick alone overflow the cache
-        }
-#define SNAC_STEP2D_LAUNCH(NTL, NTS)                                                                                                                                            \
-        do {                                                                                                                                                                   \
-            if (dyn) { if (f32) hipLaunchKernelGGL((k_step2d<true, float, 4, false, 64, NTL, NTS>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<true, double, 4, false, 64, NTL, NTS>), grid, block, 0, s, a); } \
-            else { if (f32) hipLaunchKernelGGL((k_step2d<false, float, 4, false, 64, NTL, NTS>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step2d<false, double, 4, false, 64, NTL, NTS>), grid, block, 0, s, a); } \
-        } while (0)
-        switch (form & 3) {
-            case 0: SNAC_STEP2D_LAUNCH(false, false); break;
-            case 1: SNAC_STEP2D_LAUNCH(true, false); break;
-            case 2: SNAC_STEP2D_LAUNCH(false, true); break;
-            default: SNAC_STEP2D_LAUNCH(true, true); break;
-        }
-#undef SNAC_STEP2D_LAUNCH
-    }
+// E envs per wave (the layout variants: 64, or 32 = half-filled tiles on twice the waves); canonical rows: 64 and a form
+void launch_step2d(const snac_env_desc* d, const KArgs& a, int E, int form, hipStream_t s) {
+    const dim3 grid((unsigned)(((a.n + E - 1) / E + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (a.variant && E == 32) hipLaunchKernelGGL((k_step2d<DYN, OT, 4, true, 32>), grid, block, 0, s, a);
+        else if (a.variant) hipLaunchKernelGGL((k_step2d<DYN, OT, 4, true>), grid, block, 0, s, a);
+        else if (form == 0) hipLaunchKernelGGL((k_step2d<DYN, OT, 4, false, 64, false, false>), grid, block, 0, s, a);
+        else if (form == 1) hipLaunchKernelGGL((k_step2d<DYN, OT, 4, false, 64, true, false>), grid, block, 0, s, a);
+        else if (form == 2) hipLaunchKernelGGL((k_step2d<DYN, OT, 4, false, 64, false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_step2d<DYN, OT, 4, false, 64, true, true>), grid, block, 0, s, a);
+    });
 }
 
 void launch_step3d(const snac_env_desc* d, const KArgs& a, bool span, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    const int tiles = (a.n + 63) / 64;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (a.variant) {
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_step3d<true, float, 4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step3d<true, double, 4, true>), grid, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_step3d<false, float, 4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step3d<false, double, 4, true>), grid, block, 0, s, a); }
-    } else if (span) {                                              // the canonical rows of large batches: cooperative span loads (k_step3ds)
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_step3ds<true, float, 4>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step3ds<true, double, 4>), grid, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_step3ds<false, float, 4>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step3ds<false, double, 4>), grid, block, 0, s, a); }
-    } else {
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_step3d<true, float, 4>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step3d<true, double, 4>), grid, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_step3d<false, float, 4>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_step3d<false, double, 4>), grid, block, 0, s, a); }
-    }
+    const dim3 grid((unsigned)(((a.n + 63) / 64 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (a.variant) hipLaunchKernelGGL((k_step3d<DYN, OT, 4, true>), grid, block, 0, s, a);
+        else if (span) hipLaunchKernelGGL((k_step3ds<DYN, OT, 4>), grid, block, 0, s, a);   // the canonical rows of large batches: cooperative span loads
+        else hipLaunchKernelGGL((k_step3d<DYN, OT, 4>), grid, block, 0, s, a);
+    });
 }
 
 }  // namespace snac_detail

@@ -284,59 +284,43 @@ __global__ __launch_bounds__(WPB * 64) void k_edges1d(const KArgs a) {
     }
 }
 
-template <bool DYN, typename OT>
-void launch_e1(const KArgs& a, hipStream_t s) {
-    const int tiles = (a.n + 63) / 64;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    const bool vec = !a.obs || ((a.n & 3) == 0 && ((uintptr_t)a.obs & 15) == 0);
-    if (vec) hipLaunchKernelGGL((k_edges1d<DYN, OT, 4, true, ROWS_NT_EDGES>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_edges1d<DYN, OT, 4, false, false>), grid, block, 0, s, a);
-}
-
-template <bool DYN, typename OT>
-void launch_a1(const KArgs& a, hipStream_t s) {                     // masked reset / observe: the canonical layout, plain loads and rows
-    const int tiles = (a.n + 63) / 64;
-    hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, false, false, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
-}
-
-template <bool DYN, typename OT>
-void launch_s1(const KArgs& a, hipStream_t s) {
-    const int tiles = (a.n + 63) / 64;
-    if (a.variant) {                                                 // the layout variants: plain loads and rows; four waves per block while their tiles fit 64 KB
-        const size_t wave_bytes = (size_t)(((64 * 17 + 3) & ~3) + ((64 * a.ld * (int)sizeof(OT) / 4 + 3) & ~3)) * 4;
-        if (wave_bytes * 4 <= 65536) hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, false, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), wave_bytes * 4, s, a);
-        else hipLaunchKernelGGL((k_step1d<DYN, OT, 2, false, false, true>), dim3((unsigned)((tiles + 1) / 2)), dim3(128), wave_bytes * 2, s, a);
-        return;
-    }
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    switch (snac_detail::tune(snac_detail::TN_STEP1D_FORM) & 3) {    // bit 0: non-temporal record loads, bit 1: non-temporal row stores
-        case 0: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, false>), grid, block, 0, s, a); break;
-        case 1: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, true, false>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, true>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, true, true>), grid, block, 0, s, a); break;
-    }
-}
-
 }  // namespace
 
 namespace snac_detail {
 
-void launch_step1d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_s1<true, float>(a, s) : launch_s1<true, double>(a, s);
-    else f32 ? launch_s1<false, float>(a, s) : launch_s1<false, double>(a, s);
+void launch_step1d(const snac_env_desc* d, const KArgs& a, int form, hipStream_t s) {   // form bit 0: non-temporal record loads, bit 1: non-temporal row stores
+    const int tiles = (a.n + 63) / 64;
+    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (a.variant) {                                             // the layout variants: plain loads and rows; four waves per block while their tiles fit 64 KB
+            const size_t wave_bytes = (size_t)(((64 * 17 + 3) & ~3) + ((64 * a.ld * (int)sizeof(OT) / 4 + 3) & ~3)) * 4;
+            if (wave_bytes * 4 <= 65536) hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, false, true>), grid, block, wave_bytes * 4, s, a);
+            else hipLaunchKernelGGL((k_step1d<DYN, OT, 2, false, false, true>), dim3((unsigned)((tiles + 1) / 2)), dim3(128), wave_bytes * 2, s, a);
+            return;
+        }
+        switch (form) {
+            case 0: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, false>), grid, block, 0, s, a); break;
+            case 1: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, true, false>), grid, block, 0, s, a); break;
+            case 2: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, false, true>), grid, block, 0, s, a); break;
+            default: hipLaunchKernelGGL((k_step1d<DYN, OT, 4, true, true>), grid, block, 0, s, a); break;
+        }
+    });
 }
 
-void launch_aux1d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_a1<true, float>(a, s) : launch_a1<true, double>(a, s);
-    else f32 ? launch_a1<false, float>(a, s) : launch_a1<false, double>(a, s);
+void launch_aux1d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {   // masked reset / observe: the canonical layout, plain loads and rows
+    const dim3 grid((unsigned)(((a.n + 63) / 64 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) { hipLaunchKernelGGL((k_step1d<decltype(dyn)::value, decltype(ot), 4, false, false, false, true>), grid, block, 0, s, a); });
 }
 
 void launch_edges1d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_e1<true, float>(a, s) : launch_e1<true, double>(a, s);
-    else f32 ? launch_e1<false, float>(a, s) : launch_e1<false, double>(a, s);
+    const dim3 grid((unsigned)(((a.n + 63) / 64 + 3) / 4)), block(256);
+    const bool vec = !a.obs || ((a.n & 3) == 0 && ((uintptr_t)a.obs & 15) == 0);
+    by_rows(d, [&](auto dyn, auto ot) {
+        if (vec) hipLaunchKernelGGL((k_edges1d<decltype(dyn)::value, decltype(ot), 4, true, ROWS_NT_EDGES>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_edges1d<decltype(dyn)::value, decltype(ot), 4, false, false>), grid, block, 0, s, a);
+    });
 }
 
 }  // namespace snac_detail

@@ -195,41 +195,27 @@ __global__ __launch_bounds__(WPB * 64) void k_step3dq(const KArgs a) {
     }
 }
 
-template <bool DYN, typename OT>
-void launch_q(const KArgs& a, hipStream_t s) {
-    const int tiles = (a.n + 15) / 16;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    using namespace snac_detail;
-    int form = tune(TN_STEP3D_FORM);                                 // bit 0: non-temporal span loads, bit 1: non-temporal row stores; < 0: by batch size
-    if (form < 0) form = a.n < tune(TN_STEP3D_NTLOAD_MIN) ? 2 : (a.n < tune(TN_STEP3D_HUGE_MIN) ? 1 : tune(TN_STEP3D_HUGE_FORM));
-    switch (form & 3) {
-        case 0: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, false, false>), grid, block, 0, s, a); break;
-        case 1: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, true, false>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, false, true>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, true, true>), grid, block, 0, s, a); break;
-    }
-}
-
-template <bool DYN, typename OT>
-void launch_qa(const KArgs& a, hipStream_t s) {                     // masked reset / observe: plain span loads and rows
-    const int tiles = (a.n + 15) / 16;
-    hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, false, false, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, a);
-}
-
 }  // namespace
 
 namespace snac_detail {
 
-void launch_aux3d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_qa<true, float>(a, s) : launch_qa<true, double>(a, s);
-    else f32 ? launch_qa<false, float>(a, s) : launch_qa<false, double>(a, s);
+void launch_aux3d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {   // masked reset / observe: plain span loads and rows
+    const dim3 grid((unsigned)(((a.n + 15) / 16 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) { hipLaunchKernelGGL((k_step3dq<decltype(dyn)::value, decltype(ot), 4, false, false, true>), grid, block, 0, s, a); });
 }
 
-void launch_step3dq(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    if (dyn) f32 ? launch_q<true, float>(a, s) : launch_q<true, double>(a, s);
-    else f32 ? launch_q<false, float>(a, s) : launch_q<false, double>(a, s);
+void launch_step3dq(const snac_env_desc* d, const KArgs& a, int form, hipStream_t s) {   // form bit 0: non-temporal span loads, bit 1: non-temporal row stores
+    const dim3 grid((unsigned)(((a.n + 15) / 16 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        switch (form) {
+            case 0: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, false, false>), grid, block, 0, s, a); break;
+            case 1: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, true, false>), grid, block, 0, s, a); break;
+            case 2: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, false, true>), grid, block, 0, s, a); break;
+            default: hipLaunchKernelGGL((k_step3dq<DYN, OT, 4, true, true>), grid, block, 0, s, a); break;
+        }
+    });
 }
 
 }  // namespace snac_detail

@@ -420,21 +420,6 @@ __global__ __launch_bounds__(WPB * 64) void k_transition2d(const KArgs a) {
 }
 
 
-// E edges per wave.  The kernel is bound by HBM traffic from N = 2^19 down to where the launch itself dominates; 32 edges per
-// wave were 4 % ahead of 64 there (two rounds of waves: the second round's loads run under the first round's row stores),
-// small batches take 16 so that a step() on 4096 envs is still 256 waves.  SNAC_T2D_E overrides (tuning).
-template <bool DYN, typename OT>
-void launch_trans2d_e(const KArgs& a, hipStream_t s) {
-    const int forced = snac_detail::tune(snac_detail::TN_T2D_E);
-    const int E = (forced == 16 || forced == 32 || forced == 64) ? forced : (a.n >= 65536 ? 32 : 16);
-    const int tiles = (a.n + E - 1) / E;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (E == 64) hipLaunchKernelGGL((k_transition2d<DYN, OT, 4, 64>), grid, block, 0, s, a);
-    else if (E == 32) hipLaunchKernelGGL((k_transition2d<DYN, OT, 4, 32>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_transition2d<DYN, OT, 4, 16>), grid, block, 0, s, a);
-}
-
-
 // ------------------------------------------------------------------------------------------------
 // k_edges2d (round 5): 2D tree edges with gathered rows, the records through LDS.  k_transition2d reads an edge's source record with eight
 // 4-byte loads per LANE (the agent's row word + the seven window rows, every lane in another record) and then once more for the copy to the
@@ -553,41 +538,32 @@ __global__ __launch_bounds__(WPB * 64) void k_edges2d(const KArgs a) {
 namespace snac_detail {
 
 void launch_trans3d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    const int tiles = (a.n + 31) / 32;
-    const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (!a.src_index && !a.dst_index) {   // identity rows (snac_step, or a transition on rows i -> i)
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_transition3d<true, float, 4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_transition3d<true, double, 4, true>), grid, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_transition3d<false, float, 4, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_transition3d<false, double, 4, true>), grid, block, 0, s, a); }
-        return;
-    }
-    // gathered / scattered rows (tree edges): the records through LDS, every memory instruction wide (k_edges3d); SNAC_EDGES3D=0 keeps
-    // them on k_transition3d (A/B timing, tests of both paths)
-    const bool edges_off = tune(TN_EDGES3D) == 0;
-    if (!edges_off && a.obs && (a.n & 3) == 0 && ((uintptr_t)a.obs & 15) == 0) {
-        g_kernel = "k_edges3d";
-        const dim3 g2((unsigned)((tiles + 1) / 2)), b2(128);     // two waves per block: 51 KB of LDS, three blocks per CU
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_edges3d<true, float, 2>), g2, b2, 0, s, a); else hipLaunchKernelGGL((k_edges3d<true, double, 2>), g2, b2, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_edges3d<false, float, 2>), g2, b2, 0, s, a); else hipLaunchKernelGGL((k_edges3d<false, double, 2>), g2, b2, 0, s, a); }
-        return;
-    }
-    if (dyn) { if (f32) hipLaunchKernelGGL((k_transition3d<true, float, 4, false>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_transition3d<true, double, 4, false>), grid, block, 0, s, a); }
-    else { if (f32) hipLaunchKernelGGL((k_transition3d<false, float, 4, false>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_transition3d<false, double, 4, false>), grid, block, 0, s, a); }
+    const dim3 grid((unsigned)(((a.n + 31) / 32 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) {
+        if (!a.src_index && !a.dst_index) hipLaunchKernelGGL((k_transition3d<decltype(dyn)::value, decltype(ot), 4, true>), grid, block, 0, s, a);   // identity rows (snac_step, or a transition on rows i -> i)
+        else hipLaunchKernelGGL((k_transition3d<decltype(dyn)::value, decltype(ot), 4, false>), grid, block, 0, s, a);
+    });
 }
 
-void launch_trans2d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
-    const bool dyn = d->dynamic != 0, f32 = d->obs_dtype == SNAC_OBS_F32;
-    // gathered / scattered rows (tree edges): the records through LDS, every memory instruction wide (k_edges2d); SNAC_EDGES2D=0 keeps
-    // them on k_transition2d (A/B timing, tests of both paths), SNAC_EDGES2D_MIN=n moves the wave size from which it takes them
-    if ((a.src_index || a.dst_index) && tune(TN_EDGES2D) != 0 && a.n >= tune(TN_EDGES2D_MIN) && a.obs && (a.n & 3) == 0 && ((uintptr_t)a.obs & 15) == 0) {
-        g_kernel = "k_edges2d";
-        const dim3 grid((unsigned)(((a.n + 63) / 64 + 3) / 4)), block(256);
-        if (dyn) { if (f32) hipLaunchKernelGGL((k_edges2d<true, float, 4>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_edges2d<true, double, 4>), grid, block, 0, s, a); }
-        else { if (f32) hipLaunchKernelGGL((k_edges2d<false, float, 4>), grid, block, 0, s, a); else hipLaunchKernelGGL((k_edges2d<false, double, 4>), grid, block, 0, s, a); }
-        return;
-    }
-    if (dyn) f32 ? launch_trans2d_e<true, float>(a, s) : launch_trans2d_e<true, double>(a, s);
-    else f32 ? launch_trans2d_e<false, float>(a, s) : launch_trans2d_e<false, double>(a, s);
+void launch_edges3d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)(((a.n + 31) / 32 + 1) / 2)), block(128);   // two waves per block: 51 KB of LDS, three blocks per CU
+    by_rows(d, [&](auto dyn, auto ot) { hipLaunchKernelGGL((k_edges3d<decltype(dyn)::value, decltype(ot), 2>), grid, block, 0, s, a); });
+}
+
+void launch_trans2d(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s) {   // E edges per wave
+    const dim3 grid((unsigned)(((a.n + E - 1) / E + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) {
+        constexpr bool DYN = decltype(dyn)::value;
+        using OT = decltype(ot);
+        if (E == 64) hipLaunchKernelGGL((k_transition2d<DYN, OT, 4, 64>), grid, block, 0, s, a);
+        else if (E == 32) hipLaunchKernelGGL((k_transition2d<DYN, OT, 4, 32>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_transition2d<DYN, OT, 4, 16>), grid, block, 0, s, a);
+    });
+}
+
+void launch_edges2d(const snac_env_desc* d, const KArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)(((a.n + 63) / 64 + 3) / 4)), block(256);
+    by_rows(d, [&](auto dyn, auto ot) { hipLaunchKernelGGL((k_edges2d<decltype(dyn)::value, decltype(ot), 4>), grid, block, 0, s, a); });
 }
 
 }  // namespace snac_detail

@@ -27,7 +27,8 @@
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows
 //   k_tile{1,2,3}d.hip  the tile kernels k_rollout / k_transition / k_aux (rounds 1-2) behind all of them (templates: k_tile.inc)
 //   k_misc.hip      export / import / equality / plan generators / replay gather, with their entry points
-//   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch (launch(): one table of thresholds)
+//   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
+//                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory
 // The env records are read from HBM once per launch, kept on chip for all T steps, written back once.  Rollout outputs are [T][N][D]
 // or, with SNAC_OBS_TILED, tile-major [N / 64][T][64][D].
@@ -114,22 +115,54 @@ KArgs make_args(const snac_env_desc* d, const snac_state* st);
 int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m);
 // the checks the self-play and Reanalyse entry points share (num_actions, stats, B, cap, B * (cap + 1) rows), defined in k_uct_play.hip
 int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap);
+// ---- the dispatch, defined in snac_hip.hip.  choose() is the whole decision, a pure function of its arguments and tune(): the kernel, its
+// size parameter E where it has several (tile size of the tile kernels; envs per block of k_rollout2db / 2dt / 1dt; envs per wave of
+// k_step2d; edges per wave of k_transition2d; else 0) and its form where it has them (k_step2d / k_step3dq / k_step1d / k_rollout1dl:
+// bit 0 non-temporal record loads, bit 1 non-temporal row stores; else 0).  launch() names the kernel for snac_last_kernel() and calls
+// its launcher.  tests/native/dispatch_table.cpp pins choose() over a grid of calls against tests/golden/dispatch_table.txt, on the host.
+enum Kernel { K_ROLLOUT, K_TRANSITION, K_AUX, K_RESET, K_IOU, K_STEP1D, K_STEP2D, K_STEP3D, K_STEP3DS, K_STEP3DQ, K_EDGES1D, K_EDGES2D, K_EDGES3D,
+              K_TRANSITION2D, K_TRANSITION3D, K_ROLLOUT1DL, K_ROLLOUT1DT, K_ROLLOUT2D, K_ROLLOUT2DB, K_ROLLOUT2DT, K_ROLLOUT3D, K_ROLLOUT3DB, K_COUNT };
+struct Choice { Kernel kernel; int E; int form; };
+Choice choose(Op op, const snac_env_desc* d, const KArgs& a);
 int launch(Op op, const snac_env_desc* d, const KArgs& a, void* stream);
 
-// ---- the launch functions of the kernel families (each defined beside its kernels; the dispatch decides, they only launch)
+// ---- the launch functions of the kernel families, each defined beside its kernels.  They launch what choose() decided (E, form: the
+// fields of its Choice) and read no knob; what they still pick follows from the call's data alone (explicit actions, record outputs,
+// identity rows, the row-length classes of the 1D layout variants)
 void launch_tile1d(Op op, bool dyn, int E, int obs_dtype, const KArgs& a, hipStream_t s);      // k_tile1d.hip
 void launch_tile2d(Op op, bool dyn, int E, int obs_dtype, const KArgs& a, hipStream_t s);      // k_tile2d.hip
 void launch_tile3d(Op op, bool dyn, int E, int obs_dtype, const KArgs& a, hipStream_t s);      // k_tile3d.hip
 void launch_roll2d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                     // k_roll2d.hip
-void launch_roll2dt(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_roll2dt.hip
-void launch_roll1dt(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_roll1dt.hip
-void launch_roll1dl(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_roll1dl.hip
+void launch_roll2db(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s);             // k_roll2db.hip
+void launch_roll2dbv(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s);            // k_roll2dbv.hip: k_rollout2db for the layout variants
+void launch_roll2dt(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s);             // k_roll2dt.hip
+void launch_roll1dt(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s);             // k_roll1dt.hip
+void launch_roll1dl(const snac_env_desc* d, const KArgs& a, int form, hipStream_t s);          // k_roll1dl.hip
 void launch_roll3d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                     // k_roll3d.hip
 void launch_roll3db(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_roll3db.hip
-void launch_step2d(const snac_env_desc* d, const KArgs& a, bool half, hipStream_t s);          // k_step.hip
+void launch_roll3dbv(const snac_env_desc* d, const KArgs& a, hipStream_t s);                   // k_roll3dbv.hip: k_rollout3db for the layout variants
+void launch_step1d(const snac_env_desc* d, const KArgs& a, int form, hipStream_t s);           // k_step1d.hip
+void launch_aux1d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                      // k_step1d.hip
+void launch_edges1d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_step1d.hip
+void launch_step2d(const snac_env_desc* d, const KArgs& a, int E, int form, hipStream_t s);    // k_step.hip
+void launch_aux2d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                      // k_step.hip
 void launch_step3d(const snac_env_desc* d, const KArgs& a, bool span, hipStream_t s);          // k_step.hip (span: k_step3ds)
-void launch_trans2d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_trans.hip
-void launch_trans3d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_trans.hip (k_edges3d for gathered rows)
+void launch_step3dq(const snac_env_desc* d, const KArgs& a, int form, hipStream_t s);          // k_step3dq.hip
+void launch_aux3d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                      // k_step3dq.hip
+void launch_trans2d(const snac_env_desc* d, const KArgs& a, int E, hipStream_t s);             // k_trans.hip
+void launch_edges2d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_trans.hip
+void launch_trans3d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_trans.hip
+void launch_edges3d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_trans.hip
+void launch_reset(const snac_env_desc* d, const KArgs& a, hipStream_t s);                      // k_reset.hip
+void launch_iou(const snac_env_desc* d, const KArgs& a, hipStream_t s);                        // k_reset.hip
+
+// the four (dynamic, row type) instantiations a launcher chooses among: f(std::bool_constant<DYN>(), OT()) with OT = float / double
+template <typename F>
+void by_rows(const snac_env_desc* d, F f) {
+    const bool f32 = d->obs_dtype == SNAC_OBS_F32;
+    if (d->dynamic != 0) { if (f32) f(std::true_type(), float()); else f(std::true_type(), double()); }
+    else { if (f32) f(std::false_type(), float()); else f(std::false_type(), double()); }
+}
 }  // namespace snac_detail
 using snac_detail::fail;
 using snac_detail::fail_hip;

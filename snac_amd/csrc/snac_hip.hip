@@ -1,21 +1,10 @@
-// snac_hip.hip -- the C ABI of include/snac_hip.h and the dispatch: which kernel a call runs on (launch()).  The kernels live in the
-// k_*.hip translation units beside this one (snac_dev.h has the map), trajectory memory in snac_traj.hip.
+// snac_hip.hip -- the C ABI of include/snac_hip.h and the dispatch: which kernel a call runs on (choose()) and its launch (launch()).
+// The kernels live in the k_*.hip translation units beside this one (snac_dev.h has the map), trajectory memory in snac_traj.hip.
 #include "snac_dev.h"
 
 #include <atomic>
 
 namespace snac_detail {
-void launch_step3dq(const snac_env_desc* d, const KArgs& a, hipStream_t s);                   // k_step3dq.hip
-void launch_step1d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                    // k_step1d.hip
-void launch_edges1d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                   // k_step1d.hip
-void launch_reset(const snac_env_desc* d, const KArgs& a, hipStream_t s);                     // k_reset.hip
-void launch_iou(const snac_env_desc* d, const KArgs& a, hipStream_t s);                       // k_reset.hip
-void launch_aux1d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                     // k_step1d.hip
-void launch_aux2d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                     // k_step.hip
-void launch_aux3d(const snac_env_desc* d, const KArgs& a, hipStream_t s);                     // k_step3dq.hip
-void launch_roll2db(const snac_env_desc* d, const KArgs& a, int steppers, hipStream_t s);   // k_roll2db.hip
-void launch_roll2dbv(const snac_env_desc* d, const KArgs& a, int steppers, hipStream_t s);  // k_roll2dbv.hip: the same kernel for the layout variants: k_rollout2db (declared here for the same reason as the next one)
-void launch_roll3dbv(const snac_env_desc* d, const KArgs& a, hipStream_t s);   // k_roll3dbv.hip: k_rollout3db for the layout variants (declared here: snac_dev.h is hashed into profiles/traffic.json)
 thread_local char g_err[256] = "";
 thread_local const char* g_kernel = "";
 
@@ -101,6 +90,9 @@ KArgs make_args(const snac_env_desc* d, const snac_state* st) {
 // (environment variable, default, what it decides); the defaults are what was measured on the MI355X boxes of the build pool
 // (profiles/ files named per entry).  Overrides are read once per process.  snac_tuning() prints the effective values;
 // tools/retune.py re-measures the crossovers on the box it runs on and prints the overrides that would move them.
+// The entries of the env-batch entry points (snac_rollout*, snac_step*, snac_transition, snac_reset*, snac_observe, snac_iou) are read by
+// choose() below and nowhere else; SNAC_2D_STAGE_XCD (a grid order, k_roll2d.hip) and those of the node-pool, evaluation and UCT entry
+// points (k_nodes.hip, k_eval.hip, k_uct.hip) by their own launches.  tests/test_dispatch_host.py holds choose() to the committed table.
 struct Knob { const char* env; int def; const char* what; };
 const Knob KNOBS[TN_COUNT] = {
     /* TN_PIPELINE        */ {"SNAC_3D_PIPELINE", 1, "0: every launch on the generic tile kernels (k_rollout / k_transition / k_aux)"},
@@ -223,39 +215,44 @@ int pick_tile(int kind, int n) {
     return 8;                        // small batches: one-wave blocks of 8 envs, so that 4096 envs still reach every CU
 }
 
-bool pipeline_off() { return tune(TN_PIPELINE) == 0; }
+// The predicates below are what choose() is made of.  choose() has already sent every call to the tile kernels when SNAC_3D_PIPELINE=0
+// and computed f32 (float32 rows) once; a predicate holds the conditions of ONE kernel.
 inline bool every_row(const KArgs& a) { return a.obs_mode == SNAC_OBS_ALL || a.obs_mode == SNAC_OBS_TILED; }
 inline bool pieces16(const KArgs& a) { return (a.n & 3) == 0 && (((uintptr_t)a.obs) & 15) == 0; }
+inline bool gathered(const KArgs& a) { return a.src_index || a.dst_index; }
 
 // 3D rollouts by blocks of 64 envs (k_rollout3db): every row written, <= TB_MAX plans, 16-byte pieces; the layout variants on its VAR form
 bool roll3db_ok(const KArgs& a, bool f32) {
-    const int lim = tune(TN_3D_BLOCK_MIN) >= 0 ? tune(TN_3D_BLOCK_MIN) : tune(f32 ? TN_3D_BLOCK_MIN_F32 : TN_3D_BLOCK_MIN_F64);
+    if (tune(TN_3D_BLOCK) == 0 || !every_row(a) || a.num_plans > TB_MAX || !pieces16(a)) return false;
     if (a.variant) {   // k_rollout3db<.., VAR>: its writers copy plan rows 16 bytes at a time
         const int from = (a.tail & SNAC_TAIL_PLAN) ? tune(f32 ? TN_3D_BLOCK_VAR_PLAN_F32 : TN_3D_BLOCK_VAR_PLAN_F64) : tune(TN_3D_BLOCK_VAR_MIN);
-        if (tune(TN_3D_BLOCK_VAR) == 0 || a.n < from || (((uintptr_t)a.plans) & 15) != 0) return false;
-        return tune(TN_3D_BLOCK) != 0 && every_row(a) && a.num_plans <= TB_MAX && pieces16(a) && !pipeline_off();
+        return tune(TN_3D_BLOCK_VAR) != 0 && a.n >= from && (((uintptr_t)a.plans) & 15) == 0;
     }
-    return tune(TN_3D_BLOCK) != 0 && a.n >= lim && every_row(a) && a.num_plans <= TB_MAX && pieces16(a) && !pipeline_off();
+    return a.n >= (tune(TN_3D_BLOCK_MIN) >= 0 ? tune(TN_3D_BLOCK_MIN) : tune(f32 ? TN_3D_BLOCK_MIN_F32 : TN_3D_BLOCK_MIN_F64));
 }
 
-// 2D rollouts by blocks of 64 envs (k_rollout2db): the middle batches, every row written, canonical layout, 16-byte pieces
+// 2D rollouts by blocks of 64 envs (k_rollout2db): the middle batches, every row written, 16-byte pieces; E: the envs of a block, 64 per stepper wave
 bool roll2db_ok(const KArgs& a, bool f32) {
-    if (tune(TN_2D_BLOCK) == 0 || !every_row(a) || !pieces16(a) || pipeline_off()) return false;
+    if (tune(TN_2D_BLOCK) == 0 || !every_row(a) || !pieces16(a)) return false;
     if (a.variant) return !(a.tail & SNAC_TAIL_PLAN) && a.n >= tune(TN_2D_BLOCK_VAR_MIN) && a.n <= tune(TN_2D_BLOCK_VAR_MAX);   // k_roll2dbv.hip
     return a.n >= tune(f32 ? TN_2D_BLOCK_MIN_F32 : TN_2D_BLOCK_MIN_F64) &&
            a.n <= std::max(tune(f32 ? TN_2D_BLOCK_MAX_F32 : TN_2D_BLOCK_MAX_F64), tune(f32 ? TN_2D_BLOCK_FOUR_F32 : TN_2D_BLOCK_FOUR_F64));
 }
-
-// the headline kernel k_rollout2d: tiles of 64 envs, every row written, 16-byte pieces
-bool roll2d_ok(const KArgs& a, int E) {
-    return E == 64 && every_row(a) && pieces16(a) && !pipeline_off() && tune(TN_2D_STAGE) != 0;
+int roll2db_E(const KArgs& a, bool f32) {
+    if (!a.variant && a.n > tune(f32 ? TN_2D_BLOCK_MAX_F32 : TN_2D_BLOCK_MAX_F64)) return 256;   // (up to SNAC_2D_BLOCK_FOUR_MAX_*: roll2db_ok)
+    return a.n >= tune(a.variant ? TN_2D_BLOCK_VAR_TWO : (f32 ? TN_2D_BLOCK_TWO_F32 : TN_2D_BLOCK_TWO_F64)) ? 128 : 64;
 }
-int roll2d_from(bool f32) { return tune(TN_2D_STAGE_MIN) ? tune(TN_2D_STAGE_MIN) : tune(f32 ? TN_2D_STAGE_MIN_F32 : TN_2D_STAGE_MIN_F64); }
+
+// the headline kernel k_rollout2d: tiles of 64 envs (from roll2d_from() envs, or where the tile kernel would take 64 too), every row written, 16-byte pieces
+bool roll2d_ok(const KArgs& a, bool f32, int tile_E) {
+    const int from = tune(TN_2D_STAGE_MIN) ? tune(TN_2D_STAGE_MIN) : tune(f32 ? TN_2D_STAGE_MIN_F32 : TN_2D_STAGE_MIN_F64);
+    return (a.n >= from || tile_E == 64) && every_row(a) && pieces16(a) && tune(TN_2D_STAGE) != 0;
+}
 
 // time-parallel 2D rollouts (k_rollout2dt: one wave per env, lane = tick): small and middle batches, where the lane-per-env kernels are
 // bound by the chain of their ticks (0.5-0.7 ms per 600 ticks at every N <= 16 384) or leave CUs empty
 bool roll2dt_ok(const KArgs& a, bool f32) {
-    if (tune(TN_2D_TP) == 0 || !every_row(a) || pipeline_off()) return false;
+    if (tune(TN_2D_TP) == 0 || !every_row(a)) return false;
     if (a.variant) {   // k_rollout2dt<.., VAR>: whole groups of four envs and 16-byte pieces only
         const int lim = tune(TN_2D_TP_VAR_MAX) ? tune(TN_2D_TP_VAR_MAX) : tune((a.tail & SNAC_TAIL_PLAN) ? TN_2D_TP_VAR_PLAN : TN_2D_TP_VAR_SHORT);
         return pieces16(a) && a.n <= lim;
@@ -267,23 +264,33 @@ bool roll2dt_ok(const KArgs& a, bool f32) {
     if (f32) return a.n <= tune(TN_2D_TP_MAX_F32);
     return a.n <= tune(TN_2D_TP_MAX_F64) && !(a.n >= tune(TN_2D_TP_GAP_LO) && a.n <= tune(TN_2D_TP_GAP_HI));
 }
+// its blocks: 8 envs (runs of 3264 / 1632 bytes per tick) from SNAC_2D_TP_EB8 envs, below a block per CU first (1536 envs: 0.097 against
+// 0.086 ms); the VAR form 4
+int roll2dt_E(const KArgs& a) { return !a.variant && a.n >= tune(TN_2D_TP_EB8) ? 8 : 4; }
 
 // time-parallel 1D rollouts (k_rollout1dt).  Its rate levels off at 6-7e10 env-steps/s (instruction issue), the tile kernel's keeps growing
 bool roll1dt_ok(const KArgs& a, bool f32) {
-    if (tune(TN_1D_TP) == 0 || !every_row(a) || pipeline_off()) return false;
+    if (tune(TN_1D_TP) == 0 || !every_row(a)) return false;
     if (a.variant) return pieces16(a) && a.n <= tune(TN_1D_TP_VAR_MAX);   // k_rollout1dt<.., VAR>: blocks of four envs
     return a.n <= (tune(TN_1D_TP_MAX) ? tune(TN_1D_TP_MAX) : tune(f32 ? TN_1D_TP_MAX_F32 : TN_1D_TP_MAX_F64));
+}
+// its blocks: 8 envs where two blocks share a CU, 16 (runs of 896 / 448 bytes per tick) from SNAC_1D_TP_EB16 envs outside that range, small
+// batches 4 (more blocks than CUs first); the VAR form 4
+int roll1dt_E(const KArgs& a) {
+    if (a.variant) return 4;
+    if (a.n >= tune(TN_1D_TP_EB8_MIN) && a.n <= tune(TN_1D_TP_EB8_MAX)) return 8;
+    return a.n >= tune(TN_1D_TP_EB16) ? 16 : 4;
 }
 
 // lane-per-env 1D rollouts (k_rollout1dl): batches with a 64-env wave for (nearly) every SIMD; every row written, 16-byte pieces; canonical rows and the layout variants
 bool roll1dl_ok(const KArgs& a, bool f32) {
-    if (tune(TN_1D_LANE) == 0 || !every_row(a) || !pieces16(a) || pipeline_off()) return false;
+    if (tune(TN_1D_LANE) == 0 || !every_row(a) || !pieces16(a)) return false;
     if (a.variant) return a.ld <= 46 && a.n >= tune(a.ld > 16 ? TN_1D_LANE_VAR_MIN : TN_1D_LANE_VAR_SHORT_MIN);
     return a.n >= tune(f32 ? TN_1D_LANE_MIN_F32 : TN_1D_LANE_MIN_F64);
 }
 
 // snac_step on identity rows: k_step2d / k_step3d (wide loads, rows through emit_tile)
-bool step_stage_ok(const KArgs& a) { return tune(TN_STEP_STAGE) != 0 && !a.src_index && !a.dst_index && pieces16(a); }
+bool step_stage_ok(const KArgs& a) { return tune(TN_STEP_STAGE) != 0 && !gathered(a) && pieces16(a); }
 // ... with a layout variant: 64 envs per wave are 64 rows of kilobytes per wave -- batches large enough to fill the CUs that way;
 // below, the 8-env tiles of k_transition spread the rows over more waves
 bool step_var_ok(const KArgs& a, bool f32) {
@@ -297,77 +304,121 @@ bool step_var_half(const KArgs& a) {
 }
 bool step_var3_ok(const KArgs& a) { return a.n >= tune(TN_STEP_VAR3_MIN) && a.frame_val == -1; }
 
-int launch(Op op, const snac_env_desc* d, const KArgs& a, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const bool dyn = d->dynamic != 0;
+// The forms of the canonical step kernels (bit 0: the records by non-temporal loads, bit 1: the rows by non-temporal stores), picked by
+// what fits the Infinity Cache at this batch size (profiles/r06_step_loads.txt); SNAC_STEP2D_FORM / SNAC_STEP3D_FORM force one
+int step2d_form(int n) {
+    if (tune(TN_STEP2D_FORM) >= 0) return tune(TN_STEP2D_FORM) & 3;
+    if (n < tune(TN_STEP2D_PLAIN_LO)) return 1;                      // small batches: round 5's form
+    if (n <= tune(TN_STEP2D_RES_HI)) return 2;                       // "resident": plain loads keep the state cached, non-temporal rows stay out of it
+    if (n <= tune(TN_STEP2D_PLAIN_HI)) return 0;                     // plain loads, plain rows
+    if (n < tune(TN_STEP2D_HUGE_MIN)) return 1;                      // the state streams
+    return tune(TN_STEP2D_HUGE_FORM) & 3;                            // the rows of one tick alone overflow the cache
+}
+int step3dq_form(int n) {
+    if (tune(TN_STEP3D_FORM) >= 0) return tune(TN_STEP3D_FORM) & 3;
+    return n < tune(TN_STEP3D_NTLOAD_MIN) ? 2 : (n < tune(TN_STEP3D_HUGE_MIN) ? 1 : tune(TN_STEP3D_HUGE_FORM) & 3);
+}
+
+// E edges per wave of k_transition2d.  The kernel is bound by HBM traffic from N = 2^19 down to where the launch itself dominates; 32 edges
+// per wave were 4 % ahead of 64 there (two rounds of waves: the second round's loads run under the first round's row stores), small
+// batches take 16 so that a step() on 4096 envs is still 256 waves.  SNAC_T2D_E overrides (tuning).
+int trans2d_E(int n) {
+    const int forced = tune(TN_T2D_E);
+    return (forced == 16 || forced == 32 || forced == 64) ? forced : (n >= 65536 ? 32 : 16);
+}
+// tree edges with gathered rows whose rows leave in 16-byte pieces: the records through LDS, every memory instruction wide (k_edges2d /
+// k_edges3d); SNAC_EDGES2D=0 / SNAC_EDGES3D=0 keep them on k_transition2d / 3d (A/B timing, tests of both paths)
+bool edges_lds_ok(const KArgs& a) { return gathered(a) && a.obs && pieces16(a); }
+
+Choice choose(Op op, const snac_env_desc* d, const KArgs& a) {
+    const bool f32 = d->obs_dtype == SNAC_OBS_F32;
     int E = pick_tile(d->kind, a.n);
     if (d->kind == SNAC_ENV_2D && op == OP_ROLLOUT && E == 16 && tune(TN_TILE) == 0 && a.n >= tune(TN_2D_TILE32_MIN)) E = 32;   // one wave of 32 per SIMD beats 1.5 of 16
-    const char* const tile_name = op == OP_ROLLOUT ? "k_rollout" : (op == OP_TRANSITION ? "k_transition" : "k_aux");
-    g_kernel = tile_name;
-    if (op == OP_AUX && a.aux_op == AUX_RESET && !a.mask && !a.variant && pieces16(a) && !pipeline_off() && tune(TN_RESET_FAST) != 0 && a.n >= tune(TN_RESET_FAST_MIN)) {
-        g_kernel = "k_reset";
-        launch_reset(d, a, s);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SNAC_OK : fail_hip(e, "kernel launch");
+    const Choice tile = {op == OP_ROLLOUT ? K_ROLLOUT : (op == OP_TRANSITION ? K_TRANSITION : K_AUX), E, 0};
+    if (tune(TN_PIPELINE) == 0) return tile;
+    if (op == OP_AUX) {
+        if (a.aux_op == AUX_RESET && !a.mask && !a.variant && pieces16(a) && tune(TN_RESET_FAST) != 0 && a.n >= tune(TN_RESET_FAST_MIN)) return {K_RESET, 0, 0};
+        if ((a.aux_op == AUX_RESET || a.aux_op == AUX_OBSERVE) && a.obs && !a.variant && pieces16(a) && tune(TN_AUX_STEP) != 0 && tune(TN_STEP_STAGE) != 0 && a.n >= 256)
+            return d->kind == SNAC_ENV_1D ? Choice{K_STEP1D, 0, 0} : (d->kind == SNAC_ENV_2D ? Choice{K_STEP2D, 64, 0} : Choice{K_STEP3DQ, 0, 0});   // the AUX forms: plain loads and rows
+        if (a.aux_op == AUX_IOU && tune(TN_IOU_FAST) != 0 && a.n >= 256 && (((uintptr_t)a.grid | (uintptr_t)a.plans) & 15) == 0) return {K_IOU, 0, 0};
+        return tile;
     }
-    if (op == OP_AUX && (a.aux_op == AUX_RESET || a.aux_op == AUX_OBSERVE) && a.obs && !a.variant && pieces16(a) && !pipeline_off() &&
-        tune(TN_AUX_STEP) != 0 && tune(TN_STEP_STAGE) != 0 && a.n >= 256) {
-        if (d->kind == SNAC_ENV_1D) { g_kernel = "k_step1d"; launch_aux1d(d, a, s); }
-        else if (d->kind == SNAC_ENV_2D) { g_kernel = "k_step2d"; launch_aux2d(d, a, s); }
-        else { g_kernel = "k_step3dq"; launch_aux3d(d, a, s); }
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SNAC_OK : fail_hip(e, "kernel launch");
-    }
-    if (op == OP_AUX && a.aux_op == AUX_IOU && tune(TN_IOU_FAST) != 0 && a.n >= 256 && (((uintptr_t)a.grid | (uintptr_t)a.plans) & 15) == 0 && !pipeline_off()) {
-        g_kernel = "k_iou";
-        launch_iou(d, a, s);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? SNAC_OK : fail_hip(e, "kernel launch");
-    }
+    const bool roll = op == OP_ROLLOUT;                              // else: OP_TRANSITION
     switch (d->kind) {
         case SNAC_ENV_1D:
             // rollouts that write every row: the time-parallel kernel while its rate beats the tile kernel's (lane-per-env transition)
-            if (op == OP_ROLLOUT && roll1dl_ok(a, d->obs_dtype == SNAC_OBS_F32)) { g_kernel = "k_rollout1dl"; launch_roll1dl(d, a, s); break; }
-            if (op == OP_ROLLOUT && roll1dt_ok(a, d->obs_dtype == SNAC_OBS_F32)) { g_kernel = "k_rollout1dt"; launch_roll1dt(d, a, s); break; }
-            if (op == OP_TRANSITION && !pipeline_off() && (a.src_index || a.dst_index) && !a.variant && tune(TN_EDGES1D) != 0 && a.n >= tune(TN_EDGES1D_MIN)) { g_kernel = "k_edges1d"; launch_edges1d(d, a, s); break; }
-            if (op == OP_TRANSITION && !pipeline_off() && step_stage_ok(a) && tune(TN_STEP1D) != 0 && a.n >= tune(a.variant ? TN_STEP1D_VAR_MIN : TN_STEP1D_MIN) && a.ld <= 46) { g_kernel = "k_step1d"; launch_step1d(d, a, s); break; }
-            launch_tile1d(op, dyn, E, d->obs_dtype, a, s); break;
+            if (roll) {
+                if (roll1dl_ok(a, f32)) return {K_ROLLOUT1DL, 0, !a.variant && tune(TN_1D_LANE_NT) != 0 ? 2 : 0};
+                if (roll1dt_ok(a, f32)) return {K_ROLLOUT1DT, roll1dt_E(a), 0};
+                return tile;
+            }
+            if (gathered(a) && !a.variant && tune(TN_EDGES1D) != 0 && a.n >= tune(TN_EDGES1D_MIN)) return {K_EDGES1D, 0, 0};
+            if (step_stage_ok(a) && tune(TN_STEP1D) != 0 && a.n >= tune(a.variant ? TN_STEP1D_VAR_MIN : TN_STEP1D_MIN) && a.ld <= 46)
+                return {K_STEP1D, 0, a.variant ? 0 : tune(TN_STEP1D_FORM) & 3};   // the layout variants: plain loads and rows
+            return tile;
         case SNAC_ENV_2D:
-            if (op == OP_TRANSITION && !pipeline_off() && step_stage_ok(a) && (!a.variant || step_var_ok(a, d->obs_dtype == SNAC_OBS_F32))) { g_kernel = "k_step2d"; launch_step2d(d, a, a.variant && step_var_half(a), s); break; }
-            if (op == OP_TRANSITION && !a.variant && !pipeline_off()) { g_kernel = "k_transition2d"; launch_trans2d(d, a, s); break; }
-            if (op == OP_ROLLOUT && roll2db_ok(a, d->obs_dtype == SNAC_OBS_F32)) {
-                g_kernel = "k_rollout2db";
-                const bool f32 = d->obs_dtype == SNAC_OBS_F32;
-                int steppers = a.n >= tune(a.variant ? TN_2D_BLOCK_VAR_TWO : (f32 ? TN_2D_BLOCK_TWO_F32 : TN_2D_BLOCK_TWO_F64)) ? 2 : 1;
-                if (!a.variant && a.n > tune(f32 ? TN_2D_BLOCK_MAX_F32 : TN_2D_BLOCK_MAX_F64)) steppers = 4;   // (up to SNAC_2D_BLOCK_FOUR_MAX_*: roll2db_ok)
-                if (a.variant) launch_roll2dbv(d, a, steppers, s); else launch_roll2db(d, a, steppers, s);
-                break;
+            if (roll) {
+                if (roll2db_ok(a, f32)) return {K_ROLLOUT2DB, roll2db_E(a, f32), 0};
+                if (roll2dt_ok(a, f32)) return {K_ROLLOUT2DT, roll2dt_E(a), 0};
+                if (roll2d_ok(a, f32, E)) return {K_ROLLOUT2D, 0, 0};
+                return tile;
             }
-            if (op == OP_ROLLOUT && roll2dt_ok(a, d->obs_dtype == SNAC_OBS_F32)) { g_kernel = "k_rollout2dt"; launch_roll2dt(d, a, s); break; }
-            if (op == OP_ROLLOUT && roll2d_ok(a, a.n >= roll2d_from(d->obs_dtype == SNAC_OBS_F32) ? 64 : E)) { g_kernel = "k_rollout2d"; launch_roll2d(d, a, s); break; }
-            launch_tile2d(op, dyn, E, d->obs_dtype, a, s); break;
+            if (step_stage_ok(a) && (!a.variant || step_var_ok(a, f32)))   // the variants: full tiles of 64 envs per wave or half-filled ones, plain loads and rows
+                return a.variant ? Choice{K_STEP2D, step_var_half(a) ? 32 : 64, 0} : Choice{K_STEP2D, 64, step2d_form(a.n)};
+            if (a.variant) return tile;
+            if (edges_lds_ok(a) && tune(TN_EDGES2D) != 0 && a.n >= tune(TN_EDGES2D_MIN)) return {K_EDGES2D, 0, 0};
+            return {K_TRANSITION2D, trans2d_E(a.n), 0};
         default:   // 3D: 2.1 KB of LDS per env -> tiles of 16 (or 8 for small batches: two waves per SIMD sooner)
-            if (op == OP_ROLLOUT && roll3db_ok(a, d->obs_dtype == SNAC_OBS_F32)) {
-                g_kernel = "k_rollout3db";
-                if (a.variant) launch_roll3dbv(d, a, s); else launch_roll3db(d, a, s);
-                break;
+            if (roll) {
+                if (roll3db_ok(a, f32)) return {K_ROLLOUT3DB, 0, 0};
+                if (E == 8 && !a.variant && every_row(a) && a.num_plans <= TB_MAX) return {K_ROLLOUT3D, 0, 0};
+                return tile;
             }
-            if (op == OP_ROLLOUT && E == 8 && !a.variant && (a.obs_mode == SNAC_OBS_ALL || a.obs_mode == SNAC_OBS_TILED) && a.num_plans <= TB_MAX && !pipeline_off()) { g_kernel = "k_rollout3d"; launch_roll3d(d, a, s); break; }
-            if (op == OP_TRANSITION && !pipeline_off() && step_stage_ok(a) && !a.variant && tune(TN_STEP3D_QUARTER) != 0 &&
-                a.n >= tune(TN_STEP3D_QUARTER_MIN) && a.n <= tune(TN_STEP3D_QUARTER_MAX)) { g_kernel = "k_step3dq"; launch_step3dq(d, a, s); break; }
-            if (op == OP_TRANSITION && !pipeline_off() && step_stage_ok(a) && (!a.variant || step_var3_ok(a))) {
-                const bool span = !a.variant && tune(TN_STEP3D_SPAN) != 0 && a.n >= tune(TN_STEP3D_SPAN_MIN);   // large batches of canonical rows
-                g_kernel = span ? "k_step3ds" : "k_step3d";
-                launch_step3d(d, a, span, s);
-                break;
-            }
-            if (op == OP_TRANSITION && !a.variant && !pipeline_off()) { g_kernel = "k_transition3d"; launch_trans3d(d, a, s); break; }
-            launch_tile3d(op, dyn, E, d->obs_dtype, a, s);
-            break;
+            if (step_stage_ok(a) && !a.variant && tune(TN_STEP3D_QUARTER) != 0 && a.n >= tune(TN_STEP3D_QUARTER_MIN) && a.n <= tune(TN_STEP3D_QUARTER_MAX))
+                return {K_STEP3DQ, 0, step3dq_form(a.n)};
+            if (step_stage_ok(a) && (!a.variant || step_var3_ok(a)))   // k_step3ds: large batches of canonical rows
+                return {!a.variant && tune(TN_STEP3D_SPAN) != 0 && a.n >= tune(TN_STEP3D_SPAN_MIN) ? K_STEP3DS : K_STEP3D, 0, 0};
+            if (a.variant) return tile;
+            return {edges_lds_ok(a) && tune(TN_EDGES3D) != 0 ? K_EDGES3D : K_TRANSITION3D, 0, 0};
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "kernel launch");
-    return SNAC_OK;
+}
+
+// the names behind snac_last_kernel(), in the order of enum Kernel
+const char* const NAME[] = {"k_rollout", "k_transition", "k_aux", "k_reset", "k_iou", "k_step1d", "k_step2d", "k_step3d", "k_step3ds", "k_step3dq", "k_edges1d", "k_edges2d",
+                            "k_edges3d", "k_transition2d", "k_transition3d", "k_rollout1dl", "k_rollout1dt", "k_rollout2d", "k_rollout2db", "k_rollout2dt", "k_rollout3d", "k_rollout3db"};
+static_assert(sizeof(NAME) / sizeof(NAME[0]) == K_COUNT, "one name per Kernel");
+
+int launch(Op op, const snac_env_desc* d, const KArgs& a, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const Choice c = choose(op, d, a);
+    g_kernel = NAME[c.kernel];
+    const bool aux = op == OP_AUX;                                   // the step kernels' forms without a step: masked resets and observe
+    switch (c.kernel) {
+        case K_ROLLOUT: case K_TRANSITION: case K_AUX:
+            (d->kind == SNAC_ENV_1D ? launch_tile1d : (d->kind == SNAC_ENV_2D ? launch_tile2d : launch_tile3d))(op, d->dynamic != 0, c.E, d->obs_dtype, a, s);
+            break;
+        case K_RESET: launch_reset(d, a, s); break;
+        case K_IOU: launch_iou(d, a, s); break;
+        case K_STEP1D: if (aux) launch_aux1d(d, a, s); else launch_step1d(d, a, c.form, s); break;
+        case K_STEP2D: if (aux) launch_aux2d(d, a, s); else launch_step2d(d, a, c.E, c.form, s); break;
+        case K_STEP3D: case K_STEP3DS: launch_step3d(d, a, c.kernel == K_STEP3DS, s); break;
+        case K_STEP3DQ: if (aux) launch_aux3d(d, a, s); else launch_step3dq(d, a, c.form, s); break;
+        case K_EDGES1D: launch_edges1d(d, a, s); break;
+        case K_EDGES2D: launch_edges2d(d, a, s); break;
+        case K_EDGES3D: launch_edges3d(d, a, s); break;
+        case K_TRANSITION2D: launch_trans2d(d, a, c.E, s); break;
+        case K_TRANSITION3D: launch_trans3d(d, a, s); break;
+        case K_ROLLOUT1DL: launch_roll1dl(d, a, c.form, s); break;
+        case K_ROLLOUT1DT: launch_roll1dt(d, a, c.E, s); break;
+        case K_ROLLOUT2D: launch_roll2d(d, a, s); break;
+        case K_ROLLOUT2DB: if (a.variant) launch_roll2dbv(d, a, c.E, s); else launch_roll2db(d, a, c.E, s); break;
+        case K_ROLLOUT2DT: launch_roll2dt(d, a, c.E, s); break;
+        case K_ROLLOUT3D: launch_roll3d(d, a, s); break;
+        case K_ROLLOUT3DB: if (a.variant) launch_roll3dbv(d, a, s); else launch_roll3db(d, a, s); break;
+        case K_COUNT: break;
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? SNAC_OK : fail_hip(e, "kernel launch");
 }
 
 }  // namespace snac_detail

@@ -1,8 +1,12 @@
 """Which kernel takes which call: snac_rollout (T = 4 ticks, rows into plain memory), snac_step, snac_reset (all envs / with a mask), snac_observe,
 snac_iou and snac_transition (a wave of N / 2 edges) for every kind, row type and layout over a ladder of batch sizes, as the library's dispatch table (snac_hip.hip KNOBS, environment overrides included) decides it on
-this box.  One line per (entry point, kind, rows): the batch sizes at which the kernel CHANGES.  Run it after touching a threshold:
+this box.  One line per (entry point, kind, rows): the batch sizes at which the kernel CHANGES.  A GPU tool: real calls on real batches,
+what snac_last_kernel() reports after each (profiles/r06_dispatch.txt).  The decision itself (snac_hip.hip choose(): kernel, size and
+form, over every threshold and knob override) is pinned without a GPU by tests/test_dispatch_host.py against
+tests/golden/dispatch_table.txt, which tests/native/dispatch_table.cpp prints in this tool's format; after touching a threshold,
+regenerate that golden (tests/golden/README.md) and run this for the view from outside:
 
-    gpurun -- python tools/dispatch_table.py > gpurun_out/dispatch.txt        (copied to profiles/r06_dispatch.txt)
+    python tools/dispatch_table.py > dispatch.txt
 """
 import os
 import sys
