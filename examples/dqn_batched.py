@@ -4,11 +4,15 @@ are appended with ReplayRing.append), minibatches come from snac_replay_gather. 
 reference's 2D dynamic DQN (script/DQN/2d/DQN_2d_dynamic.py: observation 51 + plan 400 -> 5 Q values, target network,
 replace every `replace` steps); this file is an illustration of the API, not part of the parity surface.
 
-    python examples/dqn_batched.py --envs 4096 --ticks 200 [--prioritized]
+    python examples/dqn_batched.py --envs 4096 --ticks 200 [--prioritized] [--n-step N]
 
 --prioritized: prioritised replay as in the reference's script/Rainbow, with the sum tree on the device (ReplayRing(prioritized=True)):
 minibatches are drawn in proportion to |td|, the loss is weighted by the importance weights, and the sampled transitions get their new
 priorities after every step.
+
+--n-step N: Rainbow's multi-step target (ReplayRing.sample(n_step=N, gamma=gamma), one gather launch): the minibatch carries the discounted
+sum of up to N rewards, the row N steps on (or where the episode or the ring ended) and the discount that goes with it, and the target is
+return + discount * max Q(s_next).  It works together with --prioritized.
 """
 import argparse
 import os
@@ -33,7 +37,7 @@ class QNet(nn.Module):
         return self.body(torch.cat([obs, plan.flatten(1)], dim=1))
 
 
-def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4):
+def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None):
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev = env.device
@@ -55,10 +59,16 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
         ring.append(actions)                                       # one env tick, recorded in the ring (auto-reset)
         obs = env.observe()
         plan = env.input_plan().float()                            # resets change plans
-        mb = ring.sample(batch, **(dict(prioritized=True, beta=beta) if prioritized else {}))
+        how = dict(prioritized=True, beta=beta) if prioritized else {}
+        if n_step is not None:
+            how.update(n_step=n_step, gamma=gamma)
+        mb = ring.sample(batch, **how)
         with torch.no_grad():
             q_next = target(mb["s_next"], mb["plan"]).max(dim=1).values
-            y = mb["reward"] + gamma * q_next * (~mb["done"]).float()
+            if n_step is None:
+                y = mb["reward"] + gamma * q_next * (~mb["done"]).float()
+            else:                                                  # the plan does not change inside an episode: step 0's serves s_next
+                y = mb["return"] + mb["discount"] * q_next
         q = net(mb["s"], mb["plan"]).gather(1, mb["action"][:, None]).squeeze(1)
         if prioritized:
             td = q - y
@@ -86,5 +96,6 @@ if __name__ == "__main__":
     ap.add_argument("--ticks", type=int, default=200)
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample in proportion to |td|")
+    ap.add_argument("--n-step", type=int, default=None, help="multi-step targets: the discounted sum of up to N rewards, bootstrapped N steps on")
     a = ap.parse_args()
-    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized)
+    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step)

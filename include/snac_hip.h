@@ -357,6 +357,47 @@ int snac_replay_gather_tiled(const snac_env_desc* desc, const snac_state* st, in
                              const int32_t* env_idx, int32_t batch, float* s_out, float* s_next_out, float* plan_out,
                              void* stream);
 
+/* n-step transitions and episode windows: walks along one env's column of the ring from a sample (t, i), bounded by the episode flags
+ * and by the ring's ends, one launch each.  first_ring / done_ring (uint8), reward_ring (float32), action_ring (int8) and plan_idx_ring
+ * are the [cap][N] arrays snac_rollout_rec fills; obs_ring is [cap][N][obs_dim], or with tiled != 0 the tile-major ring of
+ * snac_replay_gather_tiled.  slot(k) = (t + k) mod cap.  "The tuple of a step" is snac_replay_gather's: s' is the step's own row, s the
+ * previous slot's row or the reset observation when first is set; the same row lengths are supported (the base row plus the position
+ * tail, else SNAC_ERR_UNSUPPORTED), outputs are float32, indices are clamped into range, plan_out may be NULL (2D / 3D: 16-byte aligned).
+ * action_out is int64 and done_out / mask_out are bytes 0 / 1.  Every argument is checked before any HIP call (cap >= 2, batch >= 0, n / L
+ * in [1, 64], newest / oldest in [0, cap), gamma finite, no null array); batch == 0 returns SNAC_OK without a launch.  No host
+ * synchronisation.
+ *
+ * snac_replay_gather_nstep (Rainbow's multi-step memory): newest = (head - 1) mod cap, the slot written last.  Take steps k = 0, 1, ...
+ * and stop after step k when  done_ring[slot(k)] != 0,  or k + 1 == n,  or slot(k) == newest,  or first_ring[slot(k + 1)] != 0 (an
+ * episode that ended without done, e.g. a ring attached after a reset).  m = k + 1 steps were taken, 1 <= m <= n.  Per sample:
+ *   s_out, action_out   those of step 0                          s_next_out   the row of step m - 1
+ *   done_out            done_ring[slot(m - 1)] != 0              steps_out    m
+ *   return_out          g = 0.0 (double); for k = m - 1 down to 0: g = (double)reward_ring[slot(k)] + gamma * g, product and sum each
+ *                       rounded (no fused multiply-add); then (float)g
+ *   discount_out        d = 1.0 (double); m times d = d * gamma; (float)d, or 0.0f when done_out
+ *   plan_out            the plan row at step 0
+ * The caller's target is return + discount * max_a Q(s_next).  With n = 1 every output is snac_replay_gather's tuple of (t, i), with
+ * return == reward and discount == (float)gamma or 0.
+ *
+ * snac_replay_gather_windows (DRQN's Memory.get_batch): the window ENDS at (t, i).  oldest = (head - valid_ticks) mod cap, the oldest
+ * addressable transition (its predecessor row is still in the ring).  Start with len = 1 and extend to the earlier step while
+ * len < L,  the window's earliest step is not at oldest,  the earliest step has first == 0  and the step before it has done == 0.
+ * Outputs are [batch][L][..]: position j < len holds the tuple of step (t - len + 1 + j) mod cap -- s_out, s_next_out, action_out,
+ * reward_out, done_out -- and positions j >= len are zero in every output; mask_out[b][j] = j < len, length_out[b] = len (int32).  Valid
+ * steps come first, so a recurrent net starts from its zero state at the window's real start.  plan_out [batch][400 | 30]: the plan row at
+ * the window's last step.  The len + 1 distinct rows of a window are read once each (consecutive tuples chain: s[j + 1] == s_next[j]).
+ * With L = 1 this is snac_replay_gather's tuple again. */
+int snac_replay_gather_nstep(const snac_env_desc* desc, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring,
+                             const uint8_t* first_ring, const uint8_t* done_ring, const float* reward_ring, const int8_t* action_ring,
+                             const int16_t* plan_idx_ring, int32_t newest, const int32_t* tick_idx, const int32_t* env_idx, int32_t batch,
+                             int32_t n, double gamma, float* s_out, float* s_next_out, float* plan_out, int64_t* action_out,
+                             float* return_out, float* discount_out, uint8_t* done_out, int32_t* steps_out, void* stream);
+int snac_replay_gather_windows(const snac_env_desc* desc, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring,
+                               const uint8_t* first_ring, const uint8_t* done_ring, const float* reward_ring, const int8_t* action_ring,
+                               const int16_t* plan_idx_ring, int32_t oldest, const int32_t* tick_idx, const int32_t* env_idx, int32_t batch,
+                               int32_t L, float* s_out, float* s_next_out, float* plan_out, int64_t* action_out, float* reward_out,
+                               uint8_t* done_out, uint8_t* mask_out, int32_t* length_out, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

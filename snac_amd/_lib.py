@@ -36,7 +36,8 @@ EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", 
            "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds",
            "snac_uct_select_gumbel", "snac_uct_gumbel_candidates", "snac_uct_set_priors_value", "snac_uct_select_gumbel_interior",
            "snac_uct_improved_policy", "snac_uct_save_roots", "snac_uct_load_roots", "snac_uct_store_targets", "snac_uct_returns_nstep",
-           "snac_prio_layout", "snac_prio_init", "snac_prio_update", "snac_prio_fill", "snac_prio_sample", "snac_episodic_sums")
+           "snac_prio_layout", "snac_prio_init", "snac_prio_update", "snac_prio_fill", "snac_prio_sample", "snac_episodic_sums",
+           "snac_replay_gather_nstep", "snac_replay_gather_windows")
 
 
 class Sizes(C.Structure):
@@ -130,6 +131,9 @@ def lib():
                                        C.POINTER(RolloutRecord), vp]
         L.snac_replay_gather.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
         L.snac_replay_gather_tiled.argtypes = L.snac_replay_gather.argtypes
+        walk = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32]
+        L.snac_replay_gather_nstep.argtypes = walk + [C.c_double] + [vp] * 9     # desc .. batch, n; gamma; eight outputs, the stream
+        L.snac_replay_gather_windows.argtypes = walk + [vp] * 9                  # desc .. batch, L; eight outputs, the stream
         L.snac_rollout_tiled.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_uint32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp,
                                          C.POINTER(RolloutRecord), vp]
         L.snac_make_plans.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, vp, vp, vp]

@@ -1,5 +1,6 @@
 // k_misc.hip -- environment_memory export, state import, observation equality, plan generators, replay gather, the episodic sums: kernels and entry points
 #include "snac_dev.h"
+#include "replay_dev.h"
 
 using namespace snac_detail;
 
@@ -303,7 +304,7 @@ template <int KIND, typename OT>
 __global__ __launch_bounds__(256) void k_gather(const GArgs g) {
     // S samples per wave: the index loads of all of them first (lane u = sample u), then every row load of the group in flight
     // before the first store -- one sample per wave was a chain of three dependent loads with a single row in flight.
-    constexpr int D = KIND == 1 ? 7 : 51, W = KIND == 1 ? 5 : 49, PC = KIND == 1 ? 30 : 400, S = 4;
+    constexpr int PC = KIND == 1 ? 30 : 400, S = 4;
     const int lane = threadIdx.x & 63;
     const int b0 = ((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * S;
     if (b0 >= g.batch) return;
@@ -326,8 +327,7 @@ __global__ __launch_bounds__(256) void k_gather(const GArgs g) {
         const int tu = __builtin_amdgcn_readlane(t, u), iu = __builtin_amdgcn_readlane(i, u);
         fst[u] = __builtin_amdgcn_readlane(first, u);
         const int tp = tu == 0 ? g.cap - 1 : tu - 1;
-        const size_t ocur = g.tiled ? ((size_t)(iu >> 6) * g.cap + tu) * 64 + (iu & 63) : (size_t)tu * g.n + iu;
-        const size_t oprev = g.tiled ? ((size_t)(iu >> 6) * g.cap + tp) * 64 + (iu & 63) : (size_t)tp * g.n + iu;
+        const size_t ocur = ring_row(g.tiled, g.cap, g.n, tu, iu), oprev = ring_row(g.tiled, g.cap, g.n, tp, iu);
         vcur[u] = (OT)0; vprev[u] = (OT)0;
         if (u < ns && lane < LD) {
             vcur[u] = o[ocur * LD + lane];
@@ -339,15 +339,7 @@ __global__ __launch_bounds__(256) void k_gather(const GArgs g) {
         if (u < ns && lane < LD) {
             const size_t b = (size_t)(b0 + u);
             g.s_next[b * LD + lane] = (float)vcur[u];
-            float sv;
-            if (fst[u]) {   // reset observation: window at the start position over an empty grid, both scalar slots 0
-                const int wi = lane / 7, wj = lane - 7 * wi;
-                const bool frame = KIND == 1 ? lane < 2 : (wi < 3 || wj < 3);
-                sv = (lane < W && frame) ? (float)g.frame_val : 0.0f;
-                if (lane >= D) sv = KIND == 1 ? 2.0f : 3.0f;         // position tail: the start position
-            } else {
-                sv = (float)vprev[u];
-            }
+            const float sv = fst[u] ? reset_obs<KIND>(lane, g.frame_val) : (float)vprev[u];
             g.s[b * LD + lane] = sv;
         }
     }
@@ -356,25 +348,7 @@ __global__ __launch_bounds__(256) void k_gather(const GArgs g) {
         for (int u = 0; u < S; ++u) {
             if (u >= ns) break;
             const int pu = __builtin_amdgcn_readlane(p, u);
-            float* po = g.plan_out + (size_t)(b0 + u) * PC;
-            if (KIND == 1) {
-                if (lane < PC) po[lane] = (float)((const int16_t*)g.plans)[pu * 32 + lane];
-            } else {
-                // four consecutive cells per lane (a row of 20 holds five such groups): one 16-byte store each, 100 lanes a plan
-                for (int q = lane; q < PC / 4; q += 64) {
-                    const int c = q * 4;
-                    float4 v;
-                    if (KIND == 2) {
-                        const int row = c / 20, col = c - row * 20;
-                        const uint32_t w = ((const uint32_t*)g.plans)[pu * 20 + row] >> col;
-                        v = make_float4((float)(w & 1u), (float)((w >> 1) & 1u), (float)((w >> 2) & 1u), (float)((w >> 3) & 1u));
-                    } else {
-                        const short4 h = *(const short4*)((const int16_t*)g.plans + (size_t)pu * 400 + c);
-                        v = make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
-                    }
-                    *(float4*)(po + c) = v;
-                }
-            }
+            expand_plan<KIND>(g.plans, pu, g.plan_out + (size_t)(b0 + u) * PC, lane);
         }
     }
 }

@@ -1,0 +1,335 @@
+// k_replay.hip -- walks along one env's column of the replay ring: snac_replay_gather_nstep (Rainbow's multi-step transition: s, the
+// discounted sum of up to n rewards, the row to bootstrap from) and snac_replay_gather_windows (DRQN's Memory.get_batch: up to L
+// consecutive tuples of one episode that end at the sample).  include/snac_hip.h, "n-step transitions and episode windows", has the
+// rules; the tuple of a step, the reset observation and the plan expansion are k_gather's (replay_dev.h).
+#include <cmath>
+#include <cstddef>
+
+#include "snac_dev.h"
+#include "replay_dev.h"
+
+// Both kernels have k_gather's shape: 4 waves a block, S samples a wave, and three rounds of loads that each go out for the whole group
+// before anything waits on them -- the samples' indices (lane u = sample u), the flags along the walk (lane k = step k of the walk; one
+// ballot turns them into the walk's length), then the rows -- and only then the stores.
+namespace {
+
+using namespace snac_detail;
+
+constexpr int S = 4;                                                 // samples per wave
+
+struct RArgs {
+    int32_t n, cap, batch, num_plans;
+    int32_t ld, frame_val, tiled;                                    // as k_gather's
+    int32_t end;                                                     // n-step: the newest slot; windows: the oldest addressable slot
+    int32_t steps;                                                   // n, or L
+    double gamma;
+    const void* obs;
+    const uint8_t* first;
+    const uint8_t* done;
+    const float* reward;
+    const int8_t* action;
+    const int16_t* plan_idx;
+    const int32_t* tick;
+    const int32_t* env;
+    const void* plans;
+    float* s;
+    float* s_next;
+    float* plan_out;
+    int64_t* action_out;
+    float* reward_out;                                               // n-step: the return
+    float* discount_out;
+    uint8_t* done_out;
+    uint8_t* mask_out;
+    int32_t* steps_out;                                              // n-step: m; windows: len
+};
+
+template <int KIND, typename OT>
+__global__ __launch_bounds__(256) void k_gather_nstep(const RArgs g) {
+    constexpr int PC = KIND == 1 ? 30 : 400;
+    const int lane = threadIdx.x & 63;
+    const int b0 = ((int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * S;   // in scalar registers: the group's control flow is uniform
+    if (b0 >= g.batch) return;
+    const int ns = min(S, g.batch - b0);
+    const int LD = g.ld;
+    const OT* o = (const OT*)g.obs;
+    // lane u < ns: the sample's slot and env, and what step 0 gives: its first flag, action and plan row
+    int t = 0, i = 0, first = 0, act = 0, p = 0;
+    if (lane < ns) {
+        t = min(max(g.tick[b0 + lane], 0), g.cap - 1);
+        i = min(max(g.env[b0 + lane], 0), g.n - 1);
+        const size_t cur = (size_t)t * g.n + i;
+        first = g.first[cur] != 0;
+        act = g.action[cur];
+        if (g.plan_out) p = min(max((int)g.plan_idx[cur], 0), g.num_plans - 1);
+    }
+    // lane k < n: step k of each sample's walk.  The loads of the whole group stand in one block, before anything reads them (a sample
+    // past the batch's end walks from (0, 0): valid addresses, results unused)
+    int tu[S], iu[S], sk[S], dnr[S], fnr[S];
+    float rw[S];
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        tu[u] = __builtin_amdgcn_readlane(t, u); iu[u] = __builtin_amdgcn_readlane(i, u);
+        sk[u] = (tu[u] + lane) % g.cap;
+        dnr[u] = 0; fnr[u] = 0; rw[u] = 0.0f;
+    }
+    if (lane < g.steps) {
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            const size_t at = (size_t)sk[u] * g.n + iu[u];
+            dnr[u] = g.done[at];
+            rw[u] = g.reward[at];
+        }
+    }
+    if (lane + 1 < g.steps) {                                        // step n - 1 stops whatever follows it: one scattered read less
+#pragma unroll
+        for (int u = 0; u < S; ++u) fnr[u] = g.first[(size_t)(sk[u] + 1 == g.cap ? 0 : sk[u] + 1) * g.n + iu[u]];
+    }
+    int dn[S], stop[S];
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        dn[u] = dnr[u] != 0;
+        stop[u] = lane < g.steps && (dn[u] | (lane + 1 == g.steps) | (sk[u] == g.end) | (fnr[u] != 0));
+    }
+    // one ballot a sample gives m; then the two rows of every sample: the last step's own and step 0's predecessor.  All row loads are
+    // unconditional and stand in one block, so that none waits for a branch: a lane past the row's end reads its last value again, and
+    // the predecessor is read (not stored) also where step 0 opened an episode
+    int m[S], fst[S];
+    OT vcur[S], vprev[S];
+    const int ll = min(lane, LD - 1);
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        m[u] = u < ns ? __ffsll((unsigned long long)__ballot(stop[u])) : 0;   // lane n - 1 stops: never 0 for a sample
+        fst[u] = __builtin_amdgcn_readlane(first, u);
+        const int tl = (tu[u] + max(m[u] - 1, 0)) % g.cap, tp = tu[u] == 0 ? g.cap - 1 : tu[u] - 1;
+        vcur[u] = o[ring_row(g.tiled, g.cap, g.n, tl, iu[u]) * LD + ll];
+        vprev[u] = o[ring_row(g.tiled, g.cap, g.n, tp, iu[u]) * LD + ll];
+    }
+    // the two recurrences, while the rows are on their way: every lane runs them on the same values (the rewards come by readlane), and
+    // lane u keeps the scalars of sample u
+    float ret = 0.0f, disc = 0.0f;
+    int dlast = 0, taken = 0;
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        double sum = 0.0, d = 1.0;
+        {
+#pragma clang fp contract(off)                                      // no fma: product and sum each rounded, in the header's order
+            for (int k = m[u] - 1; k >= 0; --k) {
+                const double r = (double)__int_as_float(__builtin_amdgcn_readlane(__float_as_int(rw[u]), k));
+                const double tt = g.gamma * sum;
+                sum = r + tt;
+            }
+            for (int k = 0; k < m[u]; ++k) d = d * g.gamma;
+        }
+        const int dl = __builtin_amdgcn_readlane(dn[u], max(m[u] - 1, 0));
+        if (lane == u) { ret = (float)sum; disc = dl ? 0.0f : (float)d; dlast = dl; taken = m[u]; }
+    }
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        if (u < ns && lane < LD) {
+            const size_t b = (size_t)(b0 + u);
+            g.s_next[b * LD + lane] = (float)vcur[u];
+            g.s[b * LD + lane] = fst[u] ? reset_obs<KIND>(lane, g.frame_val) : (float)vprev[u];
+        }
+    }
+    if (lane < ns) {
+        g.action_out[b0 + lane] = (int64_t)act;
+        g.reward_out[b0 + lane] = ret;
+        g.discount_out[b0 + lane] = disc;
+        g.done_out[b0 + lane] = (uint8_t)dlast;
+        g.steps_out[b0 + lane] = taken;
+    }
+    if (g.plan_out) {
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            if (u >= ns) break;
+            expand_plan<KIND>(g.plans, __builtin_amdgcn_readlane(p, u), g.plan_out + (size_t)(b0 + u) * PC, lane);
+        }
+    }
+}
+
+template <int KIND, typename OT>
+__global__ __launch_bounds__(256) void k_gather_windows(const RArgs g) {
+    constexpr int PC = KIND == 1 ? 30 : 400, RU = 4;                 // rows per sample and round
+    const int lane = threadIdx.x & 63;
+    const int b0 = ((int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * S;   // in scalar registers: the group's control flow is uniform
+    if (b0 >= g.batch) return;
+    const int ns = min(S, g.batch - b0);
+    const int LD = g.ld, L = g.steps;
+    const OT* o = (const OT*)g.obs;
+    int t = 0, i = 0, p = 0;
+    if (lane < ns) {
+        t = min(max(g.tick[b0 + lane], 0), g.cap - 1);
+        i = min(max(g.env[b0 + lane], 0), g.n - 1);
+        if (g.plan_out) p = min(max((int)g.plan_idx[(size_t)t * g.n + i], 0), g.num_plans - 1);
+    }
+    // lane j < L: the step j before the window's end -- the window's earliest step when its length is j + 1.  The loads of the whole group
+    // stand in one block, before anything reads them (a sample past the batch's end walks from (0, 0): valid addresses, results unused)
+    int tu[S], iu[S], es[S], act[S], dnr[S], fr[S], dpr[S];
+    float rw[S];
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        tu[u] = __builtin_amdgcn_readlane(t, u); iu[u] = __builtin_amdgcn_readlane(i, u);
+        es[u] = ((tu[u] - lane) % g.cap + g.cap) % g.cap;
+        act[u] = 0; dnr[u] = 0; fr[u] = 0; dpr[u] = 0; rw[u] = 0.0f;
+    }
+    if (lane < L) {
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            const size_t at = (size_t)es[u] * g.n + iu[u];
+            fr[u] = g.first[at];
+            dnr[u] = g.done[at];
+            act[u] = g.action[at];
+            rw[u] = g.reward[at];
+            dpr[u] = g.done[(size_t)(es[u] == 0 ? g.cap - 1 : es[u] - 1) * g.n + iu[u]];
+        }
+    }
+    int dn[S], f[S], stop[S];
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        dn[u] = dnr[u] != 0; f[u] = fr[u] != 0;
+        stop[u] = lane < L && ((lane + 1 == L) | (es[u] == g.end) | f[u] | (dpr[u] != 0));
+    }
+    // one ballot a sample: its length.  Its len + 1 distinct rows are the rows of steps t - len .. t: row r is s of position r and s_next
+    // of position r - 1; row 0 is the reset observation instead when the earliest step opened an episode
+    int len[S], fst[S], start[S];
+    int longest = 0;
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        len[u] = u < ns ? __ffsll((unsigned long long)__ballot(stop[u])) : 0;   // lane L - 1 stops: never 0 for a sample
+        fst[u] = __builtin_amdgcn_readlane(f[u], max(len[u] - 1, 0));
+        start[u] = ((tu[u] - len[u]) % g.cap + g.cap) % g.cap;
+        longest = max(longest, len[u]);
+    }
+    // RU rows of each sample a round: S * RU row loads in flight before the round's first store
+    for (int r0 = 0; r0 <= longest; r0 += RU) {
+        // every load of the round unconditional, in one block: a row past the window's last is its last again and a lane past the row's end
+        // its last value again (the same lines; nothing of them is stored), so that no load waits for a branch
+        OT v[S][RU];
+        const int ll = min(lane, LD - 1);
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+#pragma unroll
+            for (int x = 0; x < RU; ++x)
+                v[u][x] = o[ring_row(g.tiled, g.cap, g.n, (start[u] + min(r0 + x, len[u])) % g.cap, iu[u]) * LD + ll];
+        }
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+#pragma unroll
+            for (int x = 0; x < RU; ++x) {
+                const int r = r0 + x;
+                if (u < ns && r <= len[u] && lane < LD) {
+                    const size_t b = (size_t)(b0 + u) * L;
+                    const float val = r == 0 && fst[u] ? reset_obs<KIND>(lane, g.frame_val) : (float)v[u][x];
+                    if (r < len[u]) g.s[(b + r) * LD + lane] = val;
+                    if (r >= 1) g.s_next[(b + r - 1) * LD + lane] = val;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        if (u >= ns) break;
+        const size_t b = (size_t)(b0 + u) * L;
+        // positions >= len: zero rows, as one run
+        const size_t z0 = (b + len[u]) * LD;
+        const int zn = (L - len[u]) * LD;
+        for (int x = lane; x < zn; x += 64) { g.s[z0 + x] = 0.0f; g.s_next[z0 + x] = 0.0f; }
+        if (lane < L) {                                              // lane j < len holds position len - 1 - j; lane j >= len zeroes position j
+            const bool in = lane < len[u];
+            const size_t at = b + (in ? len[u] - 1 - lane : lane);
+            g.action_out[at] = in ? (int64_t)act[u] : 0;
+            g.reward_out[at] = in ? rw[u] : 0.0f;
+            g.done_out[at] = in ? (uint8_t)dn[u] : (uint8_t)0;
+            g.mask_out[b + lane] = in ? 1 : 0;
+        }
+        if (lane == 0) g.steps_out[b0 + u] = len[u];
+        if (g.plan_out) expand_plan<KIND>(g.plans, __builtin_amdgcn_readlane(p, u), g.plan_out + (size_t)(b0 + u) * PC, lane);
+    }
+}
+
+// the checks both entry points share, every one before any HIP call; steps: n or L, end: newest or oldest
+int walk_check(const snac_env_desc* d, const snac_state* st, int32_t cap, const void* obs_ring, const uint8_t* first_ring, const uint8_t* done_ring,
+               const float* reward_ring, const int8_t* action_ring, const int16_t* plan_idx_ring, int32_t end, const char* end_msg,
+               const int32_t* tick_idx, const int32_t* env_idx, int32_t batch, int32_t steps, const char* steps_msg, const float* plan_out) {
+    if (int rc = check_common(d, st)) return rc;
+    if (cap < 2 || batch < 0) return fail(SNAC_ERR_ARG, "cap must be >= 2 and batch >= 0");
+    if (steps < 1 || steps > 64) return fail(SNAC_ERR_ARG, steps_msg);
+    if (end < 0 || end >= cap) return fail(SNAC_ERR_ARG, end_msg);
+    if (!obs_ring || !first_ring || !done_ring || !reward_ring || !action_ring) return fail(SNAC_ERR_ARG, "null ring array");
+    if (!tick_idx || !env_idx) return fail(SNAC_ERR_ARG, "null index array");
+    if (plan_out && !plan_idx_ring) return fail(SNAC_ERR_ARG, "plan_out needs plan_idx_ring");
+    if (plan_out && d->kind != SNAC_ENV_1D && ((uintptr_t)plan_out & 15)) return fail(SNAC_ERR_ARG, "plan_out must be 16-byte aligned");
+    if (d->obs_tail & ~SNAC_TAIL_POSITION) return fail(SNAC_ERR_UNSUPPORTED, "replay gather supports the position tail only");
+    return SNAC_OK;
+}
+
+RArgs walk_args(const snac_env_desc* d, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring, const uint8_t* first_ring,
+                const uint8_t* done_ring, const float* reward_ring, const int8_t* action_ring, const int16_t* plan_idx_ring, int32_t end,
+                const int32_t* tick_idx, const int32_t* env_idx, int32_t batch, int32_t steps) {
+    RArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.n = d->num_envs; g.cap = cap; g.batch = batch; g.num_plans = d->num_plans;
+    g.ld = base_obs_dim(d->kind) + tail_len(d->kind, d->obs_tail); g.frame_val = d->frame_value == 2 ? 2 : -1; g.tiled = tiled != 0;
+    g.end = end; g.steps = steps;
+    g.obs = obs_ring; g.first = first_ring; g.done = done_ring; g.reward = reward_ring; g.action = action_ring; g.plan_idx = plan_idx_ring;
+    g.tick = tick_idx; g.env = env_idx; g.plans = st->plans;
+    return g;
+}
+
+template <typename F>
+void by_kind(const snac_env_desc* d, F f) {                          // the six (kind, row type) instantiations
+    const bool f32 = d->obs_dtype == SNAC_OBS_F32;
+    if (d->kind == SNAC_ENV_1D) { if (f32) f(std::integral_constant<int, 1>(), float()); else f(std::integral_constant<int, 1>(), double()); }
+    else if (d->kind == SNAC_ENV_2D) { if (f32) f(std::integral_constant<int, 2>(), float()); else f(std::integral_constant<int, 2>(), double()); }
+    else { if (f32) f(std::integral_constant<int, 3>(), float()); else f(std::integral_constant<int, 3>(), double()); }
+}
+
+}  // namespace
+
+extern "C" {
+
+int snac_replay_gather_nstep(const snac_env_desc* d, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring,
+                             const uint8_t* first_ring, const uint8_t* done_ring, const float* reward_ring, const int8_t* action_ring,
+                             const int16_t* plan_idx_ring, int32_t newest, const int32_t* tick_idx, const int32_t* env_idx, int32_t batch,
+                             int32_t n, double gamma, float* s_out, float* s_next_out, float* plan_out, int64_t* action_out,
+                             float* return_out, float* discount_out, uint8_t* done_out, int32_t* steps_out, void* stream) {
+    if (int rc = walk_check(d, st, cap, obs_ring, first_ring, done_ring, reward_ring, action_ring, plan_idx_ring, newest,
+                            "newest must be in [0, cap)", tick_idx, env_idx, batch, n, "n must be in [1, 64]", plan_out))
+        return rc;
+    if (!std::isfinite(gamma)) return fail(SNAC_ERR_ARG, "gamma must be finite");
+    if (!s_out || !s_next_out || !action_out || !return_out || !discount_out || !done_out || !steps_out) return fail(SNAC_ERR_ARG, "null output");
+    if (batch == 0) return SNAC_OK;                                  // no sample: no launch
+    RArgs g = walk_args(d, st, cap, tiled, obs_ring, first_ring, done_ring, reward_ring, action_ring, plan_idx_ring, newest, tick_idx, env_idx, batch, n);
+    g.gamma = gamma;
+    g.s = s_out; g.s_next = s_next_out; g.plan_out = plan_out; g.action_out = action_out; g.reward_out = return_out;
+    g.discount_out = discount_out; g.done_out = done_out; g.steps_out = steps_out;
+    const dim3 grid((unsigned)((batch + 4 * S - 1) / (4 * S))), block(256);
+    g_kernel = "k_gather_nstep";
+    by_kind(d, [&](auto kind, auto ot) {
+        hipLaunchKernelGGL((k_gather_nstep<decltype(kind)::value, decltype(ot)>), grid, block, 0, (hipStream_t)stream, g);
+    });
+    return launched("snac_replay_gather_nstep");
+}
+
+int snac_replay_gather_windows(const snac_env_desc* d, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring,
+                               const uint8_t* first_ring, const uint8_t* done_ring, const float* reward_ring, const int8_t* action_ring,
+                               const int16_t* plan_idx_ring, int32_t oldest, const int32_t* tick_idx, const int32_t* env_idx, int32_t batch,
+                               int32_t L, float* s_out, float* s_next_out, float* plan_out, int64_t* action_out, float* reward_out,
+                               uint8_t* done_out, uint8_t* mask_out, int32_t* length_out, void* stream) {
+    if (int rc = walk_check(d, st, cap, obs_ring, first_ring, done_ring, reward_ring, action_ring, plan_idx_ring, oldest,
+                            "oldest must be in [0, cap)", tick_idx, env_idx, batch, L, "L must be in [1, 64]", plan_out))
+        return rc;
+    if (!s_out || !s_next_out || !action_out || !reward_out || !done_out || !mask_out || !length_out) return fail(SNAC_ERR_ARG, "null output");
+    if (batch == 0) return SNAC_OK;                                  // no window: no launch
+    RArgs g = walk_args(d, st, cap, tiled, obs_ring, first_ring, done_ring, reward_ring, action_ring, plan_idx_ring, oldest, tick_idx, env_idx, batch, L);
+    g.s = s_out; g.s_next = s_next_out; g.plan_out = plan_out; g.action_out = action_out; g.reward_out = reward_out;
+    g.done_out = done_out; g.mask_out = mask_out; g.steps_out = length_out;
+    const dim3 grid((unsigned)((batch + 4 * S - 1) / (4 * S))), block(256);
+    g_kernel = "k_gather_windows";
+    by_kind(d, [&](auto kind, auto ot) {
+        hipLaunchKernelGGL((k_gather_windows<decltype(kind)::value, decltype(ot)>), grid, block, 0, (hipStream_t)stream, g);
+    });
+    return launched("snac_replay_gather_windows");
+}
+
+}  // extern "C"

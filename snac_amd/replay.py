@@ -15,8 +15,15 @@ PriorityTree (snac_amd/priority.py; include/snac_hip.h, "Prioritised replay") ov
 collect() gives every transition it writes the largest priority seen so far; sample(batch, prioritized=True, beta=...) draws in
 proportion to the priorities and adds slot, env, index, prob and the importance weights `weight`; update_priorities(index, |td|)
 stores new ones.
+
+Walks along an env's column (include/snac_hip.h, "n-step transitions and episode windows"): gather_nstep() / sample(n_step=, gamma=)
+give Rainbow's multi-step transition (s, the discounted sum of up to n rewards, the row to bootstrap from and its discount), cut at the
+episode's end and at the newest slot; gather_windows() / sample_windows() give DRQN's windows of up to L consecutive tuples of one
+episode that END at the drawn transition, valid steps first, with a mask.  One launch each, no torch index kernel, no host
+synchronisation.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -25,6 +32,19 @@ from . import _lib
 
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _walk_steps(name, v):
+    """n of an n-step transition / L of a window: an integer in [1, 64] (a wave's lanes hold the steps of a walk)"""
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 64:
+        raise ValueError("%s must be an integer in [1, 64]" % name)
+    return v
+
+
+def _walk_gamma(gamma):
+    if gamma is None or isinstance(gamma, bool) or not isinstance(gamma, (int, float)) or not math.isfinite(gamma):
+        raise ValueError("n_step needs gamma: a finite number")
+    return float(gamma)
 
 
 class ReplayRing:
@@ -187,12 +207,70 @@ class ReplayRing:
             out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
         return out
 
-    def sample(self, batch, generator=None, with_plan=True, prioritized=False, beta=0.4, stratified=True):
-        """Uniform minibatch over the addressable transitions (random.sample in the reference, :144).  prioritized=True (a
-        ReplayRing(prioritized=True); generator None): the transitions are drawn from the priority tree, with replacement, stratified
-        over the total unless stratified=False, and the gather() dict gains slot, env and index = slot * N + env (int64 [n]; what
-        update_priorities() takes), prob float32 [n] and the importance weights weight = (len(self) * prob) ** -beta / their largest
-        over the batch (beta = 0: all ones)."""
+    def _walk_call(self, fn, slot, env_index, end, steps, gamma, outs):
+        """The arguments the two walking entry points share, up to the outputs."""
+        e = self.env
+        head = (C.byref(e._desc), C.byref(e._state), self.cap, int(self.tiled), _ptr(self.obs), _ptr(self.first), _ptr(self.done),
+                _ptr(self.reward), _ptr(self.action), _ptr(self.plan_idx), end, _ptr(slot), _ptr(env_index), int(slot.numel()), steps)
+        with torch.cuda.device(e.device):
+            _lib.check(fn(*head, *gamma, *[_ptr(o) for o in outs], e._stream()))
+
+    def gather_nstep(self, slot, env_index, n, gamma, with_plan=True):
+        """n-step transitions from explicit (slot, env) pairs (Rainbow's multi-step memory): the walk starts at the pair's step and ends
+        after n steps, at a done, at an episode's end without one, or at the newest slot, whichever comes first.  -> the gather() dict
+        with `return` float32 [B] in the place of `reward` (the discounted sum of the rewards taken, in float64), and discount float32
+        [B] (gamma ** steps, 0 where done), steps int32 [B]; s and action are step 0's, s_next and done the last step's.  The target is
+        out["return"] + out["discount"] * max_a Q(out["s_next"]).  One launch; n = 1 is gather()."""
+        n, gamma = _walk_steps("n", n), _walk_gamma(gamma)
+        e = self.env
+        slot = torch.as_tensor(slot, device=e.device).to(torch.int32).contiguous()
+        env_index = torch.as_tensor(env_index, device=e.device).to(torch.int32).contiguous()
+        B = int(slot.numel())
+        s = torch.empty((B, e.obs_dim), dtype=torch.float32, device=e.device)
+        s_next = torch.empty((B, e.obs_dim), dtype=torch.float32, device=e.device)
+        plan = torch.empty((B, self.plan_cells), dtype=torch.float32, device=e.device) if with_plan else None
+        action = torch.empty((B,), dtype=torch.int64, device=e.device)
+        ret = torch.empty((B,), dtype=torch.float32, device=e.device)
+        discount = torch.empty((B,), dtype=torch.float32, device=e.device)
+        done = torch.empty((B,), dtype=torch.bool, device=e.device)
+        steps = torch.empty((B,), dtype=torch.int32, device=e.device)
+        self._walk_call(e._lib.snac_replay_gather_nstep, slot, env_index, (self.head - 1) % self.cap, n, (gamma,),
+                        (s, s_next, plan, action, ret, discount, done, steps))
+        out = dict(s=s, s_next=s_next, action=action, done=done, discount=discount, steps=steps)
+        out["return"] = ret
+        if with_plan:
+            out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
+        return out
+
+    def gather_windows(self, slot, env_index, length, with_plan=True):
+        """Windows of up to `length` consecutive transitions of one env inside ONE episode that END at the explicit (slot, env) pairs
+        (DRQN's Memory.get_batch): a window reaches back until it has `length` steps, or meets the episode's first step or the oldest
+        addressable slot.  -> s / s_next float32 [B, L, D], action int64 / reward float32 / done bool / mask bool [B, L], length int32
+        [B], plan [B, 20, 20] (1D: [B, 30]; the plan at the window's last step).  The valid steps come first (position j holds step
+        slot - length[b] + 1 + j) and everything past them is zero, so a recurrent net starts from its zero state at the window's real
+        start.  One launch that reads the length + 1 distinct rows of a window once each; length = 1 is gather()."""
+        L = _walk_steps("length", length)
+        e = self.env
+        slot = torch.as_tensor(slot, device=e.device).to(torch.int32).contiguous()
+        env_index = torch.as_tensor(env_index, device=e.device).to(torch.int32).contiguous()
+        B = int(slot.numel())
+        s = torch.empty((B, L, e.obs_dim), dtype=torch.float32, device=e.device)
+        s_next = torch.empty((B, L, e.obs_dim), dtype=torch.float32, device=e.device)
+        plan = torch.empty((B, self.plan_cells), dtype=torch.float32, device=e.device) if with_plan else None
+        action = torch.empty((B, L), dtype=torch.int64, device=e.device)
+        reward = torch.empty((B, L), dtype=torch.float32, device=e.device)
+        done = torch.empty((B, L), dtype=torch.bool, device=e.device)
+        mask = torch.empty((B, L), dtype=torch.bool, device=e.device)
+        length = torch.empty((B,), dtype=torch.int32, device=e.device)
+        self._walk_call(e._lib.snac_replay_gather_windows, slot, env_index, (self.head - self.valid_ticks()) % self.cap, L, (),
+                        (s, s_next, plan, action, reward, done, mask, length))
+        out = dict(s=s, s_next=s_next, action=action, reward=reward, done=done, mask=mask, length=length)
+        if with_plan:
+            out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
+        return out
+
+    def _draw(self, batch, generator, prioritized, beta, stratified):
+        """The transitions of a minibatch -> slot, env, and for prioritized=True what sample() adds (index, prob, weight), else None."""
         if not isinstance(prioritized, bool):
             raise ValueError("prioritized must be a bool")
         if prioritized and self.tree is None:
@@ -210,15 +288,41 @@ class ReplayRing:
         if prioritized:
             N = self.env.num_envs
             flat, prob = self.tree.sample(int(batch), stratified)
-            slot, env_index = flat // N, flat % N
-            out = self.gather(slot, env_index, with_plan=with_plan)
             w = (prob * float(len(self))) ** -beta
-            out.update(slot=slot, env=env_index, index=flat, prob=prob, weight=w / w.max())
-            return out
+            return flat // N, flat % N, dict(index=flat, prob=prob, weight=w / w.max())
         age = torch.randint(0, v, (batch,), device=dev, generator=generator)
         slot = (self.head - 1 - age) % self.cap
         env_index = torch.randint(0, self.env.num_envs, (batch,), device=dev, generator=generator)
-        return self.gather(slot, env_index, with_plan=with_plan)
+        return slot, env_index, None
+
+    def sample(self, batch, generator=None, with_plan=True, prioritized=False, beta=0.4, stratified=True, n_step=None, gamma=None):
+        """Uniform minibatch over the addressable transitions (random.sample in the reference, :144).  prioritized=True (a
+        ReplayRing(prioritized=True); generator None): the transitions are drawn from the priority tree, with replacement, stratified
+        over the total unless stratified=False, and the gather() dict gains slot, env and index = slot * N + env (int64 [n]; what
+        update_priorities() takes), prob float32 [n] and the importance weights weight = (len(self) * prob) ** -beta / their largest
+        over the batch (beta = 0: all ones).  n_step=n (an integer in [1, 64], with gamma): the same draw, gathered as n-step
+        transitions -- the gather_nstep() dict, with slot and env."""
+        if n_step is not None:
+            n_step, gamma = _walk_steps("n_step", n_step), _walk_gamma(gamma)
+        slot, env_index, extra = self._draw(batch, generator, prioritized, beta, stratified)
+        if n_step is None:
+            out = self.gather(slot, env_index, with_plan=with_plan)
+        else:
+            out = self.gather_nstep(slot, env_index, n_step, gamma, with_plan=with_plan)
+        if extra is not None or n_step is not None:
+            out.update(slot=slot, env=env_index, **(extra or {}))
+        return out
+
+    def sample_windows(self, batch, length, generator=None, with_plan=True, prioritized=False, beta=0.4, stratified=True):
+        """DRQN-style minibatch without a host synchronisation: the window ENDS are drawn as sample() draws transitions (uniform, or
+        prioritized=True with index, prob and weight of the end), and gather_windows() gives each its window -> the gather_windows()
+        dict with slot and env (those of the window's end).  Where sample_sequences() rejects a window that crosses an episode's start
+        and draws again, this returns it shorter, with its mask."""
+        length = _walk_steps("length", length)
+        slot, env_index, extra = self._draw(batch, generator, prioritized, beta, stratified)
+        out = self.gather_windows(slot, env_index, length, with_plan=with_plan)
+        out.update(slot=slot, env=env_index, **(extra or {}))
+        return out
 
     def update_priorities(self, index, priority):
         """New priorities for sampled transitions (PriorityTree.update): index [n], the `index` of sample(prioritized=True);
@@ -240,7 +344,8 @@ class ReplayRing:
         s / s_next [B, L, D] float32, action / reward / done [B, L], plan [B, 20, 20] (1D: [B, 30]).
         Windows are drawn uniformly over all valid windows in the ring (the reference draws an episode first, then a
         window inside it, so it favours short episodes; neither is a parity surface -- the reference uses python's
-        `random`).  Candidates are drawn `oversample` x batch at a time and filtered on the device."""
+        `random`).  Candidates are drawn `oversample` x batch at a time and filtered on the device, which waits for the device every round;
+        sample_windows() draws window ends and masks instead, in one launch and without that wait."""
         L, B = int(time_step), int(batch)
         v = self.valid_ticks()
         if L < 1 or v < L:
