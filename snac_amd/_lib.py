@@ -1,7 +1,14 @@
-"""ctypes binding of libsnac_hip.so (include/snac_hip.h).  There is no CPU fallback: if the HIP
-library is missing or a GPU is not available the product raises."""
+"""ctypes binding of libsnac_hip.so.  There is no CPU fallback: if the HIP library is missing or a GPU is not available the
+product raises.
+
+include/snac_hip.h is the one statement of the ABI.  parse_header() reads it when this module is imported (no torch, no library) and
+everything below comes from what it finds: the constants (ABI_VERSION, ENV_1D, ... are the header's SNAC_* names without the prefix),
+a ctypes.Structure per struct (STRUCTS; Sizes, EnvDesc, State, RolloutRecord and TrajInfo are the ones callers construct), EXPORTS, and
+the restype / argtypes lib() sets on every entry point.  To bind a new entry point, struct or constant, declare it in the header: that is
+all.  The parser knows only the header's own dialect and raises SnacError on anything else; it never guesses."""
 import ctypes as C
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -11,71 +18,114 @@ LIB_PATH = os.environ.get("SNAC_HIP_LIB") or os.path.join(HERE, "libsnac_hip.so"
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 
-SNAC_OK = 0
-ABI_VERSION = 12
-ENV_1D, ENV_2D, ENV_3D = 1, 2, 3
-OBS_F64, OBS_F32 = 0, 1
-OBS_NONE, OBS_ALL, OBS_LAST, OBS_TILED = 0, 1, 2, 3
-FLAG_NEED_RESET = 1
-RULE_BRICK_GT, RULE_TIME_GT = 1, 2
-SCALARS_DEFAULT, SCALARS_RAW, SCALARS_NORM = 0, 1, 2
-TAIL_POSITION, TAIL_PLAN, TAIL_RECORD = 1, 2, 4
-SUMS_SCRATCH_WORDS = 3 * 64 + 1   # SNAC_SUMS_SCRATCH_WORDS: the scratch of snac_episodic_sums, int64 words
-
-EXPORTS = ("snac_version", "snac_last_error", "snac_env_sizes", "snac_obs_dim", "snac_reset", "snac_reset_scalar", "snac_step",
-           "snac_step_scalar", "snac_rollout",
-           "snac_rollout_rec", "snac_replay_gather", "snac_make_plans", "snac_observe", "snac_iou", "snac_export_grid", "snac_transition",
-           "snac_import_state", "snac_obs_equal", "snac_discounted_return", "snac_plans_from_grids", "snac_mailbox_create", "snac_mailbox_row", "snac_mailbox_touch", "snac_mailbox_step", "snac_mailbox_step_n", "snac_mailbox_reward", "snac_mailbox_done",
-           "snac_mailbox_quit", "snac_mailbox_settle", "snac_mailbox_destroy", "snac_mailbox_stats", "snac_stream_sync", "snac_rollout_tiled", "snac_replay_gather_tiled", "snac_traj_alloc",
-           "snac_traj_alloc_ex", "snac_traj_free", "snac_traj_layout", "snac_traj_describe", "snac_traj_reserved_bytes", "snac_last_kernel", "snac_tuning",
-           "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d", "snac_nodes1d_pack", "snac_nodes1d_unpack",
-           "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d",
-           "snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d", "snac_action_dist", "snac_uct_select", "snac_uct_backup",
-           "snac_uct_advance", "snac_uct_select_paths", "snac_uct_backup_paths", "snac_observe_nodes1d", "snac_observe_nodes2d",
-           "snac_observe_nodes3d", "snac_uct_select_puct", "snac_uct_set_priors", "snac_uct_pick_moves", "snac_uct_restart",
-           "snac_uct_returns", "snac_uct_select_paths_norm", "snac_uct_select_puct_norm", "snac_uct_backup_paths_norm", "snac_uct_bounds",
-           "snac_uct_select_gumbel", "snac_uct_gumbel_candidates", "snac_uct_set_priors_value", "snac_uct_select_gumbel_interior",
-           "snac_uct_improved_policy", "snac_uct_save_roots", "snac_uct_load_roots", "snac_uct_store_targets", "snac_uct_returns_nstep",
-           "snac_prio_layout", "snac_prio_init", "snac_prio_update", "snac_prio_fill", "snac_prio_sample", "snac_episodic_sums",
-           "snac_replay_gather_nstep", "snac_replay_gather_windows")
-
-
-class Sizes(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in (
-        "obs_dim", "num_actions", "total_step", "half_window", "env_height", "env_width", "plan_height", "plan_width",
-        "grid_elems", "grid_elem_bytes", "plan_elems", "plan_elem_bytes")]
-
-
-class EnvDesc(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("dynamic", C.c_int32), ("num_envs", C.c_int32), ("num_plans", C.c_int32),
-                ("obs_dtype", C.c_int32), ("static_plan", C.c_int32), ("seed", C.c_uint64), ("env_id_base", C.c_int64),
-                ("total_step", C.c_int32), ("rules", C.c_int32), ("frame_value", C.c_int32), ("obs_scalars", C.c_int32),
-                ("obs_tail", C.c_int32), ("action_dist", C.c_int32)]
-
-
-class RolloutRecord(C.Structure):
-    _fields_ = [("actions", C.c_void_p), ("step_size", C.c_void_p), ("plan_idx", C.c_void_p), ("first", C.c_void_p)]
-
-
-class State(C.Structure):
-    _fields_ = [("hdr", C.c_void_p), ("episode", C.c_void_p), ("grid", C.c_void_p), ("plans", C.c_void_p),
-                ("plan_tb", C.c_void_p), ("stat_episodes", C.c_void_p), ("stat_return", C.c_void_p),
-                ("stat_iou_fx", C.c_void_p)]
-
-
-TRAJ_INFO_WINDOWS = 64
-
-
-class TrajInfo(C.Structure):
-    """snac_traj_info (include/snac_hip.h): what snac_traj_alloc measured while it built a block."""
-    _fields_ = ([(n, C.c_int32) for n in ("layout", "rebuilds", "pool_groups", "probe_launches", "windows", "windows_slow")]
-                + [(n, C.c_float) for n in ("self_us_per_gib", "fast_us_per_gib", "slow_us_per_gib", "window_max_us_per_gib",
-                                            "window_mean_us_per_gib", "block_us_per_gib", "build_ms")]
-                + [("bytes", C.c_uint64), ("window_us", C.c_float * TRAJ_INFO_WINDOWS)])
-
 
 class SnacError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": C.c_int, "int8_t": C.c_int8, "uint8_t": C.c_uint8, "int16_t": C.c_int16, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
+            "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "float": C.c_float, "size_t": C.c_size_t}
+_CLASS_NAMES = {"snac_sizes": "Sizes", "snac_env_desc": "EnvDesc", "snac_state": "State", "snac_rollout_record": "RolloutRecord",
+                "snac_traj_info": "TrajInfo"}      # the structs callers construct: a parameter `T*` of one of them is POINTER(class)
+
+
+def parse_header(text):
+    """(constants, structs, prototypes) of a header written like include/snac_hip.h: {SNAC_NAME: int} of the enumerators and integer
+    #defines, {struct name: ctypes.Structure} in header order, {function: (restype, argtypes)}.  Every pointer is c_void_p, except a
+    parameter pointing to one of _CLASS_NAMES and a `const char*` result (c_char_p); an array parameter is a pointer."""
+    consts, structs, protos = {}, {}, {}
+    types = dict(_SCALARS, void=None, char=None)               # every type name so far; None: only pointers to it can be declared
+
+    def bad(what):
+        raise SnacError("include/snac_hip.h: cannot bind `%s` in `%s`" % (" ".join(what.split()), " ".join(decl.split())))
+
+    def integer(expr):
+        text = re.sub(r"SNAC_\w+", lambda m: str(consts[m.group()]) if m.group() in consts else bad(expr), expr)
+        if not re.fullmatch(r"[-+*<>|&() \d]*\d[) ]*", text):  # decimal digits, + - * << >> | & and parentheses only
+            bad(expr)
+        try:
+            return int(eval(text, {"__builtins__": {}}))
+        except (SyntaxError, TypeError):
+            bad(expr)
+
+    typed = re.compile(r"(?:const )?(\w+)\b(.*)").fullmatch                        # `type` and its declarators
+    declarator = re.compile(r" ?(\**) ?(\w+) ?(?:\[ ?(\w+) ?\])?").fullmatch          # `*name[n]`
+
+    def declare(part, field):
+        """[(name, ctype)] of `type a, *b, c[n]`: the fields of a struct, or (field False) a parameter or a function's name and result."""
+        base, rest = (typed(part) or bad(part)).groups()
+        if base not in types:
+            bad(part)
+        out = []
+        for d in rest.split(","):
+            stars, name, dim = (declarator(d) or bad(part)).groups()
+            if stars or (dim and not field):
+                t = C.POINTER(structs[base]) if base in _CLASS_NAMES and stars == "*" and not (dim or field) else C.c_void_p
+            else:
+                t = types[base] or bad(part)
+                if dim:
+                    t = t * integer(dim)
+            out.append((name, t))
+        return out
+
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^#ifdef __cplusplus\n.*\n#endif$", "", text, flags=re.M)       # extern "C" { and its }
+    for decl in re.findall(r"^[ \t]*#.*$", text, flags=re.M):
+        m = re.fullmatch(r"#define (SNAC_\w+) (.+)", " ".join(decl.split()))
+        if m:
+            consts[m.group(1)] = integer(m.group(2))
+        elif not re.fullmatch(r"#(ifndef \w+|define \w+|include <\w+\.h>|endif)", decl.strip()):
+            bad(decl)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    one = re.compile(r"\s*([^;{}]*(?:\{[^{}]*\}[^;{}]*)?);")             # a declaration, with at most one { } body
+    pos = 0
+    while text[pos:].strip():
+        decl = text[pos:pos + 120]
+        m = one.match(text, pos) or bad("what follows")
+        pos, decl = m.end(), " ".join(m.group(1).split())
+        enum = re.fullmatch(r"(?:typedef )?enum(?: \w+)? \{(.*)\}(?: \w+)?", decl)
+        struct = re.fullmatch(r"typedef struct (\w+) (?:\{(.*)\} )?\1", decl)
+        if enum:
+            for e in enum.group(1).split(","):
+                name, value = (re.fullmatch(r" ?(SNAC_\w+) = (.+)", e) or bad(decl)).groups()
+                consts[name] = integer(value)
+        elif struct and struct.group(2) is None:
+            types[struct.group(1)] = None                            # typedef struct snac_mailbox snac_mailbox;
+        elif struct:
+            name, body = struct.groups()
+            fields = [f for part in body.split(";") if part.strip() for f in declare(part.strip(), True)]
+            types[name] = structs[name] = type(_CLASS_NAMES.get(name, name), (C.Structure,), {"_fields_": fields})
+        else:
+            result, params = (re.fullmatch(r"([^()]+)\((.*)\)", decl) or bad(decl)).groups()
+            (name, res), = declare(result.strip(), False)
+            if name in protos or not name.startswith("snac_"):
+                bad(decl)
+            if result.startswith("const char*"):
+                res = C.c_char_p
+            args = [] if params.strip() == "void" else [declare(a.strip(), False) for a in params.split(",")]
+            protos[name] = (res, [t for (_, t), in args])
+    return consts, structs, protos
+
+
+def _header():
+    path = os.path.join(INCLUDE, "snac_hip.h")
+    try:
+        with open(path) as fh:
+            return fh.read()
+    except OSError as e:
+        raise SnacError("the header of the C ABI is missing: %s" % path) from e
+
+
+CONSTANTS, STRUCTS, PROTOTYPES = parse_header(_header())
+globals().update({k[len("SNAC_"):]: v for k, v in CONSTANTS.items()})      # ABI_VERSION, ENV_1D .. TAIL_RECORD, SUMS_SCRATCH_WORDS, ...
+SNAC_OK = CONSTANTS["SNAC_OK"]
+Sizes, EnvDesc, State, RolloutRecord, TrajInfo = (STRUCTS[n] for n in _CLASS_NAMES)
+EXPORTS = tuple(PROTOTYPES)
+
+
+def ptr(t):
+    """A tensor's address as a pointer argument; None stays None (NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def build(force=False):
@@ -115,100 +165,10 @@ def lib():
         import torch  # noqa: F401
 
         L = C.CDLL(LIB_PATH)
-        vp = C.c_void_p
-        L.snac_version.restype = C.c_int
-        L.snac_last_error.restype = C.c_char_p
-        L.snac_last_kernel.restype = C.c_char_p
-        L.snac_stream_sync.argtypes = [vp]
-        L.snac_env_sizes.argtypes = [C.c_int, C.c_int, C.POINTER(Sizes)]
-        L.snac_obs_dim.argtypes = [C.POINTER(EnvDesc)]
-        L.snac_reset.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp, vp, vp]
-        L.snac_reset_scalar.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp]
-        L.snac_step_scalar.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_uint32, C.c_int32, C.c_int32, C.c_int, vp, vp, vp, vp]
-        L.snac_step.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_uint32, vp, vp, C.c_int, vp, vp, vp, vp]
-        L.snac_rollout.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_uint32, vp, vp, C.c_int, vp, vp, vp, vp]
-        L.snac_rollout_rec.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_uint32, vp, vp, C.c_int, vp, vp, vp,
-                                       C.POINTER(RolloutRecord), vp]
-        L.snac_replay_gather.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
-        L.snac_replay_gather_tiled.argtypes = L.snac_replay_gather.argtypes
-        walk = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32]
-        L.snac_replay_gather_nstep.argtypes = walk + [C.c_double] + [vp] * 9     # desc .. batch, n; gamma; eight outputs, the stream
-        L.snac_replay_gather_windows.argtypes = walk + [vp] * 9                  # desc .. batch, L; eight outputs, the stream
-        L.snac_rollout_tiled.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_uint32, vp, vp, C.c_int32, C.c_int32, vp, vp, vp,
-                                         C.POINTER(RolloutRecord), vp]
-        L.snac_make_plans.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, vp, vp, vp]
-        L.snac_observe.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
-        L.snac_iou.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
-        L.snac_episodic_sums.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp, vp]
-        L.snac_export_grid.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
-        L.snac_transition.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
-        L.snac_nodes2d_pack.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, vp, C.c_int32, vp, vp]
-        L.snac_nodes2d_unpack.argtypes = [C.POINTER(EnvDesc), vp, C.c_int32, vp, C.c_int32, C.POINTER(State), vp, vp]
-        L.snac_transition_nodes2d.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
-        for k in ("1d", "3d"):
-            getattr(L, "snac_nodes%s_pack" % k).argtypes = L.snac_nodes2d_pack.argtypes
-            getattr(L, "snac_nodes%s_unpack" % k).argtypes = L.snac_nodes2d_unpack.argtypes
-            getattr(L, "snac_transition_nodes%s" % k).argtypes = L.snac_transition_nodes2d.argtypes
-        L.snac_import_state.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_plans_from_grids.argtypes = [C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32, C.POINTER(State), C.c_int32, vp, vp, vp, vp]
-        L.snac_mailbox_create.argtypes = [C.POINTER(EnvDesc), C.c_uint32, C.POINTER(vp)]
-        L.snac_mailbox_row.argtypes, L.snac_mailbox_row.restype = [vp], vp
-        L.snac_mailbox_reward.argtypes, L.snac_mailbox_reward.restype = [vp], vp
-        L.snac_mailbox_done.argtypes, L.snac_mailbox_done.restype = [vp], vp
-        L.snac_mailbox_step_n.argtypes = [vp, C.POINTER(EnvDesc), C.POINTER(State), vp, vp]
-        L.snac_mailbox_touch.argtypes = [vp]
-        L.snac_mailbox_step.argtypes = [vp, C.POINTER(EnvDesc), C.POINTER(State), C.c_int32, C.c_int32]
-        L.snac_mailbox_quit.argtypes = [vp]
-        L.snac_mailbox_settle.argtypes = [vp]
-        L.snac_mailbox_destroy.argtypes = [vp]
-        L.snac_mailbox_stats.argtypes = [vp, C.POINTER(C.c_uint32 * 8)]
-        L.snac_obs_equal.argtypes = [C.POINTER(EnvDesc), vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
-        L.snac_discounted_return.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
-        for k in ("1d", "2d", "3d"):
-            getattr(L, "snac_evaluate_nodes%s" % k).argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_uint32,
-                                                                vp, vp, vp, vp]
-        L.snac_action_dist.argtypes = [C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
-        L.snac_uct_select.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_uct_backup.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_uct_advance.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_uct_select_paths.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, vp, vp, C.c_int32,
-                                            vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_uct_backup_paths.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_uct_select_puct.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp,
-                                           C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.snac_uct_set_priors.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
-        L.snac_uct_pick_moves.argtypes = [C.POINTER(EnvDesc), C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, vp, vp, vp, vp]
-        L.snac_uct_restart.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
-        L.snac_uct_returns.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp]
-        L.snac_uct_save_roots.argtypes = [C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp]
-        L.snac_uct_load_roots.argtypes = L.snac_uct_restart.argtypes[:8] + [vp, C.c_int32, vp, vp, vp]      # src, src_rows, index, used, the stream
-        L.snac_uct_store_targets.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
-        L.snac_uct_returns_nstep.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp, vp, vp, vp, vp, vp]
-        L.snac_prio_layout.argtypes = [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64 * 8)]
-        L.snac_prio_init.argtypes = [vp, C.c_int32, C.c_int32, vp]
-        L.snac_prio_update.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp]
-        L.snac_prio_fill.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, vp]
-        L.snac_prio_sample.argtypes = [vp, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
-        for n in ("snac_uct_select_paths", "snac_uct_select_puct", "snac_uct_backup_paths"):       # the arguments, bounds, the stream
-            getattr(L, n + "_norm").argtypes = getattr(L, n).argtypes[:-1] + [vp, vp]
-        L.snac_uct_bounds.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
-        L.snac_uct_select_gumbel.argtypes = L.snac_uct_select_puct_norm.argtypes[:-1] + [vp, C.c_int32, vp]     # cand, offset, the stream
-        L.snac_uct_gumbel_candidates.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double, C.c_double,
-                                                 C.c_double, vp, vp, vp, vp]
-        L.snac_uct_set_priors_value.argtypes = L.snac_uct_set_priors.argtypes[:-2] + [vp, C.c_int32, vp]        # value, only_unvisited, the stream
-        L.snac_uct_select_gumbel_interior.argtypes = L.snac_uct_select_gumbel.argtypes[:-1] + [C.c_double, C.c_double, vp]  # c_visit, c_scale
-        L.snac_uct_improved_policy.argtypes = [C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_double, C.c_double, vp, vp, vp]
-        for k in ("1d", "2d", "3d"):
-            getattr(L, "snac_observe_nodes%s" % k).argtypes = [C.POINTER(EnvDesc), C.POINTER(State), vp, C.c_int32, C.c_int32, vp, vp, vp]
-        L.snac_traj_alloc.argtypes = [C.c_size_t, C.c_int, C.POINTER(vp)]
-        L.snac_traj_alloc_ex.argtypes = [C.c_size_t, C.c_int, C.c_size_t, vp, C.POINTER(vp)]
-        L.snac_traj_free.argtypes = [vp]
-        L.snac_traj_layout.argtypes = [vp]
-        L.snac_traj_describe.argtypes = [vp, C.POINTER(TrajInfo)]
-        L.snac_traj_reserved_bytes.restype = C.c_uint64
-        for n in EXPORTS:
-            getattr(L, n)
-        if L.snac_version() != ABI_VERSION:
+        for name, (restype, argtypes) in PROTOTYPES.items():        # a symbol the library lacks raises here
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if L.snac_version() != CONSTANTS["SNAC_ABI_VERSION"]:
             raise SnacError("libsnac_hip.so ABI version mismatch")
         _lib = L
     return _lib

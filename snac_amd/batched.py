@@ -11,14 +11,11 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 from . import plans as _plans
 
 _KINDS = {1: 1, 2: 2, 3: 3, "1d": 1, "2d": 2, "3d": 3, "1D": 1, "2D": 2, "3D": 3}
 _GRID_DTYPE = {1: torch.int16, 2: torch.int32, 3: torch.int16}
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 # the per-tick fast path of step(): torch's raw accessors (no Stream / device objects are built)

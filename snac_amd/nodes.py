@@ -22,10 +22,12 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+def _words(struct):
+    """int32 words of a record of include/snac_hip.h."""
+    return C.sizeof(_lib.STRUCTS[struct]) // 4
 
 
 class _NodePool:
@@ -208,7 +210,7 @@ class _NodePool:
 
 class NodePool2D(_NodePool):
     """2D node records (snac_node2d: 32 int32 words, one line)."""
-    KIND, WORDS, CANONICAL_OBS = 2, 32, 51
+    KIND, WORDS, CANONICAL_OBS = 2, _words("snac_node2d"), 51
     PACK, UNPACK, TRANSITION = "snac_nodes2d_pack", "snac_nodes2d_unpack", "snac_transition_nodes2d"
     EVALUATE, OBSERVE = "snac_evaluate_nodes2d", "snac_observe_nodes2d"
 
@@ -220,7 +222,7 @@ class NodePool2D(_NodePool):
 
 class NodePool1D(_NodePool):
     """1D node records (snac_node1d: 32 int32 words, one line)."""
-    KIND, WORDS, CANONICAL_OBS = 1, 32, 7
+    KIND, WORDS, CANONICAL_OBS = 1, _words("snac_node1d"), 7
     PACK, UNPACK, TRANSITION = "snac_nodes1d_pack", "snac_nodes1d_unpack", "snac_transition_nodes1d"
     EVALUATE, OBSERVE = "snac_evaluate_nodes1d", "snac_observe_nodes1d"
 
@@ -232,7 +234,7 @@ class NodePool1D(_NodePool):
 
 class NodePool3D(_NodePool):
     """3D node records (snac_node3d: 224 int32 words, seven lines)."""
-    KIND, WORDS, CANONICAL_OBS = 3, 224, 51
+    KIND, WORDS, CANONICAL_OBS = 3, _words("snac_node3d"), 51
     PACK, UNPACK, TRANSITION = "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d"
     EVALUATE, OBSERVE = "snac_evaluate_nodes3d", "snac_observe_nodes3d"
 

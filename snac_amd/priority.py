@@ -18,13 +18,10 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 
 MAX_ENTRIES = (1 << 31) - 64
 MAX_DRAWS = 1 << 31
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def layout(entries):

@@ -28,10 +28,7 @@ import math
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._lib import ptr as _ptr
 
 
 def _walk_steps(name, v):

@@ -55,10 +55,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+from ._lib import ptr as _ptr
 
 
 class SelfPlay:

@@ -136,14 +136,23 @@ import math
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr
 from .nodes import NodePool
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+_NODE = _lib.STRUCTS["snac_uct_node"]
+WORDS = C.sizeof(_NODE) // 4                                         # int32 words per snac_uct_node (256 bytes)
 
 
-WORDS = 64                                                           # int32 words per snac_uct_node (256 bytes)
+def _words(field):
+    """The int32 words of a snac_uct_node field within a row of `stats`, as a slice."""
+    f = getattr(_NODE, field)
+    return slice(f.offset // 4, (f.offset + f.size) // 4)
+
+
+_CHILD, _CHILD_VISITS, _CHILD_VALUE, _VALUE_SUM, _REWARD = (_words(f) for f in ("child", "child_visits", "child_value", "value_sum", "reward"))
+_PARENT, _ACTION, _TERMINAL, _VISITS = (_words(f).start for f in ("parent", "action", "terminal", "visits"))
+_PRIOR, _NET_VALUE = _lib.UCT_PRIOR_WORD, _lib.UCT_NET_VALUE_WORD    # first words of prior[0 .. 7] (float32) and net_value (float64)
 
 
 def uct_tables(n):
@@ -354,9 +363,9 @@ class UCTSearch:
         self.pool.load(rows=rows, node_rows=roots)
         self.pool.load(rows=rows, node_rows=B * cap + torch.arange(B, device=env.device))
         self.stats.zero_()
-        self.stats[:, 0:8] = -1                                      # child[]
-        self.stats[:, 32:34] = -1                                    # parent, action
-        self.stats[roots, 34] = self.pool.need_reset[roots].to(torch.int32)
+        self.stats[:, _CHILD] = -1
+        self.stats[:, _PARENT:_ACTION + 1] = -1                      # parent, action: neighbours
+        self.stats[roots, _TERMINAL] = self.pool.need_reset[roots].to(torch.int32)
         self._used.fill_(1)
         self._iteration = 0
         if self.q_normalise:
@@ -635,7 +644,7 @@ class UCTSearch:
         priors, value = self._call(self._obs, self.trees * self.paths)
         self._priors.copy_(priors)
         torch.index_select(self._done, 0, self._first_idx, out=self._term_new)       # the expander's done (a fresh leaf: another slot's)
-        torch.index_select(self.stats[:, 34], 0, self._leaf, out=self._term_old)     # else the stored node's terminal
+        torch.index_select(self.stats[:, _TERMINAL], 0, self._leaf, out=self._term_old)     # else the stored node's terminal
         torch.where(self._first_has, self._term_new != 0, self._term_old != 0, out=self._term)
         torch.where(self._term, self._zero, value, out=self._value)
         self._est.add_(self._value)
@@ -655,7 +664,7 @@ class UCTSearch:
         priors, value = self._call(self._root_obs, self.trees)
         self._root_priors.copy_(priors)
         if self.gumbel_interior:
-            torch.index_select(self.stats[:, 34], 0, self._roots, out=self._root_term)
+            torch.index_select(self.stats[:, _TERMINAL], 0, self._roots, out=self._root_term)
             torch.where(self._root_term != 0, self._root_zero, value, out=self._root_value)
             _lib.check(self._lib.snac_uct_set_priors_value(self.num_actions, _ptr(self.stats), self.rows, self.trees, _ptr(self._root_rows),
                                                            _ptr(self._root_priors), _ptr(self._root_value), 1, env._stream()))
@@ -779,8 +788,8 @@ class UCTSearch:
                 _lib.check(self._lib.snac_uct_improved_policy(*self._policy_args, _ptr(pi), self.env._stream()))
             return pi
         r = self.stats[self._roots]
-        child, N = r[:, :A], r[:, 8:8 + A]
-        W = r[:, 16:32].contiguous().view(torch.float64)[:, :A]
+        child, N = r[:, _CHILD][:, :A], r[:, _CHILD_VISITS][:, :A]
+        W = r[:, _CHILD_VALUE].contiguous().view(torch.float64)[:, :A]
         visited = (child >= 0) & (N > 0)
         zero = torch.zeros_like(W)
         n = torch.where(visited, N.to(torch.float64), zero)
@@ -801,18 +810,18 @@ class UCTSearch:
     # ---- readers ----------------------------------------------------------------------------------------------------------
     def root_visits(self):
         """[B, A] int32: the visits of each root child (0 where untried)."""
-        return self.stats[self._roots][:, 8:8 + self.num_actions].clone()
+        return self.stats[self._roots][:, _CHILD_VISITS][:, :self.num_actions].clone()
 
     def root_q(self):
         """[B, A] float64: W / N of each root child, NaN where untried."""
         r = self.stats[self._roots]
-        w = r[:, 16:32].contiguous().view(torch.float64)[:, :self.num_actions]
-        q = w / r[:, 8:8 + self.num_actions].to(torch.float64)
-        return torch.where(r[:, :self.num_actions] >= 0, q, torch.full_like(q, float("nan")))
+        w = r[:, _CHILD_VALUE].contiguous().view(torch.float64)[:, :self.num_actions]
+        q = w / r[:, _CHILD_VISITS][:, :self.num_actions].to(torch.float64)
+        return torch.where(r[:, _CHILD][:, :self.num_actions] >= 0, q, torch.full_like(q, float("nan")))
 
     def root_priors(self):
         """[B, A] float32: the priors of each root (zero in a rollout search)."""
-        return self.stats[self._roots][:, 48:48 + self.num_actions].contiguous().view(torch.float32)
+        return self.stats[self._roots][:, _PRIOR:_PRIOR + self.num_actions].contiguous().view(torch.float32)
 
     def best_actions(self):
         """[B] int64: the most-visited root action, ties to the lowest."""
@@ -831,39 +840,39 @@ class UCTSearch:
     # views over all node rows (scratch rows included), decoded from snac_uct_node
     @property
     def children(self):
-        return self.stats[:, :self.num_actions]
+        return self.stats[:, _CHILD][:, :self.num_actions]
 
     @property
     def parent(self):
-        return self.stats[:, 32]
+        return self.stats[:, _PARENT]
 
     @property
     def action(self):
-        return self.stats[:, 33]
+        return self.stats[:, _ACTION]
 
     @property
     def terminal(self):
-        return self.stats[:, 34] != 0
+        return self.stats[:, _TERMINAL] != 0
 
     @property
     def visits(self):
-        return self.stats[:, 35]
+        return self.stats[:, _VISITS]
 
     @property
     def value_sum(self):
-        return self.stats[:, 36:38].view(torch.float64)[:, 0]
+        return self.stats[:, _VALUE_SUM].view(torch.float64)[:, 0]
 
     @property
     def reward(self):
-        return self.stats[:, 38:39].view(torch.float32)[:, 0]
+        return self.stats[:, _REWARD].view(torch.float32)[:, 0]
 
     @property
     def prior(self):
         """[rows, A] float32: the PUCT priors (zero in a rollout search)."""
-        return self.stats[:, 48:48 + self.num_actions].view(torch.float32)
+        return self.stats[:, _PRIOR:_PRIOR + self.num_actions].view(torch.float32)
 
     @property
     def net_values(self):
         """[rows] float64: the value the evaluator gave for each node's state, 0 at a terminal node (a gumbel_interior search; zero in
         every other)."""
-        return self.stats[:, 56:58].view(torch.float64)[:, 0]
+        return self.stats[:, _NET_VALUE:_NET_VALUE + 2].view(torch.float64)[:, 0]

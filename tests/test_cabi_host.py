@@ -4,6 +4,8 @@ run without its HIP path."""
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -26,6 +28,12 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(L, n), n
     assert L.snac_version() == _lib.ABI_VERSION
+    # EXPORTS is derived from the header, so the other direction is asked of the library itself: it defines no snac_* symbol
+    # that the header does not declare
+    nm = shutil.which("nm") or "/opt/rocm/lib/llvm/bin/llvm-nm"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.LIB_PATH], check=True, capture_output=True, text=True, timeout=60).stdout
+    defined = sorted(ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("snac_"))
+    assert defined == names
 
 
 def test_env_sizes_match_reference_constants():
