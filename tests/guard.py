@@ -113,14 +113,32 @@ def unwritten(view):
 
 
 @contextlib.contextmanager
-def allocations(module, views):
-    """Inside: torch.empty / torch.empty_like / torch.zeros called from `module` (one of the package's, through its global `torch`) return
-    `views` in turn -- shape and dtype must match; zeros() zeroes the view.  The outputs that a call allocates itself then come from
-    the arena, and the call stays the package's own.  Every other attribute of torch is torch's."""
-    queue = list(views)
+def allocations(module, views=None, arena=None, offset=None):
+    """Inside: torch.empty / torch.empty_like / torch.zeros called from `module` (one of the package's, through its global `torch`) come
+    from the test's arena; every other attribute of torch is torch's (torch.tensor, torch.full, torch.arange: tables and constant inputs).
+    Several modules are patched at once by nesting the context.  Two modes:
+
+    allocations(module, views): the calls return `views` in turn -- shape and dtype must match; zeros() zeroes the view.  The outputs that
+    a call allocates itself then come from the arena, and the call stays the package's own.
+
+    allocations(module, arena=A, offset=None): on demand -- every such call is carved from A as it is made, `offset` bytes (None: 0; a
+    multiple of 128 below 512, so that records, statistics and bounds keep the alignment the header asks for) past a 512-byte boundary,
+    zeros() zeroed, named "<module>#<k> <shape> <dtype>" with k counting the module's allocations from this arena.  For objects that
+    allocate in their constructors and keep raw pointers: build them, and call them, inside the context."""
+    assert (views is None) != (arena is None), "give the views in call order, or an arena to carve from on demand"
+    queue = list(views) if views is not None else None
+    short = module.__name__.rsplit(".", 1)[-1]
+    count = None if arena is None else arena.__dict__.setdefault("allocated", {})      # per arena and module: names stay unique across contexts
+    off = 0 if offset is None else int(offset)
+    assert off % 128 == 0 and 0 <= off < 512, off
 
     def take(shape, dtype):
         shape = (int(shape),) if isinstance(shape, int) else tuple(int(s) for s in shape)
+        dtype = torch.get_default_dtype() if dtype is None else dtype
+        if queue is None:
+            k = count[short] = count.get(short, -1) + 1
+            name = "%s#%d %s %s" % (short, k, shape, str(dtype).replace("torch.", ""))
+            return arena.carve(shape, dtype, offset=off, name=name)
         v = queue.pop(0)
         assert tuple(v.shape) == shape and v.dtype == dtype, ("the call allocates", shape, dtype, "the test carved", tuple(v.shape), v.dtype)
         return v
@@ -145,3 +163,25 @@ def allocations(module, views):
     finally:
         module.torch = torch
     assert not queue, "the call allocated fewer outputs than the test carved"
+
+
+@contextlib.contextmanager
+def fresh_allocations(module):
+    """The twin's side of the on-demand mode: torch's own tensors, but what torch.empty / torch.empty_like give is filled with FRESH_BYTE as
+    a carved view is, so that a byte neither object ever writes (the tail of a work array) compares equal between the two."""
+    class Proxy:
+        def __getattr__(self, name):
+            return getattr(torch, name)
+
+        def empty(self, *a, **kw):
+            return fresh(torch.empty(*a, **kw))
+
+        def empty_like(self, *a, **kw):
+            return fresh(torch.empty_like(*a, **kw))
+
+    assert module.torch is torch
+    module.torch = Proxy()
+    try:
+        yield
+    finally:
+        module.torch = torch

@@ -84,6 +84,85 @@ def _cases(device):
         arena.carve((arena.buf.numel(),), torch.uint8)
 
 
+_OWNER = '''
+class Owner:
+    """An object as the package's: it allocates in its constructor and in a call, through its module's global `torch`."""
+    def __init__(self, n):
+        self.stats = torch.zeros((n, 64), dtype=torch.int32, device="cpu")
+        self.work = torch.empty(2 * n, dtype=torch.int32, device="cpu")
+        self.bounds = torch.empty_like(torch.ones((n, 2), dtype=torch.float64))
+        self.table = torch.tensor([0.0, 1.0, 2.0])
+        self.rows = torch.arange(n)
+        self.none = torch.full((n,), -1, dtype=torch.int32)
+
+    def call(self, n):
+        return torch.empty(n, dtype=torch.uint8)
+'''
+
+
+def test_on_demand_allocations_come_from_the_arena():
+    import types
+
+    mod = types.ModuleType("package.owner")
+    mod.torch = torch
+    exec(_OWNER, mod.__dict__)
+    other = types.ModuleType("package.other")
+    other.torch = torch
+    exec(_OWNER, other.__dict__)
+    n = 5
+    arena = guard.Arena(12 * (guard.BAND + 4096), "cpu")
+    lo, hi = arena.buf.data_ptr(), arena.buf.data_ptr() + arena.buf.numel()
+    with guard.allocations(mod, arena=arena):
+        with guard.allocations(other, arena=arena, offset=128):        # nested: two modules at once
+            assert mod.torch is not torch and other.torch is not torch
+            o, p = mod.Owner(n), other.Owner(n)
+            done = o.call(3)
+    assert mod.torch is torch and other.torch is torch
+    names = [v[2] for v in arena.views]
+    assert names == ["owner#0 (5, 64) int32", "owner#1 (10,) int32", "owner#2 (5, 2) float64", "other#0 (5, 64) int32", "other#1 (10,) int32",
+                     "other#2 (5, 2) float64", "owner#3 (3,) uint8"], names
+    for t, off in [(o.stats, 0), (o.work, 0), (o.bounds, 0), (done, 0), (p.stats, 128), (p.work, 128), (p.bounds, 128)]:
+        assert lo <= t.data_ptr() and t.data_ptr() + t.numel() * t.element_size() <= hi and t.data_ptr() % 512 == off and t.is_contiguous()
+    for t in (o.table, o.rows, o.none):                                # tables and constant inputs stay torch's own
+        assert not lo <= t.data_ptr() < hi
+    assert o.table.tolist() == [0.0, 1.0, 2.0] and o.rows.tolist() == list(range(n)) and o.none.tolist() == [-1] * n
+    assert not o.stats.any() and not p.stats.any()                     # zeros() is zeroed,
+    guard.view_untouched(o.work, "work"), guard.view_untouched(o.bounds, "bounds"), guard.view_untouched(done, "done")   # empty() is fresh
+    # in-bounds writes leave the bands intact
+    o.stats.fill_(7), o.work.fill_(-1), o.bounds.fill_(1.5), done.fill_(1), p.stats.fill_(3)
+    arena.check()
+    # one byte past a view is reported against that view's name
+    start, end = _span(arena, o.work)
+    arena.buf[end] = 0x11
+    with pytest.raises(guard.GuardError) as e:
+        arena.check()
+    assert e.value.first == ("owner#1 (10,) int32", "after", 0) and e.value.count == 1 and "+0 .. +0 after `owner#1 (10,) int32`" in str(e.value)
+    arena.buf[end] = guard.BAND_BYTE
+    start, _ = _span(arena, p.bounds)
+    arena.buf[start - 1] = 0x11
+    with pytest.raises(guard.GuardError) as e:
+        arena.check()
+    assert e.value.first == ("other#2 (5, 2) float64", "before", -1), e.value.first
+    # the module's torch is restored on an exception too, and the first mode is what it was
+    with pytest.raises(ZeroDivisionError):
+        with guard.allocations(mod, arena=arena):
+            assert mod.torch is not torch
+            1 / 0
+    assert mod.torch is torch
+    with pytest.raises(AssertionError):
+        with guard.allocations(mod):                                   # neither views nor an arena
+            pass
+    assert mod.torch is torch
+    v = arena.carve((3,), torch.uint8, name="listed")
+    with guard.allocations(mod, [v]):
+        assert mod.Owner.call(None, 3) is v
+    # the twin's side: torch's own tensors, empty() fresh like a carved view
+    with guard.fresh_allocations(mod):
+        t = mod.Owner(n)
+    assert mod.torch is torch and not lo <= t.work.data_ptr() < hi and not t.stats.any()
+    guard.view_untouched(t.work, "the twin's work"), guard.view_untouched(t.bounds, "the twin's bounds")
+
+
 def test_the_checker_on_cpu_tensors():
     _cases("cpu")
 

@@ -68,6 +68,75 @@ def test_hip_rasteriser_reproduces_the_cv2_drawn_datasets(dim, dens, split):
     assert np.array_equal(env._plan_tb.cpu().numpy().astype(np.int64), np.maximum(tb, 30) if dim == 2 else tb)
 
 
+LATTICE = (0, 1, 9, 10, 18, 19)                                        # both ends, both sides of the middle
+_LATTICE_REF = {}
+
+
+def _lattice_triangles():
+    """All 6^6 = 46 656 ORDERED vertex triples over LATTICE^2 as int [n, 6] = x0 y0 x1 y1 x2 y2 (the order matters to the edge walk)."""
+    g = np.array(np.meshgrid(*([LATTICE] * 6), indexing="ij")).reshape(6, -1).T
+    return np.ascontiguousarray(g)
+
+
+def _lattice_reference(sparse):
+    """(masks [n, 20, 20] int32, areas [n]) of the oracle's rasteriser for every triple: computed once per fill mode, never changed."""
+    if sparse not in _LATTICE_REF:
+        orc = helpers.oracle()
+        v = _lattice_triangles()
+        masks, areas = np.zeros((len(v), 20, 20), np.int32), np.zeros(len(v), np.int64)
+        for i, q in enumerate(v):
+            masks[i], areas[i] = orc.raster_triangle(q[0::2], q[1::2], sparse)
+        masks.setflags(write=False), areas.setflags(write=False)
+        _LATTICE_REF[sparse] = (masks, areas)
+    return _LATTICE_REF[sparse]
+
+
+def test_oracle_rasteriser_on_small_and_degenerate_triangles():
+    """What the lattice holds, by the oracle: the 36 single points, lines, slivers, the half square -- and, for 42 % of the triples, an
+    area of 50 or less that the random form of the generator redraws and never writes."""
+    orc = helpers.oracle()
+    for sparse in (False, True):
+        assert orc.raster_triangle([9, 9, 9], [9, 9, 9], sparse)[1] == 1                          # a point
+        for vx, vy in (([0, 19, 9], [9, 9, 9]), ([9, 9, 9], [0, 19, 10]), ([0, 19, 9], [0, 19, 9])):
+            assert orc.raster_triangle(vx, vy, sparse)[1] == 20                                   # horizontal, vertical, diagonal lines
+        assert orc.raster_triangle([0, 0, 1], [0, 1, 0], sparse)[1] == 3                          # a corner triangle
+    assert orc.raster_triangle([0, 19, 0], [0, 0, 19], False)[1] == 210 and orc.raster_triangle([0, 19, 0], [0, 0, 19], True)[1] == 57
+    v = _lattice_triangles()
+    masks, areas = _lattice_reference(False)
+    assert len(v) == 46656 and len({tuple(q) for q in v}) == 46656
+    points = (v[:, 0] == v[:, 2]) & (v[:, 2] == v[:, 4]) & (v[:, 1] == v[:, 3]) & (v[:, 3] == v[:, 5])
+    assert int(points.sum()) == 36 and (areas[points] == 1).all() and (areas >= 1).all()
+    assert np.array_equal(masks.sum((1, 2)), areas)
+    assert 0.41 < float((areas <= 50).mean()) < 0.43
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "sparse"])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_hip_rasteriser_on_every_small_and_degenerate_triangle(dim, sparse):
+    """The explicit-vertex form of snac_make_plans on every ordered triple of the lattice against the oracle's rasteriser, exactly: the
+    plan rows, area_out and plan_tb (2D: max(area, 30); 3D: 6 * area -- include/snac_hip.h, "plan generators").  A plan table holds at
+    most 32 767 rows (plan rows are int16: snac_env_desc.num_plans), so the 46 656 triples go through two calls of 23 328 rows each."""
+    from snac_amd import BatchedDMPEnv
+
+    v = _lattice_triangles()
+    masks, areas = _lattice_reference(sparse)
+    P = len(v) // 2
+    assert 2 * P == len(v) and P <= 32767
+    env = BatchedDMPEnv(dim, True, 4, plans=np.zeros((P, 26, 26)))
+    for lo in (0, P):
+        area = env.generate_plans(0, P, sparse=sparse, vertices=v[lo:lo + P]).cpu().numpy()
+        env._sync_plans_full()
+        got = np.asarray(env.plans_full).reshape(P, 26, 26)
+        want = np.zeros((P, 26, 26), np.float64)
+        want[:, 3:23, 3:23] = masks[lo:lo + P] * (6 if dim == 3 else 1)
+        bad = np.flatnonzero((got != want).any((1, 2)))
+        assert bad.size == 0, ("%d plan rows differ; the first: vertices %s" % (bad.size, v[lo + bad[0]].tolist()), got[bad[0], 3:23, 3:23], want[bad[0], 3:23, 3:23])
+        assert np.array_equal(area.astype(np.int64), areas[lo:lo + P])
+        tb = env._plan_tb.cpu().numpy().astype(np.int64)
+        assert np.array_equal(tb, np.maximum(areas[lo:lo + P], 30) if dim == 2 else 6 * areas[lo:lo + P])
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("dim,sparse,P", [(1, 0, 5000), (2, 0, 20000), (2, 1, 20000), (3, 0, 20000), (3, 1, 20000)])
 def test_generated_plans_hip_vs_oracle_and_rollouts_on_them(dim, sparse, P):
