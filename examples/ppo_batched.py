@@ -1,0 +1,84 @@
+"""A vectorised PPO loop on the batched API -- everything stays on the GPU: N envs step per tick with the policy's actions, the steps land
+in a RolloutBuffer (a ReplayRing of horizon + 1 slots with the critic's values and the actions' log-probabilities beside it), the
+advantages and returns of a horizon come from one launch (snac_gae), and every minibatch of the update from one more
+(snac_replay_gather_onpolicy).  The update rule is PPO2's, as in the reference's script/PPO: the clipped surrogate, a value loss and an
+entropy bonus, with advantages normalised over the horizon and an episode's end treated as terminal.  The network is an actor-critic MLP
+over observation + plan; this file is an illustration of the API, not part of the parity surface.
+
+    python examples/ppo_batched.py --envs 4096 --iterations 20
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
+
+from snac_amd import BatchedDMPEnv, RolloutBuffer  # noqa: E402
+
+
+class ActorCritic(nn.Module):
+    def __init__(self, obs_dim, plan_cells, actions, hidden=256):
+        super().__init__()
+        self.body = nn.Sequential(nn.Linear(obs_dim + plan_cells, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh())
+        self.policy = nn.Linear(hidden, actions)
+        self.value = nn.Linear(hidden, 1)
+
+    def forward(self, obs, plan):
+        h = self.body(torch.cat([obs, plan.flatten(1)], dim=1))
+        return self.policy(h), self.value(h).squeeze(1)
+
+
+def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, seed=1,
+        log=print):
+    """-> (the loss of every minibatch update, the mean episodic return after every iteration)"""
+    torch.manual_seed(seed)
+    env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
+    dev = env.device
+    env.reset()
+    buf = RolloutBuffer(env, horizon, gamma, lam)
+    net = ActorCritic(env.obs_dim, 400, env.num_actions).to(dev)
+    opt = torch.optim.Adam(net.parameters(), lr=lr)
+    t0, losses, returns = time.time(), [], []
+    for it in range(iterations):
+        for _ in range(horizon):
+            with torch.no_grad():
+                logits, value = net(env.observe().float(), env.input_plan().float())     # resets change plans
+                dist = torch.distributions.Categorical(logits=logits)
+                actions = dist.sample()
+                buf.act(actions.to(torch.int8), value, dist.log_prob(actions))           # one env tick, recorded in the ring (auto-reset)
+        with torch.no_grad():
+            _, bootstrap = net(env.observe().float(), env.input_plan().float())
+        buf.finish(bootstrap)                                      # advantages and returns of the horizon: one launch
+        for mb in buf.minibatches(batch, epochs):                  # one gather launch each
+            logits, value = net(mb["s"], mb["plan"])
+            dist = torch.distributions.Categorical(logits=logits)
+            ratio = torch.exp(dist.log_prob(mb["action"]) - mb["logp"])
+            surrogate = torch.min(ratio * mb["adv"], torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * mb["adv"]).mean()
+            value_loss = 0.5 * ((value - mb["ret"]) ** 2).mean()
+            loss = -surrogate + vf_coef * value_loss - ent_coef * dist.entropy().mean()
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            nn.utils.clip_grad_norm_(net.parameters(), 0.5)
+            opt.step()
+            losses.append(float(loss.detach()))
+        st = env.episodic_stats()
+        returns.append(st["return_sum"] / max(st["episodes"], 1))
+        log("iteration %3d  loss %.4f  episodes %d  mean return %.2f  mean IoU %.4f  (%.0f env-steps/s incl. learning)" % (
+            it + 1, losses[-1], st["episodes"], returns[-1], st["iou_fx_sum"] / 2.0**40 / max(st["episodes"], 1),
+            envs * horizon * (it + 1) / (time.time() - t0)))
+    return losses, returns
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--iterations", type=int, default=20)
+    ap.add_argument("--horizon", type=int, default=32)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=8192)
+    a = ap.parse_args()
+    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch)

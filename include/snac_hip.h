@@ -398,6 +398,45 @@ int snac_replay_gather_windows(const snac_env_desc* desc, const snac_state* st, 
                                int32_t L, float* s_out, float* s_next_out, float* plan_out, int64_t* action_out, float* reward_out,
                                uint8_t* done_out, uint8_t* mask_out, int32_t* length_out, void* stream);
 
+/* ---- On-policy rollouts (the reference's script/PPO; snac_amd/onpolicy.py: RolloutBuffer; k_onpolicy.hip, k_replay.hip): generalised
+ * advantage estimation over a span of the ring, and a PPO minibatch in one launch.
+ *
+ * snac_gae: reward, done, value, adv and ret are [cap][N].  The span is the `count` slots from `first`, taken modulo cap as in
+ * snac_uct_returns: slot(j) = (first + j) mod cap, j < count; slot(count - 1) is the newest.  value[slot][i] is the critic's value of the
+ * observation env i acted on in that slot; bootstrap[i] is the value of env i's current observation, after the newest slot (NULL: zeros).
+ * Per env i, from the newest slot back to the oldest, in float64:
+ *     c = gamma * lambda            (rounded once, before the loop)
+ *     nv = bootstrap[i]; a = 0.0
+ *     for each slot, newest first:
+ *         r, v, d = reward, value, done != 0
+ *         delta = (r + (d ? 0.0 : gamma * nv)) - v
+ *         a     = delta + (d ? 0.0 : c * a)
+ *         adv[slot][i] = (float)a;  ret[slot][i] = (float)(a + v);  nv = v
+ * Every product, sum and difference is rounded on its own (no fused multiply-add).  done cuts both the bootstrap and the trace: an episode
+ * end is terminal, as in the reference's PPO2 (there is no separate time-limit flag).  Slots outside the span are not written.  adv and ret
+ * must not alias reward, done, value or bootstrap, or each other (documented, not checked).  Checks, all before any HIP call: N >= 1,
+ * cap >= 1, first in [0, cap), count in [0, cap], gamma and lambda finite, no null among reward / done / value / adv / ret; count == 0
+ * returns SNAC_OK without a launch.  No host synchronisation.
+ *
+ * snac_replay_gather_onpolicy: per sample (t, i) = (tick_idx[b], env_idx[b]), clamped into range,
+ *   s_out       the observation acted on: snac_replay_gather's s (the previous slot's row, or the reset observation when
+ *               first_ring[t][i] != 0); there is no s_next
+ *   plan_out    the plan row as in snac_replay_gather, [batch][400 | 30]; may be NULL (2D / 3D: 16-byte aligned)
+ *   action_out  (int64) action_ring[t][i];  value_out, logp_out, ret_out: the float32 entries at [t][i] of their rings
+ *   adv_out     adv_ring[t][i], or with norm != NULL (two floats on the device, {mean, rstd}) (adv - mean) * rstd in float32, difference
+ *               and product each rounded
+ * The conventions are snac_replay_gather_nstep's: tiled != 0 is the tile-major obs_ring, both ring dtypes, the same row lengths (the base
+ * row plus the position tail, else SNAC_ERR_UNSUPPORTED), every argument checked before any HIP call (cap >= 2, batch >= 0, no null ring,
+ * index or output array but plan_out, plan_out needs plan_idx_ring), batch == 0 returns SNAC_OK without a launch, no host synchronisation. */
+#define SNAC_GAE_CHUNK 16 /* slots whose loads snac_gae's kernel issues together (a span's chunk boundaries, for the tests) */
+int snac_gae(int32_t N, int32_t cap, int32_t first, int32_t count, double gamma, double lambda, const float* reward, const uint8_t* done,
+             const float* value, const float* bootstrap, float* adv, float* ret, void* stream);
+int snac_replay_gather_onpolicy(const snac_env_desc* desc, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring,
+                                const uint8_t* first_ring, const int16_t* plan_idx_ring, const int8_t* action_ring, const float* value_ring,
+                                const float* logp_ring, const float* adv_ring, const float* ret_ring, const float* norm,
+                                const int32_t* tick_idx, const int32_t* env_idx, int32_t batch, float* s_out, float* plan_out,
+                                int64_t* action_out, float* value_out, float* logp_out, float* adv_out, float* ret_out, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

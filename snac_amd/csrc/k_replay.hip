@@ -1,7 +1,8 @@
 // k_replay.hip -- walks along one env's column of the replay ring: snac_replay_gather_nstep (Rainbow's multi-step transition: s, the
 // discounted sum of up to n rewards, the row to bootstrap from) and snac_replay_gather_windows (DRQN's Memory.get_batch: up to L
 // consecutive tuples of one episode that end at the sample).  include/snac_hip.h, "n-step transitions and episode windows", has the
-// rules; the tuple of a step, the reset observation and the plan expansion are k_gather's (replay_dev.h).
+// rules; the tuple of a step, the reset observation and the plan expansion are k_gather's (replay_dev.h).  In the same shape, without a
+// walk: snac_replay_gather_onpolicy (PPO's minibatch: s, the plan and five scalars of a sample; the header's "On-policy rollouts").
 #include <cmath>
 #include <cstddef>
 
@@ -247,6 +248,91 @@ __global__ __launch_bounds__(256) void k_gather_windows(const RArgs g) {
     }
 }
 
+// snac_replay_gather_onpolicy (include/snac_hip.h, "On-policy rollouts"): the sample's s, its plan and five scalars of the [cap][N] rings.
+struct PArgs {
+    int32_t n, cap, batch, num_plans;
+    int32_t ld, frame_val, tiled;                                    // as k_gather's
+    const void* obs;
+    const uint8_t* first;
+    const int16_t* plan_idx;
+    const int8_t* action;
+    const float* value;
+    const float* logp;
+    const float* adv;
+    const float* ret;
+    const float* norm;                                               // {mean, rstd} or NULL
+    const int32_t* tick;
+    const int32_t* env;
+    const void* plans;
+    float* s;
+    float* plan_out;
+    int64_t* action_out;
+    float* value_out;
+    float* logp_out;
+    float* adv_out;
+    float* ret_out;
+};
+
+// k_gather's shape without the s_next row: the samples' indices, then their flags and scalars (lane u = sample u), then the predecessor
+// row of every sample of the group, each round issued whole before anything waits on it; then the stores
+template <int KIND, typename OT>
+__global__ __launch_bounds__(256) void k_gather_onpolicy(const PArgs g) {
+    constexpr int PC = KIND == 1 ? 30 : 400;
+    const int lane = threadIdx.x & 63;
+    const int b0 = ((int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * S;   // in scalar registers: the group's control flow is uniform
+    if (b0 >= g.batch) return;
+    const int ns = min(S, g.batch - b0);
+    const int LD = g.ld;
+    const OT* o = (const OT*)g.obs;
+    int t = 0, i = 0, first = 0, act = 0, p = 0;
+    float val = 0.0f, lp = 0.0f, ad = 0.0f, rt = 0.0f, mean = 0.0f, rstd = 1.0f;
+    if (lane < ns) {
+        t = min(max(g.tick[b0 + lane], 0), g.cap - 1);
+        i = min(max(g.env[b0 + lane], 0), g.n - 1);
+        const size_t cur = (size_t)t * g.n + i;
+        first = g.first[cur] != 0;
+        act = g.action[cur];
+        val = g.value[cur]; lp = g.logp[cur]; ad = g.adv[cur]; rt = g.ret[cur];
+        if (g.plan_out) p = min(max((int)g.plan_idx[cur], 0), g.num_plans - 1);
+        if (g.norm) { mean = g.norm[0]; rstd = g.norm[1]; }
+    }
+    // the row loads unconditional, in one block: a lane past the row's end reads its last value again, a sample past the batch's end the
+    // predecessor of (0, 0) (valid addresses, results unused), and the predecessor is read (not stored) also where the step opened an episode
+    OT vprev[S];
+    int fst[S];
+    const int ll = min(lane, LD - 1);
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        const int tu = __builtin_amdgcn_readlane(t, u), iu = __builtin_amdgcn_readlane(i, u);
+        fst[u] = __builtin_amdgcn_readlane(first, u);
+        vprev[u] = o[ring_row(g.tiled, g.cap, g.n, tu == 0 ? g.cap - 1 : tu - 1, iu) * LD + ll];
+    }
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+        if (u < ns && lane < LD) g.s[(size_t)(b0 + u) * LD + lane] = fst[u] ? reset_obs<KIND>(lane, g.frame_val) : (float)vprev[u];
+    }
+    if (lane < ns) {
+        float an = ad;
+        if (g.norm) {
+#pragma clang fp contract(off)                                      // no fma: difference and product each rounded
+            const float df = ad - mean;
+            an = df * rstd;
+        }
+        g.action_out[b0 + lane] = (int64_t)act;
+        g.value_out[b0 + lane] = val;
+        g.logp_out[b0 + lane] = lp;
+        g.adv_out[b0 + lane] = an;
+        g.ret_out[b0 + lane] = rt;
+    }
+    if (g.plan_out) {
+#pragma unroll
+        for (int u = 0; u < S; ++u) {
+            if (u >= ns) break;
+            expand_plan<KIND>(g.plans, __builtin_amdgcn_readlane(p, u), g.plan_out + (size_t)(b0 + u) * PC, lane);
+        }
+    }
+}
+
 // the checks both entry points share, every one before any HIP call; steps: n or L, end: newest or oldest
 int walk_check(const snac_env_desc* d, const snac_state* st, int32_t cap, const void* obs_ring, const uint8_t* first_ring, const uint8_t* done_ring,
                const float* reward_ring, const int8_t* action_ring, const int16_t* plan_idx_ring, int32_t end, const char* end_msg,
@@ -330,6 +416,36 @@ int snac_replay_gather_windows(const snac_env_desc* d, const snac_state* st, int
         hipLaunchKernelGGL((k_gather_windows<decltype(kind)::value, decltype(ot)>), grid, block, 0, (hipStream_t)stream, g);
     });
     return launched("snac_replay_gather_windows");
+}
+
+int snac_replay_gather_onpolicy(const snac_env_desc* d, const snac_state* st, int32_t cap, int32_t tiled, const void* obs_ring,
+                                const uint8_t* first_ring, const int16_t* plan_idx_ring, const int8_t* action_ring, const float* value_ring,
+                                const float* logp_ring, const float* adv_ring, const float* ret_ring, const float* norm,
+                                const int32_t* tick_idx, const int32_t* env_idx, int32_t batch, float* s_out, float* plan_out,
+                                int64_t* action_out, float* value_out, float* logp_out, float* adv_out, float* ret_out, void* stream) {
+    if (int rc = check_common(d, st)) return rc;
+    if (cap < 2 || batch < 0) return fail(SNAC_ERR_ARG, "cap must be >= 2 and batch >= 0");
+    if (!obs_ring || !first_ring || !action_ring || !value_ring || !logp_ring || !adv_ring || !ret_ring) return fail(SNAC_ERR_ARG, "null ring array");
+    if (!tick_idx || !env_idx) return fail(SNAC_ERR_ARG, "null index array");
+    if (plan_out && !plan_idx_ring) return fail(SNAC_ERR_ARG, "plan_out needs plan_idx_ring");
+    if (plan_out && d->kind != SNAC_ENV_1D && ((uintptr_t)plan_out & 15)) return fail(SNAC_ERR_ARG, "plan_out must be 16-byte aligned");
+    if (d->obs_tail & ~SNAC_TAIL_POSITION) return fail(SNAC_ERR_UNSUPPORTED, "replay gather supports the position tail only");
+    if (!s_out || !action_out || !value_out || !logp_out || !adv_out || !ret_out) return fail(SNAC_ERR_ARG, "null output");
+    if (batch == 0) return SNAC_OK;                                  // no sample: no launch
+    PArgs g;
+    std::memset(&g, 0, sizeof(g));
+    g.n = d->num_envs; g.cap = cap; g.batch = batch; g.num_plans = d->num_plans;
+    g.ld = base_obs_dim(d->kind) + tail_len(d->kind, d->obs_tail); g.frame_val = d->frame_value == 2 ? 2 : -1; g.tiled = tiled != 0;
+    g.obs = obs_ring; g.first = first_ring; g.plan_idx = plan_idx_ring; g.action = action_ring; g.value = value_ring; g.logp = logp_ring;
+    g.adv = adv_ring; g.ret = ret_ring; g.norm = norm; g.tick = tick_idx; g.env = env_idx; g.plans = st->plans;
+    g.s = s_out; g.plan_out = plan_out; g.action_out = action_out; g.value_out = value_out; g.logp_out = logp_out; g.adv_out = adv_out;
+    g.ret_out = ret_out;
+    const dim3 grid((unsigned)((batch + 4 * S - 1) / (4 * S))), block(256);
+    g_kernel = "k_gather_onpolicy";
+    by_kind(d, [&](auto kind, auto ot) {
+        hipLaunchKernelGGL((k_gather_onpolicy<decltype(kind)::value, decltype(ot)>), grid, block, 0, (hipStream_t)stream, g);
+    });
+    return launched("snac_replay_gather_onpolicy");
 }
 
 }  // extern "C"

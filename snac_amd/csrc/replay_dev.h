@@ -1,4 +1,4 @@
-// replay_dev.h -- what the replay gathers share (k_gather in k_misc.hip; k_gather_nstep and k_gather_windows in k_replay.hip): where a
+// replay_dev.h -- what the replay gathers share (k_gather in k_misc.hip; k_gather_nstep, k_gather_windows and k_gather_onpolicy in k_replay.hip): where a
 // ring row lies in either layout, the reset observation, and the expansion of a plan row into float32 cells.  include/snac_hip.h,
 // "Minibatch assembly", has the semantics.
 #pragma once

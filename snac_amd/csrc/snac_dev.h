@@ -27,8 +27,10 @@
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows
 //   k_tile{1,2,3}d.hip  the tile kernels k_rollout / k_transition / k_aux (rounds 1-2) behind all of them (templates: k_tile.inc)
 //   k_misc.hip      export / import / equality / plan generators / replay gather, with their entry points
-//   k_replay.hip    k_gather_nstep / k_gather_windows   walks along an env's column of the replay ring: n-step transitions, episode windows
+//   k_replay.hip    k_gather_nstep / k_gather_windows   walks along an env's column of the replay ring: n-step transitions, episode windows;
+//                   k_gather_onpolicy   PPO's minibatch: s, the plan and five scalars of a sample
 //                   (replay_dev.h: the ring's row address, the reset observation and the plan expansion, for these and k_gather)
+//   k_onpolicy.hip  k_gae         generalised advantage estimation over a span of the ring: lane = env, the loads of a chunk of slots issued together
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory
