@@ -37,7 +37,10 @@ class QNet(nn.Module):
         return self.body(torch.cat([obs, plan.flatten(1)], dim=1))
 
 
-def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None):
+def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None,
+        device_sampling=False):
+    """device_sampling: the epsilon-greedy actions come from one launch per tick (BatchedDMPEnv.epsilon_greedy: counter-RNG stream 5,
+    independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax."""
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev = env.device
@@ -53,9 +56,13 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     for tick in range(ticks):
         eps = max(0.05, 1.0 - tick / (0.6 * ticks))
         with torch.no_grad():
-            greedy = net(obs.float(), plan).argmax(dim=1)
-        explore = torch.rand(envs, device=dev) < eps
-        actions = torch.where(explore, torch.randint(0, env.num_actions, (envs,), device=dev), greedy).to(torch.int8)
+            q_now = net(obs.float(), plan)
+        if device_sampling:
+            actions = env.epsilon_greedy(q_now, eps)
+        else:
+            greedy = q_now.argmax(dim=1)
+            explore = torch.rand(envs, device=dev) < eps
+            actions = torch.where(explore, torch.randint(0, env.num_actions, (envs,), device=dev), greedy).to(torch.int8)
         ring.append(actions)                                       # one env tick, recorded in the ring (auto-reset)
         obs = env.observe()
         plan = env.input_plan().float()                            # resets change plans
@@ -97,5 +104,6 @@ if __name__ == "__main__":
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample in proportion to |td|")
     ap.add_argument("--n-step", type=int, default=None, help="multi-step targets: the discounted sum of up to N rewards, bootstrapped N steps on")
+    ap.add_argument("--device-sampling", action="store_true", help="epsilon-greedy on the device from the counter RNG (epsilon_greedy)")
     a = ap.parse_args()
-    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step)
+    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling)

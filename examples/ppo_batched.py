@@ -33,8 +33,10 @@ class ActorCritic(nn.Module):
 
 
 def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, seed=1,
-        log=print):
-    """-> (the loss of every minibatch update, the mean episodic return after every iteration)"""
+        log=print, device_sampling=False):
+    """-> (the loss of every minibatch update, the mean episodic return after every iteration).  device_sampling: draw the actions and
+    their log-probabilities with one launch per tick (RolloutBuffer.act_logits: counter-RNG stream 5, independent of the sharding and of
+    torch's generator) instead of torch.distributions."""
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev = env.device
@@ -47,6 +49,9 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
         for _ in range(horizon):
             with torch.no_grad():
                 logits, value = net(env.observe().float(), env.input_plan().float())     # resets change plans
+                if device_sampling:
+                    buf.act_logits(logits, value)                                        # draw, log-probability and env tick
+                    continue
                 dist = torch.distributions.Categorical(logits=logits)
                 actions = dist.sample()
                 buf.act(actions.to(torch.int8), value, dist.log_prob(actions))           # one env tick, recorded in the ring (auto-reset)
@@ -80,5 +85,6 @@ if __name__ == "__main__":
     ap.add_argument("--horizon", type=int, default=32)
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--device-sampling", action="store_true", help="draw the actions on the device from the counter RNG (act_logits)")
     a = ap.parse_args()
-    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch)
+    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling)

@@ -61,6 +61,8 @@
  *                                   u = (word * total) >> 32, action = the lowest a with N_0 + ... + N_a > u
  *   stream 4 (per sample, draw d):  the entry a prioritised-replay tree draws (snac_prio_sample; "Prioritised replay" below):
  *                                   r = (word(.., 2 * d) << 32) | word(.., 2 * d + 1), keyed by sampler_id + j for sample j of a call
+ *   stream 5 (per env, tick t):     the action a policy's scores give (snac_policy_act; "Acting from a policy" below): categorical
+ *                                   u = (word * total) >> 32 over integer weights, epsilon-greedy from word >> 16 and word & 0xffff
  *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.  The node-pool entry points key edge /
  *   leaf i of a call by env_id_base + i; a search with K paths per tree hands them its B * K slots with env_id_base * K in the descriptor,
  *   so that slot k of tree b draws with (env_id_base + b) * K + k, its slot in the search over all envs ("K paths per tree" below).
@@ -436,6 +438,53 @@ int snac_replay_gather_onpolicy(const snac_env_desc* desc, const snac_state* st,
                                 const float* logp_ring, const float* adv_ring, const float* ret_ring, const float* norm,
                                 const int32_t* tick_idx, const int32_t* env_idx, int32_t batch, float* s_out, float* plan_out,
                                 int64_t* action_out, float* value_out, float* logp_out, float* adv_out, float* ret_out, void* stream);
+
+/* ---- Acting from a policy (snac_amd/batched.py: sample_actions / epsilon_greedy; snac_amd/onpolicy.py: act_logits; k_policy.hip): one
+ * action per env from a row of A = num_actions float32 scores (a policy's logits, or Q-values), in one launch, drawn from counter-RNG stream
+ * 5 so that a trained run does not depend on how its envs are sharded.  The model-free counterpart of snac_uct_pick_moves: the choice is
+ * made in integers.
+ *
+ * snac_policy_act: scores is [N][A], A the num_actions of desc->kind, rows contiguous, the base aligned as a float (a slice of a tensor
+ * will do).  Env i of the call draws with  w = word(desc->seed, 5, desc->env_id_base + i, t).  Per row, s_a = scores[i][a]:
+ *     m    = s_0; for a = 1 .. A-1: if (s_a > m) m = s_a                    (float compares; m is the largest score)
+ *     bad  = some s_a is a NaN or +inf, or m is -inf (every score -inf).  A bad row is drawn in every mode as if all its scores were 0
+ *            (m = 0 too), and adds one to bad_rows[0] (int32 on the device, an atomic add; bad_rows may be NULL).
+ *     g    = the lowest a with s_a == m                                     (the greedy action; +0 and -0 tie)
+ *   mode SNAC_POLICY_CATEGORICAL (softmax sampling).  In float64, every product, sum, difference and quotient rounded on its own (no fused
+ *   multiply-add), sums in index order starting from 0.0:
+ *     x_a   = (double)s_a - (double)m                      e_a = EXP(x_a)
+ *     w_a   = (uint64)floor(e_a * 2^28)                    (exactly 2^28 for a = g; 0 for s_a = -inf or x_a below about -19.4)
+ *     total = w_0 + ... + w_{A-1}   (<= 2^31)              u = ((uint64)w * total) >> 32
+ *     action = the lowest a with w_0 + ... + w_a > u       (an action of weight 0 is never drawn)
+ *     S     = e_0 + ... + e_{A-1}                          T = sum of (e_a == 0 ? 0.0 : e_a * x_a)
+ *     logp[i]    = (float)(x_action - LOG(S))
+ *     entropy[i] = (float)(LOG(S) - T / S)
+ *   mode SNAC_POLICY_GREEDY: action = g.
+ *   mode SNAC_POLICY_EPS_GREEDY: eps = epsilon_per_env ? epsilon_per_env[i] : epsilon (Ape-X's per-actor epsilons);
+ *     v = floor((double)eps * 65536.0); eps_fx = v >= 65536 ? 65536 : v > 0 ? (uint32)v : 0   (a NaN gives 0)
+ *     action = (w >> 16) < eps_fx ? ((w & 0xffff) * A) >> 16 : g
+ *   logp and entropy are defined by the categorical mode only and must be NULL in the other two.
+ * EXP and LOG are these sequences of float64 operations, not a library's (each line's operations rounded one by one, left to right as
+ * parenthesised; constants in C's hexadecimal notation):
+ *     LOG2E = 0x1.71547652b82fep+0   LN2_HI = 0x1.62e42feep-1   LN2_LO = 0x1.a39ef35793c76p-33     (k * LN2_HI is exact for |k| < 2^20)
+ *   EXP(x), x <= 0:  0.0 when x < -45.0 (also -inf: below 2^-53, it would not change S); else
+ *     k = rint(x * LOG2E)  (ties to even)      r = (x - k * LN2_HI) - k * LN2_LO              (|r| < 0.3466)
+ *     p = c_13; for n = 12 down to 0: p = p * r + c_n,   c_n = 1.0 / n!  (n! is exact in float64; the quotient rounded)
+ *     EXP = ldexp(p, (int)k)                   (exact: no subnormal for k >= -65)
+ *   LOG(S), 1 <= S <= 8:
+ *     f, e = frexp(S)  (S = f * 2^e, 0.5 <= f < 1);  if f < 0x1.6a09e667f3bcdp-1 (sqrt 1/2): f = f * 2.0, e = e - 1
+ *     z = (f - 1.0) / (f + 1.0);  z2 = z * z   (|z| < 0.1716)
+ *     q = d_10; for n = 9 down to 0: q = q * z2 + d_n,   d_n = 1.0 / (2 n + 1)
+ *     LOG = (double)e * LN2_HI + ((2.0 * z) * q + (double)e * LN2_LO)
+ *   Both stay within 1e-12 (absolute) of the exact functions over x in [-45, 0] and S in [1, 8]; the truncated series leave less than 5e-18.
+ * Outputs: action int8[N], logp float[N], entropy float[N]; each may be NULL, and with all three NULL nothing is launched.  The kernel never
+ * writes an action outside [0, A), reads scores only and writes nothing but the outputs given and bad_rows[0].
+ * Checks, all before any HIP call: desc and scores non-null, desc->kind one of SNAC_ENV_*, N >= 1, mode one of the three, epsilon finite and
+ * in [0, 1] (every mode), epsilon_per_env NULL unless the mode is SNAC_POLICY_EPS_GREEDY, logp and entropy NULL unless it is
+ * SNAC_POLICY_CATEGORICAL.  desc->num_envs is not read: N is the number of rows.  No host synchronisation. */
+enum { SNAC_POLICY_CATEGORICAL = 0, SNAC_POLICY_GREEDY = 1, SNAC_POLICY_EPS_GREEDY = 2 };
+int snac_policy_act(const snac_env_desc* desc, int32_t N, uint32_t t, int32_t mode, const float* scores, double epsilon,
+                    const float* epsilon_per_env, int8_t* action, float* logp, float* entropy, int32_t* bad_rows, void* stream);
 
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from

@@ -920,6 +920,67 @@ class BatchedDMPEnv:
             _lib.check(self._lib.snac_observe(C.byref(self._desc), C.byref(self._state), _ptr(obs), self._stream()))
         return obs
 
+    # ---- acting from a policy (include/snac_hip.h, "Acting from a policy": counter-RNG stream 5) ------------------------------------
+    def _scores(self, x, what):
+        """`x` as the kernel reads it: float32 [N, num_actions], contiguous, on the device (taken as it is when it is that already)."""
+        if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.device == self.device and x.is_contiguous()):
+            x = torch.as_tensor(x, device=self.device).detach().to(torch.float32).contiguous()
+        if tuple(x.shape) != (self.num_envs, self.num_actions):
+            raise ValueError("%s must have shape (%d, %d), got %s" % (what, self.num_envs, self.num_actions, tuple(x.shape)))
+        return x
+
+    def _policy_act(self, mode, scores, t, epsilon=0.0, epsilon_per_env=None, action=None, logp=None, entropy=None):
+        """One snac_policy_act launch on the current stream; bad rows (NaN, +inf, all -inf) are counted in policy_bad_rows."""
+        if t is None:
+            t = self.t
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0:
+            raise ValueError("t must be an integer >= 0 (None: env.t)")
+        if getattr(self, "policy_bad_rows", None) is None:
+            self.policy_bad_rows = torch.zeros((1,), dtype=torch.int32, device=self.device)   # rows drawn as if all their scores were 0, so far
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.snac_policy_act(C.byref(self._desc), self.num_envs, t & 0xFFFFFFFF, mode, _ptr(scores), epsilon,
+                                                 _ptr(epsilon_per_env), _ptr(action), _ptr(logp), _ptr(entropy), _ptr(self.policy_bad_rows),
+                                                 self._current_stream()))
+
+    def sample_actions(self, logits, t=None, want_logp=True, want_entropy=False, out=None):
+        """One action per env from the softmax of `logits` float32 [N, num_actions], in one launch: the categorical mode of snac_policy_act
+        -- integer weights floor(exp(l - max) * 2^28), the draw from counter-RNG stream 5 keyed by (seed, env_id_base + i, t), so that it
+        does not depend on how the envs are sharded.  t=None: env.t, the tick the action is for (consecutive ticks draw different words, a
+        replay of the run the same ones).  A logit of -inf masks its action; the caller scales logits for a temperature.
+        out: optional preallocated (action int8 [N], logp float32 [N] or None, entropy float32 [N] or None) reused every tick.
+        Returns (action int8 [N], logp float32 [N] or None, entropy float32 [N] or None); logp is the drawn action's log-probability."""
+        scores = self._scores(logits, "logits")
+        N = self.num_envs
+        if out is not None:
+            action, logp, entropy = out
+            action = self._buf(action, (N,), torch.int8, "out[0]")
+            logp = self._buf(logp, (N,), torch.float32, "out[1]") if want_logp else None
+            entropy = self._buf(entropy, (N,), torch.float32, "out[2]") if want_entropy else None
+        else:
+            action = torch.empty((N,), dtype=torch.int8, device=self.device)
+            logp = torch.empty((N,), dtype=torch.float32, device=self.device) if want_logp else None
+            entropy = torch.empty((N,), dtype=torch.float32, device=self.device) if want_entropy else None
+        self._policy_act(_lib.POLICY_CATEGORICAL, scores, t, action=action, logp=logp, entropy=entropy)
+        return action, logp, entropy
+
+    def epsilon_greedy(self, q, epsilon, t=None):
+        """One action per env from Q-values `q` float32 [N, num_actions], in one launch: with probability floor(epsilon * 65536) / 65536 a
+        uniform action, else the lowest index of the largest value, both from one word of counter-RNG stream 5 (snac_policy_act).  epsilon:
+        a number in [0, 1] (0.0: the greedy mode, no draw) or a float32 [N] tensor of per-env epsilons (Ape-X).  t=None: env.t.
+        Returns action int8 [N]."""
+        scores = self._scores(q, "q")
+        action = torch.empty((self.num_envs,), dtype=torch.int8, device=self.device)
+        if torch.is_tensor(epsilon) or isinstance(epsilon, np.ndarray):
+            eps = torch.as_tensor(epsilon, device=self.device).detach().to(torch.float32).contiguous()
+            if tuple(eps.shape) != (self.num_envs,):
+                raise ValueError("epsilon must be a number or hold one value per env")
+            self._policy_act(_lib.POLICY_EPS_GREEDY, scores, t, epsilon_per_env=eps, action=action)
+            return action
+        if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float)) or not 0.0 <= epsilon <= 1.0:
+            raise ValueError("epsilon must be a number in [0, 1] or a float32 [N] tensor")
+        self._policy_act(_lib.POLICY_EPS_GREEDY if epsilon > 0.0 else _lib.POLICY_GREEDY, scores, t, epsilon=float(epsilon), action=action)
+        return action
+
     def iou(self):
         """float64 [N]: env.iou() (1D, 3D) / the caller-side boolean IoU of the 2D scripts."""
         out = torch.empty((self.num_envs,), dtype=torch.float64, device=self.device)

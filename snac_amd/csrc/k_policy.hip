@@ -1,0 +1,182 @@
+// k_policy.hip -- snac_policy_act: one action per env from a row of A float32 scores (categorical, greedy, epsilon-greedy), with the
+// categorical draw's log-probability and entropy.  include/snac_hip.h, "Acting from a policy", has the rule.
+#include <cmath>
+#include <cstddef>
+
+#include "snac_dev.h"
+
+// lane = env: the outputs of a wave are coalesced spans of action / logp / entropy, and nothing crosses lanes.  The scores are read as A
+// strided dword loads per lane, all issued before the first use.  A wave's rows are one contiguous span of 64 * A floats (768 / 1280 /
+// 2048 bytes), so every line a load fetches is used whole and the A - 1 loads after the first hit the lines the first brought in; the rows
+// of 12 and 20 bytes are no multiple of 16 and `scores` is only aligned as a float, so a wide-load form would need an aligned body with
+// ragged ends and an LDS or cross-lane transpose -- for an input of 2 MB at 65 536 envs x 8 actions, which the float64 series below
+// outweighs.  All arrays are indexed by unrolled constants: they live in registers, there is no scratch.
+namespace {
+
+using namespace snac_detail;
+
+struct PolicyArgs {
+    int32_t n;
+    uint32_t t, key;                                                 // key = stream_key(seed, 5)
+    int64_t env_id_base;
+    const float* scores;
+    double epsilon;
+    const float* eps_env;
+    int8_t* action;
+    float* logp;
+    float* entropy;
+    int32_t* bad_rows;
+};
+
+constexpr double LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42feep-1, LN2_LO = 0x1.a39ef35793c76p-33, SQRT_HALF = 0x1.6a09e667f3bcdp-1;
+
+// EXP of the header: x <= 0 (or -inf), never a NaN
+__device__ __forceinline__ double spec_exp(double x) {
+#pragma clang fp contract(off)                                      // every operation rounded on its own, in the header's order
+    constexpr double c[14] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0,
+                              1.0 / 3628800.0, 1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0};
+    const double xc = x < -45.0 ? -45.0 : x;                         // the series runs on a finite argument; the result is dropped below
+    const double k = rint(xc * LOG2E);
+    const double r = (xc - k * LN2_HI) - k * LN2_LO;
+    double p = c[13];
+#pragma unroll
+    for (int n = 12; n >= 0; --n) p = p * r + c[n];
+    const double e = ldexp(p, (int)k);
+    return x < -45.0 ? 0.0 : e;
+}
+
+// LOG of the header: 1 <= s <= 8
+__device__ __forceinline__ double spec_log(double s) {
+#pragma clang fp contract(off)
+    constexpr double d[11] = {1.0, 1.0 / 3.0, 1.0 / 5.0, 1.0 / 7.0, 1.0 / 9.0, 1.0 / 11.0, 1.0 / 13.0, 1.0 / 15.0, 1.0 / 17.0, 1.0 / 19.0, 1.0 / 21.0};
+    int e;
+    double f = frexp(s, &e);
+    if (f < SQRT_HALF) { f = f * 2.0; e = e - 1; }
+    const double z = (f - 1.0) / (f + 1.0);
+    const double z2 = z * z;
+    double q = d[10];
+#pragma unroll
+    for (int n = 9; n >= 0; --n) q = q * z2 + d[n];
+    return (double)e * LN2_HI + ((2.0 * z) * q + (double)e * LN2_LO);
+}
+
+template <int A, int MODE>
+__global__ __launch_bounds__(64) void k_policy_act(const PolicyArgs g) {
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i >= g.n) return;
+    const float* row = g.scores + (size_t)i * A;
+    float s[A];
+#pragma unroll
+    for (int a = 0; a < A; ++a) s[a] = row[a];                       // A loads on their way together
+    float eps = 0.0f;
+    if (MODE == SNAC_POLICY_EPS_GREEDY && g.eps_env) eps = g.eps_env[i];
+    const uint32_t w = rng_word(env_keys(g.key, (uint64_t)(g.env_id_base + i)), g.t);
+
+    float m = s[0];
+    bool bad = false;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+        if (a && s[a] > m) m = s[a];
+        bad |= __builtin_isnan(s[a]) || s[a] == INFINITY;
+    }
+    bad |= m == -INFINITY;
+    if (bad) {                                                       // drawn as if every score were 0
+        m = 0.0f;
+#pragma unroll
+        for (int a = 0; a < A; ++a) s[a] = 0.0f;
+        if (g.bad_rows) atomicAdd(g.bad_rows, 1);
+    }
+    int greedy = A - 1;
+#pragma unroll
+    for (int a = A - 2; a >= 0; --a) greedy = s[a] == m ? a : greedy;    // the lowest index of the largest score
+
+    int action = greedy;
+    if (MODE == SNAC_POLICY_EPS_GREEDY) {
+        const double v = floor((g.eps_env ? (double)eps : g.epsilon) * 65536.0);
+        const uint32_t eps_fx = v >= 65536.0 ? 65536u : v > 0.0 ? (uint32_t)v : 0u;
+        if ((w >> 16) < eps_fx) action = (int)(((w & 0xffffu) * (uint32_t)A) >> 16);
+    }
+    if (MODE == SNAC_POLICY_CATEGORICAL) {
+        double x[A], e[A];
+        uint32_t wt[A], total = 0;                                   // total <= 8 * 2^28 = 2^31
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+            {
+#pragma clang fp contract(off)
+                x[a] = (double)s[a] - (double)m;
+            }
+            e[a] = spec_exp(x[a]);
+            wt[a] = (uint32_t)(uint64_t)floor(e[a] * 268435456.0);   // a power of two: the product is exact
+            total += wt[a];
+        }
+        const uint32_t u = __umulhi(w, total);                       // ((uint64)w * total) >> 32, below total
+        uint32_t cum = 0;
+        bool found = false;
+        double xa = x[A - 1];
+        action = A - 1;
+#pragma unroll
+        for (int a = 0; a < A; ++a) {
+            cum += wt[a];
+            const bool hit = !found && cum > u;
+            action = hit ? a : action;
+            xa = hit ? x[a] : xa;
+            found |= hit;
+        }
+        if (g.logp || g.entropy) {                                   // uniform: kernel arguments
+            double S = 0.0, T = 0.0;
+            {
+#pragma clang fp contract(off)
+#pragma unroll
+                for (int a = 0; a < A; ++a) {
+                    S = S + e[a];
+                    T = T + (e[a] == 0.0 ? 0.0 : e[a] * x[a]);      // x may be -inf where e is 0: that term is 0.0
+                }
+            }
+            const double L = spec_log(S);
+            if (g.logp) {
+#pragma clang fp contract(off)
+                g.logp[i] = (float)(xa - L);
+            }
+            if (g.entropy) {
+#pragma clang fp contract(off)
+                g.entropy[i] = (float)(L - T / S);
+            }
+        }
+    }
+    if (g.action) g.action[i] = (int8_t)action;
+}
+
+template <int A>
+void launch_policy(int mode, const PolicyArgs& g, hipStream_t s) {
+    const dim3 grid((unsigned)(((long long)g.n + 63) / 64)), block(64);
+    if (mode == SNAC_POLICY_CATEGORICAL) hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_CATEGORICAL>), grid, block, 0, s, g);
+    else if (mode == SNAC_POLICY_GREEDY) hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_GREEDY>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_EPS_GREEDY>), grid, block, 0, s, g);
+}
+
+}  // namespace
+
+extern "C" int snac_policy_act(const snac_env_desc* desc, int32_t N, uint32_t t, int32_t mode, const float* scores, double epsilon,
+                               const float* epsilon_per_env, int8_t* action, float* logp, float* entropy, int32_t* bad_rows, void* stream) {
+    using namespace snac_detail;
+    if (!desc || !scores) return fail(SNAC_ERR_ARG, "null desc/scores");
+    snac_sizes sz;
+    if (snac_env_sizes(desc->kind, desc->dynamic != 0, &sz) != SNAC_OK) return fail(SNAC_ERR_ARG, "unknown env kind");
+    if (N < 1) return fail(SNAC_ERR_ARG, "N must be >= 1");
+    if (mode != SNAC_POLICY_CATEGORICAL && mode != SNAC_POLICY_GREEDY && mode != SNAC_POLICY_EPS_GREEDY)
+        return fail(SNAC_ERR_ARG, "mode must be SNAC_POLICY_CATEGORICAL, _GREEDY or _EPS_GREEDY");
+    if (!std::isfinite(epsilon) || epsilon < 0.0 || epsilon > 1.0) return fail(SNAC_ERR_ARG, "epsilon must be finite and in [0, 1]");
+    if (epsilon_per_env && mode != SNAC_POLICY_EPS_GREEDY) return fail(SNAC_ERR_ARG, "epsilon_per_env belongs to the epsilon-greedy mode");
+    if ((logp || entropy) && mode != SNAC_POLICY_CATEGORICAL) return fail(SNAC_ERR_ARG, "logp / entropy are defined by the categorical mode only");
+    if (!action && !logp && !entropy) return SNAC_OK;                // nothing asked for
+    const PolicyArgs g{N, t, stream_key(desc->seed, 5), desc->env_id_base, scores, epsilon, epsilon_per_env, action, logp, entropy, bad_rows};
+    g_kernel = "k_policy_act";
+    const hipStream_t s = (hipStream_t)stream;
+    switch (sz.num_actions) {
+        case 3: launch_policy<3>(mode, g, s); break;
+        case 5: launch_policy<5>(mode, g, s); break;
+        case 8: launch_policy<8>(mode, g, s); break;
+        default: return fail(SNAC_ERR_UNSUPPORTED, "num_actions must be 3, 5 or 8");
+    }
+    return launched("snac_policy_act");
+}

@@ -31,6 +31,7 @@
 //                   k_gather_onpolicy   PPO's minibatch: s, the plan and five scalars of a sample
 //                   (replay_dev.h: the ring's row address, the reset observation and the plan expansion, for these and k_gather)
 //   k_onpolicy.hip  k_gae         generalised advantage estimation over a span of the ring: lane = env, the loads of a chunk of slots issued together
+//   k_policy.hip    k_policy_act  one action per env from a row of policy scores (categorical / greedy / epsilon-greedy), logp and entropy: lane = env
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory

@@ -52,6 +52,7 @@ class RolloutBuffer:
         self.adv = torch.zeros(shape, dtype=torch.float32, device=dev)
         self.ret = torch.zeros(shape, dtype=torch.float32, device=dev)
         self.norm = torch.zeros((2,), dtype=torch.float32, device=dev)    # {mean, 1 / (std + 1e-8)} of adv over the span
+        self._actions = torch.empty((env.num_envs,), dtype=torch.int8, device=dev)      # act_logits(): the actions of the tick, reused
         self.collected = 0                                           # ticks since the last finish()
         self.first = None                                            # the oldest slot of the span finish() filled
 
@@ -63,6 +64,18 @@ class RolloutBuffer:
         self.logp[head].copy_(torch.as_tensor(logp, device=self.env.device).reshape(-1))
         self.ring.append(actions)
         self.collected += 1
+
+    def act_logits(self, logits, value):
+        """act() with the draw on the device: one snac_policy_act launch (BatchedDMPEnv.sample_actions' rule, keyed by env.t) samples the
+        actions from `logits` float32 [N, num_actions] into a reused int8 buffer and writes their log-probabilities straight into the head
+        slot's row of `logp`; then `value` [N] goes to the head slot and the envs step, as in act().  Returns the actions (int8 [N], the
+        buffer the next call overwrites)."""
+        e, head = self.env, self.ring.head
+        e.sample_actions(logits, out=(self._actions, self.logp[head], None))
+        self.value[head].copy_(torch.as_tensor(value, device=e.device).reshape(-1))
+        self.ring.append(self._actions)
+        self.collected += 1
+        return self._actions
 
     def span(self):
         """(first, count): the newest `horizon` slots, oldest first, as snac_gae takes them."""
