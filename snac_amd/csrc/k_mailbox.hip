@@ -15,7 +15,7 @@
 // The state in HBM is complete whenever the host has seen an acknowledgement (the write-through is fenced before the ack), so every
 // other entry point may READ it at any time; entry points that WRITE it bump the mailbox's generation (snac_mailbox_touch) and the
 // wave reloads the records before its next step.
-#include "snac_dev.h"
+#include "snac_units.h"
 
 #include "mailbox_host.h"   // struct snac_mailbox, the host half of the protocol and the entry points (also built by gcc against a fake HIP layer: tests/native)
 

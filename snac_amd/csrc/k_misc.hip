@@ -1,5 +1,5 @@
 // k_misc.hip -- environment_memory export, state import, observation equality, plan generators, replay gather, the episodic sums: kernels and entry points
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "replay_dev.h"
 
 using namespace snac_detail;

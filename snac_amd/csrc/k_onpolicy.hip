@@ -3,7 +3,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 
 // lane = env, as k_uct_returns: every load and store of a wave is one coalesced span of a slot's row.  k_uct_returns walks its slots with
 // one dependent load trip per slot; here the reward / value / done loads of a chunk of K slots all go out before the first dependent

@@ -3,7 +3,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 
 // lane = env: the outputs of a wave are coalesced spans of action / logp / entropy, and nothing crosses lanes.  The scores are read as A
 // strided dword loads per lane, all issued before the first use.  A wave's rows are one contiguous span of 64 * A floats (768 / 1280 /

@@ -3,7 +3,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 
 // Small, latency-bound kernels.  The leaves are written lane = entry; every sum is recomputed from its 64 children by one wavefront
 // (lane = child, a wave reduction, one lane stores the parent), level by level, one launch per level: the launches' order on the stream

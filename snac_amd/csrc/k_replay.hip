@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "replay_dev.h"
 
 // Both kernels have k_gather's shape: 4 waves a block, S samples a wave, and three rounds of loads that each go out for the whole group

@@ -1,5 +1,5 @@
 // k_reset.hip -- k_reset: snac_reset / snac_reset_scalar of EVERY env of a batch (no mask), the canonical layout; k_iou: snac_iou (round 6)
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "rows1d.h"
 
 #ifndef SNAC_RESET_NTZ_MIN_BYTES

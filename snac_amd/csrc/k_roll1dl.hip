@@ -1,5 +1,5 @@
 // k_roll1dl.hip -- k_rollout1dl: 1D fused rollouts of LARGE batches, lane = env (round 6)
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "rows1d.h"
 
 namespace {

@@ -1,5 +1,5 @@
 // k_roll1dt.hip -- k_rollout1dt: time-parallel 1D rollouts
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

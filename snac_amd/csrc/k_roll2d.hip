@@ -1,5 +1,5 @@
 // k_roll2d.hip -- k_rollout2d: the headline kernel
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "tile_order.h"
 
 using snac_detail::tile_order_block;

@@ -1,7 +1,7 @@
 // k_roll2db.h -- k_rollout2db: 2D rollouts by blocks of 64 / 128 / 256 envs (round 5; the kernel: instantiated by k_roll2db.hip for the canonical
 // rows and by k_roll2dbv.hip for the layout variants without the plan tail)
 #pragma once
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

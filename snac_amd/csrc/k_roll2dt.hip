@@ -1,5 +1,5 @@
 // k_roll2dt.hip -- k_rollout2dt: time-parallel 2D rollouts
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // k_roll3d.hip -- k_rollout3d: 3D rollouts of small / odd batches
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

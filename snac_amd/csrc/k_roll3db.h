@@ -1,7 +1,7 @@
 // k_roll3db.h -- k_rollout3db: 3D rollouts by blocks of 64 envs (the kernel; instantiated by k_roll3db.hip for the canonical rows and by
 // k_roll3dbv.hip for the layout variants)
 #pragma once
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

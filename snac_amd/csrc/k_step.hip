@@ -1,5 +1,5 @@
 // k_step.hip -- k_step2d / k_step3d: snac_step on identity rows
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

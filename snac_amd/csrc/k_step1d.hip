@@ -1,5 +1,5 @@
 // k_step1d.hip -- k_step1d: the canonical 1D snac_step on identity rows; k_edges1d: 1D tree edges with gathered rows (round 6)
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "rows1d.h"
 
 namespace {

@@ -1,5 +1,5 @@
 // k_step3dq.hip -- k_step3dq: the canonical 3D step() of trainer-sized batches, 16 envs per wave, four lanes per env
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // k_tile.inc -- the tile kernels of rounds 1-2 (k_rollout / k_transition / k_aux: one tile of E envs per wave, K::step on the
 // bordered LDS image, rows by write_obs) and their launch templates; included by k_tile1d.hip / k_tile2d.hip / k_tile3d.hip, which
 // instantiate them for one env kind each.  Everything the specialised kernels do not take runs here.
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // k_trans.hip -- k_transition2d / k_transition3d / k_edges3d: single steps and tree edges with gathered rows
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

@@ -8,7 +8,7 @@
 #include <cstddef>
 #include <type_traits>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "snac_tune.h"
 #include "uct_dev.h"
 

@@ -5,7 +5,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "uct_dev.h"
 
 // Three small, latency-bound kernels beside k_uct_advance.  pick and returns are lane = tree: a root is one 128-byte line (two when the
@@ -237,7 +237,7 @@ __global__ __launch_bounds__(64) void k_uct_gumbel(const UctGumbel v) {
 }  // namespace
 
 namespace snac_detail {
-// declared in snac_dev.h: k_uct_reanalyse.hip runs the same checks
+// declared in snac_units.h: k_uct_reanalyse.hip runs the same checks
 int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap) {
     if (A != 3 && A != 5 && A != 8) return fail(SNAC_ERR_ARG, "num_actions must be 3, 5 or 8");
     if (!stats) return fail(SNAC_ERR_ARG, "null stats");

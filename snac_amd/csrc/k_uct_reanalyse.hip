@@ -5,7 +5,7 @@
 #include <cmath>
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 #include "uct_dev.h"
 
 // Four small, latency-bound kernels beside those of k_uct_play.hip, with its shapes.  save is lane = piece: the B root records leave as

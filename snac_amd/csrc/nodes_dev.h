@@ -4,7 +4,7 @@
 #pragma once
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 
 // ------------------------------------------------------------------------------------------------
 // The record map, in 16-byte pieces (include/snac_hip.h has the structs):

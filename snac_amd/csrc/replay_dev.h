@@ -2,7 +2,7 @@
 // ring row lies in either layout, the reset observation, and the expansion of a plan row into float32 cells.  include/snac_hip.h,
 // "Minibatch assembly", has the semantics.
 #pragma once
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace snac_detail {
 

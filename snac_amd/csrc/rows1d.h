@@ -1,6 +1,6 @@
 // rows1d.h -- the 1D observation rows of a wave of 64 envs (lane = env) as ONE run of 64 x 7 values: k_rollout1dl, k_step1d.  Internal.
 #pragma once
-#include "snac_dev.h"
+#include "snac_units.h"
 
 namespace {
 

@@ -1,6 +1,6 @@
 // snac_hip.hip -- the C ABI of include/snac_hip.h and the dispatch: which kernel a call runs on (choose()) and its launch (launch()).
-// The kernels live in the k_*.hip translation units beside this one (snac_dev.h has the map), trajectory memory in snac_traj.hip.
-#include "snac_dev.h"
+// The kernels live in the k_*.hip translation units beside this one (snac_units.h has the map), trajectory memory in snac_traj.hip.
+#include "snac_units.h"
 
 #include <atomic>
 

@@ -8,7 +8,7 @@
 #pragma once
 #include <cstddef>
 
-#include "snac_dev.h"
+#include "snac_units.h"
 
 // ------------------------------------------------------------------------------------------------
 // The row's map, in 16-byte pieces (include/snac_hip.h has the struct): line 0 is all that selection compares, line 1 the node's own.

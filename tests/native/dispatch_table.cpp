@@ -12,7 +12,7 @@
 // the aligned pointers only (the runs under a knob override: the environment is read once per process).
 // tests/test_dispatch_host.py compares the sha256 of every run with tests/golden/dispatch_overrides.sha256, and the lines of the full run
 // that carry a list (with the static float64 canonical aligned ones) with tests/golden/dispatch_table.txt.
-#include "snac_dev.h"
+#include "snac_units.h"
 
 #include <cstdint>
 #include <map>
@@ -28,7 +28,7 @@ hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "(no HIP runtime in this program)"; }
 }
 
-// ---- the stubs: the signatures of snac_dev.h
+// ---- the stubs: the signatures of snac_units.h
 namespace snac_detail {
 void launch_tile1d(Op, bool, int E, int, const KArgs&, hipStream_t) { REC("tile1d E=%d", E); }
 void launch_tile2d(Op, bool, int E, int, const KArgs&, hipStream_t) { REC("tile2d E=%d", E); }

@@ -36,6 +36,30 @@ def test_library_exports_every_declared_symbol():
     assert defined == names
 
 
+def test_kernel_source_header_holds_no_unit_map_and_no_host_side():
+    """snac_dev.h is kernel source only (its hash stamps profiles/traffic.json): snac_units.h alone includes it, and the map of the
+    translation units, the shared checks, the dispatch and the launcher declarations stay out of it."""
+    csrc = os.path.join(helpers.ROOT, "snac_amd", "csrc")
+    includers = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))
+                       and re.search(r'#\s*include\s*[<"]snac_dev\.h[>"]', open(os.path.join(csrc, f), errors="replace").read()))
+    assert includers == ["snac_units.h"]
+    dev = open(os.path.join(csrc, "snac_dev.h")).read()
+    for word in ("launch_", "check_common", "nodes_check", "play_check", "choose("):
+        assert word not in dev, word
+    assert not re.findall(r"\bk_\w*\.hip\b", dev)
+
+
+def test_traffic_profile_is_stamped_with_the_kernel_source():
+    """profiles/traffic.json carries the counters of the headline kernel as it is now: a change to snac_dev.h or k_roll2d.hip takes
+    the FETCH_SIZE / WRITE_SIZE passes again in the same change (bench.py reports no measured traffic otherwise)."""
+    import json
+
+    from snac_amd import _lib
+
+    with open(os.path.join(helpers.ROOT, "profiles", "traffic.json")) as fh:
+        assert json.load(fh)["source_sha16"] == _lib.kernel_source_sha16()
+
+
 def test_env_sizes_match_reference_constants():
     from snac_amd import _lib
 

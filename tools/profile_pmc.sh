@@ -15,7 +15,7 @@ for C in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE
          "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_ACTIVE_INST_FLAT SQ_INSTS_BRANCH SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_IFETCH" \
          "SQ_INSTS_VMEM SQ_INST_CYCLES_VMEM_WR SQ_VMEM_WR_TA_DATA_FIFO_FULL SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   i=$((i+1))
-  timeout 150 rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -o pmc -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu $ARGS > $OUT/p$i.log 2>&1
+  timeout -k 10 150 rocprofv3 --pmc $C --output-format csv -d $OUT/p$i -o pmc -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu $ARGS > $OUT/p$i.log 2>&1 || exit $?
 done
 cd $ROOT
 python3 tools/summarize_prof.py $OUT > $OUT/summary.txt 2>&1
