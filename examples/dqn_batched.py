@@ -4,7 +4,7 @@ are appended with ReplayRing.append), minibatches come from snac_replay_gather. 
 reference's 2D dynamic DQN (script/DQN/2d/DQN_2d_dynamic.py: observation 51 + plan 400 -> 5 Q values, target network,
 replace every `replace` steps); this file is an illustration of the API, not part of the parity surface.
 
-    python examples/dqn_batched.py --envs 4096 --ticks 200 [--prioritized] [--n-step N]
+    python examples/dqn_batched.py --envs 4096 --ticks 200 [--prioritized] [--n-step N] [--distributional [--atoms K --vmin V --vmax V]]
 
 --prioritized: prioritised replay as in the reference's script/Rainbow, with the sum tree on the device (ReplayRing(prioritized=True)):
 minibatches are drawn in proportion to |td|, the loss is weighted by the importance weights, and the sampled transitions get their new
@@ -13,6 +13,14 @@ priorities after every step.
 --n-step N: Rainbow's multi-step target (ReplayRing.sample(n_step=N, gamma=gamma), one gather launch): the minibatch carries the discounted
 sum of up to N rewards, the row N steps on (or where the episode or the ring ended) and the discount that goes with it, and the target is
 return + discount * max Q(s_next).  It works together with --prioritized.
+
+--distributional: Rainbow's categorical (C51) value head with CategoricalSupport.  The network ends in A * K logits, a softmax per action;
+the agent acts on the expected values (expected(), one launch), and the target is the projection of return + discount * z under the target
+network's distribution of the action the online network prefers in s_next (project(), one launch, the same bytes on every run; double DQN
+as in the reference's Rainbow).  The loss is the cross-entropy between that target and the online distribution of the action taken; with
+--prioritized it is weighted by the importance weights and its per-sample values are the new priorities.  The support: a 2D step pays 0
+or 5 and never less, so a return lies in [0, 5 / (1 - gamma)] = [0, 100] at gamma = 0.95; these are the defaults of --vmin / --vmax.  The
+projection clamps what falls outside, so a narrower choice is safe too, only coarser at its ends.
 """
 import argparse
 import os
@@ -24,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, ReplayRing  # noqa: E402
+from snac_amd import BatchedDMPEnv, CategoricalSupport, ReplayRing  # noqa: E402
 
 
 class QNet(nn.Module):
@@ -38,8 +46,11 @@ class QNet(nn.Module):
 
 
 def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None,
-        device_sampling=False):
-    """device_sampling: the epsilon-greedy actions come from one launch per tick (BatchedDMPEnv.epsilon_greedy: counter-RNG stream 5,
+        device_sampling=False, distributional=False, atoms=51, vmin=None, vmax=None, info=None, projection=None):
+    """distributional: the C51 head and target (the module's docstring); vmin / vmax None: 0 and 5 / (1 - gamma).  info: an optional dict
+    that receives the run's device counters ("bad_rows": the samples project() zeroed).  projection: a callable
+    (p_next, ret, discount, p_select=) -> m in place of CategoricalSupport.project, for comparisons (tools/c51_time.py).
+    device_sampling: the epsilon-greedy actions come from one launch per tick (BatchedDMPEnv.epsilon_greedy: counter-RNG stream 5,
     independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax."""
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
@@ -49,14 +60,25 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     ring.collect(prefill)                                          # random policy, one fused launch
     obs = env.observe()
     plan = env.input_plan().float()
-    net, target = QNet(env.obs_dim, 400, env.num_actions).to(dev), QNet(env.obs_dim, 400, env.num_actions).to(dev)
+    heads = env.num_actions
+    if distributional:
+        support = CategoricalSupport(env, atoms=atoms, vmin=0.0 if vmin is None else vmin, vmax=5.0 / (1.0 - gamma) if vmax is None else vmax)
+        heads = env.num_actions * atoms
+
+        def dist(model, o, pl, log=False):                         # [B, A, K]: a distribution per action
+            logits = model(o, pl).view(-1, env.num_actions, atoms)
+            return logits.log_softmax(-1) if log else logits.softmax(-1).contiguous()
+
+        def project(p_next, ret, disc, p_select):
+            return support.project(p_next, ret, disc, p_select=p_select, want_action=False)[0]
+    net, target = QNet(env.obs_dim, 400, heads).to(dev), QNet(env.obs_dim, 400, heads).to(dev)
     target.load_state_dict(net.state_dict())
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     t0, losses, returns = time.time(), [], []
     for tick in range(ticks):
         eps = max(0.05, 1.0 - tick / (0.6 * ticks))
         with torch.no_grad():
-            q_now = net(obs.float(), plan)
+            q_now = support.expected(dist(net, obs.float(), plan)) if distributional else net(obs.float(), plan)
         if device_sampling:
             actions = env.epsilon_greedy(q_now, eps)
         else:
@@ -70,19 +92,33 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
         if n_step is not None:
             how.update(n_step=n_step, gamma=gamma)
         mb = ring.sample(batch, **how)
-        with torch.no_grad():
-            q_next = target(mb["s_next"], mb["plan"]).max(dim=1).values
-            if n_step is None:
-                y = mb["reward"] + gamma * q_next * (~mb["done"]).float()
-            else:                                                  # the plan does not change inside an episode: step 0's serves s_next
-                y = mb["return"] + mb["discount"] * q_next
-        q = net(mb["s"], mb["plan"]).gather(1, mb["action"][:, None]).squeeze(1)
-        if prioritized:
-            td = q - y
-            loss = (mb["weight"] * td ** 2).mean()
-            ring.update_priorities(mb["index"], td.detach().abs())
+        if distributional:
+            with torch.no_grad():                                  # the plan does not change inside an episode: step 0's serves s_next
+                ret = mb["reward"] if n_step is None else mb["return"]
+                disc = gamma * (~mb["done"]).float() if n_step is None else mb["discount"]
+                m = (projection or project)(dist(target, mb["s_next"], mb["plan"]), ret.float().contiguous(), disc.float().contiguous(),
+                                            p_select=dist(net, mb["s_next"], mb["plan"]))
+            logp = dist(net, mb["s"], mb["plan"], log=True)[torch.arange(batch, device=dev), mb["action"]]
+            ce = -(m * logp).sum(1)                                # per sample: the cross-entropy of the target and the online distribution
+            if prioritized:
+                loss = (mb["weight"] * ce).mean()
+                ring.update_priorities(mb["index"], ce.detach())
+            else:
+                loss = ce.mean()
         else:
-            loss = nn.functional.mse_loss(q, y)
+            with torch.no_grad():
+                q_next = target(mb["s_next"], mb["plan"]).max(dim=1).values
+                if n_step is None:
+                    y = mb["reward"] + gamma * q_next * (~mb["done"]).float()
+                else:                                              # the plan does not change inside an episode: step 0's serves s_next
+                    y = mb["return"] + mb["discount"] * q_next
+            q = net(mb["s"], mb["plan"]).gather(1, mb["action"][:, None]).squeeze(1)
+            if prioritized:
+                td = q - y
+                loss = (mb["weight"] * td ** 2).mean()
+                ring.update_priorities(mb["index"], td.detach().abs())
+            else:
+                loss = nn.functional.mse_loss(q, y)
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
@@ -94,6 +130,8 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
             log("tick %4d  eps %.2f  loss %.4f  episodes %d  mean return %.2f  mean IoU %.4f  (%.0f env-steps/s incl. learning)" % (
                 tick + 1, eps, losses[-1], st["episodes"], returns[-1], st["iou_fx_sum"] / 2.0**40 / max(st["episodes"], 1),
                 envs * (tick + 1) / (time.time() - t0)))
+    if info is not None and distributional:
+        info["bad_rows"] = int(support.bad_rows.cpu()[0])
     return losses, returns
 
 
@@ -105,5 +143,10 @@ if __name__ == "__main__":
     ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample in proportion to |td|")
     ap.add_argument("--n-step", type=int, default=None, help="multi-step targets: the discounted sum of up to N rewards, bootstrapped N steps on")
     ap.add_argument("--device-sampling", action="store_true", help="epsilon-greedy on the device from the counter RNG (epsilon_greedy)")
+    ap.add_argument("--distributional", action="store_true", help="the categorical (C51) head and the projected target (CategoricalSupport)")
+    ap.add_argument("--atoms", type=int, default=51, help="--distributional: the atoms of the support")
+    ap.add_argument("--vmin", type=float, default=None, help="--distributional: the support's lowest value (default 0)")
+    ap.add_argument("--vmax", type=float, default=None, help="--distributional: the support's highest value (default 5 / (1 - gamma))")
     a = ap.parse_args()
-    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling)
+    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling, distributional=a.distributional,
+        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax)

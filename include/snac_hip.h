@@ -486,6 +486,45 @@ enum { SNAC_POLICY_CATEGORICAL = 0, SNAC_POLICY_GREEDY = 1, SNAC_POLICY_EPS_GREE
 int snac_policy_act(const snac_env_desc* desc, int32_t N, uint32_t t, int32_t mode, const float* scores, double epsilon,
                     const float* epsilon_per_env, int8_t* action, float* logp, float* entropy, int32_t* bad_rows, void* stream);
 
+/* ---- Distributional targets (the reference's script/Rainbow; snac_amd/distributional.py: CategoricalSupport; k_dist.hip): the expected
+ * values of categorical (C51) value distributions, the greedy / double-DQN choice of the next action, and the projection of the
+ * distributional TD target onto the support, each in one launch and by a rule that restates in numpy byte for byte: no atomics on
+ * floats, every sum in a stated order.
+ *
+ * Support: K = atoms, 2 <= K <= 64, vmin < vmax, both finite.  dz = (vmax - vmin) / (double)(K - 1), computed once on the host in double;
+ * z_i = vmin + (double)i * dz.  All arithmetic below is float64, and every product, sum, difference and quotient is rounded on its own (no
+ * fused multiply-add).  Distributions are float32, [B][A][K] with A = num_actions (3, 5 or 8, else SNAC_ERR_UNSUPPORTED), contiguous, the
+ * base aligned as a float (a row is 204 bytes at K = 51).
+ *
+ * The expected value E(p) of a row p[0..K):
+ *     x_j = (double)p_j * z_j for j < K, x_j = 0.0 for K <= j < 64
+ *     for s = 32, 16, 8, 4, 2, 1:  x_j = x_j + x_{j+s} for every j < s     (all j of a step together: a shuffle-down tree, lane = atom)
+ *     E(p) = x_0
+ * snac_c51_expect: q[b][a] = (float)E(p[b][a]); q is [B][A].
+ *
+ * snac_c51_project, per sample b:
+ *   The choice.  q_a = E(p_select[b][a]), with p_select = p_next when it is NULL (double DQN gives the online network's distributions as
+ *   p_select and the target network's as p_next).  best = q_0, a_star = 0; for a = 1 .. A-1: if (q_a > best) { best = q_a; a_star = a; }.
+ *   So ties go to the lowest index, a NaN never wins, and no input gives an a_star outside [0, A).  q_star[b] = (float)E(p_next[b][a_star]).
+ *   The projection.  r = (double)ret[b], d = (double)discount[b], p_i = (double)p_next[b][a_star][i], acc[0..K) = 0.0.
+ *   For i = 0 .. K-1, in this order:
+ *     t = r + d * z_i;   t = t < vmin ? vmin : t;   t = t > vmax ? vmax : t
+ *     pos = (t - vmin) / dz;   l = min((int)floor(pos), K - 1);   f = pos - (double)l
+ *     if l == K - 1:  acc[l] = acc[l] + p_i
+ *     else:           acc[l] = acc[l] + p_i * (1.0 - f);  then  acc[l+1] = acc[l+1] + p_i * f
+ *   m[b][j] = (float)acc[j].  (The l, l + 1, fraction form of the textbook's floor / ceil projection: it needs none of its l == u repairs
+ *   and stays within 2^-24 of it.)  The rule fixes the order of the additions into each acc[j] -- i ascending, within one i the lower term
+ *   first -- not how a kernel finds them.
+ *   Bad samples.  A sample whose ret or discount is not finite, or whose discount < 0, gets a row m[b] of zeros, a_star[b] = 0,
+ *   q_star[b] = 0 and adds one to bad_rows[0] (int32 on the device, an atomic add).  Probabilities are not checked: a NaN in p_next shows
+ *   in m (and in q_star); it never indexes anything.
+ * Outputs: m float[B][K]; a_star int8[B], q_star float[B] and bad_rows may each be NULL and are then not written.  The kernels read their
+ * inputs only and write nothing but the outputs given.  Checks, all before any HIP call: p (p_next), ret, discount, m (q) non-null,
+ * B >= 1, atoms in [2, 64], vmin and vmax finite with vmin < vmax, num_actions 3, 5 or 8.  No host synchronisation. */
+int snac_c51_expect(int32_t B, int32_t num_actions, int32_t atoms, double vmin, double vmax, const float* p, float* q, void* stream);
+int snac_c51_project(int32_t B, int32_t num_actions, int32_t atoms, double vmin, double vmax, const float* p_next, const float* p_select,
+                     const float* ret, const float* discount, float* m, int8_t* a_star, float* q_star, int32_t* bad_rows, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

@@ -33,6 +33,8 @@
 //                   (replay_dev.h: the ring's row address, the reset observation and the plan expansion, for these and k_gather)
 //   k_onpolicy.hip  k_gae         generalised advantage estimation over a span of the ring: lane = env, the loads of a chunk of slots issued together
 //   k_policy.hip    k_policy_act  one action per env from a row of policy scores (categorical / greedy / epsilon-greedy), logp and entropy: lane = env
+//   k_dist.hip      k_c51_expect / k_c51_project   categorical (C51) value distributions: expected values, the choice of the next action and the
+//                                 projected TD target: lane = atom, a wave per sample, the scatter turned into an ordered gather
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory

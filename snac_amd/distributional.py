@@ -1,0 +1,133 @@
+"""CategoricalSupport: categorical (C51) value distributions on the device (include/snac_hip.h, "Distributional targets";
+snac_amd/csrc/k_dist.hip).
+
+A support of `atoms` values z_i = vmin + i * dz behind two launches that never wait for the device: the expected values of a batch of
+distributions (what an agent acts on), and Rainbow's target -- the greedy or double-DQN choice of the next action and the projection of
+return + discount * z onto the support.  Both follow a rule of float64 operations in a stated order, so the same inputs give the same
+bytes on every run; the textbook composition in torch ends in index_add_, whose float atomics land in any order.
+
+    support = CategoricalSupport(env, atoms=51, vmin=-10.0, vmax=10.0)           # or CategoricalSupport(5, ..., device="cuda:0")
+    q = support.expected(online(s).view(-1, A, 51).softmax(-1))                  # float32 [B, A]
+    action = env.epsilon_greedy(q, eps)
+    m, a_star, _ = support.project(target_p(s_next), ret, discount, p_select=online_p(s_next))      # m: float32 [B, 51]
+    loss = -(m * online(s).view(-1, A, 51).log_softmax(-1)[range(B), action]).sum(1)
+
+The loss and its gradient are the caller's, in torch.
+"""
+import ctypes as C
+import math
+
+import torch
+
+from . import _lib
+from ._lib import ptr as _ptr
+
+MAX_ATOMS = 64
+
+
+class CategoricalSupport:
+    def __init__(self, num_actions, atoms=51, vmin=-10.0, vmax=10.0, device=None):
+        """num_actions: 3, 5 or 8 (the envs' action counts), or a BatchedDMPEnv, whose num_actions, device and stream are then taken;
+        atoms: 2 .. 64; vmin < vmax, both finite; device: a cuda device (not with an env)."""
+        self.env = None
+        if hasattr(num_actions, "num_actions") and hasattr(num_actions, "device"):
+            if device is not None:
+                raise ValueError("device is the env's when an env is given")
+            self.env, device, num_actions = num_actions, num_actions.device, num_actions.num_actions
+        if isinstance(num_actions, bool) or not isinstance(num_actions, int) or num_actions not in (3, 5, 8):
+            raise ValueError("num_actions must be 3, 5 or 8 (or a BatchedDMPEnv)")
+        if isinstance(atoms, bool) or not isinstance(atoms, int) or not 2 <= atoms <= MAX_ATOMS:
+            raise ValueError("atoms must be an integer in [2, %d]" % MAX_ATOMS)
+        for name, v in (("vmin", vmin), ("vmax", vmax)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError("%s must be a finite number" % name)
+        if not vmin < vmax:
+            raise ValueError("vmin must be below vmax")
+        if device is None:
+            raise ValueError("device must be given (or an env)")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("device must be a cuda device: the distributions live in device memory")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.num_actions, self.atoms, self.vmin, self.vmax = num_actions, atoms, float(vmin), float(vmax)
+        self.dz = (self.vmax - self.vmin) / float(atoms - 1)          # the header's dz: one float64 quotient
+        self._lib = _lib.lib()
+        self._z = self._bad = None                                   # made on first use: the constructor does not touch the device
+
+    def _stream(self):
+        if self.env is not None:
+            return self.env._current_stream()
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    @property
+    def z(self):
+        """float32 [atoms] on the device: the support, rounded from the rule's float64 z_i (for the caller's own losses)."""
+        if self._z is None:
+            self._z = torch.tensor([self.vmin + float(i) * self.dz for i in range(self.atoms)], dtype=torch.float64).to(torch.float32).to(self.device)
+        return self._z
+
+    @property
+    def bad_rows(self):
+        """int32 [1] on the device: the samples project() has zeroed so far (ret or discount not finite, or discount < 0)."""
+        if self._bad is None:
+            self._bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        return self._bad
+
+    def _check(self, t, shape, dtype, what):
+        """`t` is what the kernel reads or writes: a contiguous `dtype` tensor of `shape` (None: any size) on the device."""
+        shown = "(%s)" % ", ".join("B" if s is None else str(s) for s in shape) if len(shape) > 1 else "(%s,)" % ("B" if shape[0] is None else shape[0])
+        if not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shown, self.device))
+        if t.dim() != len(shape) or any(s is not None and int(g) != s for g, s in zip(t.shape, shape)) or t.shape[0] < 1:
+            raise ValueError("%s must have shape %s, got %s" % (what, shown, tuple(t.shape)))
+        if t.device != self.device:
+            raise ValueError("%s must be on %s" % (what, self.device))
+        return t
+
+    def _call(self, fn, B, *args):
+        with torch.cuda.device(self.device):
+            _lib.check(fn(B, self.num_actions, self.atoms, self.vmin, self.vmax, *args, self._stream()))
+
+    def expected(self, p, out=None):
+        """float32 [B, A]: the expected value of every distribution of p, float32 [B, A, atoms] (snac_c51_expect, one launch).  It feeds
+        env.epsilon_greedy(q, eps) when acting.  out: an optional preallocated float32 [B, A]."""
+        A, K = self.num_actions, self.atoms
+        p = self._check(p, (None, A, K), torch.float32, "p")
+        B = int(p.shape[0])
+        q = torch.empty((B, A), dtype=torch.float32, device=self.device) if out is None else self._check(out, (B, A), torch.float32, "out")
+        self._call(self._lib.snac_c51_expect, B, _ptr(p), _ptr(q))
+        return q
+
+    def project(self, p_next, ret, discount, p_select=None, out=None, want_action=True, want_q=False):
+        """The distributional target of a minibatch (snac_c51_project, one launch): per sample the action a_star with the largest expected
+        value under p_select (None: p_next itself; double DQN gives the online network's distributions of s_next), lowest index on ties,
+        and the distribution of ret + discount * z under p_next[b, a_star], clamped to [vmin, vmax] and shared between the two nearest
+        atoms.  p_next, p_select: float32 [B, A, atoms]; ret, discount: float32 [B] (mb["return"], mb["discount"] of an n-step sample, or
+        reward and gamma * (1 - done)).  A sample whose ret or discount is not finite, or whose discount is negative, gets a zero row,
+        action 0 and value 0, and is counted in bad_rows.  out: optional preallocated (m float32 [B, atoms], a_star int8 [B] or None,
+        q_star float32 [B] or None).  Returns (m, a_star or None, q_star or None); q_star is the expected value of p_next[b, a_star]."""
+        A, K = self.num_actions, self.atoms
+        p_next = self._check(p_next, (None, A, K), torch.float32, "p_next")
+        B = int(p_next.shape[0])
+        if p_select is not None:
+            p_select = self._check(p_select, (B, A, K), torch.float32, "p_select")
+        ret = self._check(ret, (B,), torch.float32, "ret")
+        discount = self._check(discount, (B,), torch.float32, "discount")
+        m, a_star, q_star = out if out is not None else (None, None, None)
+        m = torch.empty((B, K), dtype=torch.float32, device=self.device) if m is None else self._check(m, (B, K), torch.float32, "out[0]")
+        if not want_action:
+            a_star = None
+        elif a_star is None:
+            a_star = torch.empty((B,), dtype=torch.int8, device=self.device)
+        else:
+            a_star = self._check(a_star, (B,), torch.int8, "out[1]")
+        if not want_q:
+            q_star = None
+        elif q_star is None:
+            q_star = torch.empty((B,), dtype=torch.float32, device=self.device)
+        else:
+            q_star = self._check(q_star, (B,), torch.float32, "out[2]")
+        self._call(self._lib.snac_c51_project, B, _ptr(p_next), _ptr(p_select), _ptr(ret), _ptr(discount), _ptr(m), _ptr(a_star), _ptr(q_star),
+                   _ptr(self.bad_rows))
+        return m, a_star, q_star
