@@ -525,6 +525,47 @@ int snac_c51_expect(int32_t B, int32_t num_actions, int32_t atoms, double vmin, 
 int snac_c51_project(int32_t B, int32_t num_actions, int32_t atoms, double vmin, double vmax, const float* p_next, const float* p_select,
                      const float* ret, const float* discount, float* m, int8_t* a_star, float* q_star, int32_t* bad_rows, void* stream);
 
+/* ---- Soft values (discrete SAC) (the reference's script/SAC; snac_amd/sac.py: SoftValue; k_soft.hip, soft_rule.h): the three losses of
+ * discrete SAC are functions of one softmax of the policy's logits and one elementwise minimum of two critics over A = num_actions values
+ * per sample.  One launch gives the soft state value, the TD target, the entropy and the gradient of the actor loss with respect to the
+ * logits, by a rule that restates in numpy byte for byte; the entropy is snac_policy_act's, the same bytes.
+ *
+ * Inputs per sample b: logits[b][A], q1[b][A] and q2[b][A] (q2 may be NULL: one critic), float32, rows contiguous, every base aligned as
+ * a float (a slice of a tensor will do); ret[b] and discount[b], float32, read only for y; alpha[0], one float32 on the device (the
+ * temperature is a learned parameter; no host synchronisation).  A = 3, 5 or 8, else SNAC_ERR_UNSUPPORTED.
+ * All arithmetic is float64, every product, sum, difference and quotient rounded on its own (no fused multiply-add), sums in index order
+ * starting from 0.0; EXP and LOG are the sequences of "Acting from a policy".  With l_a = logits[b][a]:
+ *     m      = l_0; for a = 1 .. A-1: if (l_a > m) m = l_a                     (float compares, as snac_policy_act)
+ *     x_a    = (double)l_a - (double)m             e_a = EXP(x_a)
+ *     S      = e_0 + ... + e_{A-1}                 T = sum of (e_a == 0 ? 0.0 : e_a * x_a)            L = LOG(S)
+ *     live_a = e_a != 0                            (not live: l_a = -inf, or more than 45 below the largest -- a masked action)
+ *     pi_a   = e_a / S                             lp_a = x_a - L
+ *     qm_a   = (double)(q2 && q2_a < q1_a ? q2_a : q1_a)                       (a float compare; a NaN in q2 never wins)
+ *     al     = (double)alpha[0]
+ *     d_a    = live_a ? qm_a - al * lp_a : 0.0
+ *     V      = sum of (live_a ? pi_a * d_a : 0.0)
+ *     v[b]       = (float)V
+ *     y[b]       = (float)((double)ret[b] + (double)discount[b] * V)
+ *     entropy[b] = (float)(L - T / S)
+ *     grad[b][a] = live_a ? (float)(scale * (pi_a * (V - d_a))) : 0.0f         (scale: e.g. 1.0 / B for the mean over a minibatch)
+ *   grad is the derivative with respect to the logits of the actor loss J = sum_a pi_a (al * log pi_a - qm_a) = -V, with qm and al held
+ *   constant: dJ/dl_j = pi_j ((al * lp_j - qm_j) - J) = pi_j (V - d_j) (DESIGN.md section 3.10 derives it).
+ *   Masked actions.  A q-value at a masked action is never read into a sum: a NaN there does not show, and grad there is exactly 0.
+ *   A q-value that is not finite at a live action shows in that sample's v, y and grad as the rule's operations carry it (a NaN, or an
+ *   infinity); which NaN is not part of the rule.  It never indexes anything.
+ *   Bad samples.  A sample is bad if some l_a is a NaN or +inf or every l_a is -inf; if y is asked for and ret or discount is not finite
+ *   or discount < 0; or if alpha[0] is read (below) and is not finite or negative -- then every sample of the call is bad.  A bad sample
+ *   gets v = y = entropy = 0, a row of zeros in grad, and adds one to bad_rows[0] (int32 on the device, an atomic add).
+ * Outputs: v float[B], y float[B], entropy float[B], grad float[B][A] and bad_rows may each be NULL and are then not written; with v, y,
+ * entropy and grad all NULL nothing is launched.  With v, y and grad all NULL (the entropy alone) q1, q2 and alpha are not read and may
+ * be NULL; otherwise q1 and alpha are required.  ret and discount are required when y is given and must be NULL when it is not.  The
+ * kernel reads its inputs only and writes nothing but the outputs given.
+ * Checks, all before any HIP call: logits non-null, B >= 1, scale finite, the pointers as just stated, num_actions 3, 5 or 8.  No host
+ * synchronisation. */
+int snac_soft_value(int32_t B, int32_t num_actions, const float* logits, const float* q1, const float* q2, const float* alpha,
+                    const float* ret, const float* discount, double scale, float* v, float* y, float* entropy, float* grad,
+                    int32_t* bad_rows, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

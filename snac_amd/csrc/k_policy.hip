@@ -4,6 +4,7 @@
 #include <cstddef>
 
 #include "snac_units.h"
+#include "spec_math.h"
 
 // lane = env: the outputs of a wave are coalesced spans of action / logp / entropy, and nothing crosses lanes.  The scores are read as A
 // strided dword loads per lane, all issued before the first use.  A wave's rows are one contiguous span of 64 * A floats (768 / 1280 /
@@ -14,6 +15,7 @@
 namespace {
 
 using namespace snac_detail;
+using namespace snac_spec;                                          // spec_exp / spec_log: EXP and LOG of the header
 
 struct PolicyArgs {
     int32_t n;
@@ -27,38 +29,6 @@ struct PolicyArgs {
     float* entropy;
     int32_t* bad_rows;
 };
-
-constexpr double LOG2E = 0x1.71547652b82fep+0, LN2_HI = 0x1.62e42feep-1, LN2_LO = 0x1.a39ef35793c76p-33, SQRT_HALF = 0x1.6a09e667f3bcdp-1;
-
-// EXP of the header: x <= 0 (or -inf), never a NaN
-__device__ __forceinline__ double spec_exp(double x) {
-#pragma clang fp contract(off)                                      // every operation rounded on its own, in the header's order
-    constexpr double c[14] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0,
-                              1.0 / 3628800.0, 1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0};
-    const double xc = x < -45.0 ? -45.0 : x;                         // the series runs on a finite argument; the result is dropped below
-    const double k = rint(xc * LOG2E);
-    const double r = (xc - k * LN2_HI) - k * LN2_LO;
-    double p = c[13];
-#pragma unroll
-    for (int n = 12; n >= 0; --n) p = p * r + c[n];
-    const double e = ldexp(p, (int)k);
-    return x < -45.0 ? 0.0 : e;
-}
-
-// LOG of the header: 1 <= s <= 8
-__device__ __forceinline__ double spec_log(double s) {
-#pragma clang fp contract(off)
-    constexpr double d[11] = {1.0, 1.0 / 3.0, 1.0 / 5.0, 1.0 / 7.0, 1.0 / 9.0, 1.0 / 11.0, 1.0 / 13.0, 1.0 / 15.0, 1.0 / 17.0, 1.0 / 19.0, 1.0 / 21.0};
-    int e;
-    double f = frexp(s, &e);
-    if (f < SQRT_HALF) { f = f * 2.0; e = e - 1; }
-    const double z = (f - 1.0) / (f + 1.0);
-    const double z2 = z * z;
-    double q = d[10];
-#pragma unroll
-    for (int n = 9; n >= 0; --n) q = q * z2 + d[n];
-    return (double)e * LN2_HI + ((2.0 * z) * q + (double)e * LN2_LO);
-}
 
 template <int A, int MODE>
 __global__ __launch_bounds__(64) void k_policy_act(const PolicyArgs g) {

@@ -35,6 +35,8 @@
 //   k_policy.hip    k_policy_act  one action per env from a row of policy scores (categorical / greedy / epsilon-greedy), logp and entropy: lane = env
 //   k_dist.hip      k_c51_expect / k_c51_project   categorical (C51) value distributions: expected values, the choice of the next action and the
 //                                 projected TD target: lane = atom, a wave per sample, the scatter turned into an ordered gather
+//   k_soft.hip      k_soft_value  discrete SAC's soft state value, TD target, entropy and actor-loss gradient from one softmax: lane = sample
+//                   (spec_math.h: EXP and LOG of the header, for this and k_policy.hip; soft_rule.h: the per-sample rule, host and device)
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory
