@@ -1,6 +1,5 @@
-// k_misc.hip -- environment_memory export, state import, observation equality, plan generators, replay gather, the episodic sums: kernels and entry points
+// k_misc.hip -- environment_memory export, state import, observation equality, plan generators, the episodic sums: kernels and entry points
 #include "snac_units.h"
-#include "replay_dev.h"
 
 using namespace snac_detail;
 
@@ -281,80 +280,6 @@ __global__ __launch_bounds__(256) void k_discount(int H, int m, const float* rew
 }
 
 // ------------------------------------------------------------------------------------------------
-// replay sampling (the step after the env path: script/DQN/2d/DQN_2d_dynamic.py:122-124,145-166 keeps
-// (s, a, r, s', plan) tuples in a python deque and re-assembles float32 minibatches on the host).  The rollout output
-// ring obs[cap][N][D] already holds every s' -- and s is the previous tick's row, or the constant reset observation when
-// the step opened an episode -- so sampling is a gather: one wave per sample, float32 out, plan expanded from the table.
-struct GArgs {
-    int32_t n, cap, batch, num_plans;
-    int32_t ld, frame_val;     // row length (K::D, + the position tail) and frame value of the ring's layout
-    int32_t tiled;             // obs is [ceil(n / 64)][cap][64][ld] instead of [cap][n][ld]
-    const void* obs;
-    const uint8_t* first;
-    const int16_t* plan_idx;
-    const int32_t* tick;
-    const int32_t* env;
-    const void* plans;
-    float* s;
-    float* s_next;
-    float* plan_out;
-};
-
-template <int KIND, typename OT>
-__global__ __launch_bounds__(256) void k_gather(const GArgs g) {
-    // S samples per wave: the index loads of all of them first (lane u = sample u), then every row load of the group in flight
-    // before the first store -- one sample per wave was a chain of three dependent loads with a single row in flight.
-    constexpr int PC = KIND == 1 ? 30 : 400, S = 4;
-    const int lane = threadIdx.x & 63;
-    const int b0 = ((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * S;
-    if (b0 >= g.batch) return;
-    const int ns = min(S, g.batch - b0);
-    const int LD = g.ld;                                         // D, or D + the position tail (1 / 2 values)
-    const OT* o = (const OT*)g.obs;
-    // lane u < ns: the sample's slot, env, first-step flag and plan row
-    int t = 0, i = 0, first = 0, p = 0;
-    if (lane < ns) {
-        t = min(max(g.tick[b0 + lane], 0), g.cap - 1);
-        i = min(max(g.env[b0 + lane], 0), g.n - 1);
-        const size_t cur = (size_t)t * g.n + i;
-        first = g.first[cur] != 0;
-        if (g.plan_out) p = min(max((int)g.plan_idx[cur], 0), g.num_plans - 1);
-    }
-    OT vcur[S], vprev[S];
-    int fst[S];
-#pragma unroll
-    for (int u = 0; u < S; ++u) {
-        const int tu = __builtin_amdgcn_readlane(t, u), iu = __builtin_amdgcn_readlane(i, u);
-        fst[u] = __builtin_amdgcn_readlane(first, u);
-        const int tp = tu == 0 ? g.cap - 1 : tu - 1;
-        const size_t ocur = ring_row(g.tiled, g.cap, g.n, tu, iu), oprev = ring_row(g.tiled, g.cap, g.n, tp, iu);
-        vcur[u] = (OT)0; vprev[u] = (OT)0;
-        if (u < ns && lane < LD) {
-            vcur[u] = o[ocur * LD + lane];
-            if (!fst[u]) vprev[u] = o[oprev * LD + lane];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < S; ++u) {
-        if (u < ns && lane < LD) {
-            const size_t b = (size_t)(b0 + u);
-            g.s_next[b * LD + lane] = (float)vcur[u];
-            const float sv = fst[u] ? reset_obs<KIND>(lane, g.frame_val) : (float)vprev[u];
-            g.s[b * LD + lane] = sv;
-        }
-    }
-    if (g.plan_out) {
-#pragma unroll
-        for (int u = 0; u < S; ++u) {
-            if (u >= ns) break;
-            const int pu = __builtin_amdgcn_readlane(p, u);
-            expand_plan<KIND>(g.plans, pu, g.plan_out + (size_t)(b0 + u) * PC, lane);
-        }
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------
 // plan rows from grids (hindsight relabelling): the DRQN_hindsight scripts overwrite the hindsight env's
 // plan with the finished episode's own final grid and replay the recorded actions against it
 // (script/DRQN_hindsight/2d/DRQN_hindsight_2D_dynamic.py:270-282: plan[3:23, 3:23] = environment_memory[3:23, 3:23]).  Here the
@@ -501,52 +426,6 @@ int snac_episodic_sums(const snac_env_desc* d, const snac_state* st, int64_t* ou
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail_hip(e, "episodic sums launch");
     return SNAC_OK;
-}
-
-static int replay_gather(const snac_env_desc* d, const snac_state* st, int32_t cap, const void* obs_ring,
-                         const uint8_t* first_ring, const int16_t* plan_idx_ring, const int32_t* tick_idx,
-                         const int32_t* env_idx, int32_t batch, float* s_out, float* s_next_out, float* plan_out,
-                         void* stream, int tiled) {
-    if (int rc = check_common(d, st)) return rc;
-    if (cap < 2 || batch < 0) return fail(SNAC_ERR_ARG, "cap must be >= 2 and batch >= 0");
-    if (!obs_ring || !first_ring || !tick_idx || !env_idx || !s_out || !s_next_out) return fail(SNAC_ERR_ARG, "null pointer");
-    if (plan_out && !plan_idx_ring) return fail(SNAC_ERR_ARG, "plan_out needs plan_idx_ring");
-    if (plan_out && d->kind != SNAC_ENV_1D && ((uintptr_t)plan_out & 15)) return fail(SNAC_ERR_ARG, "plan_out must be 16-byte aligned");
-    if (d->obs_tail & ~SNAC_TAIL_POSITION) return fail(SNAC_ERR_UNSUPPORTED, "replay gather supports the position tail only");
-    if (batch == 0) return SNAC_OK;
-    GArgs g;
-    g.ld = base_obs_dim(d->kind) + tail_len(d->kind, d->obs_tail); g.frame_val = d->frame_value == 2 ? 2 : -1;
-    g.n = d->num_envs; g.cap = cap; g.batch = batch; g.num_plans = d->num_plans; g.tiled = tiled;
-    g.obs = obs_ring; g.first = first_ring; g.plan_idx = plan_idx_ring; g.tick = tick_idx; g.env = env_idx;
-    g.plans = st->plans; g.s = s_out; g.s_next = s_next_out; g.plan_out = plan_out;
-    hipStream_t s = (hipStream_t)stream;
-    const bool f32 = d->obs_dtype == SNAC_OBS_F32;
-    // (round 4: a variant that takes whole groups of 16 samples with 16-byte stores -- lane = piece of the group's consecutive rows --
-    // was built and measured: 0.0382 against 0.0352 ms per 65 536 samples for this kernel, which already runs at 5.3 TB/s = 0.66 of the
-    // peak; what rounds 2 and 3 reported as "0.23-0.30" was the Python wrapper's own index kernels.  Not kept; tools/gather_time.py)
-    const dim3 grid((unsigned)((batch + 15) / 16)), block(256);   // 4 waves x 4 samples (S of k_gather; 8 were no faster)
-    void (*kern)(const GArgs);
-    if (d->kind == SNAC_ENV_1D) kern = f32 ? k_gather<1, float> : k_gather<1, double>;
-    else if (d->kind == SNAC_ENV_2D) kern = f32 ? k_gather<2, float> : k_gather<2, double>;
-    else kern = f32 ? k_gather<3, float> : k_gather<3, double>;
-    hipLaunchKernelGGL(kern, grid, block, 0, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "gather launch");
-    return SNAC_OK;
-}
-
-int snac_replay_gather(const snac_env_desc* d, const snac_state* st, int32_t cap, const void* obs_ring,
-                       const uint8_t* first_ring, const int16_t* plan_idx_ring, const int32_t* tick_idx,
-                       const int32_t* env_idx, int32_t batch, float* s_out, float* s_next_out, float* plan_out,
-                       void* stream) {
-    return replay_gather(d, st, cap, obs_ring, first_ring, plan_idx_ring, tick_idx, env_idx, batch, s_out, s_next_out, plan_out, stream, 0);
-}
-
-int snac_replay_gather_tiled(const snac_env_desc* d, const snac_state* st, int32_t cap, const void* obs_ring,
-                             const uint8_t* first_ring, const int16_t* plan_idx_ring, const int32_t* tick_idx,
-                             const int32_t* env_idx, int32_t batch, float* s_out, float* s_next_out, float* plan_out,
-                             void* stream) {
-    return replay_gather(d, st, cap, obs_ring, first_ring, plan_idx_ring, tick_idx, env_idx, batch, s_out, s_next_out, plan_out, stream, 1);
 }
 
 int snac_import_state(const snac_env_desc* d, const snac_state* st, int32_t m, const int32_t* dst_index, const int32_t* position,

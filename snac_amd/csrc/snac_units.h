@@ -27,10 +27,12 @@
 //   k_mailbox.hip   k_mailbox     the resident stepper behind the drop-in classes (mailbox_host.h: the host half of its protocol)
 //   k_trans.hip     k_transition2d / 3d, k_edges3d: single steps and tree edges with gathered rows
 //   k_tile{1,2,3}d.hip  the tile kernels k_rollout / k_transition / k_aux (rounds 1-2) behind all of them (templates: k_tile.inc)
-//   k_misc.hip      export / import / equality / plan generators / replay gather, with their entry points
-//   k_replay.hip    k_gather_nstep / k_gather_windows   walks along an env's column of the replay ring: n-step transitions, episode windows;
+//   k_misc.hip      export / import / equality / plan generators / the episodic sums, with their entry points
+//   k_replay.hip    k_gather      minibatches out of the replay ring: the tuple of a step (s, s', the plan), 4 samples a wave;
+//                   k_gather_nstep / k_gather_windows   walks along an env's column of the ring: n-step transitions, episode windows;
 //                   k_gather_onpolicy   PPO's minibatch: s, the plan and five scalars of a sample
-//                   (replay_dev.h: the ring's row address, the reset observation and the plan expansion, for these and k_gather)
+//                   (at its head, once for all four: the argument head, a lane's sample pick, the ring's row address, the reset
+//                   observation and the plan expansion; on the host the two halves of the shared check and by_kind)
 //   k_onpolicy.hip  k_gae         generalised advantage estimation over a span of the ring: lane = env, the loads of a chunk of slots issued together
 //   k_policy.hip    k_policy_act  one action per env from a row of policy scores (categorical / greedy / epsilon-greedy), logp and entropy: lane = env
 //   k_dist.hip      k_c51_expect / k_c51_project   categorical (C51) value distributions: expected values, the choice of the next action and the

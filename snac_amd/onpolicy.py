@@ -13,14 +13,13 @@ finish()).  The extra slot is the predecessor row of the oldest step, so all `ho
         ...                                              # mb["s"], ["plan"], ["action"], ["value"], ["logp"], ["adv"], ["ret"]
 
 include/snac_hip.h, "On-policy rollouts", has both rules.  Nothing here waits for the device."""
-import ctypes as C
 import math
 
 import torch
 
 from . import _lib
 from ._lib import ptr as _ptr
-from .replay import ReplayRing
+from .replay import ReplayRing, _outputs, _pairs, _with_plan
 
 GAE_CHUNK = _lib.GAE_CHUNK                                           # slots per chunk of snac_gae's kernel (SNAC_GAE_CHUNK)
 
@@ -117,25 +116,13 @@ class RolloutBuffer:
         if not isinstance(normalise, bool):
             raise ValueError("normalise must be a bool")
         e, r = self.env, self.ring
-        slot = torch.as_tensor(slot, device=e.device).to(torch.int32).contiguous()
-        env_index = torch.as_tensor(env_index, device=e.device).to(torch.int32).contiguous()
-        B = int(slot.numel())
-        s = torch.empty((B, e.obs_dim), dtype=torch.float32, device=e.device)
-        plan = torch.empty((B, r.plan_cells), dtype=torch.float32, device=e.device) if with_plan else None
-        action = torch.empty((B,), dtype=torch.int64, device=e.device)
-        value = torch.empty((B,), dtype=torch.float32, device=e.device)
-        logp = torch.empty((B,), dtype=torch.float32, device=e.device)
-        adv = torch.empty((B,), dtype=torch.float32, device=e.device)
-        ret = torch.empty((B,), dtype=torch.float32, device=e.device)
-        with torch.cuda.device(e.device):
-            _lib.check(e._lib.snac_replay_gather_onpolicy(
-                C.byref(e._desc), C.byref(e._state), r.cap, int(r.tiled), _ptr(r.obs), _ptr(r.first), _ptr(r.plan_idx), _ptr(r.action),
-                _ptr(self.value), _ptr(self.logp), _ptr(self.adv), _ptr(self.ret), _ptr(self.norm) if normalise else None, _ptr(slot),
-                _ptr(env_index), B, _ptr(s), _ptr(plan), _ptr(action), _ptr(value), _ptr(logp), _ptr(adv), _ptr(ret), e._stream()))
-        out = dict(s=s, action=action, value=value, logp=logp, adv=adv, ret=ret)
-        if with_plan:
-            out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
-        return out
+        slot, env_index, B = _pairs(e, slot, env_index)
+        new = _outputs(torch.empty, e)
+        s, plan, action = new(B, e.obs_dim), new(B, r.plan_cells) if with_plan else None, new(B, dtype=torch.int64)
+        value, logp, adv, ret = new(B), new(B), new(B), new(B)
+        rings = (r.obs, r.first, r.plan_idx, r.action, self.value, self.logp, self.adv, self.ret, self.norm if normalise else None)
+        r._gather_call(e._lib.snac_replay_gather_onpolicy, rings, slot, env_index, (), (s, plan, action, value, logp, adv, ret))
+        return _with_plan(e, dict(s=s, action=action, value=value, logp=logp, adv=adv, ret=ret), plan)
 
     def minibatches(self, batch, epochs=1, normalise=True, generator=None):
         """`epochs` passes over the span finish() filled, each in a new random order: every (slot, env) of the span once per epoch, in

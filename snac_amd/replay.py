@@ -44,6 +44,25 @@ def _walk_gamma(gamma):
     return float(gamma)
 
 
+def _pairs(env, slot, env_index):
+    """(slot, env) pairs as the gather entry points take them: two contiguous int32 tensors on the env's device, and their count B"""
+    slot = torch.as_tensor(slot, device=env.device).to(torch.int32).contiguous()
+    env_index = torch.as_tensor(env_index, device=env.device).to(torch.int32).contiguous()
+    return slot, env_index, int(slot.numel())
+
+
+def _outputs(empty, env):
+    """new(*shape, dtype=float32): an output of a gather call on the env's device, allocated by `empty`, the calling module's torch.empty"""
+    return lambda *shape, dtype=torch.float32: empty(shape, dtype=dtype, device=env.device)
+
+
+def _with_plan(env, out, plan):
+    """The dict of a gather with the plan in its shape, [B, 20, 20] (1D: [B, 30]), where one was asked for"""
+    if plan is not None:
+        out["plan"] = plan if env.kind == 1 else plan.view(plan.shape[0], 20, 20)
+    return out
+
+
 class ReplayRing:
     def __init__(self, env, capacity_ticks, layout="ticks", place_candidates=0, memory="malloc", prioritized=False, priority_scale_log2=16):
         """env: BatchedDMPEnv (already reset); capacity_ticks: ring length in vector steps (>= 2).
@@ -185,32 +204,26 @@ class ReplayRing:
         """Minibatch for explicit (slot, env) pairs -> dict of float32 / int tensors on the device:
         s [B, D], s_next [B, D], action [B], reward [B], done [B] (bool), plan [B, 20, 20] (1D: [B, 30])."""
         e = self.env
-        slot = torch.as_tensor(slot, device=e.device).to(torch.int32).contiguous()
-        env_index = torch.as_tensor(env_index, device=e.device).to(torch.int32).contiguous()
-        B = int(slot.numel())
-        s = torch.empty((B, e.obs_dim), dtype=torch.float32, device=e.device)
-        s_next = torch.empty_like(s)
-        plan = torch.empty((B, self.plan_cells), dtype=torch.float32, device=e.device) if with_plan else None
-        with torch.cuda.device(e.device):
-            fn = e._lib.snac_replay_gather_tiled if self.tiled else e._lib.snac_replay_gather
-            _lib.check(fn(C.byref(e._desc), C.byref(e._state), self.cap, _ptr(self.obs), _ptr(self.first),
-                          _ptr(self.plan_idx), _ptr(slot), _ptr(env_index), B, _ptr(s), _ptr(s_next), _ptr(plan), e._stream()))
+        slot, env_index, B = _pairs(e, slot, env_index)
+        new = _outputs(torch.empty, e)
+        s, s_next, plan = new(B, e.obs_dim), new(B, e.obs_dim), new(B, self.plan_cells) if with_plan else None
+        self._gather_call(e._lib.snac_replay_gather_tiled if self.tiled else e._lib.snac_replay_gather, (self.obs, self.first, self.plan_idx),
+                          slot, env_index, (), (s, s_next, plan), layout_arg=False)
         # action / reward / done of the samples: ONE flat index and three 1-D gathers (two-index advanced indexing was five index
         # kernels that took as long as the gather kernel itself, tools/gather_time.py)
         flat = slot.long() * e.num_envs + env_index.long()
-        out = dict(s=s, s_next=s_next, action=self.action.view(-1)[flat].long(), reward=self.reward.view(-1)[flat],
-                   done=self.done.view(-1)[flat].bool())
-        if with_plan:
-            out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
-        return out
+        return _with_plan(e, dict(s=s, s_next=s_next, action=self.action.view(-1)[flat].long(), reward=self.reward.view(-1)[flat],
+                                  done=self.done.view(-1)[flat].bool()), plan)
 
-    def _walk_call(self, fn, slot, env_index, end, steps, gamma, outs):
-        """The arguments the two walking entry points share, up to the outputs."""
+    def _gather_call(self, fn, rings, slot, env_index, extra, outs, layout_arg=True):
+        """The one place that builds a gather call: desc, state, cap, the layout flag (the plain gather has an entry point per layout
+        instead), the ring arrays (an integer among them, the walks' end, passes as it is), the pairs and their count, `extra`, the
+        outputs and the stream; on the env's device, checked."""
         e = self.env
-        head = (C.byref(e._desc), C.byref(e._state), self.cap, int(self.tiled), _ptr(self.obs), _ptr(self.first), _ptr(self.done),
-                _ptr(self.reward), _ptr(self.action), _ptr(self.plan_idx), end, _ptr(slot), _ptr(env_index), int(slot.numel()), steps)
+        head = [C.byref(e._desc), C.byref(e._state), self.cap] + ([int(self.tiled)] if layout_arg else [])
+        rings = [a if isinstance(a, int) else _ptr(a) for a in rings]
         with torch.cuda.device(e.device):
-            _lib.check(fn(*head, *gamma, *[_ptr(o) for o in outs], e._stream()))
+            _lib.check(fn(*head, *rings, _ptr(slot), _ptr(env_index), int(slot.numel()), *extra, *[_ptr(o) for o in outs], e._stream()))
 
     def gather_nstep(self, slot, env_index, n, gamma, with_plan=True):
         """n-step transitions from explicit (slot, env) pairs (Rainbow's multi-step memory): the walk starts at the pair's step and ends
@@ -220,24 +233,16 @@ class ReplayRing:
         out["return"] + out["discount"] * max_a Q(out["s_next"]).  One launch; n = 1 is gather()."""
         n, gamma = _walk_steps("n", n), _walk_gamma(gamma)
         e = self.env
-        slot = torch.as_tensor(slot, device=e.device).to(torch.int32).contiguous()
-        env_index = torch.as_tensor(env_index, device=e.device).to(torch.int32).contiguous()
-        B = int(slot.numel())
-        s = torch.empty((B, e.obs_dim), dtype=torch.float32, device=e.device)
-        s_next = torch.empty((B, e.obs_dim), dtype=torch.float32, device=e.device)
-        plan = torch.empty((B, self.plan_cells), dtype=torch.float32, device=e.device) if with_plan else None
-        action = torch.empty((B,), dtype=torch.int64, device=e.device)
-        ret = torch.empty((B,), dtype=torch.float32, device=e.device)
-        discount = torch.empty((B,), dtype=torch.float32, device=e.device)
-        done = torch.empty((B,), dtype=torch.bool, device=e.device)
-        steps = torch.empty((B,), dtype=torch.int32, device=e.device)
-        self._walk_call(e._lib.snac_replay_gather_nstep, slot, env_index, (self.head - 1) % self.cap, n, (gamma,),
-                        (s, s_next, plan, action, ret, discount, done, steps))
+        slot, env_index, B = _pairs(e, slot, env_index)
+        new = _outputs(torch.empty, e)
+        s, s_next, plan = new(B, e.obs_dim), new(B, e.obs_dim), new(B, self.plan_cells) if with_plan else None
+        action, ret, discount = new(B, dtype=torch.int64), new(B), new(B)
+        done, steps = new(B, dtype=torch.bool), new(B, dtype=torch.int32)
+        rings = (self.obs, self.first, self.done, self.reward, self.action, self.plan_idx, (self.head - 1) % self.cap)
+        self._gather_call(e._lib.snac_replay_gather_nstep, rings, slot, env_index, (n, gamma), (s, s_next, plan, action, ret, discount, done, steps))
         out = dict(s=s, s_next=s_next, action=action, done=done, discount=discount, steps=steps)
         out["return"] = ret
-        if with_plan:
-            out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
-        return out
+        return _with_plan(e, out, plan)
 
     def gather_windows(self, slot, env_index, length, with_plan=True):
         """Windows of up to `length` consecutive transitions of one env inside ONE episode that END at the explicit (slot, env) pairs
@@ -248,23 +253,14 @@ class ReplayRing:
         start.  One launch that reads the length + 1 distinct rows of a window once each; length = 1 is gather()."""
         L = _walk_steps("length", length)
         e = self.env
-        slot = torch.as_tensor(slot, device=e.device).to(torch.int32).contiguous()
-        env_index = torch.as_tensor(env_index, device=e.device).to(torch.int32).contiguous()
-        B = int(slot.numel())
-        s = torch.empty((B, L, e.obs_dim), dtype=torch.float32, device=e.device)
-        s_next = torch.empty((B, L, e.obs_dim), dtype=torch.float32, device=e.device)
-        plan = torch.empty((B, self.plan_cells), dtype=torch.float32, device=e.device) if with_plan else None
-        action = torch.empty((B, L), dtype=torch.int64, device=e.device)
-        reward = torch.empty((B, L), dtype=torch.float32, device=e.device)
-        done = torch.empty((B, L), dtype=torch.bool, device=e.device)
-        mask = torch.empty((B, L), dtype=torch.bool, device=e.device)
-        length = torch.empty((B,), dtype=torch.int32, device=e.device)
-        self._walk_call(e._lib.snac_replay_gather_windows, slot, env_index, (self.head - self.valid_ticks()) % self.cap, L, (),
-                        (s, s_next, plan, action, reward, done, mask, length))
-        out = dict(s=s, s_next=s_next, action=action, reward=reward, done=done, mask=mask, length=length)
-        if with_plan:
-            out["plan"] = plan if e.kind == 1 else plan.view(B, 20, 20)
-        return out
+        slot, env_index, B = _pairs(e, slot, env_index)
+        new = _outputs(torch.empty, e)
+        s, s_next, plan = new(B, L, e.obs_dim), new(B, L, e.obs_dim), new(B, self.plan_cells) if with_plan else None
+        action, reward = new(B, L, dtype=torch.int64), new(B, L)
+        done, mask, length = new(B, L, dtype=torch.bool), new(B, L, dtype=torch.bool), new(B, dtype=torch.int32)
+        rings = (self.obs, self.first, self.done, self.reward, self.action, self.plan_idx, (self.head - self.valid_ticks()) % self.cap)
+        self._gather_call(e._lib.snac_replay_gather_windows, rings, slot, env_index, (L,), (s, s_next, plan, action, reward, done, mask, length))
+        return _with_plan(e, dict(s=s, s_next=s_next, action=action, reward=reward, done=done, mask=mask, length=length), plan)
 
     def _draw(self, batch, generator, prioritized, beta, stratified):
         """The transitions of a minibatch -> slot, env, and for prioritized=True what sample() adds (index, prob, weight), else None."""

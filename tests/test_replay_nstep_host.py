@@ -1,6 +1,6 @@
 """Host: snac_replay_gather_nstep and snac_replay_gather_windows are exported and check every argument before any HIP call -- each failing
 call below fails its checks first, so the placeholder pointers are never dereferenced, and an empty batch returns 0 although no device
-exists to launch on -- and ReplayRing.sample(n_step=) / gather_nstep() / gather_windows() / sample_windows() reject bad arguments on an
+exists to launch on (so do snac_replay_gather and snac_replay_gather_tiled, the plain gather beside them) -- and ReplayRing.sample(n_step=) / gather_nstep() / gather_windows() / sample_windows() reject bad arguments on an
 object that was never built on a device.  Last, the two rules as include/snac_hip.h states them ("n-step transitions and episode
 windows"), in numpy, independently of the kernels (tests/test_gpu_replay_nstep.py compares the kernels with them): n = 1 and L = 1 are the
 tuple of snac_replay_gather, and the constructed rings that the GPU test uses meet every stop of both walks."""
@@ -92,6 +92,42 @@ def test_gather_windows_validates_its_arguments_before_any_hip_call():
     for name in ("reward_out", "mask", "length_out"):
         _err(L, _windows(L, **{name: None}), b"null output")
     assert _windows(L, batch=0, length=64, oldest=7) == 0
+
+
+def _plain(L, fn="snac_replay_gather", desc=True, st=True, kind=2, tail=0, cap=8, obs=PH, first=PH, plan_idx=PH, tick=PH, env=PH, batch=4, s=PH,
+           s_next=PH, plan=PH):
+    d, state = _desc(kind, tail), _lib.State(1, 1, 1, 1, 1, 1, 1, 1)     # never dereferenced
+    return getattr(L, fn)(C.byref(d) if desc else None, C.byref(state) if st else None, cap, obs, first, plan_idx, tick, env, batch, s, s_next,
+                          plan, None)
+
+
+@pytest.mark.parametrize("fn", ["snac_replay_gather", "snac_replay_gather_tiled"])
+def test_the_plain_gather_validates_its_arguments_before_any_hip_call(fn):
+    L = _lib.lib()
+    assert len(getattr(L, fn).argtypes) == 13
+    call = lambda **kw: _plain(L, fn, **kw)  # noqa: E731
+    _err(L, call(desc=False), b"null desc/state")
+    _err(L, call(st=False), b"null desc/state")
+    _err(L, call(cap=1), b"cap must be")
+    _err(L, call(batch=-1), b"batch >= 0")
+    for name in ("obs", "first", "tick", "env", "s", "s_next"):
+        _err(L, call(**{name: None}), b"null pointer")
+        _err(L, call(batch=0, **{name: None}), b"null pointer")      # the checks come before the empty batch
+    _err(L, call(plan_idx=None), b"plan_out needs plan_idx_ring")
+    for kind in (2, 3):
+        _err(L, call(kind=kind, plan=C.c_void_p((1 << 20) + 4)), b"16-byte")
+    for tail in (2, 4, 3):                                           # the plan tail, the record tail, position + plan
+        rc = call(tail=tail)
+        assert rc == -3 and b"position tail only" in L.snac_last_error(), (rc, L.snac_last_error())   # SNAC_ERR_UNSUPPORTED
+    # the order: cap and batch before the null tests, those before the plan checks, those before the tail
+    _err(L, call(cap=1, obs=None), b"cap must be")
+    _err(L, call(obs=None, plan_idx=None), b"null pointer")
+    _err(L, call(plan_idx=None, tail=2), b"plan_out needs plan_idx_ring")
+    # an empty batch: no launch -- but the checks come first
+    assert call(batch=0) == 0
+    assert call(batch=0, plan=None, plan_idx=None) == 0
+    assert call(batch=0, kind=1, tail=1, plan=C.c_void_p((1 << 20) + 4)) == 0    # 1D: plan_out needs no alignment; the position tail
+    assert call(batch=0, plan=ODD) == 0
 
 
 # ---- the python layer -----------------------------------------------------------------------------------------------------------------
