@@ -160,6 +160,24 @@ typedef struct snac_env_desc {
                                    unaffected) */
 } snac_env_desc;
 
+/* Alignment of the state arrays.  The kernels read the caller's arrays with wide and with scalar loads, whatever kernel the dispatch
+ * picks, so each array of snac_state starts at an address that is a multiple of (bytes):
+ *     hdr            16    one int4 per env
+ *     episode         4    natural
+ *     grid           16    records read and written as 16-byte pieces (uint4)
+ *     plans          16    rows read as 16-byte pieces (uint4) and through the scalar cache
+ *     plan_tb         4    fetched as the aligned 32-bit word that holds the row (the half by row & 1)
+ *     stat_episodes   8    natural
+ *     stat_return     8    natural
+ *     stat_iou_fx     8    natural
+ * Every entry point that takes a snac_state tests these before any HIP call and refuses a state that breaks one: SNAC_ERR_ARG,
+ * "snac_state.plan_tb must be 4-byte aligned".  A precondition, not a dispatch condition: no kernel is chosen by it.  Whatever an allocator
+ * returns (hipMalloc, a torch tensor) meets all of them; a caller that packs its state into one allocation, or passes a slice of a table
+ * (plan_tb + k), has to keep them itself -- a slice of plan_tb starts at an even row.
+ * plan_tb's word read: for an odd num_plans the word of the last row also covers the two bytes after the array.  They lie inside the same
+ * aligned 4-byte word as the row (so on the same page: the read cannot fault), their value is never used, and nothing is written there.
+ * The per-element inputs of the entry points -- mask, plan_idx_in, actions, step_size, src_index, dst_index -- may sit at the natural
+ * alignment of their element type (1, 2, 1, 1, 4, 4 bytes); where an output or another array needs more, its entry point says so. */
 typedef struct snac_state {
     snac_env_hdr* hdr;          /* [N] */
     int32_t* episode;           /* [N] */

@@ -415,8 +415,8 @@ int snac_episodic_sums(const snac_env_desc* d, const snac_state* st, int64_t* ou
     if (d->num_envs < 1) return fail(SNAC_ERR_ARG, "num_envs must be positive");
     if (!out3 || !scratch) return fail(SNAC_ERR_ARG, "null out3 / scratch");
     if (!st->stat_episodes || !st->stat_return || !st->stat_iou_fx) return fail(SNAC_ERR_ARG, "null pointer in snac_state");
-    if (((uintptr_t)st->stat_episodes | (uintptr_t)st->stat_return | (uintptr_t)st->stat_iou_fx | (uintptr_t)out3 | (uintptr_t)scratch) & 7)
-        return fail(SNAC_ERR_ARG, "the sums, out3 and scratch must be 8-byte aligned");
+    if (int rc = check_state_align(st)) return rc;
+    if (((uintptr_t)out3 | (uintptr_t)scratch) & 7) return fail(SNAC_ERR_ARG, "out3 and scratch must be 8-byte aligned");
     SumArgs g;
     g.n = d->num_envs;
     g.blocks = std::min(SUMS_BLOCKS, (d->num_envs + 1023) / 1024);   // two 16-byte loads per lane and array before another block pays
@@ -528,6 +528,8 @@ int snac_plans_from_grids(const snac_env_desc* d, const snac_state* st, int32_t 
     if (m < 0 || first < 0 || (int64_t)first + m > d->num_plans) return fail(SNAC_ERR_ARG, "plan rows out of range");
     if ((src != nullptr) == (environment_memory != nullptr)) return fail(SNAC_ERR_ARG, "exactly one of src / environment_memory");
     if (src && (!src->grid || !src->hdr || src_envs <= 0)) return fail(SNAC_ERR_ARG, "src needs grid, hdr and src_envs > 0");
+    if (src)
+        if (int rc = check_state_align(src)) return rc;
     if (src && !src_rows && m > src_envs) return fail(SNAC_ERR_ARG, "m exceeds the source batch");
     if (!src && src_rows) return fail(SNAC_ERR_ARG, "src_rows index a source batch");
     if (!src && !total_brick) return fail(SNAC_ERR_ARG, "environment_memory needs total_brick");

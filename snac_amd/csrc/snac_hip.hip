@@ -56,6 +56,24 @@ int check_common(const snac_env_desc* d, const snac_state* st) {
     if (!st->hdr || !st->episode || !st->grid || !st->plans || !st->plan_tb || !st->stat_episodes || !st->stat_return ||
         !st->stat_iou_fx)
         return fail(SNAC_ERR_ARG, "null pointer in snac_state");
+    return check_state_align(st);
+}
+
+// The alignment of the caller's state arrays (include/snac_hip.h, "Alignment of the state arrays": the same numbers, held together by
+// tests/test_cabi_host.py).  A precondition of every kernel, not a dispatch condition: the kernels read hdr as int4, cast grid and plans to
+// uint4 and fetch plan_tb as aligned 32-bit words, whatever choose() picks.  A null pointer passes: whether an array may be absent is the
+// entry point's own test.
+int check_state_align(const snac_state* st) {
+    const struct { const void* p; unsigned need; const char* name; } arrays[] = {
+        {st->hdr, 16, "hdr"},           {st->episode, 4, "episode"},          {st->grid, 16, "grid"},
+        {st->plans, 16, "plans"},       {st->plan_tb, 4, "plan_tb"},          {st->stat_episodes, 8, "stat_episodes"},
+        {st->stat_return, 8, "stat_return"}, {st->stat_iou_fx, 8, "stat_iou_fx"}};
+    for (const auto& a : arrays)
+        if ((uintptr_t)a.p & (a.need - 1)) {
+            char msg[96];
+            std::snprintf(msg, sizeof msg, "snac_state.%s must be %u-byte aligned", a.name, a.need);
+            return fail(SNAC_ERR_ARG, msg);
+        }
     return SNAC_OK;
 }
 

@@ -55,7 +55,8 @@ extern thread_local const char* g_kernel;
 int check_layout(const snac_env_desc* d);
 int base_obs_dim(int kind);
 int tail_len(int kind, int tail);
-int check_common(const snac_env_desc* d, const snac_state* st);
+int check_common(const snac_env_desc* d, const snac_state* st);   // ends with check_state_align
+int check_state_align(const snac_state* st);                      // for the entry points that take a state without check_common
 KArgs make_args(const snac_env_desc* d, const snac_state* st);
 // the checks of the node-pool entry points (kind: the record's kind), defined in k_nodes.hip
 int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const void* nodes, int32_t pool_rows, int32_t m);

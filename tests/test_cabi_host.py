@@ -98,6 +98,118 @@ def test_argument_validation_happens_before_any_launch():
         assert L.snac_traj_alloc(1 << 20, 0, C.byref(p)) < 0 and not p.value
 
 
+# ---- the alignment of the caller's state arrays (include/snac_hip.h, "Alignment of the state arrays"): refused on entry, on the host
+_ARRAYS = ("hdr", "episode", "grid", "plans", "plan_tb", "stat_episodes", "stat_return", "stat_iou_fx")   # snac_state's fields, in order
+_BASE = 1 << 20                                                        # a placeholder on a 512-byte boundary (never dereferenced)
+# (entry point, env kind, {argument position: value}, what refuses the call once the state has passed): a representative of every
+# translation unit that takes a state -- snac_hip.hip, k_misc.hip, k_nodes.hip, k_nodes_obs.hip, k_eval.hip, k_replay.hip -- each with an
+# argument check of its own BEHIND the state's, so that nothing here can reach a launch.  snac_step, snac_step_scalar and snac_reset have
+# no later check and share check_common with the others; k_mailbox.hip's entry points need a mailbox, which is page-locked device memory.
+_ENTRY = [
+    ("snac_iou", 2, {}, b"null out"), ("snac_observe", 2, {}, b"null obs"), ("snac_reset_scalar", 2, {2: -1}, b"plan_idx out of range"),
+    ("snac_rollout", 2, {2: -1}, b"T must be"), ("snac_rollout_rec", 2, {2: -1}, b"T must be"), ("snac_rollout_tiled", 2, {2: -1}, b"outside the ring"),
+    ("snac_transition", 2, {2: -1}, b"m must be"),
+    ("snac_export_grid", 2, {}, b"null out"), ("snac_import_state", 2, {2: -1}, b"m must be"), ("snac_make_plans", 2, {2: -1}, b"plan rows out of range"),
+    ("snac_plans_from_grids", 2, {2: 2, 3: 99}, b"plan rows out of range"), ("snac_episodic_sums", 2, {2: _BASE + 4, 3: _BASE}, b"out3 and scratch"),
+    ("snac_nodes2d_pack", 2, {4: _BASE, 5: 0}, b"pool_rows"), ("snac_nodes2d_unpack", 2, {1: _BASE, 2: 0}, b"pool_rows"),
+    ("snac_transition_nodes2d", 2, {2: _BASE, 3: 0}, b"pool_rows"), ("snac_nodes1d_pack", 1, {4: _BASE, 5: 0}, b"pool_rows"),
+    ("snac_nodes3d_unpack", 3, {1: _BASE, 2: 0}, b"pool_rows"),
+    ("snac_observe_nodes2d", 2, {2: _BASE, 3: 0}, b"pool_rows"), ("snac_observe_nodes1d", 1, {2: _BASE, 3: 0}, b"pool_rows"),
+    ("snac_evaluate_nodes2d", 2, {2: _BASE, 3: 0}, b"pool_rows"), ("snac_evaluate_nodes3d", 3, {2: _BASE, 3: 0}, b"pool_rows"),
+    ("snac_replay_gather", 2, {2: 1}, b"cap must be"), ("snac_replay_gather_tiled", 2, {2: 1}, b"cap must be"),
+    ("snac_replay_gather_nstep", 2, {2: 1}, b"cap must be"), ("snac_replay_gather_windows", 2, {2: 1}, b"cap must be"),
+    ("snac_replay_gather_onpolicy", 2, {2: 1}, b"cap must be"),
+]
+
+
+def _header_alignments():
+    """{array: bytes} as the header's block states them."""
+    src = open(os.path.join(helpers.ROOT, "include", "snac_hip.h")).read()
+    block = re.search(r"/\* Alignment of the state arrays\..*?\*/", src, flags=re.S).group()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"^ \* {5}(\w+) +(\d+) {2,}\S", block, flags=re.M)}
+
+
+def _call(name, kind, fixed, pointers):
+    """The entry point with a state of these eight pointers; every other argument NULL / 0 but `fixed`.  -> (status, error text)"""
+    from snac_amd import _lib
+
+    L = _lib.lib()
+    d = _lib.EnvDesc(kind, 1, 16, 4, 0, 0, 1, 0, 0, 0)
+    st = _lib.State(*pointers)
+    args, states = [], 0
+    for i, t in enumerate(_lib.PROTOTYPES[name][1]):
+        if t is C.POINTER(_lib.EnvDesc):
+            args.append(C.byref(d))
+        elif t is C.POINTER(_lib.State):
+            args.append(None if states else C.byref(st))              # (a second state, the source of snac_plans_from_grids: absent)
+            states += 1
+        else:
+            args.append(fixed.get(i, None if t is C.c_void_p or issubclass(t, C._Pointer) else 0))
+    rc = getattr(L, name)(*args)
+    return rc, L.snac_last_error()
+
+
+def test_header_states_an_alignment_for_every_state_array():
+    from snac_amd import _lib
+
+    assert tuple(f for f, _ in _lib.State._fields_) == _ARRAYS
+    want = _header_alignments()
+    assert sorted(want) == sorted(_ARRAYS), want
+    assert all(v in (4, 8, 16) for v in want.values()), want
+    assert want["hdr"] == 16 and want["plan_tb"] >= 4                  # the struct's own comment; the word read of k_rollout2d / k_rollout2db
+
+
+def test_the_state_check_enforces_the_numbers_of_the_header():
+    """What the library enforces, found by asking it: the smallest power-of-two offset from a 512-byte boundary at which an array passes
+    the state's check (the call then fails its own later check) is the number the header's block gives for that array."""
+    want = _header_alignments()
+    for i, name in enumerate(_ARRAYS):
+        enforced = None
+        for off in (1, 2, 4, 8, 16, 32, 64, 128, 256):
+            p = [_BASE] * 8
+            p[i] = _BASE + off
+            rc, msg = _call("snac_iou", 2, {}, p)
+            assert rc == -1
+            if b"null out" in msg:
+                enforced = off
+                break
+            assert msg == b"snac_state.%s must be %d-byte aligned" % (name.encode(), want[name]), (name, off, msg)
+        assert enforced == want[name], (name, enforced, want[name])
+
+
+@pytest.mark.parametrize("entry", _ENTRY, ids=[e[0] for e in _ENTRY])
+def test_a_misaligned_state_array_is_refused_before_anything_else_of_the_state_is_used(entry):
+    """Each of the eight arrays in turn at every power-of-two offset below its requirement, the other seven aligned placeholders: -1 and
+    the array's name.  The same array at exactly its requirement past a 512-byte boundary passes, and the call fails its later check."""
+    fn, kind, fixed, later = entry
+    want = _header_alignments()
+    rc, msg = _call(fn, kind, fixed, [_BASE] * 8)
+    assert rc == -1 and later in msg, (fn, msg)                        # the later check itself, with every array aligned
+    for i, name in enumerate(_ARRAYS):
+        for off in (1, 2, 4, 8):
+            if off >= want[name]:
+                continue
+            p = [_BASE + 512 * (j + 1) for j in range(8)]
+            p[i] += off
+            rc, msg = _call(fn, kind, fixed, p)
+            assert rc == -1 and msg == b"snac_state.%s must be %d-byte aligned" % (name.encode(), want[name]), (fn, name, off, msg)
+        p = [_BASE + 512 * (j + 1) for j in range(8)]
+        p[i] += want[name]
+        rc, msg = _call(fn, kind, fixed, p)
+        assert rc == -1 and later in msg and b"snac_state." not in msg, (fn, name, msg)
+
+
+def test_the_source_state_of_plans_from_grids_is_held_to_the_same_alignment():
+    from snac_amd import _lib
+
+    L = _lib.lib()
+    d = _lib.EnvDesc(2, 1, 16, 4, 0, 0, 1, 0, 0, 0)
+    st = _lib.State(*[_BASE] * 8)
+    src = _lib.State(_BASE, 0, _BASE + 8, 0, 0, 0, 0, 0)           # hdr and grid are what the call reads of it
+    assert L.snac_plans_from_grids(C.byref(d), C.byref(st), 2, 0, C.byref(src), 16, None, None, None, None) == -1
+    assert L.snac_last_error() == b"snac_state.grid must be 16-byte aligned"
+
+
 def test_hdr_struct_is_16_bytes():
     src = open(os.path.join(helpers.ROOT, "include", "snac_hip.h")).read()
     assert "int16_t ep_return" in src and "int16_t cross" in src
@@ -223,7 +335,7 @@ def test_round5_entry_points_validate_their_arguments_before_any_hip_call():
     assert L.snac_mailbox_settle(None) == 0 and L.snac_mailbox_quit(None) == 0 and L.snac_mailbox_destroy(None) == 0   # nothing to wait for / end
     assert not L.snac_mailbox_row(None) and not L.snac_mailbox_reward(None) and not L.snac_mailbox_done(None)
     d = _lib.EnvDesc(2, 1, 16, 4, 0, 0, 1, 0, 0, 0)
-    st = _lib.State(1, 1, 1, 1, 1, 1, 1, 1)                        # (never dereferenced: every call below fails its checks first)
+    st = _lib.State(*[1 << 20] * 8)                                # (aligned, never dereferenced: every call below fails its checks first)
     assert L.snac_plans_from_grids(C.byref(d), C.byref(st), 2, 3, None, 0, None, None, None, None) != 0 and b"out of range" in L.snac_last_error()
     assert L.snac_plans_from_grids(C.byref(d), C.byref(st), 2, 0, None, 0, None, None, None, None) != 0 and b"exactly one" in L.snac_last_error()
     mem = (C.c_double * (2 * 676))()

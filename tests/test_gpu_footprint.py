@@ -8,6 +8,12 @@ NOT written still hold 0x5A:
   * rollout(ring=): every tick of the ring outside first_tick .. first_tick + T - 1, for first_tick 0, 3 and ring_ticks - T
                                                                                          (test_inner_calls, call "roll_ring")
   * k_rollout2d: the three sums words of an env that finished nothing in the launch      (test_inner_state_arrays, child "lane_*")
+The state test binds the C ABI directly and runs every case twice: all eight arrays of snac_state on 512-byte boundaries, and ("weak")
+each at the alignment include/snac_hip.h asks for past such a boundary and no better -- hdr, grid and plans 16 bytes past, episode and
+plan_tb 4, the sums 8 (below that the library refuses the call: tests/test_cabi_host.py, on the host).  plans and plan_tb are inputs
+there: after every call they hold what the test put in.  Its per-element inputs sit at their natural alignment: plan_idx_in 2 bytes
+past a boundary, a mask 1, src_index / dst_index 4.  The 2D dynamic leg adds a table of 15 plan rows, where the 32-bit word that
+k_rollout2d / k_rollout2db fetch for the last row ends two bytes past plan_tb.
 Outputs are carved at the alignments of OFFSETS (never below the natural alignment of the element type): obs on a 512-byte boundary
 and one element past it; done 0 / 1 / 4 / 8 bytes past (8 breaks the kernels' `& 15` test and keeps `& 3`), reward 0 / 4, the byte
 records 0 / 1, the plan_idx record 0 / 2; explicit actions and step sizes -- inputs -- at the byte records' offsets.  Batch sizes: SIZES,
@@ -48,25 +54,30 @@ OFFSETS = [(0, 0, 0, 0, 0), (0, 1, 4, 1, 2), (0, 4, 0, 0, 2), (0, 8, 4, 1, 0), (
 AUXK = {1: "k_step1d", 2: "k_step2d", 3: "k_step3dq"}                 # the step kernels' AUX forms: masked resets and observe
 _LANE = {"SNAC_1D_LANE_MIN_F64": 4, "SNAC_1D_LANE_MIN_F32": 4, "SNAC_2D_BLOCK": 0, "SNAC_2D_TP": 0, "SNAC_2D_STAGE_MIN": 4, "SNAC_3D_BLOCK_MIN": 4}
 _BLOCK = {"SNAC_2D_BLOCK_MIN_F64": 4, "SNAC_2D_BLOCK_MIN_F32": 4}
-# knobs: the overrides of the child; targets: the kernels whose calls it runs (None: every call); reach: what it must reach, by name
+# knobs: the overrides of the child; targets: the kernels whose calls it runs (None: every call); reach: what it must reach, by name;
+# state: the kernels (without the envs of a block) it must reach in test_inner_state_arrays, with the state arrays at their weakest alignment
+_STEPS = ["k_reset", "k_iou", "k_step1d", "k_step2d", "k_step3dq", "k_edges1d", "k_edges2d", "k_edges3d"]
 CHILDREN = {
     "default": dict(knobs={}, targets=None, timeout=240,
                     reach=["k_rollout", "k_transition", "k_aux", "k_reset", "k_iou", "k_step1d", "k_step2d", "k_step3dq", "k_edges1d", "k_edges2d", "k_edges3d",
-                           "k_transition2d", "k_transition3d", "k_rollout1dt/E4", "k_rollout2dt/E4", "k_rollout3d"]),
+                           "k_transition2d", "k_transition3d", "k_rollout1dt/E4", "k_rollout2dt/E4", "k_rollout3d"],
+                    state=_STEPS + ["k_aux", "k_transition", "k_transition2d", "k_transition3d", "k_rollout1dt", "k_rollout2dt", "k_rollout3d"]),
     "lane_xcd0": dict(knobs=dict(_LANE, SNAC_2D_STAGE_XCD=0), targets=["k_rollout1dl", "k_rollout2d", "k_rollout3db"], timeout=150,
-                      reach=["k_rollout1dl", "k_rollout2d", "k_rollout3db"]),
+                      reach=["k_rollout1dl", "k_rollout2d", "k_rollout3db"], state=_STEPS + ["k_rollout1dl", "k_rollout2d", "k_rollout3db"]),
     "lane_xcd1": dict(knobs=dict(_LANE, SNAC_2D_STAGE_XCD=1), targets=["k_rollout1dl", "k_rollout2d", "k_rollout3db"], timeout=150,
-                      reach=["k_rollout1dl", "k_rollout2d", "k_rollout3db"]),
+                      reach=["k_rollout1dl", "k_rollout2d", "k_rollout3db"], state=_STEPS + ["k_rollout1dl", "k_rollout2d", "k_rollout3db"]),
     "block128": dict(knobs=dict(_BLOCK, SNAC_2D_BLOCK_TWO_F64=128, SNAC_2D_BLOCK_TWO_F32=128), targets=["k_rollout2db"], timeout=120,
-                     reach=["k_rollout2db/E64", "k_rollout2db/E128"]),
+                     reach=["k_rollout2db/E64", "k_rollout2db/E128"], state=["k_rollout2db"]),
     "block256": dict(knobs=dict(_BLOCK, SNAC_2D_BLOCK_MAX_F64=255, SNAC_2D_BLOCK_MAX_F32=255, SNAC_2D_BLOCK_FOUR_MAX_F64=38912, SNAC_2D_BLOCK_FOUR_MAX_F32=45056),
                      targets=["k_rollout2db"], timeout=120, reach=["k_rollout2db/E64", "k_rollout2db/E256"]),
     "tp": dict(knobs={"SNAC_2D_TP_EB8": 8, "SNAC_1D_TP_EB8_MIN": 1073741824, "SNAC_1D_TP_EB16": 16}, targets=["k_rollout1dt", "k_rollout2dt"], timeout=150,
-               reach=["k_rollout1dt/E4", "k_rollout1dt/E16", "k_rollout2dt/E4", "k_rollout2dt/E8"]),
-    "tile": dict(knobs={"SNAC_3D_PIPELINE": 0}, targets=None, timeout=240, reach=["k_rollout", "k_transition", "k_aux"]),
+               reach=["k_rollout1dt/E4", "k_rollout1dt/E16", "k_rollout2dt/E4", "k_rollout2dt/E8"], state=["k_rollout1dt", "k_rollout2dt"]),
+    "tile": dict(knobs={"SNAC_3D_PIPELINE": 0}, targets=None, timeout=240, reach=["k_rollout", "k_transition", "k_aux"],
+                 state=["k_rollout", "k_transition", "k_aux"]),
     "step3d": dict(knobs={"SNAC_STEP3D_QUARTER": 0}, targets=["k_step3d"], timeout=120, reach=["k_step3d"]),
 }
-STATE_CHILDREN = ("default", "lane_xcd0", "lane_xcd1", "tile")         # test_inner_state_arrays runs in these
+STATE_CHILDREN = tuple(c for c, spec in CHILDREN.items() if "state" in spec)   # test_inner_state_arrays runs in these
+WEAK = " (state arrays), weak"                      # the call names of its weak variant in the report
 ROLLS = ("roll_all", "roll_tiled", "roll_ring", "roll_last", "roll_none")
 
 
@@ -443,26 +454,71 @@ def test_inner_calls(kind, dyn, f32, request):
     _flush_report(request.node.name, time.time() - t0)
 
 
-# ---- the state arrays: the C ABI bound directly, hdr / episode / grid / the three sums arrays carved from the arena
-def _state_case(kind, dyn, n, f32):
+# ---- the state arrays: the C ABI bound directly, every array of snac_state carved from the arena
+# the odd plan table of the 2D dynamic leg and its seed, picked on the host with the oracle alone: of the seeds 0 .. 39, 25 give what
+# _state_case asserts of _rehearse() at every n of the case (5 envs: ten resets over 15 rows); 11, the other cases' seed, is one of them
+ODD_ROWS, ODD_SEED = 15, 11
+
+
+def _rehearse(kind, dyn, n, table, seed):
+    """The oracle alone, before anything runs on the GPU: the state case's calls up to the end of its two rollout launches, the launches
+    one tick at a time.  -> [(the env's previous plan row, the row it was reset onto)] of every reset inside those launches, and the
+    oracle's state behind them (the case compares it with its own oracle's: the launches as a whole did what the single ticks did)."""
+    orc = helpers.oracle().OracleBatch(kind, dyn, n, table, seed=seed, env_id_base=7)
+    orc.set_total_step(5)
+    orc.reset()
+    for t in range(3):
+        orc.step(t, auto_reset=True, want_obs=False)
+    resets = []
+    for t in range(3, 3 + 1 + 7):
+        before = orc.state()
+        orc.rollout(1, t0=t, obs=None)
+        after = orc.state()
+        for i in np.nonzero(after["episode"] != before["episode"])[0]:
+            resets.append((int(before["plan_idx"][i]), int(after["plan_idx"][i])))
+    return resets, orc.state()
+
+
+def _state_case(kind, dyn, n, f32, weak=False, rows=16, seed=11):
+    """weak: every array of snac_state at the alignment include/snac_hip.h asks for ("Alignment of the state arrays") past a 512-byte
+    boundary, and no better.  rows: the plan rows of the table (ODD_ROWS: the 32-bit word of plan_tb's last row ends two bytes past the
+    array, inside the band)."""
     import torch
     from snac_amd import _lib, plans
 
     L = _lib.lib()
     sz = _lib.env_sizes(kind, dyn)
     table, shaped = _tables(kind, dyn)
+    table, shaped = table[:rows], shaped[:rows]
     packed, tb = plans.pack_plans(kind, np.array(shaped, np.float64))
-    dev, seed = torch.device("cuda", torch.cuda.current_device()), 11
+    P = len(packed)
+    assert P == (rows if dyn else 1)                                   # (the static classes: their one plan)
+    rehearsed = None
+    if rows % 2:
+        # what the odd table is there for, from the oracle alone: the launches of k_rollout2d / k_rollout2db fetch total_brick as the
+        # 32-bit word that holds the row -- the low half for an even row, the high half for an odd one, the last word for row P - 1
+        resets, rehearsed = _rehearse(kind, dyn, n, table, seed)
+        fresh = [new for old, new in resets if new != old]
+        assert any(new % 2 == 0 for new in fresh), "no env is reset onto another, even plan row"
+        assert any(new % 2 == 1 for new in fresh), "no env is reset onto another, odd plan row"
+        assert P - 1 in fresh, "no env is reset onto the last row of the odd table from another row"
+    dev = torch.device("cuda", torch.cuda.current_device())
     gdt = {1: torch.int16, 2: torch.int32, 3: torch.int16}[kind]
-    A = guard.Arena(n * (16 + 4 + 24 + sz.grid_elems * sz.grid_elem_bytes) + 8 * (guard.BAND + 512) + 4096, dev)
-    hdr = A.carve((n, 4), torch.int32, name="hdr").zero_()
-    epi = A.carve((n,), torch.int32, name="episode").fill_(-1)
-    grid = A.carve((n, sz.grid_elems), gdt, name="grid").zero_()
-    sums = [A.carve((n,), torch.int64, name=nm).zero_() for nm in ("stat_episodes", "stat_return", "stat_iou_fx")]
-    assert sz.grid_elem_bytes == grid.element_size() and all(t.data_ptr() % 512 == 0 for t in [hdr, epi, grid] + sums)
-    d_plans = torch.from_numpy(packed.view(np.int32) if kind == 2 else packed).to(dev)
-    d_tb = torch.from_numpy(tb).to(dev)
-    desc = _lib.EnvDesc(kind, int(dyn), n, len(packed), _lib.OBS_F32 if f32 else _lib.OBS_F64, 0, seed, 7, 5, 0, -1, _lib.SCALARS_DEFAULT, 0, 0)
+    pdt = torch.int32 if kind == 2 else torch.int16
+    assert sz.grid_elem_bytes == torch.empty((), dtype=gdt).element_size() and sz.plan_elem_bytes == torch.empty((), dtype=pdt).element_size()
+    A = guard.Arena(n * (16 + 4 + 24 + sz.grid_elems * sz.grid_elem_bytes + 1 + 2 + 8) + P * (sz.plan_elems * sz.plan_elem_bytes + 2)
+                    + 14 * (guard.BAND + 512) + 4096, dev)
+    w = (lambda need: need) if weak else (lambda need: 0)              # the offset past a 512-byte boundary: the requirement itself, or none
+    hdr = A.carve((n, 4), torch.int32, offset=w(16), name="hdr").zero_()
+    epi = A.carve((n,), torch.int32, offset=w(4), name="episode").fill_(-1)
+    grid = A.carve((n, sz.grid_elems), gdt, offset=w(16), name="grid").zero_()
+    sums = [A.carve((n,), torch.int64, offset=w(8), name=nm).zero_() for nm in ("stat_episodes", "stat_return", "stat_iou_fx")]
+    d_plans = A.carve((P, sz.plan_elems), pdt, offset=w(16), name="plans").copy_(torch.from_numpy(packed.view(np.int32) if kind == 2 else packed))
+    d_tb = A.carve((P,), torch.int16, offset=w(4), name="plan_tb").copy_(torch.from_numpy(tb))
+    for arr, need in [(hdr, 16), (epi, 4), (grid, 16), (d_plans, 16), (d_tb, 4)] + [(s, 8) for s in sums]:
+        assert arr.data_ptr() % 512 == w(need)
+    keep_plans, keep_tb = d_plans.clone(), d_tb.clone()
+    desc = _lib.EnvDesc(kind, int(dyn), n, P, _lib.OBS_F32 if f32 else _lib.OBS_F64, 0, seed, 7, 5, 0, -1, _lib.SCALARS_DEFAULT, 0, 0)
     st = _lib.State(hdr.data_ptr(), epi.data_ptr(), grid.data_ptr(), d_plans.data_ptr(), d_tb.data_ptr(), *[s.data_ptr() for s in sums])
     dref, sref = C.byref(desc), C.byref(st)
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -470,7 +526,7 @@ def _state_case(kind, dyn, n, f32):
     D = L.snac_obs_dim(dref)
     odt = torch.float32 if f32 else torch.float64
     cast = lambda o: np.ascontiguousarray(o.astype(np.float32) if f32 else o)  # noqa: E731
-    same = lambda t, w, what: Case.same(_Where(kind, dyn, n, f32), t, w, what)  # noqa: E731
+    same = lambda got, want, what: Case.same(_Where(kind, dyn, n, f32, weak, rows), got, want, what)  # noqa: E731
     ok = lambda rc: _lib.check(rc)  # noqa: E731
     aligned = True
 
@@ -480,22 +536,27 @@ def _state_case(kind, dyn, n, f32):
     def reach(call, m=None):
         label = expect(CHILD, call, kind, n if m is None else m, aligned)
         assert _kernel() == label.split("/")[0], (call, kind, n, _kernel(), label)
-        _note(label, call + " (state arrays)", n, (0, 0, 0, 0, 0))
+        _note(label, call + (WEAK if weak else " (state arrays)"), n, (0, 0, 0, 0, 0))
         return label
+
+    def settled():
+        """No byte outside the carved arrays changed, and the plans and their total_brick -- inputs of every call here -- are as they were."""
+        A.check()
+        assert torch.equal(d_plans, keep_plans) and torch.equal(d_tb, keep_tb), ("a call wrote the plan table", kind, dyn, n, f32, weak, rows, _kernel())
 
     obs = torch.empty((n, D), dtype=odt, device=dev)
     rew, done = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
     ok(L.snac_reset(dref, sref, None, None, vp(obs), stream))
     reach("reset")
     same(obs, cast(orc.reset()), "reset rows")
-    A.check()
+    settled()
     t = 0
     for _ in range(3):
         ok(L.snac_step(dref, sref, t, None, None, 1, vp(obs), vp(rew), vp(done), stream))
         reach("step")
         oc, rc, dc = orc.step(t, auto_reset=True)
         same(obs, cast(oc), "step rows"), same(rew, rc, "step rewards"), same(done, dc, "step done flags")
-        A.check()
+        settled()
         t += 1
     for T in (1, 7):
         # the sums words pre-filled with the fresh pattern: an env that finishes nothing in the launch keeps the pattern (k_rollout2d does
@@ -511,7 +572,7 @@ def _state_case(kind, dyn, n, f32):
         label = reach("roll_all")
         oc, rc, dc = orc.rollout(T, t0=t)
         same(traj, cast(oc), "rollout rows"), same(r2, rc, "rollout rewards"), same(d2, dc, "rollout done flags")
-        A.check()
+        settled()
         idle = torch.from_numpy(~dc.astype(bool).any(axis=0)).to(dev)
         if T == 1 and n >= 64:
             assert bool(idle.any()), "some env finishes nothing in a launch of one tick"
@@ -520,24 +581,55 @@ def _state_case(kind, dyn, n, f32):
         for s, keep in zip(sums, saved):
             s.copy_(keep + (s - pattern))
         t += T
-    mask = (torch.arange(n, device=dev) % 3 == 0).to(torch.uint8)
+    if rehearsed is not None:                                          # the launches did what _rehearse()'s single ticks did
+        so = orc.state()
+        assert all(np.array_equal(so[f], rehearsed[f]) for f in ("episode", "plan_idx", "tb", "cs"))
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    ok(L.snac_iou(dref, sref, vp(out), stream))
+    reach("iou")
+    same(out, orc.iou(), "iou")
+    settled()
+    # the per-element inputs at their natural alignment and no better: plan rows (int16) 2 bytes past a 512-byte boundary, a mask 1 byte
+    # past, edge indices (int32) 4 bytes past; inputs, which a call leaves as they are
+    rng = np.random.default_rng(n)
+    rows_in = rng.integers(0, P, n).astype(np.int16)
+    t_rows = A.carve((n,), torch.int16, offset=2, name="plan_idx_in").copy_(torch.from_numpy(rows_in))
+    ok(L.snac_reset(dref, sref, None, vp(t_rows), vp(obs), stream))
+    reach("reset")
+    same(obs, cast(orc.reset(plan_idx=rows_in)), "rows of the reset onto given plan rows")
+    same(t_rows, rows_in, "plan_idx_in (input)")
+    settled()
+    ok(L.snac_step(dref, sref, t, None, None, 1, vp(obs), vp(rew), vp(done), stream))   # the masked reset then finds envs in mid-episode
+    reach("step")
+    oc, rc, dc = orc.step(t, auto_reset=True)
+    same(obs, cast(oc), "step rows"), same(rew, rc, "step rewards"), same(done, dc, "step done flags")
+    settled()
+    t += 1
+    mask_in = (np.arange(n) % 3 == 0).astype(np.uint8)
+    mask = A.carve((n,), torch.uint8, offset=1, name="mask").copy_(torch.from_numpy(mask_in))
     ok(L.snac_reset(dref, sref, vp(mask), None, vp(obs), stream))
     reach("reset_mask")
-    same(obs, cast(orc.reset(mask=mask.cpu().numpy())), "masked reset rows")
-    A.check()
-    # a wave of edges with dst: rows of the lower half stepped into the upper half
+    same(obs, cast(orc.reset(mask=mask_in)), "masked reset rows")
+    same(mask, mask_in, "mask (input)")
+    settled()
+    # two waves of edges: rows of the lower half stepped into the upper half, with dst alone and with src and dst
     m = n // 2
     if m:
-        rng = np.random.default_rng(n)
-        a, k = rng.integers(0, sz.num_actions, m).astype(np.int8), rng.integers(1, 4, m).astype(np.int8)
-        dst = (n - m + rng.permutation(m)).astype(np.int32)
-        ta, tk, td = (torch.from_numpy(x).to(dev) for x in (a, k, dst))
-        ok(L.snac_transition(dref, sref, m, None, vp(td), 9, vp(ta), vp(tk), vp(obs), vp(rew), vp(done), stream))
-        aligned = True
-        reach("edges", m)
-        oc, rc, dc = orc.transition(a, k, dst=dst, t=9)
-        same(obs[:m], cast(oc), "edge rows"), same(rew[:m], rc, "edge rewards"), same(done[:m], dc, "edge done flags")
-        A.check()
+        src = rng.permutation(n - m)[:m].astype(np.int32)
+        t_src = A.carve((m,), torch.int32, offset=4, name="src_index").copy_(torch.from_numpy(src))
+        t_dst = A.carve((m,), torch.int32, offset=4, name="dst_index")
+        for tick, with_src in ((9, False), (10, True)):
+            a, k = rng.integers(0, sz.num_actions, m).astype(np.int8), rng.integers(1, 4, m).astype(np.int8)
+            dst = (n - m + rng.permutation(m)).astype(np.int32)
+            t_dst.copy_(torch.from_numpy(dst))
+            ta, tk = (torch.from_numpy(x).to(dev) for x in (a, k))
+            ok(L.snac_transition(dref, sref, m, vp(t_src) if with_src else None, vp(t_dst), tick, vp(ta), vp(tk), vp(obs), vp(rew), vp(done), stream))
+            aligned = True
+            reach("edges", m)
+            oc, rc, dc = orc.transition(a, k, src=src if with_src else None, dst=dst, t=tick)
+            same(obs[:m], cast(oc), "edge rows"), same(rew[:m], rc, "edge rewards"), same(done[:m], dc, "edge done flags")
+            same(t_src, src, "src_index (input)"), same(t_dst, dst, "dst_index (input)")
+            settled()
     # the state, against the oracle's
     so, ss = orc.state(), orc.stats()
     h8, h16 = hdr.view(torch.int8).cpu().numpy(), hdr.view(torch.int16).cpu().numpy()
@@ -556,8 +648,8 @@ def _state_case(kind, dyn, n, f32):
 
 
 class _Where:
-    def __init__(self, kind, dyn, n, f32):
-        self.kind, self.dyn, self.n, self.f32, self.off = kind, dyn, n, f32, "state arrays"
+    def __init__(self, kind, dyn, n, f32, weak, rows):
+        self.kind, self.dyn, self.n, self.f32, self.off = kind, dyn, n, f32, "state arrays%s, %d plan rows" % (" at their weakest alignment" if weak else "", rows)
 
     rows = staticmethod(Case.rows)
 
@@ -571,7 +663,10 @@ def test_inner_state_arrays(kind, dyn, request):
     t0 = time.time()
     for n in (5, 64, 68, 260):
         for f32 in (False, True):
-            _state_case(kind, dyn, n, f32)
+            for weak in (False, True):
+                _state_case(kind, dyn, n, f32, weak=weak)
+            if kind == 2 and dyn:
+                _state_case(kind, dyn, n, f32, weak=True, rows=ODD_ROWS, seed=ODD_SEED)
     _flush_report(request.node.name, time.time() - t0)
 
 
@@ -589,9 +684,9 @@ def test_inner_the_knobs_are_what_the_child_was_given():
 
 def _table(rows):
     """kernel x call x batch sizes x offsets, as text."""
-    out = ["%-18s %-28s %-62s %s" % ("kernel", "call", "batch sizes (edges: edges per call)", "offsets (obs elements, done, reward, byte records, plan_idx)")]
+    out = ["%-18s %-34s %-62s %s" % ("kernel", "call", "batch sizes (edges: edges per call)", "offsets (obs elements, done, reward, byte records, plan_idx)")]
     for r in rows:
-        out.append("%-18s %-28s %-62s %s" % (r["kernel"], r["call"], " ".join(str(n) for n in r["n"]), " ".join("/".join(str(x) for x in o) for o in r["off"])))
+        out.append("%-18s %-34s %-62s %s" % (r["kernel"], r["call"], " ".join(str(n) for n in r["n"]), " ".join("/".join(str(x) for x in o) for o in r["off"])))
     return "\n".join(out)
 
 
@@ -629,6 +724,9 @@ def test_children(child, tmp_path):
     reached = {r["kernel"] for r in rows}
     missing = [k for k in spec["reach"] if k not in reached]
     assert not missing, "child %s no longer reaches %s (reached: %s)" % (child, missing, sorted(reached))
+    weak = {r["kernel"].split("/")[0] for r in rows if r["call"].endswith(WEAK)}
+    missing = [k for k in spec.get("state", []) if k not in weak]
+    assert not missing, "child %s no longer reaches %s with the state arrays at their weakest alignment (reached: %s)" % (child, missing, sorted(weak))
     text = "child %s  knobs: %s\n%s\nseconds per inner test: %s" % (child, spec["knobs"] or "none", _table(rows), json.dumps(seconds))
     print(text)
     dump = os.environ.get("SNAC_FOOTPRINT_TABLE_DIR")                   # a directory that receives the tables as text files

@@ -32,7 +32,7 @@ def test_the_library_exports_the_evaluation_entry_points():
 def test_evaluation_validates_its_arguments_before_any_hip_call(name):
     L = _lib.lib()
     kind = int(name[-2])
-    st = _lib.State(1, 1, 1, 1, 1, 1, 1, 1)
+    st = _lib.State(*[1 << 20] * 8)
     d = _desc(kind)
 
     def err(rc, *words):
@@ -65,7 +65,7 @@ def test_evaluation_validates_its_arguments_before_any_hip_call(name):
 def test_evaluation_of_no_leaves_returns_before_any_hip_call(name):
     L = _lib.lib()
     kind = int(name[-2])
-    st = _lib.State(1, 1, 1, 1, 1, 1, 1, 1)
+    st = _lib.State(*[1 << 20] * 8)
     assert _call(L, name, _desc(kind), st, m=0, est=None) == 0
     assert _call(L, name, _desc(kind), st, m=0, H=0, est=None, gpow=None) == 0
     assert _call(L, name, _desc(kind), st, m=0, node_rows=PH, pool_rows=1) == 0
@@ -74,7 +74,7 @@ def test_evaluation_of_no_leaves_returns_before_any_hip_call(name):
 def test_the_existing_node_entry_points_keep_their_messages():
     """nodes_check is now shared with the evaluation: the 1D / 3D messages are unchanged, 2D keeps its own check."""
     L = _lib.lib()
-    st = _lib.State(1, 1, 1, 1, 1, 1, 1, 1)
+    st = _lib.State(*[1 << 20] * 8)
     rc = L.snac_transition_nodes1d(C.byref(_desc(2)), C.byref(st), PH, 16, 4, None, None, 0, None, None, None, None, None, None)
     assert rc == -3 and L.snac_last_error() == b"snac_node1d records are for the 1D kinds"
     rc = L.snac_transition_nodes3d(C.byref(_desc(3)), C.byref(st), C.c_void_p((1 << 20) + 64), 16, 4, None, None, 0, None, None, None, None, None, None)

@@ -37,7 +37,7 @@ def test_node_entry_points_validate_their_arguments_before_any_hip_call(name):
     L = _lib.lib()
     kind = 1 if "1d" in name else 3
     other = [k for k in (1, 2, 3) if k != kind]
-    st = _lib.State(1, 1, 1, 1, 1, 1, 1, 1)
+    st = _lib.State(*[1 << 20] * 8)
     pool = C.c_void_p(1 << 20)                                       # 128-byte aligned placeholder
     d = _desc(kind)
 

@@ -19,7 +19,7 @@ def _gae(L, N=4, cap=8, first=0, count=8, gamma=0.97, lam=0.95, reward=PH, done=
 
 def _gather(L, desc=True, st=True, kind=2, tail=0, cap=8, tiled=0, obs=PH, first=PH, plan_idx=PH, action=PH, value=PH, logp=PH, adv=PH, ret=PH,
             norm=PH, tick=PH, env=PH, batch=4, s=PH, plan=PH, action_out=PH, value_out=PH, logp_out=PH, adv_out=PH, ret_out=PH):
-    d, state = _desc(kind, tail), _lib.State(1, 1, 1, 1, 1, 1, 1, 1)     # never dereferenced
+    d, state = _desc(kind, tail), _lib.State(*[1 << 20] * 8)     # never dereferenced
     return L.snac_replay_gather_onpolicy(C.byref(d) if desc else None, C.byref(state) if st else None, cap, tiled, obs, first, plan_idx, action,
                                          value, logp, adv, ret, norm, tick, env, batch, s, plan, action_out, value_out, logp_out, adv_out,
                                          ret_out, None)

@@ -14,7 +14,7 @@ def test_episodic_sums_validates_its_arguments_before_any_hip_call():
 
     L = _lib.lib()
     d = _lib.EnvDesc(2, 1, 16, 4, 0, 0, 1, 0, 0, 0)
-    st = _lib.State(8, 8, 8, 8, 8, 8, 8, 8)                        # (never dereferenced: every call below fails its checks first)
+    st = _lib.State(*[1 << 20] * 8)                                # (aligned, never dereferenced: every call below fails its checks first)
     buf = (C.c_int64 * _lib.SUMS_SCRATCH_WORDS)()
     p = C.cast(buf, C.c_void_p)
     assert L.snac_episodic_sums(C.byref(d), C.byref(st), None, p, None) == -1 and b"null out3 / scratch" in L.snac_last_error()
@@ -23,9 +23,9 @@ def test_episodic_sums_validates_its_arguments_before_any_hip_call():
     for n in (0, -5):
         bad = _lib.EnvDesc(2, 1, n, 4, 0, 0, 1, 0, 0, 0)
         assert L.snac_episodic_sums(C.byref(bad), C.byref(st), p, p, None) == -1 and b"num_envs" in L.snac_last_error()
-    nul = _lib.State(8, 8, 8, 8, 8, 8, 0, 8)
+    nul = _lib.State(*[1 << 20] * 6, 0, 1 << 20)
     assert L.snac_episodic_sums(C.byref(d), C.byref(nul), p, p, None) == -1 and b"null pointer" in L.snac_last_error()
-    odd = _lib.State(8, 8, 8, 8, 8, 8, 12, 8)
+    odd = _lib.State(*[1 << 20] * 6, (1 << 20) + 12, 1 << 20)
     assert L.snac_episodic_sums(C.byref(d), C.byref(odd), p, p, None) == -1 and b"aligned" in L.snac_last_error()
     assert all(v == 0 for v in buf)
 

@@ -90,7 +90,7 @@ def _observe(L, name, d, st, pool, pool_rows, m, idx=None, obs=PH):
 def test_observe_nodes_validates_its_arguments_before_any_hip_call(name):
     L = _lib.lib()
     kind = int(name[-2])
-    st = _lib.State(1, 1, 1, 1, 1, 1, 1, 1)
+    st = _lib.State(*[1 << 20] * 8)
     d = _desc(kind)
 
     def err(rc, *words):
