@@ -5,7 +5,11 @@ advantages and returns of a horizon come from one launch (snac_gae), and every m
 entropy bonus, with advantages normalised over the horizon and an episode's end treated as terminal.  The network is an actor-critic MLP
 over observation + plan; this file is an illustration of the API, not part of the parity surface.
 
-    python examples/ppo_batched.py --envs 4096 --iterations 20
+With --device-loss the loss of a minibatch, its gradient with respect to the logits and the value, and PPO2's diagnostics come from one
+call (PPOLoss: snac_ppo_loss) instead of the torch composition and autograd's pass back through it; --clip-vf then clips the value
+function as PPO2 does by default.
+
+    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]]
 """
 import argparse
 import os
@@ -17,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, RolloutBuffer  # noqa: E402
+from snac_amd import BatchedDMPEnv, PPOLoss, RolloutBuffer  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -33,10 +37,15 @@ class ActorCritic(nn.Module):
 
 
 def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, seed=1,
-        log=print, device_sampling=False):
+        log=print, device_sampling=False, device_loss=False, clip_vf=None, info=None):
     """-> (the loss of every minibatch update, the mean episodic return after every iteration).  device_sampling: draw the actions and
     their log-probabilities with one launch per tick (RolloutBuffer.act_logits: counter-RNG stream 5, independent of the sharding and of
-    torch's generator) instead of torch.distributions."""
+    torch's generator) instead of torch.distributions.  device_loss: the loss, its gradient and its statistics from PPOLoss (one call per
+    minibatch) instead of the torch composition; clip_vf: with device_loss, the clip range of the value function (None: not clipped,
+    as the composition).  info: a dict that receives the run's device counters with device_loss ("bad_rows": the samples PPOLoss
+    zeroed) and the statistics of the last minibatch ("stats")."""
+    if clip_vf is not None and not device_loss:
+        raise ValueError("clip_vf belongs to device_loss: the torch composition does not clip the value function")
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev = env.device
@@ -44,6 +53,7 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
     buf = RolloutBuffer(env, horizon, gamma, lam)
     net = ActorCritic(env.obs_dim, 400, env.num_actions).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
+    ppo = PPOLoss(env, clip, -1.0 if clip_vf is None else clip_vf, vf_coef, ent_coef) if device_loss else None
     t0, losses, returns = time.time(), [], []
     for it in range(iterations):
         for _ in range(horizon):
@@ -60,11 +70,14 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
         buf.finish(bootstrap)                                      # advantages and returns of the horizon: one launch
         for mb in buf.minibatches(batch, epochs):                  # one gather launch each
             logits, value = net(mb["s"], mb["plan"])
-            dist = torch.distributions.Categorical(logits=logits)
-            ratio = torch.exp(dist.log_prob(mb["action"]) - mb["logp"])
-            surrogate = torch.min(ratio * mb["adv"], torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * mb["adv"]).mean()
-            value_loss = 0.5 * ((value - mb["ret"]) ** 2).mean()
-            loss = -surrogate + vf_coef * value_loss - ent_coef * dist.entropy().mean()
+            if device_loss:
+                loss = ppo.loss(logits, value, mb)                 # the mean loss, carrying its closed-form gradient
+            else:
+                dist = torch.distributions.Categorical(logits=logits)
+                ratio = torch.exp(dist.log_prob(mb["action"]) - mb["logp"])
+                surrogate = torch.min(ratio * mb["adv"], torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * mb["adv"]).mean()
+                value_loss = 0.5 * ((value - mb["ret"]) ** 2).mean()
+                loss = -surrogate + vf_coef * value_loss - ent_coef * dist.entropy().mean()
             opt.zero_grad(set_to_none=True)
             loss.backward()
             nn.utils.clip_grad_norm_(net.parameters(), 0.5)
@@ -75,6 +88,12 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
         log("iteration %3d  loss %.4f  episodes %d  mean return %.2f  mean IoU %.4f  (%.0f env-steps/s incl. learning)" % (
             it + 1, losses[-1], st["episodes"], returns[-1], st["iou_fx_sum"] / 2.0**40 / max(st["episodes"], 1),
             envs * horizon * (it + 1) / (time.time() - t0)))
+        if device_loss:
+            st = ppo.stats_dict()
+            log("               approx KL %.5f  clip fraction %.3f  entropy %.4f  value loss %.4f" % (
+                st["approx_kl"], st["clip_fraction"], st["entropy"], st["value_loss"]))
+    if info is not None and device_loss:
+        info.update(bad_rows=int(ppo.bad_rows.cpu()[0]), stats=ppo.stats_dict())
     return losses, returns
 
 
@@ -86,5 +105,7 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=4)
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--device-sampling", action="store_true", help="draw the actions on the device from the counter RNG (act_logits)")
+    ap.add_argument("--device-loss", action="store_true", help="the loss, its gradient and its statistics from one device call (PPOLoss)")
+    ap.add_argument("--clip-vf", type=float, default=None, help="with --device-loss: clip the value function by this range, as PPO2 does")
     a = ap.parse_args()
-    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling)
+    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling, device_loss=a.device_loss, clip_vf=a.clip_vf)

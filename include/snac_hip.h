@@ -584,6 +584,64 @@ int snac_soft_value(int32_t B, int32_t num_actions, const float* logits, const f
                     const float* ret, const float* discount, double scale, float* v, float* y, float* entropy, float* grad,
                     int32_t* bad_rows, void* stream);
 
+/* ---- PPO loss (the reference's script/PPO) (stable-baselines PPO2's update; snac_amd/ppo.py: PPOLoss; k_ppo.hip, ppo_rule.h): the
+ * clipped surrogate, the (clipped) value loss and the entropy bonus of a minibatch, the mean of their sum, its gradient with respect to
+ * the logits and to the value in closed form, and PPO2's diagnostics (approximate KL, clip fraction), in one call of two launches.  Every
+ * sum over the batch is a float64 sum in the order stated below, so that two runs, and numpy, give the same bytes.
+ *
+ * Inputs per sample i: logits[i][A], logp_old[i], adv[i], value[i], value_old[i], ret[i], float32, rows contiguous, every base aligned
+ * as a float (a slice of a tensor will do); action[i], int64 (what snac_replay_gather_onpolicy writes), 8-byte aligned.  A = 3, 5 or 8,
+ * else SNAC_ERR_UNSUPPORTED.  Parameters: clip > 0; clip_vf (negative: the value function is not clipped and value_old must be NULL;
+ * >= 0: PPO2's cliprange_vf, and value_old is required); vf_coef, ent_coef; scale (e.g. 1.0 / B for the gradient of the mean).
+ * All arithmetic is float64, every product, sum, difference and quotient rounded on its own (no fused multiply-add), sums in index order
+ * starting from 0.0; EXP and LOG are the sequences of "Acting from a policy".  With l_a = logits[i][a]:
+ *     m, x_a, e_a, S, T, L = LOG(S), live_a, pi_a = e_a / S, lp_a = x_a - L      exactly as in "Soft values (discrete SAC)"
+ *     H      = L - T / S                                                         (snac_policy_act's entropy, the same bytes)
+ *     lp     = lp_action                                (the taken action's; picked by compares, never by an index into memory)
+ *     d      = lp - (double)logp_old      clamped = |d| > 20.0      dc = d < -20.0 ? -20.0 : d > 20.0 ? 20.0 : d
+ *     r      = dc <= 0 ? EXP(dc) : 1.0 / EXP(-dc)                                (EXP keeps its stated domain x <= 0)
+ *     lo     = 1.0 - clip, hi = 1.0 + clip  (once per call)                      rc = r < lo ? lo : r > hi ? hi : r
+ *     s1     = r * adv, s2 = rc * adv      Lpi = -(s2 < s1 ? s2 : s1)            g = (!(s2 < s1) && !clamped) ? -(adv * r) : 0.0
+ *     dv     = value - ret
+ *     clip_vf < 0:   Lv = 0.5 * (dv * dv), gv = dv
+ *     clip_vf >= 0:  u = value - value_old, uc = u < -clip_vf ? -clip_vf : u > clip_vf ? clip_vf : u, dc2 = (value_old + uc) - ret,
+ *                    q1 = dv * dv, q2 = dc2 * dc2;  q2 > q1 ? (Lv = 0.5 * q2, gv = (u == uc ? dc2 : 0.0)) : (Lv = 0.5 * q1, gv = dv)
+ *     kl     = 0.5 * (dc * dc)      clipped = |r - 1.0| > clip                   (PPO2's approxkl and clipfrac, per sample)
+ *     total  = (Lpi + vf_coef * Lv) - ent_coef * H
+ *     loss[i]           = (float)total
+ *     grad_logits[i][a] = live_a ? (float)(scale * (g * ((a == action ? 1.0 : 0.0) - pi_a) + ent_coef * (pi_a * (lp_a + H)))) : 0.0f
+ *     grad_value[i]     = (float)(scale * (vf_coef * gv))
+ *   g is dLpi/dlp, and dlp/dl_a = (a == action) - pi_a, dH/dl_a = -pi_a (lp_a + H); gv is dLv/dvalue.  action, logp_old, adv, ret and
+ *   value_old are constants of the loss.  Where |d| > 20 the ratio stands at e^(+-20) and carries no gradient.  On a clip boundary
+ *   (r == lo or hi, or u == +-clip_vf) the gradient is the unclipped side's.
+ *   Bad samples.  A sample is bad if some l_a is a NaN or +inf or every l_a is -inf; if action is outside [0, A) or the taken action has
+ *   no weight (e_action == 0: masked, or more than 45 below the largest); or if logp_old, adv, value, ret -- or value_old, when
+ *   clip_vf >= 0 -- is not finite.  A bad sample gets loss = grad_value = 0 and a row of zeros in grad_logits, contributes 0.0 to every
+ *   sum below, and adds one to bad_rows[0] (int32 on the device, an atomic add).
+ *   The statistics.  Every sample has eight contributions u[0..8) = total, Lpi, Lv, H, kl, clipped ? 1.0 : 0.0, 1.0, clamped ? 1.0 : 0.0
+ *   (all 0.0 for a bad sample).  The order of their sums is part of this interface.  Stage 1, per wave w of 64 consecutive samples
+ *   (the last one filled up with 0.0):
+ *       for off = 32, 16, 8, 4, 2, 1:  u_j = u_j + u_{j ^ off} for every j < 64 (all j of a step together);   partials[w][k] = u_0
+ *     -- in numpy: u = u[:, :h] + u[:, h:] for h = 32, 16, 8, 4, 2, 1.  Stage 2, with W = ceil(B / 64) waves:
+ *       t_j = 0.0; for w = j, j + 64, j + 128, ... < W: t_j = t_j + partials[w][k]      (j < 64; increasing w)
+ *       then the same butterfly over t_0 .. t_63, and sum_k = t_0.
+ *     stats[k] = sum_k / (double)B for k < 6: the means over B of total, Lpi, Lv, H and kl, and the clip fraction (bad samples count
+ *     in B and add nothing); stats[6] = sum_6, the number of good samples; stats[7] = sum_7, the number of clamped ones.
+ *     mean_loss[0] = (float)stats[0].
+ * Outputs: loss float[B], grad_logits float[B][A], grad_value float[B], mean_loss float[1] and bad_rows may each be NULL and are then not
+ * written.  stats double[SNAC_PPO_STATS] may be NULL: then nothing is reduced and the second launch does not happen (mean_loss must be
+ * NULL too).  stats needs partials: ceil(B / 64) * SNAC_PPO_STATS doubles of caller-owned scratch, 8-byte aligned as stats is; its
+ * contents after the call are stage 1's rows.  With every output NULL nothing is launched.  The kernels read their inputs only and write
+ * nothing but the outputs given and partials.
+ * Checks, all before any HIP call: logits, action, logp_old, adv, value, ret non-null; B >= 1; clip finite and > 0; clip_vf, vf_coef,
+ * ent_coef and scale finite; value_old given exactly when clip_vf >= 0; partials with stats, stats with mean_loss; the 8-byte
+ * alignments; num_actions 3, 5 or 8.  Both launches go on `stream`; no host synchronisation. */
+#define SNAC_PPO_STATS 8
+int snac_ppo_loss(int32_t B, int32_t num_actions, const float* logits, const int64_t* action, const float* logp_old, const float* adv,
+                  const float* value, const float* value_old, const float* ret, double clip, double clip_vf, double vf_coef, double ent_coef,
+                  double scale, float* loss, float* grad_logits, float* grad_value, double* stats, float* mean_loss, double* partials,
+                  int32_t* bad_rows, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

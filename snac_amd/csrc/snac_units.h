@@ -39,6 +39,8 @@
 //                                 projected TD target: lane = atom, a wave per sample, the scatter turned into an ordered gather
 //   k_soft.hip      k_soft_value  discrete SAC's soft state value, TD target, entropy and actor-loss gradient from one softmax: lane = sample
 //                   (spec_math.h: EXP and LOG of the header, for this and k_policy.hip; soft_rule.h: the per-sample rule, host and device)
+//   k_ppo.hip       k_ppo_loss / k_ppo_reduce   PPO2's clipped loss, its gradient and its statistics: lane = sample, then the batch sums in a
+//                                 fixed order: an xor butterfly per wave, one wave over the waves' partials (ppo_rule.h: the per-sample rule)
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory
