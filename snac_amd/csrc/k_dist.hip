@@ -193,12 +193,11 @@ __global__ __launch_bounds__(64 * C51_WAVES) void k_c51_expect(const C51ExpectAr
 
 unsigned c51_blocks(int32_t B, int spw) { return (unsigned)(((long long)B + C51_WAVES * spw - 1) / (C51_WAVES * spw)); }
 
-// the checks both entry points share; *dz: the support's step
-int c51_check(int32_t B, int32_t num_actions, int32_t atoms, double vmin, double vmax, double* dz) {
+// the checks both entry points share before by_actions' own; *dz: the support's step
+int c51_check(int32_t B, int32_t atoms, double vmin, double vmax, double* dz) {
     if (B < 1) return fail(SNAC_ERR_ARG, "B must be >= 1");
     if (atoms < 2 || atoms > 64) return fail(SNAC_ERR_ARG, "atoms must be in [2, 64]");
     if (!std::isfinite(vmin) || !std::isfinite(vmax) || !(vmin < vmax)) return fail(SNAC_ERR_ARG, "vmin and vmax must be finite, with vmin < vmax");
-    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_UNSUPPORTED, "num_actions must be 3, 5 or 8");
     *dz = (vmax - vmin) / (double)(atoms - 1);
     return SNAC_OK;
 }
@@ -209,17 +208,14 @@ extern "C" int snac_c51_expect(int32_t B, int32_t num_actions, int32_t atoms, do
     using namespace snac_detail;
     if (!p || !q) return fail(SNAC_ERR_ARG, "null p/q");
     double dz;
-    if (int rc = c51_check(B, num_actions, atoms, vmin, vmax, &dz)) return rc;
-    const C51ExpectArgs g{B, atoms, vmin, dz, p, q};
-    g_kernel = "k_c51_expect";
-    const dim3 grid(c51_blocks(B, C51_EXPECT_SPW)), block(64 * C51_WAVES);
-    const hipStream_t s = (hipStream_t)stream;
-    switch (num_actions) {
-        case 3: hipLaunchKernelGGL(k_c51_expect<3>, grid, block, 0, s, g); break;
-        case 5: hipLaunchKernelGGL(k_c51_expect<5>, grid, block, 0, s, g); break;
-        default: hipLaunchKernelGGL(k_c51_expect<8>, grid, block, 0, s, g); break;
-    }
-    return launched("snac_c51_expect");
+    if (int rc = c51_check(B, atoms, vmin, vmax, &dz)) return rc;
+    return by_actions(num_actions, [&](auto actions) {
+        const C51ExpectArgs g{B, atoms, vmin, dz, p, q};
+        g_kernel = "k_c51_expect";
+        const dim3 grid(c51_blocks(B, C51_EXPECT_SPW)), block(64 * C51_WAVES);
+        hipLaunchKernelGGL(k_c51_expect<decltype(actions)::value>, grid, block, 0, (hipStream_t)stream, g);
+        return launched("snac_c51_expect");
+    });
 }
 
 extern "C" int snac_c51_project(int32_t B, int32_t num_actions, int32_t atoms, double vmin, double vmax, const float* p_next,
@@ -228,15 +224,12 @@ extern "C" int snac_c51_project(int32_t B, int32_t num_actions, int32_t atoms, d
     using namespace snac_detail;
     if (!p_next || !ret || !discount || !m) return fail(SNAC_ERR_ARG, "null p_next/ret/discount/m");
     double dz;
-    if (int rc = c51_check(B, num_actions, atoms, vmin, vmax, &dz)) return rc;
-    const C51Args g{B, atoms, vmin, vmax, dz, p_next, p_select ? p_select : p_next, ret, discount, m, a_star, q_star, bad_rows};
-    g_kernel = "k_c51_project";
-    const dim3 grid(c51_blocks(B, C51_SPW)), block(64 * C51_WAVES);
-    const hipStream_t s = (hipStream_t)stream;
-    switch (num_actions) {
-        case 3: hipLaunchKernelGGL(k_c51_project<3>, grid, block, 0, s, g); break;
-        case 5: hipLaunchKernelGGL(k_c51_project<5>, grid, block, 0, s, g); break;
-        default: hipLaunchKernelGGL(k_c51_project<8>, grid, block, 0, s, g); break;
-    }
-    return launched("snac_c51_project");
+    if (int rc = c51_check(B, atoms, vmin, vmax, &dz)) return rc;
+    return by_actions(num_actions, [&](auto actions) {
+        const C51Args g{B, atoms, vmin, vmax, dz, p_next, p_select ? p_select : p_next, ret, discount, m, a_star, q_star, bad_rows};
+        g_kernel = "k_c51_project";
+        const dim3 grid(c51_blocks(B, C51_SPW)), block(64 * C51_WAVES);
+        hipLaunchKernelGGL(k_c51_project<decltype(actions)::value>, grid, block, 0, (hipStream_t)stream, g);
+        return launched("snac_c51_project");
+    });
 }

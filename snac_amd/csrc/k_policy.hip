@@ -1,10 +1,11 @@
 // k_policy.hip -- snac_policy_act: one action per env from a row of A float32 scores (categorical, greedy, epsilon-greedy), with the
-// categorical draw's log-probability and entropy.  include/snac_hip.h, "Acting from a policy", has the rule.
+// categorical draw's log-probability and entropy.  include/snac_hip.h, "Acting from a policy", has the rule; softmax_rule.h states its softmax, for this kernel and for
+// the rules of k_soft.hip and k_ppo.hip.
 #include <cmath>
 #include <cstddef>
 
 #include "snac_units.h"
-#include "spec_math.h"
+#include "softmax_rule.h"
 
 // lane = env: the outputs of a wave are coalesced spans of action / logp / entropy, and nothing crosses lanes.  The scores are read as A
 // strided dword loads per lane, all issued before the first use.  A wave's rows are one contiguous span of 64 * A floats (768 / 1280 /
@@ -15,7 +16,7 @@
 namespace {
 
 using namespace snac_detail;
-using namespace snac_spec;                                          // spec_exp / spec_log: EXP and LOG of the header
+using namespace snac_spec;
 
 struct PolicyArgs {
     int32_t n;
@@ -42,15 +43,8 @@ __global__ __launch_bounds__(64) void k_policy_act(const PolicyArgs g) {
     if (MODE == SNAC_POLICY_EPS_GREEDY && g.eps_env) eps = g.eps_env[i];
     const uint32_t w = rng_word(env_keys(g.key, (uint64_t)(g.env_id_base + i)), g.t);
 
-    float m = s[0];
-    bool bad = false;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        if (a && s[a] > m) m = s[a];
-        bad |= __builtin_isnan(s[a]) || s[a] == INFINITY;
-    }
-    bad |= m == -INFINITY;
-    if (bad) {                                                       // drawn as if every score were 0
+    float m;
+    if (softmax_scan(s, m)) {                                        // a bad row: drawn as if every score were 0
         m = 0.0f;
 #pragma unroll
         for (int a = 0; a < A; ++a) s[a] = 0.0f;
@@ -68,14 +62,10 @@ __global__ __launch_bounds__(64) void k_policy_act(const PolicyArgs g) {
     }
     if (MODE == SNAC_POLICY_CATEGORICAL) {
         double x[A], e[A];
+        softmax_terms(s, m, x, e);
         uint32_t wt[A], total = 0;                                   // total <= 8 * 2^28 = 2^31
 #pragma unroll
         for (int a = 0; a < A; ++a) {
-            {
-#pragma clang fp contract(off)
-                x[a] = (double)s[a] - (double)m;
-            }
-            e[a] = spec_exp(x[a]);
             wt[a] = (uint32_t)(uint64_t)floor(e[a] * 268435456.0);   // a power of two: the product is exact
             total += wt[a];
         }
@@ -93,35 +83,15 @@ __global__ __launch_bounds__(64) void k_policy_act(const PolicyArgs g) {
             found |= hit;
         }
         if (g.logp || g.entropy) {                                   // uniform: kernel arguments
-            double S = 0.0, T = 0.0;
-            {
-#pragma clang fp contract(off)
-#pragma unroll
-                for (int a = 0; a < A; ++a) {
-                    S = S + e[a];
-                    T = T + (e[a] == 0.0 ? 0.0 : e[a] * x[a]);      // x may be -inf where e is 0: that term is 0.0
-                }
-            }
-            const double L = spec_log(S);
+            const SoftmaxSums sm = softmax_sums(x, e);
             if (g.logp) {
 #pragma clang fp contract(off)
-                g.logp[i] = (float)(xa - L);
+                g.logp[i] = (float)(xa - sm.L);
             }
-            if (g.entropy) {
-#pragma clang fp contract(off)
-                g.entropy[i] = (float)(L - T / S);
-            }
+            if (g.entropy) g.entropy[i] = (float)softmax_entropy(sm);
         }
     }
     if (g.action) g.action[i] = (int8_t)action;
-}
-
-template <int A>
-void launch_policy(int mode, const PolicyArgs& g, hipStream_t s) {
-    const dim3 grid((unsigned)(((long long)g.n + 63) / 64)), block(64);
-    if (mode == SNAC_POLICY_CATEGORICAL) hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_CATEGORICAL>), grid, block, 0, s, g);
-    else if (mode == SNAC_POLICY_GREEDY) hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_GREEDY>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_EPS_GREEDY>), grid, block, 0, s, g);
 }
 
 }  // namespace
@@ -140,13 +110,14 @@ extern "C" int snac_policy_act(const snac_env_desc* desc, int32_t N, uint32_t t,
     if ((logp || entropy) && mode != SNAC_POLICY_CATEGORICAL) return fail(SNAC_ERR_ARG, "logp / entropy are defined by the categorical mode only");
     if (!action && !logp && !entropy) return SNAC_OK;                // nothing asked for
     const PolicyArgs g{N, t, stream_key(desc->seed, 5), desc->env_id_base, scores, epsilon, epsilon_per_env, action, logp, entropy, bad_rows};
-    g_kernel = "k_policy_act";
-    const hipStream_t s = (hipStream_t)stream;
-    switch (sz.num_actions) {
-        case 3: launch_policy<3>(mode, g, s); break;
-        case 5: launch_policy<5>(mode, g, s); break;
-        case 8: launch_policy<8>(mode, g, s); break;
-        default: return fail(SNAC_ERR_UNSUPPORTED, "num_actions must be 3, 5 or 8");
-    }
-    return launched("snac_policy_act");
+    return by_actions(sz.num_actions, [&](auto actions) {
+        constexpr int A = decltype(actions)::value;
+        g_kernel = "k_policy_act";
+        const dim3 grid((unsigned)(((long long)N + 63) / 64)), block(64);
+        const hipStream_t s = (hipStream_t)stream;
+        if (mode == SNAC_POLICY_CATEGORICAL) hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_CATEGORICAL>), grid, block, 0, s, g);
+        else if (mode == SNAC_POLICY_GREEDY) hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_GREEDY>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((k_policy_act<A, SNAC_POLICY_EPS_GREEDY>), grid, block, 0, s, g);
+        return launched("snac_policy_act");
+    });
 }

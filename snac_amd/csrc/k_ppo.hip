@@ -98,13 +98,6 @@ __global__ __launch_bounds__(64) void k_ppo_reduce(const double* partials, long 
     }
 }
 
-template <int A>
-void launch_ppo(const PpoArgs& g, bool clip_vf, hipStream_t s) {
-    const dim3 grid((unsigned)(((long long)g.B + 63) / 64)), block(64);
-    if (clip_vf) hipLaunchKernelGGL((k_ppo_loss<A, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((k_ppo_loss<A, false>), grid, block, 0, s, g);
-}
-
 }  // namespace
 
 extern "C" int snac_ppo_loss(int32_t B, int32_t num_actions, const float* logits, const int64_t* action, const float* logp_old, const float* adv,
@@ -128,20 +121,17 @@ extern "C" int snac_ppo_loss(int32_t B, int32_t num_actions, const float* logits
     if (!stats && mean_loss) return fail(SNAC_ERR_ARG, "mean_loss is stats[0]: stats is needed for it");
     if ((uintptr_t)action % 8) return fail(SNAC_ERR_ARG, "action must be 8-byte aligned");
     if (stats && ((uintptr_t)stats % 8 || (uintptr_t)partials % 8)) return fail(SNAC_ERR_ARG, "stats and partials must be 8-byte aligned");
-    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_UNSUPPORTED, "num_actions must be 3, 5 or 8");
-    if (!loss && !grad_logits && !grad_value && !stats && !bad_rows) return SNAC_OK;      // nothing asked for
-    const snac_spec::PpoParams p{clip, 1.0 - clip, 1.0 + clip, clip_vf, vf_coef, ent_coef, scale};
-    const PpoArgs g{B, logits, action, logp_old, adv, value, value_old, ret, p, loss, grad_logits, grad_value, stats ? partials : nullptr, bad_rows};
-    g_kernel = "k_ppo_loss";
-    const hipStream_t s = (hipStream_t)stream;
-    switch (num_actions) {
-        case 3: launch_ppo<3>(g, clip_v, s); break;
-        case 5: launch_ppo<5>(g, clip_v, s); break;
-        default: launch_ppo<8>(g, clip_v, s); break;
-    }
-    if (stats) {
-        const long long W = ((long long)B + 63) / 64;
-        hipLaunchKernelGGL(k_ppo_reduce, dim3(1), dim3(64), 0, s, (const double*)partials, W, B, stats, mean_loss);
-    }
-    return launched("snac_ppo_loss");
+    return by_actions(num_actions, [&](auto actions) -> int {
+        constexpr int A = decltype(actions)::value;
+        if (!loss && !grad_logits && !grad_value && !stats && !bad_rows) return SNAC_OK;      // nothing asked for
+        const snac_spec::PpoParams p{clip, 1.0 - clip, 1.0 + clip, clip_vf, vf_coef, ent_coef, scale};
+        const PpoArgs g{B, logits, action, logp_old, adv, value, value_old, ret, p, loss, grad_logits, grad_value, stats ? partials : nullptr, bad_rows};
+        g_kernel = "k_ppo_loss";
+        const long long W = ((long long)B + 63) / 64;                // waves, and rows of partials
+        const hipStream_t s = (hipStream_t)stream;
+        if (clip_v) hipLaunchKernelGGL((k_ppo_loss<A, true>), dim3((unsigned)W), dim3(64), 0, s, g);
+        else hipLaunchKernelGGL((k_ppo_loss<A, false>), dim3((unsigned)W), dim3(64), 0, s, g);
+        if (stats) hipLaunchKernelGGL(k_ppo_reduce, dim3(1), dim3(64), 0, s, (const double*)partials, W, B, stats, mean_loss);
+        return launched("snac_ppo_loss");
+    });
 }

@@ -62,13 +62,6 @@ __global__ __launch_bounds__(64) void k_soft_value(const SoftArgs g) {
     }
 }
 
-template <int A>
-void launch_soft(const SoftArgs& g, bool two_q, hipStream_t s) {
-    const dim3 grid((unsigned)(((long long)g.B + 63) / 64)), block(64);
-    if (two_q) hipLaunchKernelGGL((k_soft_value<A, true>), grid, block, 0, s, g);
-    else hipLaunchKernelGGL((k_soft_value<A, false>), grid, block, 0, s, g);
-}
-
 }  // namespace
 
 extern "C" int snac_soft_value(int32_t B, int32_t num_actions, const float* logits, const float* q1, const float* q2, const float* alpha,
@@ -82,16 +75,15 @@ extern "C" int snac_soft_value(int32_t B, int32_t num_actions, const float* logi
     if (use_q && (!q1 || !alpha)) return fail(SNAC_ERR_ARG, "q1 and alpha are needed for v, y and grad");
     if (y && (!ret || !discount)) return fail(SNAC_ERR_ARG, "ret and discount are needed for y");
     if (!y && (ret || discount)) return fail(SNAC_ERR_ARG, "ret and discount belong to y");
-    if (num_actions != 3 && num_actions != 5 && num_actions != 8) return fail(SNAC_ERR_UNSUPPORTED, "num_actions must be 3, 5 or 8");
-    if (!use_q && !entropy) return SNAC_OK;                          // nothing asked for
-    const SoftArgs g{B, logits, q1, q2, alpha, ret, discount, scale, v, y, entropy, grad, bad_rows};
-    g_kernel = "k_soft_value";
-    const hipStream_t s = (hipStream_t)stream;
-    const bool two_q = use_q && q2;
-    switch (num_actions) {
-        case 3: launch_soft<3>(g, two_q, s); break;
-        case 5: launch_soft<5>(g, two_q, s); break;
-        default: launch_soft<8>(g, two_q, s); break;
-    }
-    return launched("snac_soft_value");
+    return by_actions(num_actions, [&](auto actions) -> int {
+        constexpr int A = decltype(actions)::value;
+        if (!use_q && !entropy) return SNAC_OK;                      // nothing asked for
+        const SoftArgs g{B, logits, q1, q2, alpha, ret, discount, scale, v, y, entropy, grad, bad_rows};
+        g_kernel = "k_soft_value";
+        const dim3 grid((unsigned)(((long long)B + 63) / 64)), block(64);
+        const hipStream_t s = (hipStream_t)stream;
+        if (use_q && q2) hipLaunchKernelGGL((k_soft_value<A, true>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((k_soft_value<A, false>), grid, block, 0, s, g);
+        return launched("snac_soft_value");
+    });
 }

@@ -1001,13 +1001,6 @@ int set_priors_check(int A, const void* stats, int32_t stats_rows, int32_t m, co
     return SNAC_OK;
 }
 
-template <class F>
-void by_actions(int A, F f) {
-    if (A == 3) f(std::integral_constant<int, 3>());
-    else if (A == 5) f(std::integral_constant<int, 5>());
-    else f(std::integral_constant<int, 8>());
-}
-
 }  // namespace
 
 extern "C" {
@@ -1023,10 +1016,10 @@ int snac_uct_select(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
         return fail(SNAC_ERR_ARG, "null per-tree array (used / src / dst / action / leaf / expanded / r_leaf)");
     const UctSel v{(uint4*)stats, B, cap, c, log_table, rsqrt_table, table_len, used, src, dst, action, leaf, expanded, r_leaf};
     g_kernel = "k_uct_select";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_select<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+        return launched("snac_uct_select");
     });
-    return launched("snac_uct_select");
 }
 
 int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, double gamma, const int32_t* src,
@@ -1038,10 +1031,10 @@ int snac_uct_backup(int32_t num_actions, snac_uct_node* stats, int32_t stats_row
         return fail(SNAC_ERR_ARG, "null per-tree array (src / action / leaf / expanded / reward / done / est)");
     const UctBack v{(uint4*)stats, B, cap, gamma, src, action, leaf, expanded, reward, done, est};
     g_kernel = "k_uct_backup";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_backup<decltype(k)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+        return launched("snac_uct_backup");
     });
-    return launched("snac_uct_backup");
 }
 
 int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,
@@ -1058,12 +1051,12 @@ int snac_uct_advance(int32_t num_actions, snac_uct_node* stats, int32_t stats_ro
     if (!work) return fail(SNAC_ERR_ARG, "null work");
     const UctAdv v{(uint4*)stats, (uint4*)records, B, cap, actions, edge_reward, edge_done, used, work, reward_out, done_out};
     g_kernel = "k_uct_advance";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         constexpr int A = decltype(k)::value;
         if (record_bytes == 128) hipLaunchKernelGGL((k_uct_advance<A, 8>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, v);
         else hipLaunchKernelGGL((k_uct_advance<A, 56>), dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, v);
+        return launched("snac_uct_advance");
     });
-    return launched("snac_uct_advance");
 }
 
 // the plain and the _norm entry points share their checks and launches: bounds == nullptr is the plain form
@@ -1079,12 +1072,12 @@ static int select_paths(const char* name, int32_t num_actions, snac_uct_node* st
     if (int rc = select_check(v, "null log_table / rsqrt_table", norm, bounds)) return rc;
     const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_select_paths";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         constexpr int A = decltype(k)::value;
         if (norm) hipLaunchKernelGGL((k_uct_select_paths<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPathsNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_select_paths<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
+        return launched(name);
     });
-    return launched(name);
 }
 
 int snac_uct_select_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -1115,12 +1108,12 @@ static int backup_paths(const char* name, int32_t num_actions, snac_uct_node* st
     const UctBackPaths v{{(uint4*)stats, B, cap, gamma, src, action, leaf, expanded, reward, done, est}, paths};
     const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_backup_paths";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         constexpr int A = decltype(k)::value;
         if (norm) hipLaunchKernelGGL((k_uct_backup_paths<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctBackPathsNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_backup_paths<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
+        return launched(name);
     });
-    return launched(name);
 }
 
 int snac_uct_backup_paths(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double gamma,
@@ -1158,7 +1151,7 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
     if (interior && (!std::isfinite(c_visit) || !std::isfinite(c_scale))) return fail(SNAC_ERR_ARG, "c_visit and c_scale must be finite");
     const dim3 grid((unsigned)((B + 63) / 64));
     g_kernel = "k_uct_select_puct";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         constexpr int A = decltype(k)::value;
         if (interior)
             hipLaunchKernelGGL((k_uct_select_puct<A, true, true, true>), grid, dim3(64), 0, (hipStream_t)stream,
@@ -1166,8 +1159,8 @@ static int select_puct(const char* name, int32_t num_actions, snac_uct_node* sta
         else if (cand) hipLaunchKernelGGL((k_uct_select_puct<A, true, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelGumbel{{v, bounds}, cand, offset});
         else if (norm) hipLaunchKernelGGL((k_uct_select_puct<A, true>), grid, dim3(64), 0, (hipStream_t)stream, UctSelPuctNorm{v, bounds});
         else hipLaunchKernelGGL((k_uct_select_puct<A, false>), grid, dim3(64), 0, (hipStream_t)stream, v);
+        return launched(name);
     });
-    return launched(name);
 }
 
 int snac_uct_select_puct(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t paths, double c,
@@ -1213,11 +1206,11 @@ int snac_uct_set_priors(int32_t num_actions, snac_uct_node* stats, int32_t stats
     if (int rc = set_priors_check(num_actions, stats, stats_rows, m, rows, priors)) return rc;
     if (m == 0) return SNAC_OK;
     g_kernel = "k_uct_set_priors";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_set_priors<decltype(k)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint4*)stats,
                            stats_rows, m, rows, priors, only_unvisited != 0 ? 1 : 0);
+        return launched("snac_uct_set_priors");
     });
-    return launched("snac_uct_set_priors");
 }
 
 int snac_uct_set_priors_value(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t m, const int32_t* rows, const float* priors,
@@ -1227,11 +1220,11 @@ int snac_uct_set_priors_value(int32_t num_actions, snac_uct_node* stats, int32_t
     if (!value) return fail(SNAC_ERR_ARG, "null value");
     if (m == 0) return SNAC_OK;
     g_kernel = "k_uct_set_priors_value";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_set_priors_value<decltype(k)::value>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                            (uint4*)stats, stats_rows, m, rows, priors, value, only_unvisited != 0 ? 1 : 0);
+        return launched("snac_uct_set_priors_value");
     });
-    return launched("snac_uct_set_priors_value");
 }
 
 int snac_uct_improved_policy(int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, int32_t m,
@@ -1246,10 +1239,10 @@ int snac_uct_improved_policy(int32_t num_actions, const snac_uct_node* stats, in
     if (m == 0) return SNAC_OK;
     const UctImproved v{(const uint4*)stats, B, cap, m, rows, c_visit, c_scale, bounds, pi};
     g_kernel = "k_uct_improved_policy";
-    by_actions(num_actions, [&](auto k) {
+    return by_actions(num_actions, [&](auto k) {
         hipLaunchKernelGGL((k_uct_improved_policy<decltype(k)::value>), dim3((unsigned)((m + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+        return launched("snac_uct_improved_policy");
     });
-    return launched("snac_uct_improved_policy");
 }
 
 int snac_uct_bounds(const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, const int32_t* used, const uint8_t* mask,

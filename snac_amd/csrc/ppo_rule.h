@@ -2,12 +2,12 @@
 // per lane and that a host compiler can compile as it stands (tests/native/ppo_host.cpp, with -ffp-contract=off): PPO2's clipped
 // surrogate, its clipped value loss and the entropy bonus of one sample, the closed-form gradient with respect to the logits and to the
 // value, and the sample's eight contributions to the batch statistics.  Every float64 operation below is one operation of the rule,
-// rounded on its own; sums run in index order from 0.0.  The softmax part is soft_rule.h's, operation for operation.
+// rounded on its own; sums run in index order from 0.0.  The softmax part is softmax_rule.h's.
 #pragma once
 #include <cmath>
 #include <cstdint>
 
-#include "spec_math.h"
+#include "softmax_rule.h"
 
 #define SNAC_PPO_LOGRATIO_MAX 20.0                                    // |lp - logp_old| beyond it: the ratio is taken at the bound, no gradient
 
@@ -40,30 +40,17 @@ SNAC_SPEC_FN PpoSample<A> ppo_sample(const float (&l)[A], int64_t action, float 
     for (int a = 0; a < A; ++a) o.grad[a] = 0.0f;
 #pragma unroll
     for (int k = 0; k < PPO_STATS; ++k) o.u[k] = 0.0;
-    float m = l[0];
-    bool bad = false;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        if (a && l[a] > m) m = l[a];
-        bad |= (l[a] != l[a]) || l[a] == INFINITY;
-    }
-    bad |= m == -INFINITY;
+    float m;
+    bool bad = softmax_scan(l, m);
     bad |= action < 0 || action >= A;
     bad |= !(fabsf(logp_old) < INFINITY) || !(fabsf(adv) < INFINITY) || !(fabsf(value) < INFINITY) || !(fabsf(ret) < INFINITY);
     if (CLIP_VF) bad |= !(fabsf(value_old) < INFINITY);
     o.bad = bad;
     if (bad) return o;
     double x[A], e[A];
-    double S = 0.0, T = 0.0;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        x[a] = (double)l[a] - (double)m;
-        e[a] = spec_exp(x[a]);
-        S = S + e[a];
-        T = T + (e[a] == 0.0 ? 0.0 : e[a] * x[a]);                   // x may be -inf where e is 0: that term is 0.0
-    }
-    const double L = spec_log(S);
-    const double H = L - T / S;                                      // soft_rule.h's expression: snac_policy_act's bytes
+    softmax_terms(l, m, x, e);
+    const SoftmaxSums sm = softmax_sums(x, e);
+    const double S = sm.S, L = sm.L, H = softmax_entropy(sm);
     double pi[A], lpa[A];
     double lp = 0.0, e_act = 0.0;
 #pragma unroll

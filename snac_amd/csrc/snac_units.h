@@ -38,9 +38,11 @@
 //   k_dist.hip      k_c51_expect / k_c51_project   categorical (C51) value distributions: expected values, the choice of the next action and the
 //                                 projected TD target: lane = atom, a wave per sample, the scatter turned into an ordered gather
 //   k_soft.hip      k_soft_value  discrete SAC's soft state value, TD target, entropy and actor-loss gradient from one softmax: lane = sample
-//                   (spec_math.h: EXP and LOG of the header, for this and k_policy.hip; soft_rule.h: the per-sample rule, host and device)
+//                   (soft_rule.h: the per-sample rule, host and device)
 //   k_ppo.hip       k_ppo_loss / k_ppo_reduce   PPO2's clipped loss, its gradient and its statistics: lane = sample, then the batch sums in a
 //                                 fixed order: an xor butterfly per wave, one wave over the waves' partials (ppo_rule.h: the per-sample rule)
+//                   (for k_policy.hip and these two rules: softmax_rule.h, the float64 softmax of a row of scores in three steps, on
+//                   spec_math.h's EXP and LOG; for those three units and k_dist.hip: by_actions below, the choice of the A = 3 / 5 / 8 instance)
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory
@@ -111,5 +113,17 @@ void by_rows(const snac_env_desc* d, F f) {
     const bool f32 = d->obs_dtype == SNAC_OBS_F32;
     if (d->dynamic != 0) { if (f32) f(std::true_type(), float()); else f(std::true_type(), double()); }
     else { if (f32) f(std::false_type(), float()); else f(std::false_type(), double()); }
+}
+
+// the three action counts the units on rows of A scores are instantiated for: returns f(std::integral_constant<int, A>()), or the
+// refusal of any other count
+template <typename F>
+int by_actions(int num_actions, F f) {
+    switch (num_actions) {
+        case 3: return f(std::integral_constant<int, 3>());
+        case 5: return f(std::integral_constant<int, 5>());
+        case 8: return f(std::integral_constant<int, 8>());
+        default: return fail(SNAC_ERR_UNSUPPORTED, "num_actions must be 3, 5 or 8");
+    }
 }
 }  // namespace snac_detail

@@ -1,11 +1,11 @@
 // soft_rule.h -- the per-sample rule of include/snac_hip.h, "Soft values (discrete SAC)", as one function that k_soft.hip runs per lane
 // and that a host compiler can compile as it stands (tests/native/soft_host.cpp, with -ffp-contract=off): the soft state value, the TD
-// target, the entropy and the gradient of the actor loss with respect to the logits, all from one softmax.  Every float64 operation
-// below is one operation of the rule, rounded on its own; sums run in index order from 0.0.
+// target, the entropy and the gradient of the actor loss with respect to the logits, all from one softmax (softmax_rule.h states it).  Every float64
+// operation below is one operation of the rule, rounded on its own; sums run in index order from 0.0.
 #pragma once
 #include <cmath>
 
-#include "spec_math.h"
+#include "softmax_rule.h"
 
 namespace snac_spec {
 
@@ -23,14 +23,8 @@ SNAC_SPEC_FN SoftSample<A> soft_sample(const float (&l)[A], const float (&q1)[A]
                                        bool use_q, bool want_y, double scale) {
 #pragma clang fp contract(off)
     SoftSample<A> o;
-    float m = l[0];
-    bool bad = false;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        if (a && l[a] > m) m = l[a];
-        bad |= (l[a] != l[a]) || l[a] == INFINITY;
-    }
-    bad |= m == -INFINITY;
+    float m;
+    bool bad = softmax_scan(l, m);
     if (use_q) bad |= !(fabsf(alpha) < INFINITY) || alpha < 0.0f;
     if (want_y) bad |= !(fabsf(ret) < INFINITY) || !(fabsf(discount) < INFINITY) || discount < 0.0f;
     o.bad = bad;
@@ -41,16 +35,10 @@ SNAC_SPEC_FN SoftSample<A> soft_sample(const float (&l)[A], const float (&q1)[A]
         return o;
     }
     double x[A], e[A];
-    double S = 0.0, T = 0.0;
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        x[a] = (double)l[a] - (double)m;
-        e[a] = spec_exp(x[a]);
-        S = S + e[a];
-        T = T + (e[a] == 0.0 ? 0.0 : e[a] * x[a]);                   // x may be -inf where e is 0: that term is 0.0
-    }
-    const double L = spec_log(S);
-    o.entropy = (float)(L - T / S);                                  // snac_policy_act's expression: the same bytes
+    softmax_terms(l, m, x, e);
+    const SoftmaxSums sm = softmax_sums(x, e);
+    const double S = sm.S, L = sm.L;
+    o.entropy = (float)softmax_entropy(sm);
     o.v = o.y = 0.0f;
 #pragma unroll
     for (int a = 0; a < A; ++a) o.grad[a] = 0.0f;

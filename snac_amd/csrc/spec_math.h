@@ -1,6 +1,6 @@
 // spec_math.h -- EXP and LOG of include/snac_hip.h ("Acting from a policy"): fixed sequences of float64 operations, every one rounded on
-// its own, so that numpy restates their results byte for byte.  For k_policy.hip and k_soft.hip, and for the host: the functions are
-// __host__ __device__ under hipcc and plain inline functions under a host compiler (which then needs -ffp-contract=off; clang reads the
+// its own, so that numpy restates their results byte for byte.  For softmax_rule.h and the rules built on it (soft_rule.h, ppo_rule.h), on
+// the device and on the host: the functions are __host__ __device__ under hipcc and plain inline functions under a host compiler (which then needs -ffp-contract=off; clang reads the
 // pragmas below, gcc does not).  Not part of snac_dev.h: nothing of the env kernels needs them.
 #pragma once
 #include <cmath>

@@ -14,28 +14,21 @@ bytes on every run; the textbook composition in torch ends in index_add_, whose 
 
 The loss and its gradient are the caller's, in torch.
 """
-import ctypes as C
 import math
 
 import torch
 
-from . import _lib
 from ._lib import ptr as _ptr
+from ._rule import Rule
 
 MAX_ATOMS = 64
 
 
-class CategoricalSupport:
+class CategoricalSupport(Rule):
     def __init__(self, num_actions, atoms=51, vmin=-10.0, vmax=10.0, device=None):
         """num_actions: 3, 5 or 8 (the envs' action counts), or a BatchedDMPEnv, whose num_actions, device and stream are then taken;
         atoms: 2 .. 64; vmin < vmax, both finite; device: a cuda device (not with an env)."""
-        self.env = None
-        if hasattr(num_actions, "num_actions") and hasattr(num_actions, "device"):
-            if device is not None:
-                raise ValueError("device is the env's when an env is given")
-            self.env, device, num_actions = num_actions, num_actions.device, num_actions.num_actions
-        if isinstance(num_actions, bool) or not isinstance(num_actions, int) or num_actions not in (3, 5, 8):
-            raise ValueError("num_actions must be 3, 5 or 8 (or a BatchedDMPEnv)")
+        super().__init__(num_actions, device, "the distributions live")
         if isinstance(atoms, bool) or not isinstance(atoms, int) or not 2 <= atoms <= MAX_ATOMS:
             raise ValueError("atoms must be an integer in [2, %d]" % MAX_ATOMS)
         for name, v in (("vmin", vmin), ("vmax", vmax)):
@@ -43,22 +36,9 @@ class CategoricalSupport:
                 raise ValueError("%s must be a finite number" % name)
         if not vmin < vmax:
             raise ValueError("vmin must be below vmax")
-        if device is None:
-            raise ValueError("device must be given (or an env)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("device must be a cuda device: the distributions live in device memory")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.num_actions, self.atoms, self.vmin, self.vmax = num_actions, atoms, float(vmin), float(vmax)
+        self.atoms, self.vmin, self.vmax = atoms, float(vmin), float(vmax)
         self.dz = (self.vmax - self.vmin) / float(atoms - 1)          # the header's dz: one float64 quotient
-        self._lib = _lib.lib()
-        self._z = self._bad = None                                   # made on first use: the constructor does not touch the device
-
-    def _stream(self):
-        if self.env is not None:
-            return self.env._current_stream()
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._z = None                                               # made on first use: the constructor does not touch the device
 
     @property
     def z(self):
@@ -67,35 +47,19 @@ class CategoricalSupport:
             self._z = torch.tensor([self.vmin + float(i) * self.dz for i in range(self.atoms)], dtype=torch.float64).to(torch.float32).to(self.device)
         return self._z
 
-    @property
-    def bad_rows(self):
-        """int32 [1] on the device: the samples project() has zeroed so far (ret or discount not finite, or discount < 0)."""
-        if self._bad is None:
-            self._bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        return self._bad
-
-    def _check(self, t, shape, dtype, what):
-        """`t` is what the kernel reads or writes: a contiguous `dtype` tensor of `shape` (None: any size) on the device."""
-        shown = "(%s)" % ", ".join("B" if s is None else str(s) for s in shape) if len(shape) > 1 else "(%s,)" % ("B" if shape[0] is None else shape[0])
-        if not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shown, self.device))
-        if t.dim() != len(shape) or any(s is not None and int(g) != s for g, s in zip(t.shape, shape)) or t.shape[0] < 1:
-            raise ValueError("%s must have shape %s, got %s" % (what, shown, tuple(t.shape)))
-        if t.device != self.device:
-            raise ValueError("%s must be on %s" % (what, self.device))
-        return t
+    bad_rows = property(Rule._bad_rows, doc="""int32 [1] on the device: the samples project() has zeroed so far (ret or discount not
+    finite, or discount < 0).""")
 
     def _call(self, fn, B, *args):
-        with torch.cuda.device(self.device):
-            _lib.check(fn(B, self.num_actions, self.atoms, self.vmin, self.vmax, *args, self._stream()))
+        self._launch(fn, B, self.num_actions, self.atoms, self.vmin, self.vmax, *args)
 
     def expected(self, p, out=None):
         """float32 [B, A]: the expected value of every distribution of p, float32 [B, A, atoms] (snac_c51_expect, one launch).  It feeds
         env.epsilon_greedy(q, eps) when acting.  out: an optional preallocated float32 [B, A]."""
         A, K = self.num_actions, self.atoms
-        p = self._check(p, (None, A, K), torch.float32, "p")
+        p = self._check(p, (None, A, K), "p")
         B = int(p.shape[0])
-        q = torch.empty((B, A), dtype=torch.float32, device=self.device) if out is None else self._check(out, (B, A), torch.float32, "out")
+        q = torch.empty((B, A), dtype=torch.float32, device=self.device) if out is None else self._check(out, (B, A), "out")
         self._call(self._lib.snac_c51_expect, B, _ptr(p), _ptr(q))
         return q
 
@@ -108,26 +72,26 @@ class CategoricalSupport:
         action 0 and value 0, and is counted in bad_rows.  out: optional preallocated (m float32 [B, atoms], a_star int8 [B] or None,
         q_star float32 [B] or None).  Returns (m, a_star or None, q_star or None); q_star is the expected value of p_next[b, a_star]."""
         A, K = self.num_actions, self.atoms
-        p_next = self._check(p_next, (None, A, K), torch.float32, "p_next")
+        p_next = self._check(p_next, (None, A, K), "p_next")
         B = int(p_next.shape[0])
         if p_select is not None:
-            p_select = self._check(p_select, (B, A, K), torch.float32, "p_select")
-        ret = self._check(ret, (B,), torch.float32, "ret")
-        discount = self._check(discount, (B,), torch.float32, "discount")
+            p_select = self._check(p_select, (B, A, K), "p_select")
+        ret = self._check(ret, (B,), "ret")
+        discount = self._check(discount, (B,), "discount")
         m, a_star, q_star = out if out is not None else (None, None, None)
-        m = torch.empty((B, K), dtype=torch.float32, device=self.device) if m is None else self._check(m, (B, K), torch.float32, "out[0]")
+        m = torch.empty((B, K), dtype=torch.float32, device=self.device) if m is None else self._check(m, (B, K), "out[0]")
         if not want_action:
             a_star = None
         elif a_star is None:
             a_star = torch.empty((B,), dtype=torch.int8, device=self.device)
         else:
-            a_star = self._check(a_star, (B,), torch.int8, "out[1]")
+            a_star = self._check(a_star, (B,), "out[1]", torch.int8)
         if not want_q:
             q_star = None
         elif q_star is None:
             q_star = torch.empty((B,), dtype=torch.float32, device=self.device)
         else:
-            q_star = self._check(q_star, (B,), torch.float32, "out[2]")
+            q_star = self._check(q_star, (B,), "out[2]")
         self._call(self._lib.snac_c51_project, B, _ptr(p_next), _ptr(p_select), _ptr(ret), _ptr(discount), _ptr(m), _ptr(a_star), _ptr(q_star),
                    _ptr(self.bad_rows))
         return m, a_star, q_star

@@ -15,13 +15,12 @@ give the same bytes on every run.
 
 The value function is clipped as PPO2 does by default (clip_vf=None: by `clip`); a negative clip_vf turns that off.
 """
-import ctypes as C
 import math
 
 import torch
 
-from . import _lib
 from ._lib import ptr as _ptr
+from ._rule import Rule
 
 STATS = ("loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction", "good", "clamped")      # the places of stats[0..8)
 
@@ -51,25 +50,12 @@ class _Loss(torch.autograd.Function):
         return grad_mean * grad_logits, grad_mean * grad_value, None, None, None
 
 
-class PPOLoss:
+class PPOLoss(Rule):
     def __init__(self, num_actions, clip=0.2, clip_vf=None, vf_coef=0.5, ent_coef=0.01, device=None):
         """num_actions: 3, 5 or 8 (the envs' action counts), or a BatchedDMPEnv, whose num_actions, device and stream are then taken;
         clip: the surrogate's clip range, > 0; clip_vf: the value function's (None: `clip`, PPO2's default; negative: no clipping);
         vf_coef, ent_coef: the weights of the value loss and of the entropy bonus; device: a cuda device (not with an env)."""
-        self.env = None
-        if hasattr(num_actions, "num_actions") and hasattr(num_actions, "device"):
-            if device is not None:
-                raise ValueError("device is the env's when an env is given")
-            self.env, device, num_actions = num_actions, num_actions.device, num_actions.num_actions
-        if isinstance(num_actions, bool) or not isinstance(num_actions, int) or num_actions not in (3, 5, 8):
-            raise ValueError("num_actions must be 3, 5 or 8 (or a BatchedDMPEnv)")
-        if device is None:
-            raise ValueError("device must be given (or an env)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("device must be a cuda device: the logits and the minibatch live in device memory")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        super().__init__(num_actions, device, "the logits and the minibatch live")
 
         def number(x, what):
             if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x):
@@ -80,35 +66,11 @@ class PPOLoss:
             raise ValueError("clip must be > 0")
         self.clip_vf = self.clip if clip_vf is None else number(clip_vf, "clip_vf")
         self.vf_coef, self.ent_coef = number(vf_coef, "vf_coef"), number(ent_coef, "ent_coef")
-        self.num_actions = num_actions
-        self._lib = _lib.lib()
         self.stats = None                                            # float64 [8] on the device: the last call's
-        self._partials = self._bad = None                            # made on first use: the constructor does not touch the device
+        self._partials = None                                        # made on first use: the constructor does not touch the device
 
-    def _stream(self):
-        if self.env is not None:
-            return self.env._current_stream()
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    @property
-    def bad_rows(self):
-        """int32 [1] on the device: the samples zeroed so far (a NaN or +inf logit, every logit -inf, an action outside [0, A) or
-        without weight, a logp, adv, ret or value that is not finite)."""
-        if self._bad is None:
-            self._bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        return self._bad
-
-    def _check(self, t, shape, what, dtype=torch.float32):
-        """`t` is what the kernel reads: a contiguous tensor of `dtype` and `shape` (None: any size) on the device."""
-        def shown():
-            return "(%s)" % ", ".join("B" if s is None else str(s) for s in shape) if len(shape) > 1 else "(%s,)" % ("B" if shape[0] is None else shape[0])
-        if not torch.is_tensor(t) or t.dtype != dtype or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shown(), self.device))
-        if t.dim() != len(shape) or any(s is not None and g != s for g, s in zip(t.shape, shape)) or t.shape[0] < 1:
-            raise ValueError("%s must have shape %s, got %s" % (what, shown(), tuple(t.shape)))
-        if t.device != self.device:
-            raise ValueError("%s must be on %s" % (what, self.device))
-        return t
+    bad_rows = property(Rule._bad_rows, doc="""int32 [1] on the device: the samples zeroed so far (a NaN or +inf logit, every logit
+    -inf, an action outside [0, A) or without weight, a logp, adv, ret or value that is not finite).""")
 
     def _call(self, B, logits, value, consts, scale, loss, grad_logits, grad_value, stats, mean):
         """One snac_ppo_loss call on the current stream.  Only addresses are passed: a tensor that requires a gradient is read as data."""
@@ -116,13 +78,9 @@ class PPOLoss:
         rows = (B + 63) // 64
         if self._partials is None or self._partials.shape[0] < rows:
             self._partials = torch.empty((max(rows, 64), len(STATS)), dtype=torch.float64, device=self.device)
-        args = (B, self.num_actions, _ptr(logits), _ptr(action), _ptr(logp), _ptr(adv), _ptr(value), _ptr(value_old), _ptr(ret), self.clip,
-                self.clip_vf, self.vf_coef, self.ent_coef, scale, _ptr(loss), _ptr(grad_logits), _ptr(grad_value), _ptr(stats), _ptr(mean),
-                _ptr(self._partials), _ptr(self.bad_rows), self._stream())
-        if torch.cuda.current_device() == self.device.index:
-            return _lib.check(self._lib.snac_ppo_loss(*args))
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.snac_ppo_loss(*args))
+        self._launch(self._lib.snac_ppo_loss, B, self.num_actions, _ptr(logits), _ptr(action), _ptr(logp), _ptr(adv), _ptr(value), _ptr(value_old),
+                     _ptr(ret), self.clip, self.clip_vf, self.vf_coef, self.ent_coef, scale, _ptr(loss), _ptr(grad_logits), _ptr(grad_value), _ptr(stats),
+                     _ptr(mean), _ptr(self._partials), _ptr(self.bad_rows))
 
     def loss(self, logits, value, mb, want_per_sample=False):
         """0-dim float32: the mean over the minibatch of PPO2's loss -min(r adv, clamp(r) adv) + vf_coef * Lv - ent_coef * H, as a tensor

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _ptr
+from ._rule import OnDevice, cuda_device
 
 MAX_ENTRIES = (1 << 31) - 64
 MAX_DRAWS = 1 << 31
@@ -37,7 +38,7 @@ def _int(name, x, lo, hi):
     return x
 
 
-class PriorityTree:
+class PriorityTree(OnDevice):
     def __init__(self, entries, device, scale_log2=16, seed=0, sampler_id=0):
         """entries: 1 .. 2^31 - 64; device: a cuda device; scale_log2: 0 .. 31, a priority's weight is rint(priority * 2^scale_log2);
         seed, sampler_id: the counter RNG's (stream 4): sample j of the tree's d-th sample() draws with (seed, sampler_id + j, d).
@@ -46,22 +47,14 @@ class PriorityTree:
         self.scale_log2 = _int("scale_log2", scale_log2, 0, 31)
         self.seed = _int("seed", seed, -(1 << 63), (1 << 64) - 1) & 0xFFFFFFFFFFFFFFFF
         self.sampler_id = _int("sampler_id", sampler_id, 0, (1 << 62) - 1)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("device must be a cuda device: the tree lives in device memory")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = cuda_device(device, "the tree lives")
         self.draw = 0                                                # sample() calls so far
         self._lib = _lib.lib()
         self.bytes, self.levels, self.level_offset = layout(self.entries)
         self.buffer = torch.empty(self.bytes, dtype=torch.uint8, device=self.device)
         assert self.buffer.data_ptr() % 128 == 0
         self._tree = (_ptr(self.buffer), self.entries)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.snac_prio_init(*self._tree, self.scale_log2, self._stream()))
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._launch(self._lib.snac_prio_init, *self._tree, self.scale_log2)
 
     def _on_device(self, name, t, dtype, n=None):
         if not torch.is_tensor(t) or t.dim() != 1 or (n is not None and int(t.numel()) != n):
@@ -81,8 +74,7 @@ class PriorityTree:
         pri = self._on_device("priority", priority, torch.float32, int(idx.numel()))
         if idx.numel() == 0:                                         # an empty tensor has no address to hand over
             return
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.snac_prio_update(*self._tree, self.scale_log2, _ptr(idx), _ptr(pri), int(idx.numel()), self._stream()))
+        self._launch(self._lib.snac_prio_update, *self._tree, self.scale_log2, _ptr(idx), _ptr(pri), int(idx.numel()))
 
     def fill(self, first, count, priority=None):
         """Entries [first, first + count) get one priority; None: the largest weight any update() has stored (1.0 before the first),
@@ -94,8 +86,7 @@ class PriorityTree:
             p = float(priority)
             if p != p or p < 0:
                 raise ValueError("priority must be None or a number >= 0")
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.snac_prio_fill(*self._tree, self.scale_log2, first, count, p, self._stream()))
+        self._launch(self._lib.snac_prio_fill, *self._tree, self.scale_log2, first, count, p)
 
     def sample(self, n, stratified=True, with_weight=False):
         """n draws with replacement -> (index int64 [n], prob float32 [n]) on the device; with_weight=True: and the entries' integer
@@ -109,10 +100,9 @@ class PriorityTree:
         idx = torch.empty(n, dtype=torch.int32, device=self.device)
         prob = torch.empty(n, dtype=torch.float32, device=self.device)
         w = torch.empty(n, dtype=torch.int32, device=self.device) if with_weight else None
-        with torch.cuda.device(self.device):
-            if n:                                                    # (empty tensors have no address to hand over)
-                _lib.check(self._lib.snac_prio_sample(*self._tree, self.seed, self.sampler_id, self.draw, n, int(stratified), _ptr(idx),
-                                                      _ptr(prob), _ptr(w), self._stream()))
+        if n:                                                        # (empty tensors have no address to hand over)
+            self._launch(self._lib.snac_prio_sample, *self._tree, self.seed, self.sampler_id, self.draw, n, int(stratified), _ptr(idx), _ptr(prob),
+                         _ptr(w))
         self.draw += 1
         if with_weight:
             return idx.long(), prob, w.long() & 0xFFFFFFFF

@@ -16,13 +16,12 @@ Float64 operations in a stated order: the same inputs give the same bytes on eve
 
 A logit of -inf (or more than 45 below the row's largest) masks its action: its q-value is never read into a sum.
 """
-import ctypes as C
 import math
 
 import torch
 
-from . import _lib
 from ._lib import ptr as _ptr
+from ._rule import Rule
 
 
 class _PolicyLoss(torch.autograd.Function):
@@ -47,52 +46,15 @@ class _PolicyLoss(torch.autograd.Function):
         return grad_loss[:, None] * grad, None, None, None, None, None
 
 
-class SoftValue:
+class SoftValue(Rule):
     def __init__(self, num_actions, device=None):
         """num_actions: 3, 5 or 8 (the envs' action counts), or a BatchedDMPEnv, whose num_actions, device and stream are then taken;
         device: a cuda device (not with an env)."""
-        self.env = None
-        if hasattr(num_actions, "num_actions") and hasattr(num_actions, "device"):
-            if device is not None:
-                raise ValueError("device is the env's when an env is given")
-            self.env, device, num_actions = num_actions, num_actions.device, num_actions.num_actions
-        if isinstance(num_actions, bool) or not isinstance(num_actions, int) or num_actions not in (3, 5, 8):
-            raise ValueError("num_actions must be 3, 5 or 8 (or a BatchedDMPEnv)")
-        if device is None:
-            raise ValueError("device must be given (or an env)")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("device must be a cuda device: the logits and q-values live in device memory")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.num_actions = num_actions
-        self._lib = _lib.lib()
-        self._alpha = self._bad = None                               # made on first use: the constructor does not touch the device
+        super().__init__(num_actions, device, "the logits and q-values live")
+        self._alpha = None                                           # made on first use: the constructor does not touch the device
 
-    def _stream(self):
-        if self.env is not None:
-            return self.env._current_stream()
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    @property
-    def bad_rows(self):
-        """int32 [1] on the device: the samples zeroed so far (a NaN or +inf logit, every logit -inf, ret or discount not finite or a
-        negative discount in target(), alpha not finite or negative: then every sample of the call)."""
-        if self._bad is None:
-            self._bad = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        return self._bad
-
-    def _check(self, t, shape, what):
-        """`t` is what the kernel reads or writes: a contiguous float32 tensor of `shape` (None: any size) on the device."""
-        def shown():
-            return "(%s)" % ", ".join("B" if s is None else str(s) for s in shape) if len(shape) > 1 else "(%s,)" % ("B" if shape[0] is None else shape[0])
-        if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError("%s must be a contiguous torch.float32 tensor of shape %s on %s" % (what, shown(), self.device))
-        if t.dim() != len(shape) or any(s is not None and g != s for g, s in zip(t.shape, shape)) or t.shape[0] < 1:
-            raise ValueError("%s must have shape %s, got %s" % (what, shown(), tuple(t.shape)))
-        if t.device != self.device:
-            raise ValueError("%s must be on %s" % (what, self.device))
-        return t
+    bad_rows = property(Rule._bad_rows, doc="""int32 [1] on the device: the samples zeroed so far (a NaN or +inf logit, every logit
+    -inf, ret or discount not finite or a negative discount in target(), alpha not finite or negative: then every sample of the call).""")
 
     def _alpha_of(self, alpha):
         """The temperature as the kernel reads it: a one-element float32 tensor on the device.  A number is copied into a kept tensor."""
@@ -119,12 +81,8 @@ class SoftValue:
 
     def _call(self, B, logits, q1, q2, alpha, ret, discount, scale, v, y, entropy, grad):
         """One snac_soft_value launch on the current stream.  Only addresses are passed: a tensor that requires a gradient is read as data."""
-        args = (B, self.num_actions, _ptr(logits), _ptr(q1), _ptr(q2), _ptr(alpha), _ptr(ret), _ptr(discount), scale, _ptr(v), _ptr(y), _ptr(entropy),
-                _ptr(grad), _ptr(self.bad_rows), self._stream())
-        if torch.cuda.current_device() == self.device.index:
-            return _lib.check(self._lib.snac_soft_value(*args))
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.snac_soft_value(*args))
+        self._launch(self._lib.snac_soft_value, B, self.num_actions, _ptr(logits), _ptr(q1), _ptr(q2), _ptr(alpha), _ptr(ret), _ptr(discount), scale,
+                     _ptr(v), _ptr(y), _ptr(entropy), _ptr(grad), _ptr(self.bad_rows))
 
     def value(self, logits, q1, q2=None, alpha=0.0, out=None):
         """float32 [B]: the soft state value V = sum_a pi_a (min(q1, q2)_a - alpha * log pi_a) of every sample (one launch).  logits, q1,
