@@ -5,6 +5,7 @@ reference's 2D dynamic DQN (script/DQN/2d/DQN_2d_dynamic.py: observation 51 + pl
 replace every `replace` steps); this file is an illustration of the API, not part of the parity surface.
 
     python examples/dqn_batched.py --envs 4096 --ticks 200 [--prioritized] [--n-step N] [--distributional [--atoms K --vmin V --vmax V]]
+                                   [--device-loss [--huber D] [--double]]
 
 --prioritized: prioritised replay as in the reference's script/Rainbow, with the sum tree on the device (ReplayRing(prioritized=True)):
 minibatches are drawn in proportion to |td|, the loss is weighted by the importance weights, and the sampled transitions get their new
@@ -21,6 +22,13 @@ as in the reference's Rainbow).  The loss is the cross-entropy between that targ
 --prioritized it is weighted by the importance weights and its per-sample values are the new priorities.  The support: a 2D step pays 0
 or 5 and never less, so a return lies in [0, 5 / (1 - gamma)] = [0, 100] at gamma = 0.95; these are the defaults of --vmin / --vmax.  The
 projection clamps what falls outside, so a narrower choice is safe too, only coarser at its ends.
+
+--device-loss: the DQN loss comes from TDLoss, one call of two launches in place of max, the target arithmetic, gather, the error, the
+weighting, the mean and their backward passes: the target network's Q-values of s_next, the return and the discount go in as they are, the
+mean comes back carrying its closed-form gradient, and with --prioritized the new priorities |td| of the same call go to the ring without
+a host synchronisation.  --huber D: huber_loss(delta=D) instead of the squared error; --double: double DQN, the next action chosen by the
+online network.  With --distributional the cross-entropy comes from CategoricalSupport.loss on the raw logits (no log_softmax, no
+advanced index, no product and sum, and no backward pass through them), and its per-sample values are the new priorities.
 """
 import argparse
 import os
@@ -32,7 +40,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, CategoricalSupport, ReplayRing  # noqa: E402
+from snac_amd import BatchedDMPEnv, CategoricalSupport, ReplayRing, TDLoss  # noqa: E402
 
 
 class QNet(nn.Module):
@@ -46,16 +54,24 @@ class QNet(nn.Module):
 
 
 def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None,
-        device_sampling=False, distributional=False, atoms=51, vmin=None, vmax=None, info=None, projection=None):
+        device_sampling=False, distributional=False, atoms=51, vmin=None, vmax=None, info=None, projection=None, device_loss=False, huber=None,
+        double=False):
     """distributional: the C51 head and target (the module's docstring); vmin / vmax None: 0 and 5 / (1 - gamma).  info: an optional dict
-    that receives the run's device counters ("bad_rows": the samples project() zeroed).  projection: a callable
+    that receives the run's device counters ("bad_rows": the samples project() and the device loss zeroed; with prioritized also
+    "priorities", a copy of the priority tree's leaves at the end).  device_loss: the DQN loss from TDLoss (the module's docstring), with
+    huber: its delta, None for the squared error, and double: double DQN.  projection: a callable
     (p_next, ret, discount, p_select=) -> m in place of CategoricalSupport.project, for comparisons (tools/c51_time.py).
     device_sampling: the epsilon-greedy actions come from one launch per tick (BatchedDMPEnv.epsilon_greedy: counter-RNG stream 5,
     independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax."""
+    if (huber is not None or double) and not device_loss:
+        raise ValueError("huber and double belong to device_loss")
+    if (huber is not None or double) and distributional:
+        raise ValueError("huber and double belong to the DQN loss, not to distributional (whose target is double DQN's already)")
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev = env.device
     obs = env.reset()
+    td_loss = TDLoss(env, huber=huber) if device_loss and not distributional else None
     ring = ReplayRing(env, capacity_ticks=max(2 * prefill, 128), **(dict(prioritized=True) if prioritized else {}))
     ring.collect(prefill)                                          # random policy, one fused launch
     obs = env.observe()
@@ -98,13 +114,35 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
                 disc = gamma * (~mb["done"]).float() if n_step is None else mb["discount"]
                 m = (projection or project)(dist(target, mb["s_next"], mb["plan"]), ret.float().contiguous(), disc.float().contiguous(),
                                             p_select=dist(net, mb["s_next"], mb["plan"]))
-            logp = dist(net, mb["s"], mb["plan"], log=True)[torch.arange(batch, device=dev), mb["action"]]
-            ce = -(m * logp).sum(1)                                # per sample: the cross-entropy of the target and the online distribution
-            if prioritized:
-                loss = (mb["weight"] * ce).mean()
-                ring.update_priorities(mb["index"], ce.detach())
+            if device_loss:                                        # the mean, its gradient and the per-sample values from one call
+                out = support.loss(net(mb["s"], mb["plan"]).view(-1, env.num_actions, atoms), mb["action"], m,
+                                   weight=mb["weight"] if prioritized else None, want_per_sample=prioritized)
+                if prioritized:
+                    loss = out[0]
+                    ring.update_priorities(mb["index"], out[1])
+                else:
+                    loss = out
             else:
-                loss = ce.mean()
+                logp = dist(net, mb["s"], mb["plan"], log=True)[torch.arange(batch, device=dev), mb["action"]]
+                ce = -(m * logp).sum(1)                            # per sample: the cross-entropy of the target and the online distribution
+                if prioritized:
+                    loss = (mb["weight"] * ce).mean()
+                    ring.update_priorities(mb["index"], ce.detach())
+                else:
+                    loss = ce.mean()
+        elif device_loss:
+            with torch.no_grad():                                  # the plan does not change inside an episode: step 0's serves s_next
+                ret = (mb["reward"] if n_step is None else mb["return"]).float().contiguous()
+                disc = (gamma * (~mb["done"]).float() if n_step is None else mb["discount"].float()).contiguous()
+                q_next = target(mb["s_next"], mb["plan"])
+                q_select = net(mb["s_next"], mb["plan"]) if double else None
+            out = td_loss.loss(net(mb["s"], mb["plan"]), mb["action"], q_next=q_next, ret=ret, discount=disc, q_select=q_select,
+                               weight=mb["weight"] if prioritized else None, want_per_sample=prioritized)
+            if prioritized:
+                loss = out[0]
+                ring.update_priorities(mb["index"], out[2])       # |td| of the same call, device to device
+            else:
+                loss = out
         else:
             with torch.no_grad():
                 q_next = target(mb["s_next"], mb["plan"]).max(dim=1).values
@@ -132,6 +170,12 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
                 envs * (tick + 1) / (time.time() - t0)))
     if info is not None and distributional:
         info["bad_rows"] = int(support.bad_rows.cpu()[0])
+    if info is not None and device_loss:
+        if not distributional:
+            info["bad_rows"] = int(td_loss.bad_rows.cpu()[0])
+        info["stats"] = (support if distributional else td_loss).stats_dict()
+    if info is not None and prioritized:
+        info["priorities"] = ring.tree.weights().clone()
     return losses, returns
 
 
@@ -147,6 +191,9 @@ if __name__ == "__main__":
     ap.add_argument("--atoms", type=int, default=51, help="--distributional: the atoms of the support")
     ap.add_argument("--vmin", type=float, default=None, help="--distributional: the support's lowest value (default 0)")
     ap.add_argument("--vmax", type=float, default=None, help="--distributional: the support's highest value (default 5 / (1 - gamma))")
+    ap.add_argument("--device-loss", action="store_true", help="the DQN loss, its gradient and the new priorities from TDLoss (one call)")
+    ap.add_argument("--huber", type=float, default=None, help="--device-loss: Huber's delta (default: the squared error)")
+    ap.add_argument("--double", action="store_true", help="--device-loss: double DQN, the online network chooses the next action")
     a = ap.parse_args()
     run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling, distributional=a.distributional,
-        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax)
+        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax, device_loss=a.device_loss, huber=a.huber, double=a.double)

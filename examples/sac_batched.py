@@ -5,13 +5,16 @@ gradient and the entropy that drives the temperature in one more (policy_loss())
 (observation 51 + plan 400 -> 5 actions), with the pieces of script/SAC's algorithm: an actor MLP, twin Q networks with slowly moving
 target copies, a learned log_alpha.  This file is an illustration of the API, not part of the parity surface.
 
-    python examples/sac_batched.py --envs 4096 --ticks 200 [--prioritized] [--n-step N] [--composition]
+    python examples/sac_batched.py --envs 4096 --ticks 200 [--prioritized] [--n-step N] [--composition] [--device-loss]
 
 --prioritized / --n-step N: as in examples/dqn_batched.py (prioritised replay by |td| of the first critic; multi-step returns).
 
 --composition: the target, the actor loss and the entropy are computed by their torch forms instead (log_softmax, exp, minimum, products,
 sums, and autograd through them), for timing (tools/sac_time.py) and as a cross-check of the gradient.  Acting and the replay stay as
 they are.
+
+--device-loss: both critic losses come from TDLoss on the target y (one call each in place of the gather, the difference, the square, the
+weighting, the mean and their backward passes); with --prioritized the first critic's |td| of the same call are the new priorities.
 """
 import argparse
 import math
@@ -24,7 +27,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, ReplayRing, SoftValue  # noqa: E402
+from snac_amd import BatchedDMPEnv, ReplayRing, SoftValue, TDLoss  # noqa: E402
 
 
 class Net(nn.Module):
@@ -57,9 +60,10 @@ def torch_policy_loss(logits, q1, q2, alpha):
 
 
 def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=3e-4, tau=0.005, prefill=64, seed=1, log=print, prioritized=False, beta=0.4,
-        n_step=None, composition=False, report=50, info=None):
+        n_step=None, composition=False, report=50, info=None, device_loss=False):
     """-> (losses: per tick (critic, actor, temperature), returns: the mean episodic return at every report).  info: an optional dict
-    that receives the run's device counters ("bad_rows": the samples SoftValue zeroed) and the last temperature ("alpha")."""
+    that receives the run's device counters ("bad_rows": the samples SoftValue zeroed; with device_loss "td_bad_rows": those TDLoss
+    zeroed) and the last temperature ("alpha").  device_loss: the critic losses from TDLoss (the module's docstring)."""
     torch.manual_seed(seed)
     env = BatchedDMPEnv(2, True, envs, seed=seed, obs_dtype=torch.float32)
     dev, A = env.device, env.num_actions
@@ -69,6 +73,7 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=3e-4, tau=0.005, prefil
     obs = env.observe()
     plan = env.input_plan().float()
     soft = SoftValue(env)
+    td_loss = TDLoss(env) if device_loss else None
     actor = Net(env.obs_dim, 400, A).to(dev)
     critics = [Net(env.obs_dim, 400, A).to(dev) for _ in range(2)]
     targets = [Net(env.obs_dim, 400, A).to(dev) for _ in range(2)]
@@ -98,11 +103,18 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=3e-4, tau=0.005, prefil
             nxt = [actor(mb["s_next"], mb["plan"])] + [t(mb["s_next"], mb["plan"]) for t in targets]
             y = (torch_target if composition else soft.target)(*nxt, alpha, ret, disc)
         q = [c(mb["s"], mb["plan"]) for c in critics]
-        td = [qa[every, mb["action"]] - y for qa in q]
-        if prioritized:
+        if device_loss:
+            w = mb["weight"] if prioritized else None
+            first = td_loss.loss(q[0], mb["action"], y, weight=w, want_per_sample=prioritized)
+            critic_loss = (first[0] if prioritized else first) + td_loss.loss(q[1], mb["action"], y, weight=w)
+            if prioritized:
+                ring.update_priorities(mb["index"], first[2])     # |td| of the first critic, device to device
+        elif prioritized:
+            td = [qa[every, mb["action"]] - y for qa in q]
             critic_loss = sum((mb["weight"] * d ** 2).mean() for d in td)
             ring.update_priorities(mb["index"], td[0].detach().abs())
         else:
+            td = [qa[every, mb["action"]] - y for qa in q]
             critic_loss = sum((d ** 2).mean() for d in td)
         logits = actor(mb["s"], mb["plan"])
         if composition:
@@ -126,6 +138,8 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=3e-4, tau=0.005, prefil
     if info is not None:
         info["bad_rows"] = int(soft.bad_rows.cpu()[0]) + int(env.policy_bad_rows.cpu()[0])
         info["alpha"] = float(log_alpha.detach().exp())
+        if device_loss:
+            info["td_bad_rows"] = int(td_loss.bad_rows.cpu()[0])
     return losses, returns
 
 
@@ -137,5 +151,6 @@ if __name__ == "__main__":
     ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample in proportion to |td| of the first critic")
     ap.add_argument("--n-step", type=int, default=None, help="multi-step targets: the discounted sum of up to N rewards, bootstrapped N steps on")
     ap.add_argument("--composition", action="store_true", help="the torch forms of the target, the actor loss and the entropy instead of SoftValue")
+    ap.add_argument("--device-loss", action="store_true", help="both critic losses, their gradients and the new priorities from TDLoss")
     a = ap.parse_args()
-    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, composition=a.composition)
+    run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, composition=a.composition, device_loss=a.device_loss)

@@ -495,6 +495,7 @@ int snac_replay_gather_onpolicy(const snac_env_desc* desc, const snac_state* st,
  *     q = d_10; for n = 9 down to 0: q = q * z2 + d_n,   d_n = 1.0 / (2 n + 1)
  *     LOG = (double)e * LN2_HI + ((2.0 * z) * q + (double)e * LN2_LO)
  *   Both stay within 1e-12 (absolute) of the exact functions over x in [-45, 0] and S in [1, 8]; the truncated series leave less than 5e-18.
+ *   LOG holds the same bound over S in [1, 64], where snac_c51_loss uses it (frexp takes the exponent, the series sees f alone).
  * Outputs: action int8[N], logp float[N], entropy float[N]; each may be NULL, and with all three NULL nothing is launched.  The kernel never
  * writes an action outside [0, A), reads scores only and writes nothing but the outputs given and bad_rows[0].
  * Checks, all before any HIP call: desc and scores non-null, desc->kind one of SNAC_ENV_*, N >= 1, mode one of the three, epsilon finite and
@@ -641,6 +642,80 @@ int snac_ppo_loss(int32_t B, int32_t num_actions, const float* logits, const int
                   const float* value, const float* value_old, const float* ret, double clip, double clip_vf, double vf_coef, double ent_coef,
                   double scale, float* loss, float* grad_logits, float* grad_value, double* stats, float* mean_loss, double* partials,
                   int32_t* bad_rows, void* stream);
+
+/* ---- Q-learning losses (the reference's script/DQN, script/DRQN and script/Rainbow, and SAC's critics; snac_amd/qloss.py: TDLoss;
+ * k_qloss.hip, td_rule.h): the temporal-difference loss of a minibatch of Q-values -- the greedy or double-DQN target, the squared or
+ * Huber error, the importance weights of prioritised replay, the mean -- with its gradient with respect to q in closed form, the new
+ * priorities |td| and the batch statistics, in one call of two launches.  The conventions are "PPO loss"'s: all arithmetic is float64,
+ * every product, sum, difference and quotient rounded on its own (no fused multiply-add); rows contiguous, every base aligned as a
+ * float; action int64, 8-byte aligned; A = num_actions is 3, 5 or 8, else SNAC_ERR_UNSUPPORTED.
+ *
+ * snac_td_loss.  Inputs per sample b: q[b][A] float32 and action[b]; then exactly one of two target modes.  Mode Y: y[b] float32, a
+ * target computed elsewhere (snac_soft_value's y for SAC's critics); q_next, q_select, ret and discount are NULL.  Mode NEXT:
+ * q_next[b][A] (the target network's values of s_next), ret[b], discount[b] (mb["return"], mb["discount"] of an n-step sample, or the
+ * reward and gamma * (1 - done)) and optionally q_select[b][A] (the online network's values of s_next: double DQN; NULL: q_next
+ * itself); y is NULL.  weight[b] float32, the importance weights, may be NULL.  delta: 0 gives the squared error of
+ * torch.nn.functional.mse_loss, > 0 gives huber_loss(delta=).  scale: e.g. 1.0 / B for the gradient of the mean.
+ *     qa   = q[b][action]                       (picked by compares over a = 0 .. A-1, never by an index into registers or memory)
+ *     NEXT:  s = q_select ? q_select[b] : q_next[b];  best = s_0, a_star = 0; for a = 1 .. A-1: if (s_a > best) { best = s_a; a_star = a; }
+ *            (float compares: ties go to the lowest index, a NaN never wins)           qn = (double)q_next[b][a_star]
+ *            yv = (double)ret[b] + (double)discount[b] * qn
+ *     Y:     yv = (double)y[b]
+ *     td   = (double)qa - yv                    ab = |td|
+ *     delta == 0:  L = td * td                                                        g = 2.0 * td                        lin = false
+ *     delta  > 0:  lin = ab > delta;  L = lin ? delta * (ab - 0.5 * delta) : 0.5 * (td * td);   g = lin ? (td < 0 ? -delta : delta) : td
+ *     w    = weight ? (double)weight[b] : 1.0   total = w * L
+ *     loss[b] = (float)L        priority[b] = (float)ab        y_out[b] = (float)yv
+ *     grad_q[b][a] = a == action ? (float)(scale * (w * g)) : 0.0f                    (the whole row is written)
+ *     u[0..8) = total, L, ab, qa, yv, lin ? 1.0 : 0.0, 1.0, w
+ *   g is dL/dqa; the target, the weight and the action are constants of the loss.  loss is the unweighted error and priority the new
+ *   priority of prioritised replay (snac_prio_update takes it as it is).  The casts are plain: a |td| beyond float32's range shows as inf.
+ *   Bad samples.  A sample is bad if action is outside [0, A); if qa is not finite; in mode NEXT if ret or discount is not finite,
+ *   discount < 0, or qn is not finite; in mode Y if y is not finite; or if weight is given and is not finite or negative.  A bad sample
+ *   gets zeros in every per-sample output, contributes 0.0 to every u, and adds one to bad_rows[0] (int32 on the device, an atomic add).
+ *   A Q-value at an action that is neither taken nor chosen is never read into anything: a NaN there does not show.
+ *   The statistics.  The two stages of "PPO loss", in its order, over the eight contributions u: partials[w][k] of the waves of 64
+ *   consecutive samples, then the sums.  stats[k] = sum_k / (double)B for k != 6: the mean weighted loss, the mean loss, the mean |td|,
+ *   the mean Q taken, the mean target, Huber's linear fraction, and (k = 7) the mean weight; stats[6] = sum_6, the number of good
+ *   samples.  mean_loss[0] = (float)stats[0].
+ * Outputs: loss, priority, y_out float[B], grad_q float[B][A], mean_loss float[1] and bad_rows may each be NULL and are then not written.
+ * stats double[SNAC_Q_STATS] may be NULL: then nothing is reduced and the second launch does not happen (mean_loss must be NULL too).
+ * stats needs partials: ceil(B / 64) * SNAC_Q_STATS doubles of caller-owned scratch, 8-byte aligned as stats is.  With every output NULL
+ * nothing is launched.  The kernels read their inputs only and write nothing but the outputs given and partials.
+ * Checks, all before any HIP call: q and action non-null; B >= 1; exactly one of y and (q_next, ret, discount) -- all three -- given,
+ * q_select only with them; delta finite and >= 0; scale finite; partials with stats, stats with mean_loss; the 8-byte alignments;
+ * num_actions 3, 5 or 8.  Both launches go on `stream`; no host synchronisation.
+ *
+ * snac_c51_loss (Rainbow's cross-entropy; snac_amd/distributional.py: CategoricalSupport.loss).  Inputs per sample b: logits[b][A][K]
+ * float32, the raw output of the network (no softmax), K = atoms in [2, 64]; action[b]; m[b][K] float32, the row snac_c51_project writes;
+ * weight[b] float32 or NULL; scale.  TREE(v) is the shuffle-down tree of "Distributional targets" over v_0 .. v_63 with v_j = 0.0 for
+ * j >= K:  for s = 32, 16, 8, 4, 2, 1: v_j = v_j + v_{j+s} for every j < s (all j of a step together); TREE(v) = v_0.  EXP and LOG are
+ * the sequences of "Acting from a policy"; LOG is used here over [1, 64] and stays within 1e-12 of the exact logarithm there as well
+ * (its frexp takes any exponent; the series does not see it).  With l_j = logits[b][action][j]:
+ *     mx  = the largest l_j (float)              x_j = (double)l_j - (double)mx         e_j = EXP(x_j)
+ *     S   = TREE(e)   (1 <= S <= K)              T = TREE(e_j == 0 ? 0.0 : e_j * x_j)   Lg = LOG(S)
+ *     lp_j = x_j - Lg      p_j = e_j / S         mj = (double)m[b][j]
+ *     ce  = -TREE(mj * lp_j)                     M = TREE(mj)                           H = Lg - T / S
+ *     w   = weight ? (double)weight[b] : 1.0     total = w * ce
+ *     loss[b] = (float)ce                                              (unweighted: it is the new priority of prioritised replay)
+ *     grad[b][a][j] = a == action ? (float)(scale * (w * (M * p_j - mj))) : 0.0f        for every a < A, j < K (the whole block is written)
+ *     u[0..8) = total, ce, H, M, 0.0, 0.0, 1.0, w
+ *   d ce / d l_j = M p_j - mj, since d lp_i / d l_j = (i == j) - p_j; m, the weight and the action are constants.
+ *   Bad samples.  A sample is bad if action is outside [0, A) -- nothing is read through such an action --; if some l_j or m_j with j < K
+ *   is not finite; or if weight is given and is not finite or negative.  A bad sample gets loss 0, a block of zeros in grad, zeros in u,
+ *   and adds one to bad_rows[0].
+ *   The statistics: as snac_td_loss's, over these u: stats = the mean weighted loss, the mean loss, the mean entropy of the online
+ *   distribution of the action taken, the mean target mass, 0, 0, the number of good samples (not divided), the mean weight.
+ * Outputs: loss float[B], grad float[B][A][K], mean_loss float[1] and bad_rows may each be NULL; stats, partials and mean_loss as above.
+ * Checks, all before any HIP call: logits, action and m non-null; B >= 1; atoms in [2, 64]; scale finite; partials with stats, stats with
+ * mean_loss; the 8-byte alignments; num_actions 3, 5 or 8.  Both launches go on `stream`; no host synchronisation. */
+#define SNAC_Q_STATS 8
+int snac_c51_loss(int32_t B, int32_t num_actions, int32_t atoms, const float* logits, const int64_t* action, const float* m, const float* weight,
+                  double scale, float* loss, float* grad, double* stats, float* mean_loss, double* partials, int32_t* bad_rows, void* stream);
+int snac_td_loss(int32_t B, int32_t num_actions, const float* q, const int64_t* action, const float* y, const float* q_next,
+                 const float* q_select, const float* ret, const float* discount, const float* weight, double delta, double scale,
+                 float* loss, float* priority, float* y_out, float* grad_q, double* stats, float* mean_loss, double* partials,
+                 int32_t* bad_rows, void* stream);
 
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from

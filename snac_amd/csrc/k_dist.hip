@@ -5,6 +5,7 @@
 #include <cstddef>
 
 #include "snac_units.h"
+#include "lane_dev.h"
 
 #pragma clang fp contract(off)                                       // the whole unit: no fused multiply-add anywhere in the rule
 
@@ -38,34 +39,9 @@ struct C51Args {
     int32_t* bad_rows;
 };
 
-// lane `lane` (wave-uniform) of v, in every lane
-__device__ __forceinline__ double lane_read(double v, int lane) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// lane j's copy of lane j + S of v for S < 16, inside rows of 16 lanes (0.0 where j + S leaves the row): a DPP move, no trip through LDS
-template <int S>
-__device__ __forceinline__ double row_down(double v) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, 0x100 + S, 0xf, 0xf, true);      // row_shl:S
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), 0x100 + S, 0xf, 0xf, true);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// the expected value of the row whose atom `lane` is p (live: lane < K), in every lane.  At step s only lanes j < s are read later, and
-// their source j + s lies in the same row of 16 for s <= 8; the other lanes hold sums nobody reads
+// the expected value of the row whose atom `lane` is p (live: lane < K), in every lane: the header's tree (lane_dev.h)
 __device__ __forceinline__ double expect_row(float p, double z, bool live) {
-    double x = live ? (double)p * z : 0.0;
-    x = x + __shfl_down(x, 32, 64);
-    x = x + __shfl_down(x, 16, 64);
-    x = x + row_down<8>(x);
-    x = x + row_down<4>(x);
-    x = x + row_down<2>(x);
-    x = x + row_down<1>(x);
-    return lane_read(x, 0);
+    return tree_sum(live ? (double)p * z : 0.0);
 }
 
 __device__ __forceinline__ bool bad_sample(float r, float d) {

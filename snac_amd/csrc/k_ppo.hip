@@ -6,9 +6,10 @@
 #include <cstddef>
 
 #include "snac_units.h"
+#include "batch_sum.h"
 #include "ppo_rule.h"
 
-static_assert(SNAC_PPO_STATS == snac_spec::PPO_STATS, "the header's count of statistics is the rule's");
+static_assert(SNAC_PPO_STATS == snac_spec::PPO_STATS && snac_spec::PPO_STATS == snac_detail::BATCH_STATS, "the header's count of statistics is the rule's");
 
 // k_ppo_loss: lane = sample, blocks of one wave, as k_soft_value: a lane reads its row of logits as A strided dword loads and its six
 // scalars, all issued before the first use; a wave's rows are one contiguous span per input.  All arrays are indexed by unrolled
@@ -17,7 +18,8 @@ static_assert(SNAC_PPO_STATS == snac_spec::PPO_STATS, "the header's count of sta
 // butterfly of the header (u_j = u_j + u_{j ^ off}, off = 32 .. 1: every lane holds the same sum afterwards, since a + b == b + a bit for
 // bit), and lane 0 writes the wave's row of partials.
 // k_ppo_reduce: one wave.  Lane j adds rows j, j + 64, ... of the partials in increasing order from 0.0, then the same butterfly, the
-// divisions by B, and lane 0 writes stats and mean_loss.  No atomics on floats, nothing waits for the host.
+// divisions by B, and lane 0 writes stats and mean_loss.  No atomics on floats, nothing waits for the host.  (batch_sum.h has wave_sum
+// and the second kernel's body, for this unit and k_qloss.hip.)
 namespace {
 
 using namespace snac_detail;
@@ -39,13 +41,6 @@ struct PpoArgs {
     double* partials;
     int32_t* bad_rows;
 };
-
-__device__ __forceinline__ double wave_sum(double u) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) u = u + __shfl_xor(u, off, 64);
-    return u;
-}
 
 template <int A, bool CLIP_VF>
 __global__ __launch_bounds__(64) void k_ppo_loss(const PpoArgs g) {
@@ -78,24 +73,7 @@ __global__ __launch_bounds__(64) void k_ppo_loss(const PpoArgs g) {
 }
 
 __global__ __launch_bounds__(64) void k_ppo_reduce(const double* partials, long long W, int32_t B, double* stats, float* mean_loss) {
-#pragma clang fp contract(off)
-    double s[PPO_STATS];
-#pragma unroll
-    for (int k = 0; k < PPO_STATS; ++k) s[k] = 0.0;
-    for (long long w = threadIdx.x; w < W; w += 64) {
-#pragma unroll
-        for (int k = 0; k < PPO_STATS; ++k) s[k] = s[k] + partials[w * PPO_STATS + k];      // ppo_lane_sum's order, the eight columns together
-    }
-#pragma unroll
-    for (int k = 0; k < PPO_STATS; ++k) s[k] = wave_sum(s[k]);
-    if (threadIdx.x != 0) return;
-    const double n = (double)B;
-#pragma unroll
-    for (int k = 0; k < PPO_STATS; ++k) {
-        const double v = (k == PPO_GOOD || k == PPO_CLAMPED) ? s[k] : s[k] / n;
-        stats[k] = v;
-        if (k == PPO_TOTAL && mean_loss) mean_loss[0] = (float)v;
-    }
+    reduce_partials<(1u << PPO_GOOD | 1u << PPO_CLAMPED)>(partials, W, B, stats, mean_loss);      // the two counts are not divided by B
 }
 
 }  // namespace

@@ -1,18 +1,21 @@
 """CategoricalSupport: categorical (C51) value distributions on the device (include/snac_hip.h, "Distributional targets";
 snac_amd/csrc/k_dist.hip).
 
-A support of `atoms` values z_i = vmin + i * dz behind two launches that never wait for the device: the expected values of a batch of
-distributions (what an agent acts on), and Rainbow's target -- the greedy or double-DQN choice of the next action and the projection of
-return + discount * z onto the support.  Both follow a rule of float64 operations in a stated order, so the same inputs give the same
-bytes on every run; the textbook composition in torch ends in index_add_, whose float atomics land in any order.
+A support of `atoms` values z_i = vmin + i * dz behind calls that never wait for the device: the expected values of a batch of
+distributions (what an agent acts on), Rainbow's target -- the greedy or double-DQN choice of the next action and the projection of
+return + discount * z onto the support -- and its loss, the cross-entropy of that target and the online distribution of the action taken
+(include/snac_hip.h, "Q-learning losses"; k_qloss.hip).  All follow a rule of float64 operations in a stated order, so the same inputs
+give the same bytes on every run; the textbook composition in torch ends in index_add_, whose float atomics land in any order.
 
     support = CategoricalSupport(env, atoms=51, vmin=-10.0, vmax=10.0)           # or CategoricalSupport(5, ..., device="cuda:0")
     q = support.expected(online(s).view(-1, A, 51).softmax(-1))                  # float32 [B, A]
     action = env.epsilon_greedy(q, eps)
     m, a_star, _ = support.project(target_p(s_next), ret, discount, p_select=online_p(s_next))      # m: float32 [B, 51]
-    loss = -(m * online(s).view(-1, A, 51).log_softmax(-1)[range(B), action]).sum(1)
+    loss, ce = support.loss(online(s).view(-1, A, 51), action, m, weight=mb["weight"], want_per_sample=True)   # the raw logits, no softmax
+    loss.backward()                                                              # one product: the gradient came with the forward call
+    ring.update_priorities(mb["index"], ce)
 
-The loss and its gradient are the caller's, in torch.
+The loss is the mean over the minibatch; its gradient with respect to the logits is written in closed form by the same call.
 """
 import math
 
@@ -22,6 +25,35 @@ from ._lib import ptr as _ptr
 from ._rule import Rule
 
 MAX_ATOMS = 64
+LOSS_STATS = ("loss", "cross_entropy", "entropy", "target_mass", "unused4", "unused5", "good", "weight")      # the places of stats[0..8) of loss()
+
+
+class _Loss(torch.autograd.Function):
+    """The mean cross-entropy with d/dlogits from the same call; everything else is a constant."""
+
+    @staticmethod
+    def forward(ctx, logits, support, action, m, weight, want_per_sample):
+        B = int(logits.shape[0])
+        dev = support.device
+        grad = torch.empty_like(logits)
+        per_sample = torch.empty((B,), dtype=torch.float32, device=dev) if want_per_sample else None
+        mean = torch.empty((), dtype=torch.float32, device=dev)
+        support.stats = torch.empty((len(LOSS_STATS),), dtype=torch.float64, device=dev)
+        rows = (B + 63) // 64
+        if support._partials is None or support._partials.shape[0] < rows:
+            support._partials = torch.empty((max(rows, 64), len(LOSS_STATS)), dtype=torch.float64, device=dev)
+        support._launch(support._lib.snac_c51_loss, B, support.num_actions, support.atoms, _ptr(logits), _ptr(action), _ptr(m), _ptr(weight), 1.0 / B,
+                        _ptr(per_sample), _ptr(grad), _ptr(support.stats), _ptr(mean), _ptr(support._partials), _ptr(support.bad_rows))
+        ctx.save_for_backward(grad)
+        if not want_per_sample:
+            return mean
+        ctx.mark_non_differentiable(per_sample)
+        return mean, per_sample
+
+    @staticmethod
+    def backward(ctx, grad_mean, *unused):
+        grad, = ctx.saved_tensors
+        return grad_mean * grad, None, None, None, None, None
 
 
 class CategoricalSupport(Rule):
@@ -39,6 +71,8 @@ class CategoricalSupport(Rule):
         self.atoms, self.vmin, self.vmax = atoms, float(vmin), float(vmax)
         self.dz = (self.vmax - self.vmin) / float(atoms - 1)          # the header's dz: one float64 quotient
         self._z = None                                               # made on first use: the constructor does not touch the device
+        self.stats = None                                            # float64 [8] on the device: the last loss()'s
+        self._partials = None
 
     @property
     def z(self):
@@ -47,8 +81,9 @@ class CategoricalSupport(Rule):
             self._z = torch.tensor([self.vmin + float(i) * self.dz for i in range(self.atoms)], dtype=torch.float64).to(torch.float32).to(self.device)
         return self._z
 
-    bad_rows = property(Rule._bad_rows, doc="""int32 [1] on the device: the samples project() has zeroed so far (ret or discount not
-    finite, or discount < 0).""")
+    bad_rows = property(Rule._bad_rows, doc="""int32 [1] on the device: the samples project() (ret or discount not finite, or discount < 0)
+    and loss() (an action outside [0, A), a logit of the taken action or an entry of m that is not finite, a weight that is not finite
+    or negative) have zeroed so far.""")
 
     def _call(self, fn, B, *args):
         self._launch(fn, B, self.num_actions, self.atoms, self.vmin, self.vmax, *args)
@@ -95,3 +130,27 @@ class CategoricalSupport(Rule):
         self._call(self._lib.snac_c51_project, B, _ptr(p_next), _ptr(p_select), _ptr(ret), _ptr(discount), _ptr(m), _ptr(a_star), _ptr(q_star),
                    _ptr(self.bad_rows))
         return m, a_star, q_star
+
+    def loss(self, logits, action, m, weight=None, want_per_sample=False):
+        """0-dim float32: the mean over the minibatch of weight * cross-entropy(m[b], softmax(logits[b, action[b]])), as a tensor that
+        carries a gradient to `logits` (snac_c51_loss, two launches).  logits: float32 [B, A, atoms], contiguous: the .view(-1, A, atoms)
+        of the network's output, no softmax; action: int64 [B]; m: float32 [B, atoms], what project() gives; weight: the importance
+        weights float32 [B], or None.  The forward pass also writes the gradient of the mean in closed form (weight * (mass(m) * p - m) / B
+        in the taken action's row, zeros elsewhere); the backward pass is one product.  want_per_sample: also return the unweighted
+        cross-entropies float32 [B] of the same call (no gradient): the new priorities of prioritised replay.  self.stats holds the
+        call's statistics afterwards.  Returns mean_loss, or (mean_loss, cross_entropy)."""
+        A, K = self.num_actions, self.atoms
+        logits = self._check(logits, (None, A, K), "logits")
+        B = int(logits.shape[0])
+        action = self._check(action, (B,), "action", torch.int64)
+        m = self._check(m, (B, K), "m")
+        if weight is not None:
+            weight = self._check(weight, (B,), "weight")
+        return _Loss.apply(logits, self, action, m, weight, bool(want_per_sample))
+
+    def stats_dict(self):
+        """The statistics of the last loss() as Python floats: loss (weighted), cross_entropy, entropy (of the online distribution of the
+        action taken), target_mass, weight (means over the minibatch) and good (a count).  Waits for the device."""
+        if self.stats is None:
+            raise ValueError("no loss() has been called yet")
+        return {k: v for k, v in zip(LOSS_STATS, self.stats.tolist()) if not k.startswith("unused")}
