@@ -5,6 +5,7 @@ trainer: nothing but the final printout crosses the bus.
 
     python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20] [--normalise] [--gumbel M [--gumbel-interior]]
                                           [--reanalyse R] [--td-steps N] [--prioritized [--per-alpha A] [--per-beta B]]
+                                          [--device-loss [--huber D] [--vf-coef C]]
 
 --normalise: the search compares q normalised by each tree's min-max bounds (UCTSearch(q_normalise=True)), so that c = 1.25 weighs
 the priors against returns of any scale (a brick pays 5 here).
@@ -21,6 +22,9 @@ values reach z, in place of the return to the end of the episode.
 --prioritized: MuZero's prioritised replay (SelfPlay(prioritized=True)): minibatches -- and the positions of --reanalyse -- are drawn in
 proportion to |value - z| ** A from a sum tree on the device, the loss is weighted by the importance weights (exponent B), and the
 sampled entries get their new priorities after every step (update_priorities()).
+--device-loss: the loss, its gradient with respect to both heads, the importance weighting, the mean and the new priorities come from
+one device call (SearchLoss: float64, a stated order of the sums) in place of the float32 torch composition and its autograd pass;
+--huber D takes Huber's value error with delta D and --vf-coef C weighs the value error (they belong to --device-loss).
 """
 import argparse
 import os
@@ -30,13 +34,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, SelfPlay, UCTSearch  # noqa: E402
+from snac_amd import BatchedDMPEnv, SearchLoss, SelfPlay, UCTSearch  # noqa: E402
 
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
-          gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4):
+          gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4, device_loss=False, huber=None,
+          vf_coef=1.0, info=None):
     """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
-    SelfPlay)."""
+    SelfPlay).  info: a dict that receives bad_rows and the last step's statistics of the device loss."""
+    if not device_loss and (huber is not None or vf_coef != 1.0):
+        raise ValueError("huber and vf_coef belong to device_loss")
     env = BatchedDMPEnv(kind, True, envs, seed=seed)
     env.reset()
     A = env.num_actions
@@ -67,6 +74,7 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
     if reanalyse:                                                    # a second search over the same env and network: R trees
         again = UCTSearch(env, nodes, 0, 0.99, c=1.25, paths=paths, evaluator=evaluator, max_iterations=iterations, trees=reanalyse,
                           q_normalise=search.q_normalise, gumbel=gumbel, gumbel_interior=bool(gumbel_interior))
+    search_loss = SearchLoss(env, vf_coef=vf_coef, huber=huber) if device_loss else None
     losses = []
     for _ in range(steps):
         play.play(moves, iterations)
@@ -75,6 +83,15 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
         play.targets(td_steps=td_steps)
         b = play.sample(batch, **(dict(prioritized=True, beta=per_beta) if prioritized else {}))
         y = net(b["obs"])
+        if device_loss:                                              # both heads as contiguous tensors; pi, z and the weights are read from b
+            loss, _, priority = search_loss.loss(y[:, :A].contiguous(), y[:, A].contiguous(), b, want_per_sample=True)
+            if prioritized:
+                play.update_priorities(b["index"], priority if per_alpha == 1.0 else priority ** per_alpha)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+            losses.append(loss.detach())
+            continue
         if prioritized:                                              # the importance weights undo the sampling bias
             policy_loss = -(b["weight"] * (b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1)).mean()
             value_loss = (b["weight"] * (y[:, A] - b["z"]) ** 2).mean()
@@ -87,6 +104,8 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
         loss.backward()
         opt.step()
         losses.append(loss.detach())
+    if info is not None and device_loss:
+        info.update(search_loss.stats_dict(), bad_rows=int(search_loss.bad_rows.cpu()[0]))
     return [float(x) for x in torch.stack(losses).cpu()], play
 
 
@@ -103,12 +122,18 @@ def main():
     ap.add_argument("--prioritized", action="store_true", help="prioritised replay: sample and reanalyse in proportion to |value - z| ** alpha")
     ap.add_argument("--per-alpha", type=float, default=1.0, metavar="A", help="the priority exponent (default 1, MuZero's)")
     ap.add_argument("--per-beta", type=float, default=0.4, metavar="B", help="the exponent of the importance weights (default 0.4)")
+    ap.add_argument("--device-loss", action="store_true", help="the loss, its gradient and the new priorities from one device call (SearchLoss)")
+    ap.add_argument("--huber", type=float, default=None, metavar="D", help="with --device-loss: Huber's value error with delta D (default: squared)")
+    ap.add_argument("--vf-coef", type=float, default=1.0, metavar="C", help="with --device-loss: the weight of the value error (default 1)")
     args = ap.parse_args()
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
+    if not args.device_loss and (args.huber is not None or args.vf_coef != 1.0):
+        ap.error("--huber and --vf-coef need --device-loss")
     losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps, normalise=args.normalise, gumbel=args.gumbel,
                          gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps,
-                         prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta)
+                         prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta, device_loss=args.device_loss,
+                         huber=args.huber, vf_coef=args.vf_coef)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     if args.reanalyse:
         print("entries reanalysed: %d" % int(play.refreshed.sum()))

@@ -717,6 +717,56 @@ int snac_td_loss(int32_t B, int32_t num_actions, const float* q, const int64_t* 
                  float* loss, float* priority, float* y_out, float* grad_q, double* stats, float* mean_loss, double* partials,
                  int32_t* bad_rows, void* stream);
 
+/* ---- Search loss (AlphaZero / Gumbel self-play) (snac_amd/search_loss.py: SearchLoss; k_search.hip, search_rule.h): the loss of a
+ * minibatch of self-play positions -- the cross-entropy of the network's policy to the search's distribution pi (the visit distribution,
+ * or the improved policy of the Gumbel search), the squared or Huber error of its value to the return z, the importance weights of
+ * prioritised replay, the mean -- with its gradient with respect to the logits and the value in closed form, the new priorities
+ * |value - z| and the batch statistics, in one call of two launches.  The conventions are "PPO loss"'s: all arithmetic is float64, every
+ * product, sum, difference and quotient rounded on its own (no fused multiply-add), sums in index order starting from 0.0; rows
+ * contiguous, every base aligned as a float; A = num_actions is 3, 5 or 8, else SNAC_ERR_UNSUPPORTED.  EXP and LOG are the sequences of
+ * "Acting from a policy".
+ *
+ * Inputs per sample b: logits[b][A] float32, the raw output of the policy head (no softmax; -inf masks an action), value[b] float32;
+ * pi[b][A] float32 and z[b] float32 (what SelfPlay.sample() gives); weight[b] float32, the importance weights, may be NULL.  pi need not
+ * sum to 1: a row of zeros and a scaled row are legal.  vf_coef >= 0 weighs the value error; delta: 0 gives the squared error, > 0
+ * Huber's; scale: e.g. 1.0 / B for the gradient of the mean.  With l_a = logits[b][a]:
+ *     m, x_a, e_a, S, T, L = LOG(S), p_a = e_a / S, lp_a = x_a - L          exactly as in "Soft values (discrete SAC)"
+ *     H    = L - T / S                                                       (snac_policy_act's entropy, the same bytes)
+ *     M    = sum_a (double)pi_a                  Lpi = -(sum_a (pi_a == 0 ? 0.0 : (double)pi_a * lp_a))
+ *     dv   = (double)value - (double)z           ab = |dv|
+ *     delta == 0:  Lv = dv * dv                                                       g = 2.0 * dv
+ *     delta  > 0:  lin = ab > delta;  Lv = lin ? delta * (ab - 0.5 * delta) : 0.5 * (dv * dv);  g = lin ? (dv < 0 ? -delta : delta) : dv
+ *     per  = Lpi + vf_coef * Lv                  w = weight ? (double)weight[b] : 1.0               total = w * per
+ *     loss[b] = (float)per        priority[b] = (float)ab
+ *     grad_logits[b][a] = l_a == -inf ? 0.0f : (float)(scale * (w * (M * p_a - (double)pi_a)))
+ *     grad_value[b]     = (float)(scale * (w * (vf_coef * g)))
+ *     agree = the first largest l_a and the first largest pi_a sit at the same index      (each: best = v_0, at = 0; for a = 1 .. A-1:
+ *             if (v_a > best) { best = v_a; at = a; } -- float compares, ties go to the lowest index)
+ *     u[0..8) = total, Lpi, Lv, H, ab, agree ? 1.0 : 0.0, 1.0, w
+ *   d Lpi / d l_a = M p_a - pi_a, since d lp_i / d l_a = (i == a) - p_a; pi, z and the weight are constants of
+ *   the loss.  lp_a is x_a - L and not LOG(p_a): it is finite for every finite logit, also more than 45 below the largest, where EXP
+ *   gives e_a = 0 -- there p_a is 0 and the gradient is -scale w pi_a.  loss is the unweighted loss and priority the new priority of
+ *   prioritised replay (snac_prio_update takes it as it is).
+ *   Bad samples.  A sample is bad if some l_a is a NaN or +inf or every l_a is -inf; if some pi_a is not finite or is < 0 (-0.0 is a
+ *   zero); if pi_a > 0 where l_a is -inf (a target on a masked action; with pi_a == 0 a masked action is fine); if value or z is not
+ *   finite; or if weight is given and is not finite or negative.  A bad sample gets zeros in every per-sample output, contributes 0.0 to
+ *   every u, and adds one to bad_rows[0] (int32 on the device, an atomic add).
+ *   The statistics.  The two stages of "PPO loss", in its order, over the eight contributions u: partials[w][k] of the waves of 64
+ *   consecutive samples, then the sums.  stats[k] = sum_k / (double)B for k != 6: the mean weighted loss, the mean cross-entropy, the mean
+ *   value error, the mean entropy of the policy, the mean |value - z|, the fraction of samples whose largest logit is the search's
+ *   choice, and (k = 7) the mean weight; stats[6] = sum_6, the number of good samples.  mean_loss[0] = (float)stats[0].
+ * Outputs: loss, priority, grad_value float[B], grad_logits float[B][A], mean_loss float[1] and bad_rows may each be NULL and are then not
+ * written.  stats double[SNAC_SEARCH_STATS] may be NULL: then nothing is reduced and the second launch does not happen (mean_loss must be
+ * NULL too).  stats needs partials: ceil(B / 64) * SNAC_SEARCH_STATS doubles of caller-owned scratch, 8-byte aligned as stats is.  With
+ * every output NULL nothing is launched.  The kernels read their inputs only and write nothing but the outputs given and partials.
+ * Checks, all before any HIP call: logits, value, pi and z non-null; B >= 1; vf_coef and delta finite and >= 0; scale finite; partials
+ * with stats, stats with mean_loss; the 8-byte alignments; num_actions 3, 5 or 8.  Both launches go on `stream`; no host
+ * synchronisation. */
+#define SNAC_SEARCH_STATS 8
+int snac_search_loss(int32_t B, int32_t num_actions, const float* logits, const float* value, const float* pi, const float* z,
+                     const float* weight, double vf_coef, double delta, double scale, float* loss, float* priority, float* grad_logits,
+                     float* grad_value, double* stats, float* mean_loss, double* partials, int32_t* bad_rows, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

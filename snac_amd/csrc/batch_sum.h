@@ -1,5 +1,5 @@
-// batch_sum.h -- the two stages of the batch statistics of include/snac_hip.h ("PPO loss", "Q-learning losses"), device side, for
-// k_ppo.hip and k_qloss.hip: eight float64 sums over a minibatch in a fixed order, without atomics on floats.  Stage 1 is wave_sum in
+// batch_sum.h -- the two stages of the batch statistics of include/snac_hip.h ("PPO loss", "Q-learning losses", "Search loss"), device
+// side, for k_ppo.hip, k_qloss.hip and k_search.hip: eight float64 sums over a minibatch in a fixed order, without atomics on floats.  Stage 1 is wave_sum in
 // the loss kernel, a wave per 64 consecutive samples, whose lane 0 writes the wave's row of partials; stage 2 is reduce_partials, the
 // body of a kernel of one wave.  COUNTS: bit k set where column k is a count, which is not divided by B.
 #pragma once
@@ -7,7 +7,7 @@
 
 namespace snac_detail {
 
-constexpr int BATCH_STATS = 8;                                       // SNAC_PPO_STATS, SNAC_Q_STATS
+constexpr int BATCH_STATS = 8;                                       // SNAC_PPO_STATS, SNAC_Q_STATS, SNAC_SEARCH_STATS
 
 // the xor butterfly of the header: u_j = u_j + u_{j ^ off}, off = 32 .. 1; every lane holds the same sum afterwards, since a + b == b + a
 // bit for bit

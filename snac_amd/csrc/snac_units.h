@@ -45,10 +45,13 @@
 //                                 new priorities and its statistics: lane = sample (td_rule.h: the per-sample rule), then the batch sums
 //                   k_c51_loss    Rainbow's cross-entropy of the projected target and the online logits, its gradient and statistics:
 //                                 lane = atom, a block per 64 samples, the samples' contributions through LDS into the same sums
-//                   (for these two units: batch_sum.h, the wave's butterfly and the second stage of the batch sums; for k_dist.hip and
+//   k_search.hip    k_search_loss / k_search_reduce   the loss of self-play positions (AlphaZero, Gumbel): the cross-entropy to the search's
+//                                 distribution, the value error, their gradients, the new priorities and the statistics: lane = sample
+//                                 (search_rule.h: the per-sample rule), then the batch sums
+//                   (for these three units: batch_sum.h, the wave's butterfly and the second stage of the batch sums; for k_dist.hip and
 //                   k_c51_loss: lane_dev.h, the lane read, the DPP row move and the shuffle-down tree)
-//                   (for k_policy.hip and the soft and PPO rules: softmax_rule.h, the float64 softmax of a row of scores in three steps, on
-//                   spec_math.h's EXP and LOG; for those three units, k_dist.hip and k_qloss.hip: by_actions below, the choice of the A = 3 / 5 / 8 instance)
+//                   (for k_policy.hip and the soft, PPO and search rules: softmax_rule.h, the float64 softmax of a row of scores in three steps, on
+//                   spec_math.h's EXP and LOG; for those four units, k_dist.hip and k_qloss.hip: by_actions below, the choice of the A = 3 / 5 / 8 instance)
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory
