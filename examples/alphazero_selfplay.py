@@ -6,6 +6,7 @@ trainer: nothing but the final printout crosses the bus.
     python examples/alphazero_selfplay.py [--kind 2] [--envs 64] [--steps 20] [--normalise] [--gumbel M [--gumbel-interior]]
                                           [--reanalyse R] [--td-steps N] [--prioritized [--per-alpha A] [--per-beta B]]
                                           [--device-loss [--huber D] [--vf-coef C]]
+                                          [--dirichlet ALPHA [--noise-eps E]] [--temperature T] [--counter-noise]
 
 --normalise: the search compares q normalised by each tree's min-max bounds (UCTSearch(q_normalise=True)), so that c = 1.25 weighs
 the priors against returns of any scale (a brick pays 5 here).
@@ -25,6 +26,11 @@ sampled entries get their new priorities after every step (update_priorities()).
 --device-loss: the loss, its gradient with respect to both heads, the importance weighting, the mean and the new priorities come from
 one device call (SearchLoss: float64, a stated order of the sums) in place of the float32 torch composition and its autograd pass;
 --huber D takes Huber's value error with delta D and --vf-coef C weighs the value error (they belong to --device-loss).
+--dirichlet ALPHA: AlphaZero's root noise, (1 - E) * priors + E * Dirichlet(ALPHA) with E = --noise-eps (default 0.25), drawn on the
+device from the counter RNG before every move's search (SelfPlay(dirichlet=)), in place of the uniform share the default run mixes in.
+--temperature T: the sampled moves of an episode are drawn in proportion to N ** (1 / T) (SelfPlay(temperature=)).
+--counter-noise (with --gumbel M): the Gumbel noise comes from the counter RNG too (SelfPlay(counter_noise=True)): the run then depends
+neither on how the envs are sharded nor on a generator's state.
 """
 import argparse
 import os
@@ -39,7 +45,7 @@ from snac_amd import BatchedDMPEnv, SearchLoss, SelfPlay, UCTSearch  # noqa: E40
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
           gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4, device_loss=False, huber=None,
-          vf_coef=1.0, info=None):
+          vf_coef=1.0, info=None, dirichlet=None, noise_eps=0.25, temperature=None, counter_noise=False):
     """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
     SelfPlay).  info: a dict that receives bad_rows and the last step's statistics of the device loss."""
     if not device_loss and (huber is not None or vf_coef != 1.0):
@@ -66,10 +72,14 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
     keep = dict(keep_states=True) if reanalyse else {}
     if prioritized:
         keep["prioritized"] = True
-    if gumbel is None:
+    if temperature is not None:
+        keep["temperature"] = temperature
+    if gumbel is None and dirichlet is not None:                     # the root noise drawn on the device, keyed by the env ids
+        play = SelfPlay(search, capacity, sample_moves=8, dirichlet=(dirichlet, noise_eps), **keep)
+    elif gumbel is None:
         play = SelfPlay(search, capacity, sample_moves=8, root_noise=noise, **keep)
     else:                                                            # the Gumbel noise of the first moves explores
-        play = SelfPlay(search, capacity, sample_moves=8, gumbel=True, **keep)
+        play = SelfPlay(search, capacity, sample_moves=8, gumbel=True, **(dict(keep, counter_noise=True) if counter_noise else keep))
     again = None
     if reanalyse:                                                    # a second search over the same env and network: R trees
         again = UCTSearch(env, nodes, 0, 0.99, c=1.25, paths=paths, evaluator=evaluator, max_iterations=iterations, trees=reanalyse,
@@ -125,15 +135,26 @@ def main():
     ap.add_argument("--device-loss", action="store_true", help="the loss, its gradient and the new priorities from one device call (SearchLoss)")
     ap.add_argument("--huber", type=float, default=None, metavar="D", help="with --device-loss: Huber's value error with delta D (default: squared)")
     ap.add_argument("--vf-coef", type=float, default=1.0, metavar="C", help="with --device-loss: the weight of the value error (default 1)")
+    ap.add_argument("--dirichlet", type=float, default=None, metavar="ALPHA", help="Dirichlet(ALPHA) root noise from the counter RNG (PUCT)")
+    ap.add_argument("--noise-eps", type=float, default=0.25, metavar="E", help="with --dirichlet: the noise's share of the root priors (default 0.25)")
+    ap.add_argument("--temperature", type=float, default=None, metavar="T", help="draw the sampled moves in proportion to N ** (1 / T) (PUCT)")
+    ap.add_argument("--counter-noise", action="store_true", help="with --gumbel M: the Gumbel noise from the counter RNG")
     args = ap.parse_args()
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
+    if args.gumbel is not None and (args.dirichlet is not None or args.temperature is not None):
+        ap.error("--dirichlet and --temperature belong to the PUCT run: not with --gumbel")
+    if args.counter_noise and args.gumbel is None:
+        ap.error("--counter-noise needs --gumbel M")
+    if args.noise_eps != 0.25 and args.dirichlet is None:
+        ap.error("--noise-eps needs --dirichlet ALPHA")
     if not args.device_loss and (args.huber is not None or args.vf_coef != 1.0):
         ap.error("--huber and --vf-coef need --device-loss")
     losses, play = train(kind=args.kind, envs=args.envs, steps=args.steps, normalise=args.normalise, gumbel=args.gumbel,
                          gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps,
                          prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta, device_loss=args.device_loss,
-                         huber=args.huber, vf_coef=args.vf_coef)
+                         huber=args.huber, vf_coef=args.vf_coef, dirichlet=args.dirichlet, noise_eps=args.noise_eps, temperature=args.temperature,
+                         counter_noise=args.counter_noise)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     if args.reanalyse:
         print("entries reanalysed: %d" % int(play.refreshed.sum()))

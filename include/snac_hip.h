@@ -63,6 +63,8 @@
  *                                   r = (word(.., 2 * d) << 32) | word(.., 2 * d + 1), keyed by sampler_id + j for sample j of a call
  *   stream 5 (per env, tick t):     the action a policy's scores give (snac_policy_act; "Acting from a policy" below): categorical
  *                                   u = (word * total) >> 32 over integer weights, epsilon-greedy from word >> 16 and word & 0xffff
+ *   stream 6 (per root slot, move t): the Gamma draws of the Dirichlet root noise (snac_explore_root_dirichlet; "Exploration noise" below)
+ *   stream 7 (per root slot, move t): the Gumbel noise of the root scores (snac_explore_gumbel_scores; there)
  *   env = env_id_base + local index, so results do not depend on how envs are sharded over GPUs.  The node-pool entry points key edge /
  *   leaf i of a call by env_id_base + i; a search with K paths per tree hands them its B * K slots with env_id_base * K in the descriptor,
  *   so that slot k of tree b draws with (env_id_base + b) * K + k, its slot in the search over all envs ("K paths per tree" below).
@@ -1165,6 +1167,49 @@ int snac_observe_nodes3d(const snac_env_desc* desc, const snac_state* st, const 
  *     Hence n >= count gives snac_uct_returns bit for bit, and a window that crosses the end of an episode stops there.  Slots outside the
  *     count are not written; z must not alias value.  Checks: those of snac_uct_returns; n >= 1; value non-null.  count == 0: nothing is
  *     launched.
+ * Exploration noise: self-play's root noise, Gumbel scores and move temperature from the counter RNG (snac_explore_root_dirichlet /
+ *   snac_explore_gumbel_scores, k_explore.hip; snac_explore_pick_moves_temp, k_uct_play.hip; explore_rule.h states the rules once, for the kernels
+ *   and for a host compiler; UCTSearch.add_dirichlet_noise() / gumbel_scores(t=) / pick_moves(temperature=), SelfPlay(dirichlet=,
+ *   temperature=, counter_noise=)).  One launch each on the caller's stream, no host synchronisation, every draw keyed by env_id_base + b:
+ *   a shard of the trees draws what the same trees draw in the whole batch.  All three check every argument before any HIP call.
+ *   Everything is float64, every operation rounded on its own (no fused multiply-add), left to right as parenthesised.
+ *     U(w)    = ((double)w + 0.5) * 2^-32                          (exact; in (0, 1))
+ *     LOGP(s) = LOG's sequence of operations ("Acting from a policy") for every positive normal float64 s: frexp takes the exponent, the
+ *               fold at sqrt 1/2 keeps |z| < 0.1716, so the truncated series leaves less than 2.3e-19 everywhere, and with its roundings the result is
+ *               within 2.3e-19 + 17 * 2^-53 * (0.3466 + |log s|) of log s.  Here s runs from 2^-33 (U of word 0) to 2^31.
+ *     Streams 6 (Dirichlet) and 7 (Gumbel scores) of the counter RNG; slot (b, a) draws with the env key (env_id_base + b) * 8 + a (the
+ *     factor is 8 for every A; unsigned 64-bit wrap-around).  The temperature move keeps stream 3 and snac_uct_pick_moves' key.
+ *   log of a Gamma(alpha, 1) draw of slot (b, a) at move t with at most R attempts:
+ *     boost = alpha < 1;  a1 = boost ? alpha + 1.0 : alpha;  d = a1 - 1.0 / 3.0;  c = 1.0 / sqrt(9.0 * d)     (once per call, on the host)
+ *     attempt j = 0 .. R - 1, until one is accepted; w_k = word(seed, 6, key, t * 128 + 4 * j + k) (the counter in 32-bit wrap-around):
+ *       u1 = U(w_0), u2 = U(w_1), u3 = U(w_2);   x = (1.7156 * (u2 - 0.5)) / u1;   x2 = x * x         (the ratio-of-uniforms normal)
+ *       s = 1.0 + c * x;   v = (s * s) * s;   lv = LOGP(v > 0 ? v : 1.0)
+ *       accepted when  x2 <= -4.0 * LOGP(u1)  and  v > 0  and  LOGP(u3) < ((0.5 * x2 + d) - d * v) + d * lv      (Marsaglia and Tsang)
+ *     lg = LOGP(d) + lv of the accepted attempt; with none accepted lg = LOGP(d).  An attempt is accepted with probability about 0.70.
+ *     boost: lg = lg + LOGP(U(word(seed, 6, key, t * 128 + 3))) / alpha                                (word 3 of attempt 0)
+ *   snac_explore_root_dirichlet: for every tree with mask[b] != 0 (mask NULL: every tree), R = row b * cap, p_a = R.prior[a] for a < num_actions:
+ *     the row is bad when some p_a is a NaN, infinite or negative (-0.0 is a zero), or no p_a > 0: it keeps every byte and adds one to
+ *     bad_rows[0] (int32 on the device, an atomic add; bad_rows may be NULL).  Otherwise, with the support {a : p_a > 0}:
+ *       l_a   = (float)lg_a on the support, -inf elsewhere          (a Gamma draw per action of the support only)
+ *       m, x_a = (double)l_a - (double)m, e_a = EXP(x_a), S = e_0 + ... + e_{A-1} from 0.0: the softmax of "Acting from a policy"
+ *       eta_a = e_a / S;   p'_a = (float)(om * (double)p_a + eps * eta_a)  with  om = 1.0 - eps  (once per call): three rounded operations
+ *     R.prior[a] = p'_a on the support; a prior outside it keeps its bits.  Only these A words of the root row may be written.
+ *     Checks: desc non-null; those of snac_uct_pick_moves for num_actions, stats, B, cap and the rows; alpha in [2^-10, 2^10]; eps in
+ *     [0, 1]; attempts in [1, 32].  With eps == 0 and bad_rows NULL there is nothing to write and nothing is launched.
+ *   snac_explore_gumbel_scores: scores[b][a] for a < num_actions, float32 [B][num_actions], from the roots' priors, which are READ ONLY:
+ *       p_a finite and > 0:  (float)(LOGP((double)p_a) + n),   n = noisy[b] != 0 (noisy NULL: everywhere) ?
+ *                            -LOGP(-LOGP(U(word(seed, 7, key, t)))) : 0.0
+ *       p_a == 0: -inf;   a NaN, a negative or an infinite p_a: NaN      (snac_uct_gumbel_candidates ranks a NaN as -inf)
+ *     Checks: desc non-null; num_actions, stats, B, cap and the rows as above; scores non-null.
+ *   snac_explore_pick_moves_temp: snac_uct_pick_moves with a temperature: pi and value are exactly its outputs, and so is action where total == 0
+ *     or the tree is greedy by the mask.  Otherwise T = temperature ? (double)temperature[b] : temp, and with w the same stream-3 word:
+ *       a NaN or T <= 0: the greedy rule;   T == 1: the integer rule of snac_uct_pick_moves, bit for bit;   else, with r = 1.0 / T and
+ *       N_max the largest count:
+ *         w_a   = N_a == N_max ? 2^28 : N_a > 0 ? (uint64)floor(EXP((LOGP((double)N_a) - LOGP((double)N_max)) * r) * 2^28) : 0
+ *         total = w_0 + ... + w_{A-1}  (in [2^28, 2^31]);   u = ((uint64)w * total) >> 32;   action = the lowest a with w_0 + ... + w_a > u
+ *       T = +inf draws uniformly over the visited actions (r = 0: every visited action weighs 2^28).
+ *     Checks: those of snac_uct_pick_moves; temp >= 0, finite or +inf (a NaN is rejected).  With action, pi and value all NULL nothing is
+ *     launched.
  * Prioritised replay: a 64-ary sum tree of integer weights in device memory, updated and sampled in O(log64 entries) per item with no
  *   host synchronisation (snac_prio_layout / snac_prio_init / snac_prio_update / snac_prio_fill / snac_prio_sample, k_prio.hip;
  *   snac_amd/priority.py PriorityTree, SelfPlay(prioritized=True), ReplayRing(prioritized=True)).
@@ -1363,6 +1408,13 @@ int snac_uct_store_targets(int32_t num_actions, const snac_uct_node* stats, int3
                            int32_t entries, const float* policy, float* pi, float* value, int32_t* refreshed, void* stream);
 int snac_uct_returns_nstep(int32_t B, int32_t cap_moves, int32_t first, int32_t count, int32_t n, double gamma, const float* reward,
                            const uint8_t* done, const float* value, const float* bootstrap, float* z, void* stream);
+int snac_explore_root_dirichlet(const snac_env_desc* desc, int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap,
+                                const uint8_t* mask, uint32_t t, double alpha, double eps, int32_t attempts, int32_t* bad_rows, void* stream);
+int snac_explore_gumbel_scores(const snac_env_desc* desc, int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap,
+                               const uint8_t* noisy, uint32_t t, float* scores, void* stream);
+int snac_explore_pick_moves_temp(const snac_env_desc* desc, int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap,
+                                 const uint8_t* greedy, uint32_t t, const float* temperature, double temp, int8_t* action, float* pi, float* value,
+                                 void* stream);
 
 int snac_prio_layout(int32_t entries, int64_t* bytes, int32_t* levels, int64_t* level_offset);
 int snac_prio_init(void* tree, int32_t entries, int32_t scale_log2, void* stream);

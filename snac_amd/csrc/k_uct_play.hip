@@ -1,11 +1,13 @@
 // k_uct_play.hip -- self-play on the UCT trees of k_uct.hip: snac_uct_pick_moves (a move per tree from the root's visit counts, with the
 // visit distribution and the root value), snac_uct_restart (a new episode in some trees, the others untouched), snac_uct_returns
-// (value targets from a ring of rewards) and snac_uct_gumbel_candidates (the candidate sets and the move of the Gumbel root search).
-// include/snac_hip.h, "Self-play" and "Gumbel root", has the semantics.
+// (value targets from a ring of rewards) and snac_uct_gumbel_candidates (the candidate sets and the move of the Gumbel root search);
+// snac_explore_pick_moves_temp, the move drawn from the counts' power 1 / T, is k_uct_pick with a temperature.
+// include/snac_hip.h, "Self-play", "Gumbel root" and "Exploration noise", has the semantics.
 #include <cmath>
 #include <cstddef>
 
 #include "snac_units.h"
+#include "explore_rule.h"
 #include "uct_dev.h"
 
 // Three small, latency-bound kernels beside k_uct_advance.  pick and returns are lane = tree: a root is one 128-byte line (two when the
@@ -26,8 +28,14 @@ struct UctPick {
     float* value;
 };
 
-template <int A>
-__global__ __launch_bounds__(64) void k_uct_pick(const UctPick v) {
+struct UctPickTemp : UctPick {                                       // snac_explore_pick_moves_temp: T per tree, or one T
+    const float* temperature;
+    double temp;
+};
+
+// the move's rules are explore_rule.h's: the greedy one and the integer draw for both entry points, the weights of a T for the second
+template <int A, bool TEMP>
+__global__ __launch_bounds__(64) void k_uct_pick(const std::conditional_t<TEMP, UctPickTemp, UctPick> v) {
     const int b = (int)(blockIdx.x * 64 + threadIdx.x);
     if (b >= v.B) return;
     const uint4* const rec = v.stats + (size_t)b * v.cap * PIECES;
@@ -53,23 +61,14 @@ __global__ __launch_bounds__(64) void k_uct_pick(const UctPick v) {
     if (!v.action) return;
     int act = 0;
     if (total != 0) {
-        if (!v.greedy || v.greedy[b] != 0) {                         // the lowest a with the largest count
-            uint32_t best = n[0];
-#pragma unroll
-            for (int a = 1; a < A; ++a)
-                if (n[a] > best) { best = n[a]; act = a; }
-        } else {                                                     // proportional to the counts, in integers
-            const uint32_t w = rng_word(env_keys(v.key, (uint64_t)(v.env_id_base + b)), v.t);
-            // (w * total) >> 32 without leaving 64 bits (total < 2^35)
-            const uint64_t u = (uint64_t)w * (total >> 32) + (((uint64_t)w * (total & 0xFFFFFFFFull)) >> 32);
-            uint64_t cum = 0;
-            bool found = false;
-            act = A - 1;
-#pragma unroll
-            for (int a = 0; a < A; ++a) {                            // the lowest a whose running sum passes u (u < total: there is one)
-                cum += n[a];
-                if (!found && cum > u) { act = a; found = true; }
-            }
+        const bool greedy = !v.greedy || v.greedy[b] != 0;
+        uint32_t w = 0;
+        if (!greedy) w = rng_word(env_keys(v.key, (uint64_t)(v.env_id_base + b)), v.t);
+        if constexpr (TEMP) {
+            const double T = v.temperature ? (double)v.temperature[b] : v.temp;
+            act = snac_spec::temp_move<A>(n, total, greedy, T, w);
+        } else {
+            act = greedy ? snac_spec::pick_greedy<A>(n) : snac_spec::pick_weighted<A>(n, total, w);      // no floating point enters the choice
         }
     }
     v.action[b] = (int8_t)act;
@@ -261,10 +260,30 @@ int snac_uct_pick_moves(const snac_env_desc* desc, int32_t num_actions, const sn
     if (!action && !pi && !value) return SNAC_OK;                    // nothing asked for
     const UctPick v{(const uint4*)stats, B, cap, stream_key(desc->seed, PICK_STREAM), t, desc->env_id_base, greedy, action, pi, value};
     g_kernel = "k_uct_pick";
-    if (num_actions == 3) hipLaunchKernelGGL((k_uct_pick<3>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
-    else if (num_actions == 5) hipLaunchKernelGGL((k_uct_pick<5>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
-    else hipLaunchKernelGGL((k_uct_pick<8>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    if (num_actions == 3) hipLaunchKernelGGL((k_uct_pick<3, false>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    else if (num_actions == 5) hipLaunchKernelGGL((k_uct_pick<5, false>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
+    else hipLaunchKernelGGL((k_uct_pick<8, false>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, v);
     return launched("snac_uct_pick_moves");
+}
+
+int snac_explore_pick_moves_temp(const snac_env_desc* desc, int32_t num_actions, const snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap,
+                                 const uint8_t* greedy, uint32_t t, const float* temperature, double temp, int8_t* action, float* pi, float* value,
+                                 void* stream) {
+    using namespace snac_detail;
+    if (!desc) return fail(SNAC_ERR_ARG, "null desc");
+    if (int rc = play_check(num_actions, stats, stats_rows, B, cap)) return rc;
+    if (!(temp >= 0.0)) return fail(SNAC_ERR_ARG, "temp must be >= 0 (finite or +inf; 0: greedy)");
+    if (!action && !pi && !value) return SNAC_OK;                    // nothing asked for
+    UctPickTemp v;
+    static_cast<UctPick&>(v) = UctPick{(const uint4*)stats, B, cap, stream_key(desc->seed, PICK_STREAM), t, desc->env_id_base, greedy, action, pi, value};
+    v.temperature = temperature;
+    v.temp = temp;
+    g_kernel = "k_uct_pick_temp";
+    const dim3 grid((unsigned)((B + 63) / 64));
+    if (num_actions == 3) hipLaunchKernelGGL((k_uct_pick<3, true>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else if (num_actions == 5) hipLaunchKernelGGL((k_uct_pick<5, true>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    else hipLaunchKernelGGL((k_uct_pick<8, true>), grid, dim3(64), 0, (hipStream_t)stream, v);
+    return launched("snac_explore_pick_moves_temp");
 }
 
 int snac_uct_restart(int32_t num_actions, snac_uct_node* stats, int32_t stats_rows, int32_t B, int32_t cap, void* records, int32_t record_bytes,

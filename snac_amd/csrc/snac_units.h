@@ -48,6 +48,10 @@
 //   k_search.hip    k_search_loss / k_search_reduce   the loss of self-play positions (AlphaZero, Gumbel): the cross-entropy to the search's
 //                                 distribution, the value error, their gradients, the new priorities and the statistics: lane = sample
 //                                 (search_rule.h: the per-sample rule), then the batch sums
+//   k_explore.hip   k_root_dirichlet / k_gumbel_scores   self-play's exploration noise from the counter RNG: Dirichlet noise into the roots'
+//                                 priors, log priors plus Gumbel noise: lane = slot (b, a), eight lanes per tree, the row's softmax through
+//                                 lane reads (explore_rule.h: the Gamma draw, the slots' pieces and the move by a temperature, which
+//                                 k_uct_pick in k_uct_play.hip runs, host and device)
 //                   (for these three units: batch_sum.h, the wave's butterfly and the second stage of the batch sums; for k_dist.hip and
 //                   k_c51_loss: lane_dev.h, the lane read, the DPP row move and the shuffle-down tree)
 //                   (for k_policy.hip and the soft, PPO and search rules: softmax_rule.h, the float64 softmax of a row of scores in three steps, on

@@ -30,7 +30,8 @@ SNAC_SPEC_FN double spec_exp(double x) {
     return x < -45.0 ? 0.0 : e;
 }
 
-// LOG of the header: 1 <= s <= 8
+// LOG of the header, and its LOGP ("Exploration noise"): the same sequence for every positive normal s -- frexp takes the exponent and the
+// series sees f in [sqrt 1/2, sqrt 2) alone.  Not for 0, a subnormal, a negative, an infinity or a NaN: a caller keeps those away
 SNAC_SPEC_FN double spec_log(double s) {
 #pragma clang fp contract(off)
     constexpr double d[11] = {1.0, 1.0 / 3.0, 1.0 / 5.0, 1.0 / 7.0, 1.0 / 9.0, 1.0 / 11.0, 1.0 / 13.0, 1.0 / 15.0, 1.0 / 17.0, 1.0 / 19.0, 1.0 / 21.0};

@@ -25,6 +25,11 @@ of PUCT at the root and the visit counts: per move gumbel_begin() on log-priors 
 of an episode; without noise after that), gumbel_run(iterations), action = gumbel_actions(), pi = improved_policy(); value, reward, done
 and the re-rooting are as above.  Exploration comes from the Gumbel noise: there is no root_noise hook in this mode.
 
+Exploration from the counter RNG ("Exploration noise" in include/snac_hip.h): dirichlet=(alpha, eps) mixes AlphaZero's Dirichlet noise
+into the roots' priors before every move's search, temperature=T draws the sampled moves in proportion to N ** (1 / T), and
+counter_noise=True (with gumbel=True) takes the Gumbel noise from it too.  Each is one launch keyed by (env_id_base + b, the move
+counter), so a sharded run plays exactly the whole batch's moves; without them play() enqueues what it always did.
+
 Reanalyse: a position's pi and value come from a search guided by the network as it was when the move was played, and at a few dozen
 iterations per move they age quickly, while replaying costs far more than searching again.  SelfPlay(..., keep_states=True) also keeps
 each move's root record, a complete state (`state`: 128 bytes per ring entry for 1D and 2D, 896 for 3D), and reanalyse(search, iterations)
@@ -60,7 +65,7 @@ from ._lib import ptr as _ptr
 
 class SelfPlay:
     def __init__(self, search, capacity_moves, sample_moves=0, gamma=None, root_noise=None, gumbel=False, generator=None, keep_states=False,
-                 prioritized=False, priority_scale_log2=16):
+                 prioritized=False, priority_scale_log2=16, dirichlet=None, temperature=None, counter_noise=False):
         """search: a UCTSearch with one tree per env row (reset() by the caller); capacity_moves: ring slots; sample_moves: the moves of
         an episode drawn in proportion to the visits (the rest: argmax); gamma: of the value targets (default: the search's);
         root_noise: PUCT only, priors [B, A] -> priors [B, A], applied to the roots before every move's search (exploration noise is the
@@ -69,7 +74,33 @@ class SelfPlay:
         the default one).  keep_states=True: the ring also keeps every move's root record (`state`: 128 bytes per entry for 1D and 2D,
         896 for 3D, capacity_moves * trees entries) and a count of its reanalyses (`refreshed`), which reanalyse() needs; one more
         launch per move.  prioritized=True: a PriorityTree over the capacity_moves * trees entries (flat = slot * trees + b), seeded from
-        the env's seed, with priority_scale_log2 as its scale_log2; every move played gets the largest priority seen so far."""
+        the env's seed, with priority_scale_log2 as its scale_log2; every move played gets the largest priority seen so far.
+        Exploration from the counter RNG (include/snac_hip.h, "Exploration noise"; one launch each, independent of the sharding):
+        dirichlet=(alpha, eps) (PUCT; not with root_noise or gumbel=True): UCTSearch.add_dirichlet_noise(alpha, eps, t=moves) before
+        every move's search; temperature=T (a number >= 0; not with gumbel=True): the first sample_moves moves of an episode are drawn
+        in proportion to N ** (1 / T) in place of N; counter_noise=True (gumbel=True, generator None): the Gumbel noise comes from
+        UCTSearch.gumbel_scores(noise=mask, t=moves), one launch in place of two score tensors and a torch.where."""
+        if not isinstance(counter_noise, bool):
+            raise ValueError("counter_noise must be a bool")
+        if dirichlet is not None:
+            if callable(root_noise) or gumbel is True:
+                raise ValueError("dirichlet does not go with a root_noise callable or with gumbel=True")
+            if (not isinstance(dirichlet, (tuple, list)) or len(dirichlet) != 2
+                    or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in dirichlet)
+                    or not 2.0 ** -10 <= dirichlet[0] <= 2.0 ** 10 or not 0.0 <= dirichlet[1] <= 1.0):
+                raise ValueError("dirichlet must be (alpha in [2^-10, 2^10], eps in [0, 1])")
+            if search.evaluator is None:
+                raise ValueError("dirichlet noise belongs to the PUCT search: give the search an evaluator")
+            dirichlet = (float(dirichlet[0]), float(dirichlet[1]))
+        if temperature is not None:
+            if gumbel is True:
+                raise ValueError("temperature does not go with gumbel=True: the Gumbel search plays its survivor")
+            if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature >= 0:
+                raise ValueError("temperature must be a number >= 0")
+            temperature = float(temperature)
+        if counter_noise and (gumbel is not True or generator is not None):
+            raise ValueError("counter_noise=True belongs to gumbel=True with generator=None")
+        self.dirichlet, self.temperature, self.counter_noise = dirichlet, temperature, counter_noise
         if not isinstance(keep_states, bool):
             raise ValueError("keep_states must be a bool")
         if not isinstance(prioritized, bool):
@@ -159,6 +190,8 @@ class SelfPlay:
                 else:
                     if self.root_noise is not None:
                         s.set_root_priors(self.root_noise(s.root_priors()))
+                    if self.dirichlet is not None:
+                        s.add_dirichlet_noise(*self.dirichlet, t=self.moves)
                     s._run(n)
                 _lib.check(self._observe(C.byref(env._desc), C.byref(env._state), _ptr(P.records), P.rows, B, _ptr(self._root_rows),
                                          _ptr(self.obs[h]), env._stream()))
@@ -171,7 +204,7 @@ class SelfPlay:
                     s._pick(None, 0, None, None, self.value[h])      # the root's W / N
                 else:
                     torch.ge(self._move, self.sample_moves, out=self._greedy.view(torch.bool))
-                    s._pick(self._greedy, self.moves, self.action[h], self.pi[h], self.value[h])
+                    s._pick(self._greedy, self.moves, self.action[h], self.pi[h], self.value[h], temperature=self.temperature)
                 s._advance_into(self.action[h], self.reward[h], self.done[h], prime=False)   # restart() primes every unvisited root
                 self.move[h].copy_(self._move)
                 env.reset(mask=self.done[h], want_obs=False)         # the finished trees' env rows: the next episode (and its plan)
@@ -188,7 +221,12 @@ class SelfPlay:
         log-priors alone after that (one torch.where of the two), then the sequential-halving iterations."""
         s = self.search
         torch.lt(self._move.view(-1, 1), self.sample_moves, out=self._noisy)
-        s.gumbel_begin(torch.where(self._noisy, s.gumbel_scores(True, self.generator), s.gumbel_scores(False)))
+        if self.counter_noise:                                       # the same scores in one launch, the noise from the counter RNG
+            s._counter_scores(self._noisy, None, self.moves, out=s._gscores)
+            s._candidates(0)
+            s._gumbel_begun = True
+        else:
+            s.gumbel_begin(torch.where(self._noisy, s.gumbel_scores(True, self.generator), s.gumbel_scores(False)))
         s._gumbel_run(n)
 
     # ---- the ring ---------------------------------------------------------------------------------------------------------

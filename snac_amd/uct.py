@@ -46,9 +46,9 @@ wider than the default 0.0 (virtual visits only) at some cost in search quality:
 
 A policy / value network in place of the rollout: evaluator=fn makes the search PUCT ("PUCT" in include/snac_hip.h).  Once per iteration
 fn gets the observation rows of the B * K leaves, in slot order, on the env's device with the env's stream current, and returns
-(priors [S, A] probabilities, value [S]); the priors are stored in the expanded nodes as float32 as given (softmax, masking and root noise
-are the caller's: root_priors() / set_root_priors(p)), and first reward + value (0 at a terminal leaf) is backed up in place of a rollout
-estimate.  c is then the PUCT constant, first_play_value the q of an untried action; horizon only spaces the counter words (0 is allowed).
+(priors [S, A] probabilities, value [S]); the priors are stored in the expanded nodes as float32 as given (softmax and masking are the
+caller's; root noise is add_dirichlet_noise(), or the caller's own through root_priors() / set_root_priors(p)), and first reward +
+value (0 at a terminal leaf) is backed up in place of a rollout estimate.  c is then the PUCT constant, first_play_value the q of an untried action; horizon only spaces the counter words (0 is allowed).
 reset() and advance() call fn on the B roots for the priors of the new roots.
 
     net = torch.nn.Sequential(torch.nn.Linear(env.obs_dim, 128), torch.nn.ReLU(), torch.nn.Linear(128, env.num_actions + 1)).to(env.device)
@@ -299,6 +299,7 @@ class UCTSearch:
             self._obs_ptrs = (_ptr(P.records), P.rows, S, _ptr(self._leaf), _ptr(self._obs))
             self._root_obs_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._root_rows), _ptr(self._root_obs))
             self._prior_args = (A, _ptr(self.stats), self.rows, S, _ptr(self._prior_rows), _ptr(self._priors), 0)
+            self.noise_bad_rows = torch.zeros(1, dtype=torch.int32, device=dev)     # add_dirichlet_noise(): roots whose priors it refused
         self.q_bounds = None
         if q_normalise:                                              # the _norm entry points: the same arguments, then the bounds
             self.q_bounds = torch.empty((B, 2), dtype=torch.float64, device=dev)
@@ -469,14 +470,27 @@ class UCTSearch:
                 self._prime_roots()
 
     # ---- self-play: a move from the visit counts, a new episode in some trees ---------------------------------------------------
-    def pick_moves(self, greedy=None, t=0, out=None):
+    def pick_moves(self, greedy=None, t=0, out=None, temperature=None):
         """One move per tree from its root's visit counts (snac_uct_pick_moves; include/snac_hip.h, "Self-play").  greedy: None or True
         -- the most-visited action, ties to the lowest (best_actions()); False -- drawn in proportion to the visits with the counter
         RNG's stream 3, keyed by (env_id_base + b, t); a [B] tensor -- per tree (non-zero: greedy).  t: the caller's move counter.  A
         root without child visits (a terminal root; before any iteration) gives action 0 and pi 0.  out: (action int8 [B], pi float32
         [B, A], value float32 [B]) contiguous on the env's device to write into.  Enqueued on the env's stream, no host synchronisation.
+        temperature: None, or the T of the trees that are not greedy (snac_explore_pick_moves_temp; "Exploration noise" there): a number
+        >= 0 or a float32 [B] tensor, per tree.  Such a tree draws in proportion to N_a ** (1 / T) from the same stream-3 word: T = 1 is
+        the draw without a temperature bit for bit, T = 0 (or a NaN in the tensor) the most-visited action, T = inf uniform over the
+        visited actions.  pi and value do not depend on it.
         Returns (action, pi: the visit distribution N_a / sum N, value: the root's W / N)."""
         B, A = self.trees, self.num_actions
+        T = None
+        if torch.is_tensor(temperature):
+            if tuple(temperature.shape) != (B,) or temperature.dtype != torch.float32:
+                raise ValueError("temperature must be a number or a float32 [%d] tensor" % B)
+            T = temperature
+        elif temperature is not None:
+            if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature >= 0:
+                raise ValueError("temperature must be a number >= 0 or a float32 [%d] tensor" % B)
+            T = float(temperature)
         g = None
         if torch.is_tensor(greedy) or isinstance(greedy, (list, tuple)):
             g = greedy if torch.is_tensor(greedy) else torch.as_tensor(greedy)
@@ -502,13 +516,22 @@ class UCTSearch:
                 g = (g != 0).to(torch.uint8)
         elif greedy is not None and not greedy:
             g = self._sample_all
-        self._pick(g, t, *out)
+        if torch.is_tensor(T):
+            T = T.to(dev).contiguous()
+        self._pick(g, t, *out, temperature=T)
         return out
 
-    def _pick(self, greedy, t, action, pi, value):
-        """snac_uct_pick_moves on the env's stream; greedy uint8 [B] on the device or None, each output a tensor or None."""
+    def _pick(self, greedy, t, action, pi, value, temperature=None):
+        """snac_uct_pick_moves on the env's stream; greedy uint8 [B] on the device or None, each output a tensor or None.  temperature
+        (a float, or a contiguous float32 [B] tensor on the device): snac_explore_pick_moves_temp instead."""
         env = self.env
         with torch.cuda.device(env.device):
+            if temperature is not None:
+                per_tree = torch.is_tensor(temperature)
+                _lib.check(self._lib.snac_explore_pick_moves_temp(*self._pick_args, None if greedy is None else _ptr(greedy), int(t) & 0xFFFFFFFF,
+                                                                  _ptr(temperature) if per_tree else None, 1.0 if per_tree else temperature,
+                                                                  *(None if x is None else _ptr(x) for x in (action, pi, value)), env._stream()))
+                return
             _lib.check(self._lib.snac_uct_pick_moves(*self._pick_args, None if greedy is None else _ptr(greedy), int(t) & 0xFFFFFFFF,
                                                      *(None if x is None else _ptr(x) for x in (action, pi, value)), env._stream()))
 
@@ -705,16 +728,78 @@ class UCTSearch:
         _lib.check(self._lib.snac_uct_gumbel_candidates(*self._cand_args, mode, self.gumbel, *self._cand_tail,
                                                         None if action is None else _ptr(action), self.env._stream()))
 
-    def gumbel_scores(self, noise=True, generator=None):
+    def gumbel_scores(self, noise=True, generator=None, t=None):
         """[B, A] float32: log(root_priors()), plus a Gumbel(0, 1) sample -log(-log(U)) per entry with noise=True, U from torch.rand on the
         env's device (generator: a torch.Generator of that device).  A prior of 0 gives -inf: the action is never a candidate before
-        one with a positive prior."""
+        one with a positive prior.  t (the caller's move counter): the scores in one launch instead, the noise from the counter RNG's
+        stream 7 keyed by (env_id_base + b, a, t), so that they do not depend on the sharding or on a generator's state
+        (snac_explore_gumbel_scores; include/snac_hip.h, "Exploration noise"); noise may then also be a [B] tensor (non-zero: that tree gets
+        noise) and generator must be None.  No host synchronisation."""
         self._need_gumbel()
+        if t is not None:
+            return self._counter_scores(noise, generator, t)
         logits = torch.log(self.root_priors())
         if not noise:
             return logits
         u = torch.rand(logits.shape, dtype=torch.float32, device=self.env.device, generator=generator)
         return logits - torch.log(-torch.log(u))
+
+    def _mask8(self, m):
+        """A [B] mask tensor as contiguous uint8 on the env's device (non-zero: set); a bool or uint8 tensor there is taken as it is."""
+        m = m.to(self.env.device).reshape(-1)
+        if m.dtype == torch.bool:
+            m = m.view(torch.uint8)
+        elif m.dtype != torch.uint8:
+            m = (m != 0).view(torch.uint8)
+        return m.contiguous()
+
+    def _counter_scores(self, noise, generator, t, out=None):
+        """gumbel_scores(t=): snac_explore_gumbel_scores into `out` (None: a new [B, A] tensor)."""
+        B = self.trees
+        if generator is not None:
+            raise ValueError("generator does not go with t: the counter RNG draws the noise")
+        if isinstance(t, bool) or not isinstance(t, int):
+            raise ValueError("t must be an integer: the caller's move counter")
+        if torch.is_tensor(noise):
+            if int(noise.numel()) != B:
+                raise ValueError("noise must be a bool or a [%d] tensor" % B)
+        elif not isinstance(noise, (bool, int)):
+            raise ValueError("noise must be a bool or a [%d] tensor" % B)
+        env, dev = self.env, self.env.device
+        with torch.cuda.device(dev):
+            if torch.is_tensor(noise):
+                m = self._mask8(noise)
+            else:
+                m = None if noise else self._sample_all              # zeros: no tree gets noise
+            if out is None:
+                out = torch.empty((B, self.num_actions), dtype=torch.float32, device=dev)
+            _lib.check(self._lib.snac_explore_gumbel_scores(*self._pick_args, _ptr(m), t & 0xFFFFFFFF, _ptr(out), env._stream()))
+        return out
+
+    def add_dirichlet_noise(self, alpha, eps=0.25, t=0, mask=None, attempts=16):
+        """AlphaZero's root noise, in place: the priors of root b <- (1 - eps) * priors + eps * eta_b, eta_b ~ Dirichlet(alpha) over the
+        actions with a positive prior, drawn from the counter RNG's stream 6 keyed by (env_id_base + b, a, t) -- t: the caller's move
+        counter -- so that a shard of the trees draws what they draw in the whole batch (snac_explore_root_dirichlet; include/snac_hip.h,
+        "Exploration noise").  PUCT only.  mask: None or a [B] tensor (non-zero: that tree gets noise); attempts: the bound of the Gamma
+        draws' rejection loop, 1 .. 32.  A root whose priors hold a NaN, an infinity, a negative or no positive entry is left as it is
+        and counted in noise_bad_rows (int32 [1] on the device).  One launch on the env's stream, no host synchronisation."""
+        if self.evaluator is None:
+            raise ValueError("priors belong to the PUCT search: give an evaluator")
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 2.0 ** -10 <= alpha <= 2.0 ** 10:
+            raise ValueError("alpha must be a number in [2^-10, 2^10]")
+        if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps <= 1.0:
+            raise ValueError("eps must be a number in [0, 1]")
+        if isinstance(attempts, bool) or not isinstance(attempts, int) or not 1 <= attempts <= 32:
+            raise ValueError("attempts must be an integer in [1, 32]")
+        if isinstance(t, bool) or not isinstance(t, int):
+            raise ValueError("t must be an integer: the caller's move counter")
+        if mask is not None and (not torch.is_tensor(mask) or int(mask.numel()) != self.trees):
+            raise ValueError("mask must be None or a [%d] tensor" % self.trees)
+        env = self.env
+        with torch.cuda.device(env.device):
+            m = None if mask is None else self._mask8(mask)
+            _lib.check(self._lib.snac_explore_root_dirichlet(*self._pick_args, _ptr(m), t & 0xFFFFFFFF, float(alpha), float(eps), attempts,
+                                                             _ptr(self.noise_bad_rows), env._stream()))
 
     def gumbel_begin(self, scores):
         """Candidate sets for this move: cand[b] <- the min(m, A) root actions of tree b with the largest scores[b] ([B, A], stored as
