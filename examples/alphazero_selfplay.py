@@ -7,6 +7,7 @@ trainer: nothing but the final printout crosses the bus.
                                           [--reanalyse R] [--td-steps N] [--prioritized [--per-alpha A] [--per-beta B]]
                                           [--device-loss [--huber D] [--vf-coef C]]
                                           [--dirichlet ALPHA [--noise-eps E]] [--temperature T] [--counter-noise]
+                                          [--device-evaluator]
 
 --normalise: the search compares q normalised by each tree's min-max bounds (UCTSearch(q_normalise=True)), so that c = 1.25 weighs
 the priors against returns of any scale (a brick pays 5 here).
@@ -31,6 +32,9 @@ device from the counter RNG before every move's search (SelfPlay(dirichlet=)), i
 --temperature T: the sampled moves of an episode are drawn in proportion to N ** (1 / T) (SelfPlay(temperature=)).
 --counter-noise (with --gumbel M): the Gumbel noise comes from the counter RNG too (SelfPlay(counter_noise=True)): the run then depends
 neither on how the envs are sharded nor on a generator's state.
+--device-evaluator: the network that guides the search runs as one launch of the package's own (DeviceMLP: float64 sums in index order,
+the parameters read in place), and the search values its leaves in that same launch, in place of the torch evaluator below; training
+goes through torch autograd as before.
 """
 import argparse
 import os
@@ -40,14 +44,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, SearchLoss, SelfPlay, UCTSearch  # noqa: E402
+from snac_amd import BatchedDMPEnv, DeviceMLP, SearchLoss, SelfPlay, UCTSearch  # noqa: E402
 
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
           gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4, device_loss=False, huber=None,
-          vf_coef=1.0, info=None, dirichlet=None, noise_eps=0.25, temperature=None, counter_noise=False):
+          vf_coef=1.0, info=None, dirichlet=None, noise_eps=0.25, temperature=None, counter_noise=False, device_evaluator=False):
     """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
-    SelfPlay).  info: a dict that receives bad_rows and the last step's statistics of the device loss."""
+    SelfPlay).  info: a dict that receives bad_rows and the last step's statistics of the device loss, and evaluator_bad_rows of the
+    device evaluator."""
     if not device_loss and (huber is not None or vf_coef != 1.0):
         raise ValueError("huber and vf_coef belong to device_loss")
     env = BatchedDMPEnv(kind, True, envs, seed=seed)
@@ -61,6 +66,9 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
     def evaluator(obs):                                              # leaves' observation rows -> (priors, value)
         y = net(obs.to(torch.float32))
         return torch.softmax(y[:, :A], 1), y[:, A]
+
+    if device_evaluator:                                             # the same network, read in place by one launch per evaluation
+        evaluator = DeviceMLP(net, env)
 
     def noise(priors):                                               # exploration at the roots: the caller's (here: a uniform share)
         return 0.75 * priors + 0.25 / A
@@ -116,6 +124,8 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
         losses.append(loss.detach())
     if info is not None and device_loss:
         info.update(search_loss.stats_dict(), bad_rows=int(search_loss.bad_rows.cpu()[0]))
+    if info is not None and device_evaluator:
+        info.update(evaluator_bad_rows=int(evaluator.bad_rows.cpu()[0]))
     return [float(x) for x in torch.stack(losses).cpu()], play
 
 
@@ -139,6 +149,7 @@ def main():
     ap.add_argument("--noise-eps", type=float, default=0.25, metavar="E", help="with --dirichlet: the noise's share of the root priors (default 0.25)")
     ap.add_argument("--temperature", type=float, default=None, metavar="T", help="draw the sampled moves in proportion to N ** (1 / T) (PUCT)")
     ap.add_argument("--counter-noise", action="store_true", help="with --gumbel M: the Gumbel noise from the counter RNG")
+    ap.add_argument("--device-evaluator", action="store_true", help="the search's network as one device launch (DeviceMLP), fused into the search")
     args = ap.parse_args()
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
@@ -154,7 +165,7 @@ def main():
                          gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps,
                          prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta, device_loss=args.device_loss,
                          huber=args.huber, vf_coef=args.vf_coef, dirichlet=args.dirichlet, noise_eps=args.noise_eps, temperature=args.temperature,
-                         counter_noise=args.counter_noise)
+                         counter_noise=args.counter_noise, device_evaluator=args.device_evaluator)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     if args.reanalyse:
         print("entries reanalysed: %d" % int(play.refreshed.sum()))

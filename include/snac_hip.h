@@ -769,6 +769,60 @@ int snac_search_loss(int32_t B, int32_t num_actions, const float* logits, const 
                      const float* weight, double vf_coef, double delta, double scale, float* loss, float* priority, float* grad_logits,
                      float* grad_value, double* stats, float* mean_loss, double* partials, int32_t* bad_rows, void* stream);
 
+/* ---- Policy / value network on the device (snac_amd/mlp.py: DeviceMLP; k_mlp.hip, mlp_rule.h): the small MLP that guides the PUCT
+ * search -- an observation row through one to four dense layers, ReLU between them, A + 1 outputs: the logits of the priors and the
+ * value -- as ONE launch, with its softmax / value head and, in snac_mlp_uct_value_leaves, with the search's "value the leaves" step
+ * behind it.  Inference only: training goes through the caller's autograd.  The weights are read in place, at every launch, from the
+ * arrays the network descriptor points to (torch.nn.Linear's parameters as they lie in memory): an update enqueued on the stream before a
+ * launch is seen by it, and nothing is copied or kept between launches.
+ *
+ * The network.  snac_mlp: 1 <= layers = L <= 4 dense layers of dimensions dim[0 .. L]; dim[0], the input width, 1 .. 512; the hidden
+ * widths dim[1 .. L-1] 1 .. 256; dim[L] 1 .. 64.  Layer l has w[l] float32 [dim[l+1]][dim[l]] row-major and b[l] float32 [dim[l+1]],
+ * each 4-byte aligned; entries past L are ignored.
+ * The input.  x: rows of dim[0] values, contiguous, float32 (x_is_f64 = 0, 4-byte aligned) or float64 (x_is_f64 = 1, 8-byte aligned)
+ * rounded to float32 first (what obs.to(torch.float32) does).  No wider alignment is assumed of any array.
+ * Output j of a layer with K inputs x[0 .. K):
+ *     acc = (double)b[j];   for i = 0, 1, .., K-1 in that order:  acc = acc + (double)W[j][i] * (double)x[i]
+ *   The product of two float32 values is exact in float64, so a fused multiply-add and a multiply followed by an add give the same
+ *   bits: the step rounds once, in the addition.  The sum of one output is never split or re-associated (how rows and outputs are
+ *   mapped to lanes is free and cannot be seen in the result).
+ *     a hidden output:          acc < 0.0 ? 0.0f : (float)acc         (ReLU; a NaN stays a NaN, -0.0 stays -0.0)
+ *     an output of layer L-1:   (float)acc
+ * The head (dim[L] == A + 1 with A = num_actions 3, 5 or 8; y the row of outputs): the logits are y[0 .. A) and
+ *     m, x_a, e_a = EXP(x_a), S        exactly as in "Acting from a policy" (-inf masks an action: e_a = 0)
+ *     priors[a] = (float)(e_a / S)     value = (double)y[A]
+ *   A row is bad if some logit is a NaN or +inf, if every logit is -inf, or if y[A] is not finite: it gets priors of +0.0 in every place
+ *   and value 0.0 and adds one to bad_rows[0] (int32 on the device, an atomic add).  logits, where asked for, receives the raw row
+ *   y[0 .. A] of every row, bad or not.
+ *
+ * snac_mlp_forward        y[rows][dim[L]] float32: the outputs of the last layer.
+ * snac_mlp_policy_value   priors float32 [rows][A], value float64 [rows], logits float32 [rows][A + 1], bad_rows: each may be NULL and is then
+ *                         not written.
+ * snac_mlp_uct_value_leaves   for the S = B * paths slots of a PUCT iteration (obs: their leaves' observation rows): the head, then
+ *     term     = first_has[s] ? done[first_idx[s]] != 0 : stats[leaf[s]].terminal != 0     (first_idx clamped into [0, S), leaf into
+ *                [0, stats_rows): the expander's done for a leaf made in this iteration, else the stored node's terminal word)
+ *     value[s] = term ? 0.0 : value        est[s] = est[s] + value[s]        (one float64 addition)        priors[s][0 .. A) written whole
+ *   first_has, done: uint8 [S]; first_idx, leaf: int32 [S]; stats: the rows of snac_uct_node as int32 words; priors, value, est and
+ *   bad_rows may each be NULL.  This is what snac_amd/uct.py's UCTSearch runs between its selection and its backup when its evaluator is
+ *   a DeviceMLP, in place of the evaluator's launches and the torch operations behind them.
+ * Checks, all before any HIP call: net, its layers, every dim, its pointers and their alignment; x non-null and aligned as its type;
+ * x_is_f64 0 or 1; rows >= 1; num_actions 3, 5 or 8 (else SNAC_ERR_UNSUPPORTED) and dim[L] == num_actions + 1; the alignment of every
+ * output (float64: 8 bytes, else 4); the fused step's inputs non-null, stats_rows >= 1.  With every output NULL nothing is launched.
+ * The kernel reads its inputs only and writes nothing but the outputs given; the launch goes on `stream`; no host synchronisation.
+ * snac_last_kernel() names k_mlp_forward, k_mlp_policy_value or k_mlp_value_leaves. */
+typedef struct snac_mlp {
+    int32_t layers;
+    int32_t dim[5];
+    const float* w[4];
+    const float* b[4];
+} snac_mlp;
+int snac_mlp_forward(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows, float* y, void* stream);
+int snac_mlp_policy_value(const snac_mlp* net, int32_t num_actions, const void* x, int x_is_f64, int32_t rows, float* priors, double* value,
+                          float* logits, int32_t* bad_rows, void* stream);
+int snac_mlp_uct_value_leaves(const snac_mlp* net, int32_t num_actions, const void* obs, int obs_is_f64, int32_t S, const uint8_t* first_has,
+                              const int32_t* first_idx, const uint8_t* done, const int32_t* stats, int32_t stats_rows, const int32_t* leaf,
+                              float* priors, double* value, double* est, int32_t* bad_rows, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

@@ -3,7 +3,7 @@ product raises.
 
 include/snac_hip.h is the one statement of the ABI.  parse_header() reads it when this module is imported (no torch, no library) and
 everything below comes from what it finds: the constants (ABI_VERSION, ENV_1D, ... are the header's SNAC_* names without the prefix),
-a ctypes.Structure per struct (STRUCTS; Sizes, EnvDesc, State, RolloutRecord and TrajInfo are the ones callers construct), EXPORTS, and
+a ctypes.Structure per struct (STRUCTS; Sizes, EnvDesc, State, RolloutRecord, TrajInfo and Mlp are the ones callers construct), EXPORTS, and
 the restype / argtypes lib() sets on every entry point.  To bind a new entry point, struct or constant, declare it in the header: that is
 all.  The parser knows only the header's own dialect and raises SnacError on anything else; it never guesses."""
 import ctypes as C
@@ -26,7 +26,7 @@ class SnacError(RuntimeError):
 _SCALARS = {"int": C.c_int, "int8_t": C.c_int8, "uint8_t": C.c_uint8, "int16_t": C.c_int16, "int32_t": C.c_int32, "uint32_t": C.c_uint32,
             "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "float": C.c_float, "size_t": C.c_size_t}
 _CLASS_NAMES = {"snac_sizes": "Sizes", "snac_env_desc": "EnvDesc", "snac_state": "State", "snac_rollout_record": "RolloutRecord",
-                "snac_traj_info": "TrajInfo"}      # the structs callers construct: a parameter `T*` of one of them is POINTER(class)
+                "snac_traj_info": "TrajInfo", "snac_mlp": "Mlp"}      # the structs callers construct: a parameter `T*` of one of them is POINTER(class)
 
 
 def parse_header(text):
@@ -61,6 +61,8 @@ def parse_header(text):
             stars, name, dim = (declarator(d) or bad(part)).groups()
             if stars or (dim and not field):
                 t = C.POINTER(structs[base]) if base in _CLASS_NAMES and stars == "*" and not (dim or field) else C.c_void_p
+                if dim and field:                                    # a field `const float* w[4]`: an array of pointers
+                    t = t * integer(dim)
             else:
                 t = types[base] or bad(part)
                 if dim:
@@ -119,7 +121,7 @@ def _header():
 CONSTANTS, STRUCTS, PROTOTYPES = parse_header(_header())
 globals().update({k[len("SNAC_"):]: v for k, v in CONSTANTS.items()})      # ABI_VERSION, ENV_1D .. TAIL_RECORD, SUMS_SCRATCH_WORDS, ...
 SNAC_OK = CONSTANTS["SNAC_OK"]
-Sizes, EnvDesc, State, RolloutRecord, TrajInfo = (STRUCTS[n] for n in _CLASS_NAMES)
+Sizes, EnvDesc, State, RolloutRecord, TrajInfo, Mlp = (STRUCTS[n] for n in _CLASS_NAMES)
 EXPORTS = tuple(PROTOTYPES)
 
 

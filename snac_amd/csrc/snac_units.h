@@ -52,10 +52,14 @@
 //                                 priors, log priors plus Gumbel noise: lane = slot (b, a), eight lanes per tree, the row's softmax through
 //                                 lane reads (explore_rule.h: the Gamma draw, the slots' pieces and the move by a temperature, which
 //                                 k_uct_pick in k_uct_play.hip runs, host and device)
-//                   (for these three units: batch_sum.h, the wave's butterfly and the second stage of the batch sums; for k_dist.hip and
-//                   k_c51_loss: lane_dev.h, the lane read, the DPP row move and the shuffle-down tree)
+//                   (for k_ppo.hip, k_qloss.hip and k_search.hip: batch_sum.h, the wave's butterfly and the second stage of the batch sums; for
+//                   k_dist.hip and k_c51_loss: lane_dev.h, the lane read, the DPP row move and the shuffle-down tree)
 //                   (for k_policy.hip and the soft, PPO and search rules: softmax_rule.h, the float64 softmax of a row of scores in three steps, on
 //                   spec_math.h's EXP and LOG; for those four units, k_dist.hip and k_qloss.hip: by_actions below, the choice of the A = 3 / 5 / 8 instance)
+//   k_mlp.hip       k_mlp         the policy / value network of the PUCT search: an MLP of up to four dense layers, its softmax / value head
+//                                 (softmax_rule.h, by_actions) and the search's "value the leaves" step in one launch: 16 rows per block,
+//                                 activations and weight tiles in LDS, every output's sum one float64 chain in index order (mlp_rule.h: the
+//                                 rule per output and per row, host and device)
 //   snac_hip.hip    the C ABI of include/snac_hip.h and the dispatch: choose() decides kernel, size and form from one table of thresholds
 //                   (KNOBS), launch() calls the launcher choose() named
 //   snac_traj.hip   trajectory memory

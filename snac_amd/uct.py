@@ -63,6 +63,12 @@ reset() and advance() call fn on the B roots for the priors of the new roots.
     search.run(32)
     r, d = search.advance(search.best_actions())
 
+The network on the device: evaluator=DeviceMLP(net, env) (snac_amd/mlp.py; a Sequential of Linear and ReLU whose last output is the value
+as it is, no tanh) runs the network, its softmax / value head, the terminal mask and est += value as ONE launch per iteration
+(snac_mlp_uct_value_leaves; "Policy / value network on the device" in include/snac_hip.h) in place of fn's launches and the torch
+operations behind them, with float64 sums in a stated order: the same bytes on every run, and the bytes of
+evaluator=lambda o: mlp.policy_value(o), the generic path.  The parameters are read in place at every launch.
+
 Self-play: pick_moves() draws a move per tree from the root's visit counts (argmax, or in proportion to them: counter-RNG stream 3) and
 gives the visit distribution and the root value, the training targets of the network above; restart(mask) starts a new episode in the
 finished trees and leaves the others alone.  Neither synchronises with the host.  snac_amd/selfplay.py (SelfPlay) is the loop with a
@@ -137,6 +143,7 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _ptr
+from .mlp import DeviceMLP
 from .nodes import NodePool
 
 
@@ -300,6 +307,14 @@ class UCTSearch:
             self._root_obs_ptrs = (_ptr(P.records), P.rows, B, _ptr(self._root_rows), _ptr(self._root_obs))
             self._prior_args = (A, _ptr(self.stats), self.rows, S, _ptr(self._prior_rows), _ptr(self._priors), 0)
             self.noise_bad_rows = torch.zeros(1, dtype=torch.int32, device=dev)     # add_dirichlet_noise(): roots whose priors it refused
+            self._mlp = evaluator if isinstance(evaluator, DeviceMLP) else None
+            if self._mlp is not None:                                # the network on the device: _value_leaves() is one fused launch
+                mlp = self._mlp
+                if mlp.device != dev or mlp.num_actions != A or mlp.dims[0] != env.obs_dim:
+                    raise ValueError("the DeviceMLP must be on %s with %d inputs and num_actions = %d" % (dev, env.obs_dim, A))
+                self._leaves_args = (A, _ptr(self._obs), int(env.obs_dtype == torch.float64), S, _ptr(self._first_has), _ptr(self._first_idx),
+                                     _ptr(self._done), _ptr(self.stats), self.rows, _ptr(self._leaf), _ptr(self._priors), _ptr(self._value),
+                                     _ptr(self._est))
         self.q_bounds = None
         if q_normalise:                                              # the _norm entry points: the same arguments, then the bounds
             self.q_bounds = torch.empty((B, 2), dtype=torch.float64, device=dev)
@@ -664,6 +679,10 @@ class UCTSearch:
         self._value_leaves()
 
     def _value_leaves(self):
+        if self._mlp is not None:                                    # snac_mlp_uct_value_leaves: the network, its head and the lines below
+            mlp = self._mlp
+            _lib.check(self._lib.snac_mlp_uct_value_leaves(mlp._descriptor(), *self._leaves_args, _ptr(mlp.bad_rows), self.env._stream()))
+            return
         priors, value = self._call(self._obs, self.trees * self.paths)
         self._priors.copy_(priors)
         torch.index_select(self._done, 0, self._first_idx, out=self._term_new)       # the expander's done (a fresh leaf: another slot's)
