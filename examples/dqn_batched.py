@@ -29,6 +29,9 @@ mean comes back carrying its closed-form gradient, and with --prioritized the ne
 a host synchronisation.  --huber D: huber_loss(delta=D) instead of the squared error; --double: double DQN, the next action chosen by the
 online network.  With --distributional the cross-entropy comes from CategoricalSupport.loss on the raw logits (no log_softmax, no
 advanced index, no product and sum, and no backward pass through them), and its per-sample values are the new priorities.
+
+--device-rollout K: K epsilon-greedy ticks per update, collected by one fused launch (ReplayRing.collect_policy: a DeviceMLP over the
+Q-network's parameters acts inside the env launch) instead of one observe, forward, draw and append per tick.
 """
 import argparse
 import os
@@ -40,7 +43,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, CategoricalSupport, ReplayRing, TDLoss  # noqa: E402
+from snac_amd import BatchedDMPEnv, CategoricalSupport, DeviceMLP, ReplayRing, TDLoss  # noqa: E402
 
 
 class QNet(nn.Module):
@@ -55,14 +58,17 @@ class QNet(nn.Module):
 
 def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None,
         device_sampling=False, distributional=False, atoms=51, vmin=None, vmax=None, info=None, projection=None, device_loss=False, huber=None,
-        double=False):
+        double=False, device_rollout=None):
     """distributional: the C51 head and target (the module's docstring); vmin / vmax None: 0 and 5 / (1 - gamma).  info: an optional dict
     that receives the run's device counters ("bad_rows": the samples project() and the device loss zeroed; with prioritized also
     "priorities", a copy of the priority tree's leaves at the end).  device_loss: the DQN loss from TDLoss (the module's docstring), with
     huber: its delta, None for the squared error, and double: double DQN.  projection: a callable
     (p_next, ret, discount, p_select=) -> m in place of CategoricalSupport.project, for comparisons (tools/c51_time.py).
     device_sampling: the epsilon-greedy actions come from one launch per tick (BatchedDMPEnv.epsilon_greedy: counter-RNG stream 5,
-    independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax."""
+    independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax.  device_rollout: K, the ticks
+    collected per update by one fused launch (the module's docstring); not with distributional, whose actions need the expected values."""
+    if device_rollout is not None and (distributional or isinstance(device_rollout, bool) or not isinstance(device_rollout, int) or device_rollout < 1):
+        raise ValueError("device_rollout is a number of ticks >= 1, and not for distributional")
     if (huber is not None or double) and not device_loss:
         raise ValueError("huber and double belong to device_loss")
     if (huber is not None or double) and distributional:
@@ -90,20 +96,24 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     net, target = QNet(env.obs_dim, 400, heads).to(dev), QNet(env.obs_dim, 400, heads).to(dev)
     target.load_state_dict(net.state_dict())
     opt = torch.optim.Adam(net.parameters(), lr=lr)
+    mlp = DeviceMLP(net.body, None) if device_rollout else None    # the Q-network's parameters, read in place by every launch
     t0, losses, returns = time.time(), [], []
     for tick in range(ticks):
         eps = max(0.05, 1.0 - tick / (0.6 * ticks))
-        with torch.no_grad():
-            q_now = support.expected(dist(net, obs.float(), plan)) if distributional else net(obs.float(), plan)
-        if device_sampling:
-            actions = env.epsilon_greedy(q_now, eps)
+        if device_rollout:
+            ring.collect_policy(mlp, device_rollout, mode="eps_greedy", epsilon=eps)     # K ticks, recorded in the ring: one launch
         else:
-            greedy = q_now.argmax(dim=1)
-            explore = torch.rand(envs, device=dev) < eps
-            actions = torch.where(explore, torch.randint(0, env.num_actions, (envs,), device=dev), greedy).to(torch.int8)
-        ring.append(actions)                                       # one env tick, recorded in the ring (auto-reset)
-        obs = env.observe()
-        plan = env.input_plan().float()                            # resets change plans
+            with torch.no_grad():
+                q_now = support.expected(dist(net, obs.float(), plan)) if distributional else net(obs.float(), plan)
+            if device_sampling:
+                actions = env.epsilon_greedy(q_now, eps)
+            else:
+                greedy = q_now.argmax(dim=1)
+                explore = torch.rand(envs, device=dev) < eps
+                actions = torch.where(explore, torch.randint(0, env.num_actions, (envs,), device=dev), greedy).to(torch.int8)
+            ring.append(actions)                                   # one env tick, recorded in the ring (auto-reset)
+            obs = env.observe()
+            plan = env.input_plan().float()                        # resets change plans
         how = dict(prioritized=True, beta=beta) if prioritized else {}
         if n_step is not None:
             how.update(n_step=n_step, gamma=gamma)
@@ -194,6 +204,7 @@ if __name__ == "__main__":
     ap.add_argument("--device-loss", action="store_true", help="the DQN loss, its gradient and the new priorities from TDLoss (one call)")
     ap.add_argument("--huber", type=float, default=None, help="--device-loss: Huber's delta (default: the squared error)")
     ap.add_argument("--double", action="store_true", help="--device-loss: double DQN, the online network chooses the next action")
+    ap.add_argument("--device-rollout", type=int, default=None, metavar="K", help="collect K epsilon-greedy ticks per update in one fused launch")
     a = ap.parse_args()
     run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling, distributional=a.distributional,
-        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax, device_loss=a.device_loss, huber=a.huber, double=a.double)
+        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax, device_loss=a.device_loss, huber=a.huber, double=a.double, device_rollout=a.device_rollout)

@@ -9,7 +9,11 @@ With --device-loss the loss of a minibatch, its gradient with respect to the log
 call (PPOLoss: snac_ppo_loss) instead of the torch composition and autograd's pass back through it; --clip-vf then clips the value
 function as PPO2 does by default.
 
-    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]]
+With --device-rollout the actor-critic is one Sequential of Linear and ReLU with num_actions + 1 outputs (the logits and the value), a
+DeviceMLP over its parameters acts inside the env launch (RolloutBuffer.collect_policy: a horizon in one launch, two on a ring wrap) and
+gives the bootstrap value (one forward launch); the update trains the same parameters through autograd as before.
+
+    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]] [--device-rollout]
 """
 import argparse
 import os
@@ -21,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, PPOLoss, RolloutBuffer  # noqa: E402
+from snac_amd import BatchedDMPEnv, DeviceMLP, PPOLoss, RolloutBuffer  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -36,14 +40,29 @@ class ActorCritic(nn.Module):
         return self.policy(h), self.value(h).squeeze(1)
 
 
+class ActorCriticMLP(nn.Module):
+    """--device-rollout: the same shape with ReLU and one last layer of actions + 1 outputs, so that a DeviceMLP can run it."""
+
+    def __init__(self, obs_dim, plan_cells, actions, hidden=256):
+        super().__init__()
+        self.actions = actions
+        self.body = nn.Sequential(nn.Linear(obs_dim + plan_cells, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(),
+                                  nn.Linear(hidden, actions + 1))
+
+    def forward(self, obs, plan):
+        y = self.body(torch.cat([obs, plan.flatten(1)], dim=1))
+        return y[:, :self.actions], y[:, self.actions]
+
+
 def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, seed=1,
-        log=print, device_sampling=False, device_loss=False, clip_vf=None, info=None):
+        log=print, device_sampling=False, device_loss=False, clip_vf=None, info=None, device_rollout=False):
     """-> (the loss of every minibatch update, the mean episodic return after every iteration).  device_sampling: draw the actions and
     their log-probabilities with one launch per tick (RolloutBuffer.act_logits: counter-RNG stream 5, independent of the sharding and of
     torch's generator) instead of torch.distributions.  device_loss: the loss, its gradient and its statistics from PPOLoss (one call per
     minibatch) instead of the torch composition; clip_vf: with device_loss, the clip range of the value function (None: not clipped,
     as the composition).  info: a dict that receives the run's device counters with device_loss ("bad_rows": the samples PPOLoss
-    zeroed) and the statistics of the last minibatch ("stats")."""
+    zeroed) and the statistics of the last minibatch ("stats").  device_rollout: the horizon is collected by one fused launch with a DeviceMLP as
+    the actor-critic (the module's docstring); the draws are device_sampling's."""
     if clip_vf is not None and not device_loss:
         raise ValueError("clip_vf belongs to device_loss: the torch composition does not clip the value function")
     torch.manual_seed(seed)
@@ -51,12 +70,15 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
     dev = env.device
     env.reset()
     buf = RolloutBuffer(env, horizon, gamma, lam)
-    net = ActorCritic(env.obs_dim, 400, env.num_actions).to(dev)
+    net = (ActorCriticMLP if device_rollout else ActorCritic)(env.obs_dim, 400, env.num_actions).to(dev)
+    mlp = DeviceMLP(net.body, env) if device_rollout else None
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     ppo = PPOLoss(env, clip, -1.0 if clip_vf is None else clip_vf, vf_coef, ent_coef) if device_loss else None
     t0, losses, returns = time.time(), [], []
     for it in range(iterations):
-        for _ in range(horizon):
+        if device_rollout:
+            buf.collect_policy(mlp, horizon)                       # observe -> network -> draw -> step, the whole horizon in one launch
+        for _ in range(0 if device_rollout else horizon):
             with torch.no_grad():
                 logits, value = net(env.observe().float(), env.input_plan().float())     # resets change plans
                 if device_sampling:
@@ -66,7 +88,10 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
                 actions = dist.sample()
                 buf.act(actions.to(torch.int8), value, dist.log_prob(actions))           # one env tick, recorded in the ring (auto-reset)
         with torch.no_grad():
-            _, bootstrap = net(env.observe().float(), env.input_plan().float())
+            if device_rollout:
+                bootstrap = mlp.forward(torch.cat([env.observe().float(), env.input_plan().float().flatten(1)], dim=1))[:, env.num_actions]
+            else:
+                _, bootstrap = net(env.observe().float(), env.input_plan().float())
         buf.finish(bootstrap)                                      # advantages and returns of the horizon: one launch
         for mb in buf.minibatches(batch, epochs):                  # one gather launch each
             logits, value = net(mb["s"], mb["plan"])
@@ -107,5 +132,7 @@ if __name__ == "__main__":
     ap.add_argument("--device-sampling", action="store_true", help="draw the actions on the device from the counter RNG (act_logits)")
     ap.add_argument("--device-loss", action="store_true", help="the loss, its gradient and its statistics from one device call (PPOLoss)")
     ap.add_argument("--clip-vf", type=float, default=None, help="with --device-loss: clip the value function by this range, as PPO2 does")
+    ap.add_argument("--device-rollout", action="store_true", help="collect the horizon in one fused launch with a DeviceMLP actor-critic")
     a = ap.parse_args()
-    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling, device_loss=a.device_loss, clip_vf=a.clip_vf)
+    run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling, device_loss=a.device_loss, clip_vf=a.clip_vf,
+        device_rollout=a.device_rollout)

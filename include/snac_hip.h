@@ -823,6 +823,40 @@ int snac_mlp_uct_value_leaves(const snac_mlp* net, int32_t num_actions, const vo
                               const int32_t* first_idx, const uint8_t* done, const int32_t* stats, int32_t stats_rows, const int32_t* leaf,
                               float* priors, double* value, double* est, int32_t* bad_rows, void* stream);
 
+/* ---- Acting with the device network over a rollout (snac_amd/batched.py: rollout_policy; k_policy_roll.hip): T ticks of
+ * observe -> network -> draw -> step in ONE launch, the env state on chip from the first tick to the last.  The join of snac_rollout_rec
+ * (whose actions are the counter RNG's or the caller's) and snac_mlp_forward / snac_policy_act (one launch each per tick): a model-free
+ * actor's loop, or the greedy evaluation episodes of a trained network, without a launch between two ticks.  Nothing here is a new rule:
+ * every step is another section's, in this order.  N = desc->num_envs; env i, tick tau = t0 + j (uint32: it wraps), j = 0 .. T-1:
+ *   1. Reset.  If the env's header has SNAC_FLAG_NEED_RESET it starts a new episode exactly as snac_step(auto_reset = 1) does (the plan
+ *      row from counter-RNG stream 1 keyed by the episode, the episode counter, the grid emptied).
+ *   2. Input.  The canonical observation row that snac_observe would write now (obs_dim values of desc->obs_dtype), each rounded to
+ *      float32 as in "Policy / value network on the device".  If net->dim[0] == obs_dim + P (P = 30 for 1D, 400 for 2D / 3D) the row is
+ *      followed by the P cells of the env's plan, row-major (SNAC_TAIL_PLAN's values): what
+ *      torch.cat([obs.float(), env.input_plan().float().flatten(1)], 1) holds.  dim[0] must be obs_dim or obs_dim + P.
+ *   3. Network.  y = the outputs of layer L-1 by the rule of "Policy / value network on the device", unchanged.  dim[L] must be A or
+ *      A + 1, A the kind's num_actions.
+ *   4. Draw.  The rule of snac_policy_act, unchanged, on the scores y[0 .. A) with w = word(desc->seed, 5, desc->env_id_base + i, tau):
+ *      the same three modes, epsilon rules and bad-row rule (drawn as if every score were 0, one more in bad_rows[0]).
+ *      logp[j][i], entropy[j][i]: the categorical mode's, NULL in the other modes.  value[j][i] = y[A], the float32 as it is, finite or
+ *      not (it does not make a row bad here); NULL when dim[L] == A.
+ *   5. Step.  snac_step's tick tau with that action and the step size of counter-RNG stream 0 (step_size NULL).  The outputs are
+ *      snac_rollout_rec's: obs ([T][N][obs_dim] for SNAC_OBS_ALL, [N][obs_dim] for SNAC_OBS_LAST, untouched for SNAC_OBS_NONE;
+ *      SNAC_OBS_TILED: SNAC_ERR_UNSUPPORTED), reward float [T][N], done uint8 [T][N], and rec's actions, step_size, plan_idx and first
+ *      (1 on the first step of an episode), each [T][N].  Every output may be NULL, rec too.
+ * Afterwards the state arrays of st (headers, grids, episode counters, episodic sums) are what T calls of snac_step(auto_reset = 1)
+ * with those actions would have left.  Envs do not interact: a batch split into shards by env_id_base gives the same bytes.
+ * All three kinds, static and dynamic, desc->rules, both observation dtypes; the canonical layout only (a frame_value, obs_scalars or
+ * obs_tail that changes the row: SNAC_ERR_UNSUPPORTED).  Any N >= 1; nothing of the caller's is assumed wider-aligned than its element
+ * type, except the state arrays ("Alignment of the state arrays").  The weights are read in place during the launch.
+ * Checks, all before any HIP call: those of snac_rollout_rec on desc and st; net, its layers, dims, pointers and their alignment; T >= 1;
+ * mode, epsilon, epsilon_per_env, logp and entropy as snac_policy_act; obs_mode and obs; the canonical layout; dim[0] and dim[L] as
+ * above; value NULL when dim[L] == A; every array aligned as its element type.  One launch on `stream`, no host synchronisation.
+ * snac_last_kernel() names k_policy_rollout. */
+int snac_policy_rollout(const snac_env_desc* desc, const snac_state* st, const snac_mlp* net, int32_t T, uint32_t t0, int32_t mode,
+                        double epsilon, const float* epsilon_per_env, int obs_mode, void* obs, float* reward, uint8_t* done,
+                        const snac_rollout_record* rec, float* value, float* logp, float* entropy, int32_t* bad_rows, void* stream);
+
 /* ---- plan generators: the hindsight classes of the reference draw a fresh random plan per reset --
  * random triangles in 2D / 3D (create_plan, Env/2D/DMP_Env_2D_dynamic_hindsight_replay_usedata.py:37-59: three vertices from
  * np.random.randint(0, 20, size=3) twice, cv2.polylines (+ cv2.fillPoly when dense), redrawn until more than 50 (dense) / 20

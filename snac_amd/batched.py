@@ -981,6 +981,107 @@ class BatchedDMPEnv:
         self._policy_act(_lib.POLICY_EPS_GREEDY if epsilon > 0.0 else _lib.POLICY_GREEDY, scores, t, epsilon=float(epsilon), action=action)
         return action
 
+    # ---- acting with the device network over a rollout (include/snac_hip.h, "Acting with the device network over a rollout") --------------
+    POLICY_MODES = {"categorical": _lib.POLICY_CATEGORICAL, "greedy": _lib.POLICY_GREEDY, "eps_greedy": _lib.POLICY_EPS_GREEDY}
+    _ROLLOUT_POLICY_OUT = {"obs": None, "reward": torch.float32, "done": torch.uint8, "value": torch.float32, "logp": torch.float32,
+                           "entropy": torch.float32, "actions": torch.int8, "step_size": torch.int8, "plan_idx": torch.int16, "first": torch.uint8}
+
+    def _rollout_policy_plan(self, net, T, mode, epsilon, obs, want_value, want_logp, want_entropy, record, out):
+        """The argument checks of rollout_policy(), none of which touches a device -> (T, mode id, epsilon number, epsilon tensor or None,
+        obs mode id, the set of outputs asked for)."""
+        from .mlp import DeviceMLP
+
+        if not isinstance(net, DeviceMLP):
+            raise ValueError("net must be a DeviceMLP")
+        if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+            raise ValueError("T must be an integer >= 1")
+        if mode not in self.POLICY_MODES:
+            raise ValueError("mode must be 'categorical', 'greedy' or 'eps_greedy'")
+        D, A, P = self.base_obs_dim, self.num_actions, 30 if self.kind == 1 else 400
+        if self.obs_dim != D or self.frame_value != -1 or self.obs_scalars is not None:
+            raise ValueError("rollout_policy takes the canonical observation layout only")
+        if net.dims[0] not in (D, D + P):
+            raise ValueError("the network's input width must be obs_dim = %d, or obs_dim + the plan's %d cells, not %d" % (D, P, net.dims[0]))
+        if net.dims[-1] not in (A, A + 1):
+            raise ValueError("the network must give num_actions = %d outputs, or %d (the scores and the value), not %d" % (A, A + 1, net.dims[-1]))
+        has_value = net.dims[-1] == A + 1
+        if net.device != self.device:
+            raise ValueError("the network's parameters must be on the env's device, %s" % self.device)
+        eps_env = None
+        if torch.is_tensor(epsilon) or isinstance(epsilon, np.ndarray):
+            if mode != "eps_greedy":
+                raise ValueError("per-env epsilons belong to mode='eps_greedy'")
+            if tuple(epsilon.shape) != (self.num_envs,):
+                raise ValueError("epsilon must be a number or hold one value per env")
+            eps_env, epsilon = epsilon, 0.0
+        elif isinstance(epsilon, bool) or not isinstance(epsilon, (int, float)) or not 0.0 <= epsilon <= 1.0:
+            raise ValueError("epsilon must be a number in [0, 1] or a float32 [N] tensor")
+        if obs not in ("all", "last", None):
+            raise ValueError("obs must be 'all', 'last' or None")
+        for name, v in (("want_value", want_value), ("want_logp", want_logp)):
+            if v is not None and not isinstance(v, bool):
+                raise ValueError("%s must be None or a bool" % name)
+        if not isinstance(want_entropy, bool) or not isinstance(record, bool):
+            raise ValueError("want_entropy and record must be bools")
+        want_value = has_value if want_value is None else want_value
+        want_logp = mode == "categorical" if want_logp is None else want_logp
+        if want_value and not has_value:
+            raise ValueError("want_value needs a network with num_actions + 1 outputs")
+        if (want_logp or want_entropy) and mode != "categorical":
+            raise ValueError("logp and entropy are defined by mode='categorical' only")
+        if out is not None and (not isinstance(out, dict) or any(k not in self._ROLLOUT_POLICY_OUT for k in out)):
+            raise ValueError("out must be a dict with keys among %s" % sorted(self._ROLLOUT_POLICY_OUT))
+        names = {"reward", "done"} | ({"obs"} if obs else set()) | ({"value"} if want_value else set()) | ({"logp"} if want_logp else set())
+        names |= ({"entropy"} if want_entropy else set()) | ({"actions", "step_size", "plan_idx", "first"} if record else set())
+        names |= set(out or ())
+        if "obs" in names and not obs:
+            raise ValueError("out['obs'] needs obs='all' or 'last'")
+        if ("value" in names and not has_value) or (names & {"logp", "entropy"} and mode != "categorical"):
+            raise ValueError("out holds an output that this network / mode does not define")
+        return T, self.POLICY_MODES[mode], float(epsilon), eps_env, {"all": _lib.OBS_ALL, "last": _lib.OBS_LAST, None: _lib.OBS_NONE}[obs], names
+
+    def rollout_policy(self, net, T, mode="categorical", epsilon=0.0, obs="all", want_value=None, want_logp=None, want_entropy=False,
+                       record=False, out=None):
+        """T vector steps with auto-reset whose actions the DeviceMLP `net` chooses, in ONE launch (snac_policy_rollout): per tick the
+        envs' observation rows -- followed by their input_plan() cells when the network's input width is obs_dim + 30 / 400 -- go through
+        the network, sample_actions' / epsilon_greedy's rule draws from its first num_actions outputs (counter-RNG stream 5, keyed by the
+        tick), and the envs step as in rollout().  The network has num_actions outputs (a Q-network: DeviceMLP(module, None)) or
+        num_actions + 1 (the last one a value).  mode: "categorical", "greedy" or "eps_greedy" with epsilon a number in [0, 1] or a
+        float32 [N] tensor.  obs: "all" -> [T, N, D], "last" -> [N, D], None.  want_value (None: where the network has one), want_logp
+        (None: in the categorical mode), want_entropy, record (the action taken, the step size, the plan row and the
+        first-step-of-episode flag).  out: a dict of preallocated contiguous tensors for some of the outputs, by their names below.
+        Returns a dict of [T, N] tensors: reward float32, done bool, and where asked for obs, value / logp / entropy float32, actions /
+        step_size int8, plan_idx int16, first uint8.  Bad rows (a NaN or +inf score, every score -inf) are drawn as if all their scores
+        were 0 and counted in env.policy_bad_rows.  env.t advances by T; nothing waits."""
+        T, mode_id, eps, eps_env, obs_mode, names = self._rollout_policy_plan(net, T, mode, epsilon, obs, want_value, want_logp, want_entropy,
+                                                                                record, out)
+        if not self._was_reset:
+            raise _lib.SnacError("rollout_policy() before reset()")
+        N = self.num_envs
+        if eps_env is not None:
+            eps_env = torch.as_tensor(eps_env, device=self.device).detach().to(torch.float32).contiguous()
+        res = {}
+        for name in ("obs", "reward", "done", "value", "logp", "entropy", "actions", "step_size", "plan_idx", "first"):
+            if name not in names:
+                res[name] = None
+                continue
+            dtype = self._ROLLOUT_POLICY_OUT[name] or self.obs_dtype
+            shape = (T, N) if name != "obs" else ((T, N, self.obs_dim) if obs_mode == _lib.OBS_ALL else (N, self.obs_dim))
+            given = None if out is None else out.get(name)
+            res[name] = self._buf(given, shape, dtype, "out[%r]" % name) if given is not None else torch.empty(shape, dtype=dtype, device=self.device)
+        if getattr(self, "policy_bad_rows", None) is None:
+            self.policy_bad_rows = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        rec = _lib.RolloutRecord(*[None if res[k] is None else res[k].data_ptr() for k in ("actions", "step_size", "plan_idx", "first")])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.snac_policy_rollout(C.byref(self._desc), C.byref(self._state), net._descriptor(), T, self.t & 0xFFFFFFFF,
+                                                     mode_id, eps, _ptr(eps_env), obs_mode, _ptr(res["obs"]), _ptr(res["reward"]),
+                                                     _ptr(res["done"]), C.byref(rec), _ptr(res["value"]), _ptr(res["logp"]),
+                                                     _ptr(res["entropy"]), _ptr(self.policy_bad_rows), self._stream()))
+        self.t += T
+        res = {k: v for k, v in res.items() if v is not None}
+        res["done"] = res["done"].view(torch.bool)
+        return res
+
     def iou(self):
         """float64 [N]: env.iou() (1D, 3D) / the caller-side boolean IoU of the 2D scripts."""
         out = torch.empty((self.num_envs,), dtype=torch.float64, device=self.device)

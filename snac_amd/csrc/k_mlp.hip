@@ -8,6 +8,7 @@
 
 #include "snac_units.h"
 #include "mlp_rule.h"
+#include "mlp_dev.h"
 
 // k_mlp<A>: a block of 256 threads takes TR = 16 consecutive rows through every layer; the rows' activations stay in LDS from the input
 // to the head.  Thread (r, g) = (tid & 15, tid >> 4) owns row r and, in a pass over 64 outputs of a layer, the four outputs
@@ -29,11 +30,8 @@ namespace {
 
 using namespace snac_detail;
 using namespace snac_spec;
-
-constexpr int TR = 16, THREADS = 256, JT = 4, PASS = 64, KC = 32, WS = PASS + 4, AS = TR + 1, PRE = PASS * KC / THREADS;
-constexpr int BATCH = 8;                                             // inputs whose LDS reads are issued together
+using namespace snac_mlp_dev;                                        // mlp_dev.h: the shape's constants and the layer loop, shared with k_policy_roll.hip
 constexpr int ROW_WORDS = sizeof(snac_uct_node) / 4, TERMINAL_WORD = offsetof(snac_uct_node, terminal) / 4;
-static_assert(PRE * THREADS == PASS * KC && JT * (THREADS / TR) == PASS, "the tile is covered once by the prefetch and once by the chains");
 
 struct MlpArgs {
     snac_mlp net;
@@ -54,9 +52,9 @@ struct MlpArgs {
 
 template <int A>
 __global__ __launch_bounds__(THREADS) void k_mlp(const MlpArgs g) {
-    __shared__ float act_a[MLP_MAX_IN * AS];
-    __shared__ float act_b[MLP_MAX_HIDDEN * AS];
-    __shared__ __attribute__((aligned(16))) float wt[KC * WS];
+    __shared__ float act_a[ACT_A_WORDS];
+    __shared__ float act_b[ACT_B_WORDS];
+    __shared__ __attribute__((aligned(16))) float wt[WT_WORDS];
     const int tid = threadIdx.x, r = tid & (TR - 1), grp = tid >> 4;
     const long long row0 = (long long)blockIdx.x * TR;
     const int32_t rows = g.rows, L = g.net.layers;
@@ -68,75 +66,8 @@ __global__ __launch_bounds__(THREADS) void k_mlp(const MlpArgs g) {
         for (int i = r; i < K; i += TR) act_a[i * AS + grp] = mlp_input(g.x, f64, (size_t)row * K + i);
     }
 
-    for (int l = 0; l < L; ++l) {                                    // uniform throughout
-        const int K = g.net.dim[l], N = g.net.dim[l + 1];
-        const float* W = g.net.w[l];
-        const float* bias = g.net.b[l];
-        const float* in = (l & 1) ? act_b : act_a;
-        float* out = (l & 1) ? act_a : act_b;
-        const bool last = l == L - 1;
-        for (int jbase = 0; jbase < N; jbase += PASS) {
-            double acc[JT];
-#pragma unroll
-            for (int t = 0; t < JT; ++t) {
-                const int j = jbase + grp * JT + t;
-                acc[t] = j < N ? (double)bias[j] : 0.0;
-            }
-            float pre[PRE];
-            auto prefetch = [&](int k0) {                            // element e of the tile: input k0 + (e & 31) of output jbase + (e >> 5)
-#pragma unroll
-                for (int q = 0; q < PRE; ++q) {
-                    const int e = tid + q * THREADS, j = jbase + e / KC, k = k0 + (e & (KC - 1));
-                    pre[q] = (j < N && k < K) ? W[(size_t)j * K + k] : 0.0f;
-                }
-            };
-            prefetch(0);
-            for (int k0 = 0; k0 < K; k0 += KC) {
-                __syncthreads();                                     // the tile's readers are done; the first of a layer: its inputs are written
-#pragma unroll
-                for (int q = 0; q < PRE; ++q) {
-                    const int e = tid + q * THREADS;
-                    wt[(e & (KC - 1)) * WS + e / KC] = pre[q];
-                }
-                __syncthreads();
-                if (k0 + KC < K) prefetch(k0 + KC);
-                const int kc = K - k0 < KC ? K - k0 : KC;
-                auto steps = [&](int i) {
-                    const float xv = in[(k0 + i) * AS + r];
-                    const float* wrow = wt + i * WS + grp * JT;
-#pragma unroll
-                    for (int t = 0; t < JT; ++t) acc[t] = mlp_step(acc[t], (double)wrow[t], xv);
-                };
-                if (kc == KC) {                                      // a whole tile: the LDS reads of BATCH inputs issued together, then their steps
-#pragma unroll
-                    for (int i0 = 0; i0 < KC; i0 += BATCH) {
-                        float xv[BATCH];
-                        float w[BATCH][JT];
-#pragma unroll
-                        for (int i = 0; i < BATCH; ++i) {
-                            xv[i] = in[(k0 + i0 + i) * AS + r];
-#pragma unroll
-                            for (int t = 0; t < JT; ++t) w[i][t] = wt[(i0 + i) * WS + grp * JT + t];
-                        }
-#pragma unroll
-                        for (int i = 0; i < BATCH; ++i) {
-#pragma unroll
-                            for (int t = 0; t < JT; ++t) acc[t] = mlp_step(acc[t], (double)w[i][t], xv[i]);
-                        }
-                    }
-                } else {
-                    for (int i = 0; i < kc; ++i) steps(i);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < JT; ++t) {                           // outputs past N ran on zero weights and are dropped
-                const int j = jbase + grp * JT + t;
-                if (j < N) out[j * AS + r] = last ? mlp_last(acc[t]) : mlp_hidden(acc[t]);
-            }
-        }
-    }
-    __syncthreads();
-    const float* res = (L & 1) ? act_b : act_a;                      // where the last layer wrote
+    mlp_layers(g.net, act_a, act_b, wt, tid);
+    const float* res = mlp_result(L, act_a, act_b);
     const int N = g.net.dim[L];
     if (g.y) {                                                       // the block's rows are one contiguous span of y
         const long long left = rows - row0;
@@ -172,14 +103,9 @@ __global__ __launch_bounds__(THREADS) void k_mlp(const MlpArgs g) {
 
 int aligned(const void* p, size_t n, const char* msg) { return ((uintptr_t)p % n) ? fail(SNAC_ERR_ARG, msg) : SNAC_OK; }
 
-// the checks of all three entry points: the network, the input rows and their alignment
+// the checks of all three entry points: the network (mlp_net_check, below the namespace), the input rows and their alignment
 int mlp_check(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows) {
-    if (!net) return fail(SNAC_ERR_ARG, "null net");
-    if (const char* why = mlp_dims_refusal(net->layers, net->dim)) return fail(SNAC_ERR_ARG, why);
-    for (int l = 0; l < net->layers; ++l) {
-        if (!net->w[l] || !net->b[l]) return fail(SNAC_ERR_ARG, "null weights / bias of a layer");
-        if ((uintptr_t)net->w[l] % 4 || (uintptr_t)net->b[l] % 4) return fail(SNAC_ERR_ARG, "weights and biases must be 4-byte aligned");
-    }
+    if (int rc = mlp_net_check(net)) return rc;
     if (!x) return fail(SNAC_ERR_ARG, "null x");
     if (x_is_f64 != 0 && x_is_f64 != 1) return fail(SNAC_ERR_ARG, "x_is_f64 must be 0 or 1");
     if ((uintptr_t)x % (x_is_f64 ? 8 : 4)) return fail(SNAC_ERR_ARG, "x must be aligned as its element type");
@@ -205,6 +131,17 @@ int launch_mlp(const MlpArgs& g, const char* kernel, const char* entry, void* st
 }
 
 }  // namespace
+
+// the network's own checks (snac_units.h): its layers, every dim, its pointers and their alignment
+int snac_detail::mlp_net_check(const snac_mlp* net) {
+    if (!net) return fail(SNAC_ERR_ARG, "null net");
+    if (const char* why = snac_spec::mlp_dims_refusal(net->layers, net->dim)) return fail(SNAC_ERR_ARG, why);
+    for (int l = 0; l < net->layers; ++l) {
+        if (!net->w[l] || !net->b[l]) return fail(SNAC_ERR_ARG, "null weights / bias of a layer");
+        if ((uintptr_t)net->w[l] % 4 || (uintptr_t)net->b[l] % 4) return fail(SNAC_ERR_ARG, "weights and biases must be 4-byte aligned");
+    }
+    return SNAC_OK;
+}
 
 extern "C" int snac_mlp_forward(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows, float* y, void* stream) {
     using namespace snac_detail;

@@ -1,11 +1,12 @@
 // k_policy.hip -- snac_policy_act: one action per env from a row of A float32 scores (categorical, greedy, epsilon-greedy), with the
 // categorical draw's log-probability and entropy.  include/snac_hip.h, "Acting from a policy", has the rule; softmax_rule.h states its softmax, for this kernel and for
-// the rules of k_soft.hip and k_ppo.hip.
+// the rules of k_soft.hip and k_ppo.hip; policy_dev.h the draw of a row, for this kernel and k_policy_roll.hip.
 #include <cmath>
 #include <cstddef>
 
 #include "snac_units.h"
 #include "softmax_rule.h"
+#include "policy_dev.h"
 
 // lane = env: the outputs of a wave are coalesced spans of action / logp / entropy, and nothing crosses lanes.  The scores are read as A
 // strided dword loads per lane, all issued before the first use.  A wave's rows are one contiguous span of 64 * A floats (768 / 1280 /
@@ -17,6 +18,7 @@ namespace {
 
 using namespace snac_detail;
 using namespace snac_spec;
+using namespace snac_policy_dev;
 
 struct PolicyArgs {
     int32_t n;
@@ -43,54 +45,11 @@ __global__ __launch_bounds__(64) void k_policy_act(const PolicyArgs g) {
     if (MODE == SNAC_POLICY_EPS_GREEDY && g.eps_env) eps = g.eps_env[i];
     const uint32_t w = rng_word(env_keys(g.key, (uint64_t)(g.env_id_base + i)), g.t);
 
-    float m;
-    if (softmax_scan(s, m)) {                                        // a bad row: drawn as if every score were 0
-        m = 0.0f;
-#pragma unroll
-        for (int a = 0; a < A; ++a) s[a] = 0.0f;
-        if (g.bad_rows) atomicAdd(g.bad_rows, 1);
-    }
-    int greedy = A - 1;
-#pragma unroll
-    for (int a = A - 2; a >= 0; --a) greedy = s[a] == m ? a : greedy;    // the lowest index of the largest score
-
-    int action = greedy;
-    if (MODE == SNAC_POLICY_EPS_GREEDY) {
-        const double v = floor((g.eps_env ? (double)eps : g.epsilon) * 65536.0);
-        const uint32_t eps_fx = v >= 65536.0 ? 65536u : v > 0.0 ? (uint32_t)v : 0u;
-        if ((w >> 16) < eps_fx) action = (int)(((w & 0xffffu) * (uint32_t)A) >> 16);
-    }
-    if (MODE == SNAC_POLICY_CATEGORICAL) {
-        double x[A], e[A];
-        softmax_terms(s, m, x, e);
-        uint32_t wt[A], total = 0;                                   // total <= 8 * 2^28 = 2^31
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-            wt[a] = (uint32_t)(uint64_t)floor(e[a] * 268435456.0);   // a power of two: the product is exact
-            total += wt[a];
-        }
-        const uint32_t u = __umulhi(w, total);                       // ((uint64)w * total) >> 32, below total
-        uint32_t cum = 0;
-        bool found = false;
-        double xa = x[A - 1];
-        action = A - 1;
-#pragma unroll
-        for (int a = 0; a < A; ++a) {
-            cum += wt[a];
-            const bool hit = !found && cum > u;
-            action = hit ? a : action;
-            xa = hit ? x[a] : xa;
-            found |= hit;
-        }
-        if (g.logp || g.entropy) {                                   // uniform: kernel arguments
-            const SoftmaxSums sm = softmax_sums(x, e);
-            if (g.logp) {
-#pragma clang fp contract(off)
-                g.logp[i] = (float)(xa - sm.L);
-            }
-            if (g.entropy) g.entropy[i] = (float)softmax_entropy(sm);
-        }
-    }
+    const PolicyDraw d = policy_draw<A, MODE>(s, w, g.eps_env ? (double)eps : g.epsilon, g.logp != nullptr, g.entropy != nullptr);   // policy_dev.h
+    if (d.bad && g.bad_rows) atomicAdd(g.bad_rows, 1);
+    if (g.logp) g.logp[i] = d.logp;                                  // uniform: kernel arguments; NULL outside the categorical mode
+    if (g.entropy) g.entropy[i] = d.entropy;
+    const int action = d.action;
     if (g.action) g.action[i] = (int8_t)action;
 }
 

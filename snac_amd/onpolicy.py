@@ -76,6 +76,17 @@ class RolloutBuffer:
         self.collected += 1
         return self._actions
 
+    def collect_policy(self, net, T):
+        """T act_logits() ticks with the DeviceMLP `net` as actor-critic, in at most two launches (ReplayRing.collect_policy, the
+        categorical mode): the network takes the envs' observation rows (and their input_plan() cells, by its input width), its first
+        num_actions outputs are the logits and its last one the value; `value` and `logp` go straight into the written slots' rows."""
+        from .mlp import DeviceMLP
+
+        if not isinstance(net, DeviceMLP) or net.dims[-1] != self.env.num_actions + 1:
+            raise ValueError("collect_policy needs an actor-critic: a network with num_actions + 1 = %d outputs" % (self.env.num_actions + 1))
+        self.ring.collect_policy(net, T, mode="categorical", extra=dict(value=self.value, logp=self.logp))
+        self.collected += T
+
     def span(self):
         """(first, count): the newest `horizon` slots, oldest first, as snac_gae takes them."""
         return (self.ring.head - self.horizon) % self.ring.cap, self.horizon

@@ -189,6 +189,37 @@ class ReplayRing:
             self.tree.fill(self.head * self.env.num_envs, self.env.num_envs, 0.0)
         self._env_t = self.env.t
 
+    def collect_policy(self, net, T, mode="eps_greedy", epsilon=0.0, extra=None):
+        """collect() with the actions from the DeviceMLP `net` (BatchedDMPEnv.rollout_policy: observe -> network -> draw -> step per tick,
+        inside the launch): T vector steps appended in at most two launches (ring wrap), priorities filled as collect() does.  mode,
+        epsilon: rollout_policy's.  extra: {"value" | "logp" | "entropy": a float32 [cap, N] tensor} whose rows of the written slots
+        receive that output (RolloutBuffer.collect_policy).  layout "tiled" is not a layout of the fused launch: ValueError."""
+        if self.tiled:
+            raise ValueError("collect_policy needs layout='ticks': the fused launch writes [T, N, D] rows")
+        if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+            raise ValueError("T must be an integer >= 1")
+        if T > self.cap:
+            raise ValueError("T exceeds the ring capacity")
+        if self.env.t != self._env_t:
+            raise _lib.SnacError("the envs were stepped outside the ring since the last collect(): the predecessor rows no longer "
+                                 "match (attach a new ReplayRing)")
+        done_ticks = 0
+        while done_ticks < T:
+            n = min(T - done_ticks, self.cap - self.head)
+            sl = slice(self.head, self.head + n)
+            out = dict(obs=self.obs[sl], reward=self.reward[sl], done=self.done[sl], actions=self.action[sl], step_size=self.step_size[sl],
+                       plan_idx=self.plan_idx[sl], first=self.first[sl])
+            out.update({name: t[sl] for name, t in (extra or {}).items()})
+            self.env.rollout_policy(net, n, mode=mode, epsilon=epsilon, obs="all", want_value=False, want_logp=False, out=out)
+            if self.tree is not None:                                # the span just written: the largest priority seen so far
+                self.tree.fill(self.head * self.env.num_envs, n * self.env.num_envs)
+            self.head = (self.head + n) % self.cap
+            self.ticks += n
+            done_ticks += n
+        if self.tree is not None and self.ticks >= self.cap:         # wrapped: slot `head` survives only as a predecessor
+            self.tree.fill(self.head * self.env.num_envs, self.env.num_envs, 0.0)
+        self._env_t = self.env.t
+
     def append(self, actions, step_size=None):
         """One vector step with the caller's actions ([N], e.g. an epsilon-greedy policy's), appended to the ring."""
         actions = torch.as_tensor(actions, device=self.env.device)
