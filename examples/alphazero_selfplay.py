@@ -35,6 +35,8 @@ neither on how the envs are sharded nor on a generator's state.
 --device-evaluator: the network that guides the search runs as one launch of the package's own (DeviceMLP: float64 sums in index order,
 the parameters read in place), and the search values its leaves in that same launch, in place of the torch evaluator below; training
 goes through torch autograd as before.
+--device-backward: the training step's pass through the network and the gradients of its weights come from the device as well
+(DeviceMLP.train_forward: float64 chains in a stated order); the optimiser stays torch's.
 """
 import argparse
 import os
@@ -49,7 +51,8 @@ from snac_amd import BatchedDMPEnv, DeviceMLP, SearchLoss, SelfPlay, UCTSearch  
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
           gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4, device_loss=False, huber=None,
-          vf_coef=1.0, info=None, dirichlet=None, noise_eps=0.25, temperature=None, counter_noise=False, device_evaluator=False):
+          vf_coef=1.0, info=None, dirichlet=None, noise_eps=0.25, temperature=None, counter_noise=False, device_evaluator=False,
+          device_backward=False):
     """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
     SelfPlay).  info: a dict that receives bad_rows and the last step's statistics of the device loss, and evaluator_bad_rows of the
     device evaluator."""
@@ -69,6 +72,9 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
 
     if device_evaluator:                                             # the same network, read in place by one launch per evaluation
         evaluator = DeviceMLP(net, env)
+    trainer = None
+    if device_backward:                                              # refused here if the network is not one a DeviceMLP runs
+        trainer = evaluator if device_evaluator else DeviceMLP(net, env)
 
     def noise(priors):                                               # exploration at the roots: the caller's (here: a uniform share)
         return 0.75 * priors + 0.25 / A
@@ -100,7 +106,7 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
             play.reanalyse(again, iterations, **(dict(prioritized=True) if prioritized else {}))
         play.targets(td_steps=td_steps)
         b = play.sample(batch, **(dict(prioritized=True, beta=per_beta) if prioritized else {}))
-        y = net(b["obs"])
+        y = trainer.train_forward(b["obs"]) if device_backward else net(b["obs"])
         if device_loss:                                              # both heads as contiguous tensors; pi, z and the weights are read from b
             loss, _, priority = search_loss.loss(y[:, :A].contiguous(), y[:, A].contiguous(), b, want_per_sample=True)
             if prioritized:
@@ -150,6 +156,7 @@ def main():
     ap.add_argument("--temperature", type=float, default=None, metavar="T", help="draw the sampled moves in proportion to N ** (1 / T) (PUCT)")
     ap.add_argument("--counter-noise", action="store_true", help="with --gumbel M: the Gumbel noise from the counter RNG")
     ap.add_argument("--device-evaluator", action="store_true", help="the search's network as one device launch (DeviceMLP), fused into the search")
+    ap.add_argument("--device-backward", action="store_true", help="the training step's forward pass and weight gradients from the device (DeviceMLP)")
     args = ap.parse_args()
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
@@ -165,7 +172,8 @@ def main():
                          gumbel_interior=args.gumbel_interior, reanalyse=args.reanalyse, td_steps=args.td_steps,
                          prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta, device_loss=args.device_loss,
                          huber=args.huber, vf_coef=args.vf_coef, dirichlet=args.dirichlet, noise_eps=args.noise_eps, temperature=args.temperature,
-                         counter_noise=args.counter_noise, device_evaluator=args.device_evaluator)
+                         counter_noise=args.counter_noise, device_evaluator=args.device_evaluator,
+                         device_backward=args.device_backward)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     if args.reanalyse:
         print("entries reanalysed: %d" % int(play.refreshed.sum()))

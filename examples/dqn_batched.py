@@ -32,6 +32,10 @@ advanced index, no product and sum, and no backward pass through them), and its 
 
 --device-rollout K: K epsilon-greedy ticks per update, collected by one fused launch (ReplayRing.collect_policy: a DeviceMLP over the
 Q-network's parameters acts inside the env launch) instead of one observe, forward, draw and append per tick.
+
+--device-backward: the online network's pass of the update and the gradients of its weights come from the device (DeviceMLP.train_forward:
+one forward launch, three for the backward pass, float64 chains in a stated order) instead of torch's modules and autograd's pass back
+through them; the optimiser stays torch's.  Not with --distributional.
 """
 import argparse
 import os
@@ -58,7 +62,7 @@ class QNet(nn.Module):
 
 def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None,
         device_sampling=False, distributional=False, atoms=51, vmin=None, vmax=None, info=None, projection=None, device_loss=False, huber=None,
-        double=False, device_rollout=None):
+        double=False, device_rollout=None, device_backward=False):
     """distributional: the C51 head and target (the module's docstring); vmin / vmax None: 0 and 5 / (1 - gamma).  info: an optional dict
     that receives the run's device counters ("bad_rows": the samples project() and the device loss zeroed; with prioritized also
     "priorities", a copy of the priority tree's leaves at the end).  device_loss: the DQN loss from TDLoss (the module's docstring), with
@@ -66,7 +70,11 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     (p_next, ret, discount, p_select=) -> m in place of CategoricalSupport.project, for comparisons (tools/c51_time.py).
     device_sampling: the epsilon-greedy actions come from one launch per tick (BatchedDMPEnv.epsilon_greedy: counter-RNG stream 5,
     independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax.  device_rollout: K, the ticks
-    collected per update by one fused launch (the module's docstring); not with distributional, whose actions need the expected values."""
+    collected per update by one fused launch (the module's docstring); not with distributional, whose actions need the expected values.
+    device_backward: the online network's pass of the update and its weight gradients come from the device (DeviceMLP.train_forward: the
+    module's docstring); not with distributional, whose head is wider than a DeviceMLP's 64 outputs."""
+    if device_backward and distributional:
+        raise ValueError("device_backward is not for distributional: its head of actions * atoms outputs is wider than a DeviceMLP runs")
     if device_rollout is not None and (distributional or isinstance(device_rollout, bool) or not isinstance(device_rollout, int) or device_rollout < 1):
         raise ValueError("device_rollout is a number of ticks >= 1, and not for distributional")
     if (huber is not None or double) and not device_loss:
@@ -96,7 +104,12 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     net, target = QNet(env.obs_dim, 400, heads).to(dev), QNet(env.obs_dim, 400, heads).to(dev)
     target.load_state_dict(net.state_dict())
     opt = torch.optim.Adam(net.parameters(), lr=lr)
-    mlp = DeviceMLP(net.body, None) if device_rollout else None    # the Q-network's parameters, read in place by every launch
+    mlp = DeviceMLP(net.body, None) if device_rollout or device_backward else None     # the Q-network's parameters, read in place by every launch
+
+    def online(s, pl):                                             # the Q-values the loss differentiates
+        if device_backward:                                        # forward and backward on the device: float64 chains in a stated order
+            return mlp.train_forward(torch.cat([s, pl.flatten(1)], dim=1))
+        return net(s, pl)
     t0, losses, returns = time.time(), [], []
     for tick in range(ticks):
         eps = max(0.05, 1.0 - tick / (0.6 * ticks))
@@ -146,7 +159,7 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
                 disc = (gamma * (~mb["done"]).float() if n_step is None else mb["discount"].float()).contiguous()
                 q_next = target(mb["s_next"], mb["plan"])
                 q_select = net(mb["s_next"], mb["plan"]) if double else None
-            out = td_loss.loss(net(mb["s"], mb["plan"]), mb["action"], q_next=q_next, ret=ret, discount=disc, q_select=q_select,
+            out = td_loss.loss(online(mb["s"], mb["plan"]), mb["action"], q_next=q_next, ret=ret, discount=disc, q_select=q_select,
                                weight=mb["weight"] if prioritized else None, want_per_sample=prioritized)
             if prioritized:
                 loss = out[0]
@@ -160,7 +173,7 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
                     y = mb["reward"] + gamma * q_next * (~mb["done"]).float()
                 else:                                              # the plan does not change inside an episode: step 0's serves s_next
                     y = mb["return"] + mb["discount"] * q_next
-            q = net(mb["s"], mb["plan"]).gather(1, mb["action"][:, None]).squeeze(1)
+            q = online(mb["s"], mb["plan"]).gather(1, mb["action"][:, None]).squeeze(1)
             if prioritized:
                 td = q - y
                 loss = (mb["weight"] * td ** 2).mean()
@@ -205,6 +218,10 @@ if __name__ == "__main__":
     ap.add_argument("--huber", type=float, default=None, help="--device-loss: Huber's delta (default: the squared error)")
     ap.add_argument("--double", action="store_true", help="--device-loss: double DQN, the online network chooses the next action")
     ap.add_argument("--device-rollout", type=int, default=None, metavar="K", help="collect K epsilon-greedy ticks per update in one fused launch")
+    ap.add_argument("--device-backward", action="store_true", help="the update's forward pass and weight gradients from the device (DeviceMLP.train_forward)")
     a = ap.parse_args()
+    if a.device_backward and a.distributional:
+        ap.error("--device-backward is not for --distributional")
     run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling, distributional=a.distributional,
-        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax, device_loss=a.device_loss, huber=a.huber, double=a.double, device_rollout=a.device_rollout)
+        atoms=a.atoms, vmin=a.vmin, vmax=a.vmax, device_loss=a.device_loss, huber=a.huber, double=a.double, device_rollout=a.device_rollout,
+        device_backward=a.device_backward)

@@ -13,7 +13,11 @@ With --device-rollout the actor-critic is one Sequential of Linear and ReLU with
 DeviceMLP over its parameters acts inside the env launch (RolloutBuffer.collect_policy: a horizon in one launch, two on a ring wrap) and
 gives the bootstrap value (one forward launch); the update trains the same parameters through autograd as before.
 
-    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]] [--device-rollout]
+With --device-backward (which needs --device-rollout's network) the update's forward pass and the gradients of the weights come from the
+device too (DeviceMLP.train_forward: float64 chains in a stated order, three launches for the backward pass); the optimiser and the
+gradient clip stay torch's.
+
+    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]] [--device-rollout [--device-backward]]
 """
 import argparse
 import os
@@ -55,14 +59,18 @@ class ActorCriticMLP(nn.Module):
 
 
 def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, seed=1,
-        log=print, device_sampling=False, device_loss=False, clip_vf=None, info=None, device_rollout=False):
+        log=print, device_sampling=False, device_loss=False, clip_vf=None, info=None, device_rollout=False,
+        device_backward=False):
     """-> (the loss of every minibatch update, the mean episodic return after every iteration).  device_sampling: draw the actions and
     their log-probabilities with one launch per tick (RolloutBuffer.act_logits: counter-RNG stream 5, independent of the sharding and of
     torch's generator) instead of torch.distributions.  device_loss: the loss, its gradient and its statistics from PPOLoss (one call per
     minibatch) instead of the torch composition; clip_vf: with device_loss, the clip range of the value function (None: not clipped,
     as the composition).  info: a dict that receives the run's device counters with device_loss ("bad_rows": the samples PPOLoss
     zeroed) and the statistics of the last minibatch ("stats").  device_rollout: the horizon is collected by one fused launch with a DeviceMLP as
-    the actor-critic (the module's docstring); the draws are device_sampling's."""
+    the actor-critic (the module's docstring); the draws are device_sampling's.  device_backward: with device_rollout, the update's pass
+    through the network and its weight gradients are the device's (DeviceMLP.train_forward)."""
+    if device_backward and not device_rollout:
+        raise ValueError("device_backward needs device_rollout: the actor-critic a DeviceMLP can run")
     if clip_vf is not None and not device_loss:
         raise ValueError("clip_vf belongs to device_loss: the torch composition does not clip the value function")
     torch.manual_seed(seed)
@@ -94,7 +102,11 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
                 _, bootstrap = net(env.observe().float(), env.input_plan().float())
         buf.finish(bootstrap)                                      # advantages and returns of the horizon: one launch
         for mb in buf.minibatches(batch, epochs):                  # one gather launch each
-            logits, value = net(mb["s"], mb["plan"])
+            if device_backward:
+                y = mlp.train_forward(torch.cat([mb["s"], mb["plan"].flatten(1)], dim=1))
+                logits, value = y[:, :env.num_actions].contiguous(), y[:, env.num_actions].contiguous()     # what PPOLoss reads
+            else:
+                logits, value = net(mb["s"], mb["plan"])
             if device_loss:
                 loss = ppo.loss(logits, value, mb)                 # the mean loss, carrying its closed-form gradient
             else:
@@ -133,6 +145,9 @@ if __name__ == "__main__":
     ap.add_argument("--device-loss", action="store_true", help="the loss, its gradient and its statistics from one device call (PPOLoss)")
     ap.add_argument("--clip-vf", type=float, default=None, help="with --device-loss: clip the value function by this range, as PPO2 does")
     ap.add_argument("--device-rollout", action="store_true", help="collect the horizon in one fused launch with a DeviceMLP actor-critic")
+    ap.add_argument("--device-backward", action="store_true", help="with --device-rollout: the update's forward pass and weight gradients from the device")
     a = ap.parse_args()
+    if a.device_backward and not a.device_rollout:
+        ap.error("--device-backward needs --device-rollout")
     run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling, device_loss=a.device_loss, clip_vf=a.clip_vf,
-        device_rollout=a.device_rollout)
+        device_rollout=a.device_rollout, device_backward=a.device_backward)

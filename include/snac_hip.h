@@ -772,7 +772,7 @@ int snac_search_loss(int32_t B, int32_t num_actions, const float* logits, const 
 /* ---- Policy / value network on the device (snac_amd/mlp.py: DeviceMLP; k_mlp.hip, mlp_rule.h): the small MLP that guides the PUCT
  * search -- an observation row through one to four dense layers, ReLU between them, A + 1 outputs: the logits of the priors and the
  * value -- as ONE launch, with its softmax / value head and, in snac_mlp_uct_value_leaves, with the search's "value the leaves" step
- * behind it.  Inference only: training goes through the caller's autograd.  The weights are read in place, at every launch, from the
+ * behind it.  The gradients of its weights are the next section's ("Backward pass of the device network").  The weights are read in place, at every launch, from the
  * arrays the network descriptor points to (torch.nn.Linear's parameters as they lie in memory): an update enqueued on the stream before a
  * launch is seen by it, and nothing is copied or kept between launches.
  *
@@ -822,6 +822,52 @@ int snac_mlp_policy_value(const snac_mlp* net, int32_t num_actions, const void* 
 int snac_mlp_uct_value_leaves(const snac_mlp* net, int32_t num_actions, const void* obs, int obs_is_f64, int32_t S, const uint8_t* first_has,
                               const int32_t* first_idx, const uint8_t* done, const int32_t* stats, int32_t stats_rows, const int32_t* leaf,
                               float* priors, double* value, double* est, int32_t* bad_rows, void* stream);
+
+/* ---- Backward pass of the device network (snac_amd/mlp.py: DeviceMLP.backward, train_forward; k_mlp_grad.hip, mlp_grad_rule.h): from
+ * the gradient of a scalar loss to the network's outputs to its gradient to every weight and bias, by float64 chains over exact products
+ * in a stated order, as the forward rule's: the same inputs give the same bytes on every run.
+ *
+ * Notation.  The network is snac_mlp as above; layer l (0 .. L-1) maps h_l (width d_l = dim[l]) to h_{l+1} with W_l [d_{l+1}][d_l] and
+ * b_l.  h_0 is the input row rounded to float32; h_1 .. h_L are the forward rule's own float32 activations, bit for bit -- the launch
+ * sequence recomputes them and keeps nothing from an earlier forward call.  grad_y: float32 [rows][d_L], contiguous, 4-byte aligned: the
+ * gradient to the outputs as the loss kernels write it, already divided by the batch size.
+ * Per row b, from the top down:
+ *     delta_L[k] = grad_y[b][k], as it is
+ *     for l = L-1, L-2, .., 1 and every unit i of h_l:
+ *         acc = 0.0;   for k = 0, 1, .., d_{l+1}-1 in that order:  acc = acc + (double)W_l[k][i] * (double)delta_{l+1}[k]
+ *         delta_l[i] = h_l[i] <= 0.0f ? 0.0f : (float)acc
+ *   The product of two float32 values is exact in float64, so a fused multiply-add and a multiply followed by an add give the same
+ *   bits.  The chain of one unit is never split or re-associated.  The test h <= 0 is torch's threshold_backward: a unit cut to +0.0 or
+ *   left at -0.0 passes nothing, a NaN activation passes acc.  delta_l is rounded to float32, so that the products below are exact too.
+ *   delta_0, the gradient to the input, is not computed.
+ * Over the batch, for every weight W_l[j][i] and bias b_l[j], with C = SNAC_MLP_GRAD_CHUNK: the rows are cut into chunks c = 0, 1, ..;
+ * chunk c holds the rows [c C, min((c + 1) C, rows)).
+ *     part_c = 0.0;   for b ascending in chunk c:  part_c = part_c + (double)delta_{l+1}[b][j] * (double)h_l[b][i]
+ *                                         (a bias:  part_c = part_c + (double)delta_{l+1}[b][j])
+ *     total = 0.0;    for c ascending:  total = total + part_c
+ *     accumulate == 0:  g = (float)total          accumulate == 1:  g = (float)((double)g_old + total)
+ *   The two-level association is part of the rule and shows in the bits.  How chunks, outputs and rows are mapped to blocks and lanes
+ *   is free and cannot be seen in the result.  No float atomics.
+ * Non-finite values.  Nothing is screened and there is no bad_rows: a non-finite grad_y or activation propagates as IEEE arithmetic says,
+ * 0 * inf = NaN included.  (The loss kernels already zero the gradients of their bad samples.)
+ * The result.  grad: one contiguous float32 array of P = sum over l of d_{l+1} (d_l + 1) values, 4-byte aligned: layer 0's weights
+ * ([d_1][d_0] row-major), then layer 0's bias, then layer 1's weights, and so on.
+ *
+ * snac_mlp_backward_work_bytes   host only: the bytes of workspace a call needs,
+ *     8 * chunks * P  +  4 * rows * 2 * (d_1 + .. + d_{L-1})        chunks = ceil(rows / C)
+ *   the float64 partials of every parameter for every chunk, then the float32 hidden activations h_1 .. h_{L-1} and deltas
+ *   delta_1 .. delta_{L-1} of every row (h_0 is read from x and delta_L from grad_y, where they lie).  A refused network (the limits of
+ *   every dim, as above; its pointers are not looked at) or rows < 1: -1, with snac_last_error set.
+ * snac_mlp_backward   work: the caller's buffer, 8-byte aligned, of work_bytes >= the size above; its contents before the call do not
+ *   matter, and no byte past that size is written.  Checks, all before any HIP call: the network and x, x_is_f64 and rows as in the
+ *   section above; grad_y and grad non-null and 4-byte aligned; accumulate 0 or 1; work non-null and 8-byte aligned; work_bytes large
+ *   enough.  Three launches (two for L = 1) on `stream`, no host synchronisation; they read the inputs and the weights only and write
+ *   only grad and work.  Each launch's error is looked at before the next.  snac_last_kernel() names
+ *   the last kernel launched: k_mlp_grad_reduce, the last of the sequence, after a call that succeeded. */
+#define SNAC_MLP_GRAD_CHUNK 256
+int64_t snac_mlp_backward_work_bytes(const snac_mlp* net, int32_t rows);
+int snac_mlp_backward(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows, const float* grad_y, float* grad, int32_t accumulate,
+                      void* work, int64_t work_bytes, void* stream);
 
 /* ---- Acting with the device network over a rollout (snac_amd/batched.py: rollout_policy; k_policy_roll.hip): T ticks of
  * observe -> network -> draw -> step in ONE launch, the env state on chip from the first tick to the last.  The join of snac_rollout_rec

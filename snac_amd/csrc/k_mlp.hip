@@ -103,16 +103,6 @@ __global__ __launch_bounds__(THREADS) void k_mlp(const MlpArgs g) {
 
 int aligned(const void* p, size_t n, const char* msg) { return ((uintptr_t)p % n) ? fail(SNAC_ERR_ARG, msg) : SNAC_OK; }
 
-// the checks of all three entry points: the network (mlp_net_check, below the namespace), the input rows and their alignment
-int mlp_check(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows) {
-    if (int rc = mlp_net_check(net)) return rc;
-    if (!x) return fail(SNAC_ERR_ARG, "null x");
-    if (x_is_f64 != 0 && x_is_f64 != 1) return fail(SNAC_ERR_ARG, "x_is_f64 must be 0 or 1");
-    if ((uintptr_t)x % (x_is_f64 ? 8 : 4)) return fail(SNAC_ERR_ARG, "x must be aligned as its element type");
-    if (rows < 1) return fail(SNAC_ERR_ARG, "rows must be >= 1");
-    return SNAC_OK;
-}
-
 // the checks of the two entry points with a head
 int head_check(const snac_mlp* net, int32_t num_actions, const float* priors, const double* value, const float* logits, const int32_t* bad_rows) {
     if (int rc = by_actions(num_actions, [](auto) { return (int)SNAC_OK; })) return rc;
@@ -140,6 +130,16 @@ int snac_detail::mlp_net_check(const snac_mlp* net) {
         if (!net->w[l] || !net->b[l]) return fail(SNAC_ERR_ARG, "null weights / bias of a layer");
         if ((uintptr_t)net->w[l] % 4 || (uintptr_t)net->b[l] % 4) return fail(SNAC_ERR_ARG, "weights and biases must be 4-byte aligned");
     }
+    return SNAC_OK;
+}
+
+// the checks of the entry points on rows of inputs (snac_units.h): the network, the input rows and their alignment
+int snac_detail::mlp_check(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows) {
+    if (int rc = mlp_net_check(net)) return rc;
+    if (!x) return fail(SNAC_ERR_ARG, "null x");
+    if (x_is_f64 != 0 && x_is_f64 != 1) return fail(SNAC_ERR_ARG, "x_is_f64 must be 0 or 1");
+    if ((uintptr_t)x % (x_is_f64 ? 8 : 4)) return fail(SNAC_ERR_ARG, "x must be aligned as its element type");
+    if (rows < 1) return fail(SNAC_ERR_ARG, "rows must be >= 1");
     return SNAC_OK;
 }
 

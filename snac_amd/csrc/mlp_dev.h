@@ -1,6 +1,7 @@
-// mlp_dev.h -- the layer loop of the device network, once, for the kernels that run it: k_mlp (k_mlp.hip: rows from memory, one pass) and
-// k_policy_rollout (k_policy_roll.hip: the rows are the block's envs, one pass per tick).  A block of 256 threads takes TR = 16 rows
-// through every layer with the rows' activations in LDS; k_mlp.hip's head comment has the shape and what was measured.  Device code only.
+// mlp_dev.h -- the layer loop of the device network, once, for the kernels that run it: k_mlp (k_mlp.hip: rows from memory, one pass),
+// k_policy_rollout (k_policy_roll.hip: the rows are the block's envs, one pass per tick) and k_mlp_grad_rows (k_mlp_grad.hip: the
+// activations recomputed for the backward pass, parked through the hook below).  A block of 256 threads takes TR = 16 rows through every
+// layer with the rows' activations in LDS; k_mlp.hip's head comment has the shape and what was measured.  Device code only.
 #pragma once
 #include "snac_units.h"
 #include "mlp_rule.h"
@@ -18,7 +19,13 @@ static_assert(PRE * THREADS == PASS * KC && JT * (THREADS / TR) == PASS, "the ti
 // first barrier below orders those writes before the first read).  Out: the last layer's outputs at res[j * AS + r], res = mlp_result(),
 // visible to every thread (the loop ends in a barrier).  wt: the 16-byte aligned weight tile.  Thread (r, g) = (tid & 15, tid >> 4) owns
 // row r and, in a pass over 64 outputs, the four outputs jbase + 4 g + t.  Every thread of the block calls it (uniform throughout).
-__device__ __forceinline__ void mlp_layers(const snac_mlp& net, float* act_a, float* act_b, float* wt, int tid) {
+// park(l, j, r, v): called by the owning thread with every value v = output j of layer l for row r as it is written (k_mlp_grad.hip keeps
+// the hidden activations that the two LDS arrays, used in turn, do not); the default does nothing.
+struct MlpNoPark {
+    __device__ __forceinline__ void operator()(int, int, int, float) const {}
+};
+template <class Park = MlpNoPark>
+__device__ __forceinline__ void mlp_layers(const snac_mlp& net, float* act_a, float* act_b, float* wt, int tid, Park park = Park()) {
     const int r = tid & (TR - 1), grp = tid >> 4;
     const int32_t L = net.layers;
     for (int l = 0; l < L; ++l) {                                    // uniform throughout
@@ -84,7 +91,11 @@ __device__ __forceinline__ void mlp_layers(const snac_mlp& net, float* act_a, fl
 #pragma unroll
             for (int t = 0; t < JT; ++t) {                           // outputs past N ran on zero weights and are dropped
                 const int j = jbase + grp * JT + t;
-                if (j < N) out[j * AS + r] = last ? mlp_last(acc[t]) : mlp_hidden(acc[t]);
+                if (j < N) {
+                    const float v = last ? mlp_last(acc[t]) : mlp_hidden(acc[t]);
+                    out[j * AS + r] = v;
+                    park(l, j, r, v);
+                }
             }
         }
     }

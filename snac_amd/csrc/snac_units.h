@@ -60,6 +60,10 @@
 //                                 (softmax_rule.h, by_actions) and the search's "value the leaves" step in one launch: 16 rows per block,
 //                                 activations and weight tiles in LDS, every output's sum one float64 chain in index order (mlp_rule.h: the
 //                                 rule per output and per row, host and device)
+//   k_mlp_grad.hip  k_mlp_grad_rows / chunk / reduce   the backward pass of that network, to one flat gradient of every weight and bias: the
+//                                 activations recomputed by mlp_dev.h's layer loop and parked, the deltas downward with 16 rows per block,
+//                                 then the sums over the batch as float64 chains per chunk of rows and over the chunks, in a stated order
+//                                 (mlp_grad_rule.h: the rule per step, host and device)
 //   k_policy_roll.hip  k_policy_rollout   T ticks of observe -> network -> draw -> step in one launch: a block of 256 threads owns 16 envs,
 //                                 their K image (wave 0: lane = env, as k_rollout) and their activations in LDS (mlp_dev.h: the layer loop,
 //                                 for this unit and k_mlp.hip; policy_dev.h: the draw of snac_policy_act, for this unit and k_policy.hip)
@@ -88,6 +92,8 @@ int nodes_check(int kind, const snac_env_desc* d, const snac_state* st, const vo
 int play_check(int A, const void* stats, int32_t rows, int32_t B, int32_t cap);
 // the checks of a network descriptor (non-null, layers, dims, pointers and their alignment), defined in k_mlp.hip
 int mlp_net_check(const snac_mlp* net);
+// the checks of the entry points on rows of inputs (mlp_net_check, x non-null and aligned as its type, x_is_f64, rows), defined in k_mlp.hip
+int mlp_check(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows);
 // ---- the dispatch, defined in snac_hip.hip.  choose() is the whole decision, a pure function of its arguments and tune(): the kernel, its
 // size parameter E where it has several (tile size of the tile kernels; envs per block of k_rollout2db / 2dt / 1dt; envs per wave of
 // k_step2d; edges per wave of k_transition2d; else 0) and its form where it has them (k_step2d / k_step3dq / k_step1d / k_rollout1dl:
