@@ -37,6 +37,9 @@ the parameters read in place), and the search values its leaves in that same lau
 goes through torch autograd as before.
 --device-backward: the training step's pass through the network and the gradients of its weights come from the device as well
 (DeviceMLP.train_forward: float64 chains in a stated order); the optimiser stays torch's.
+--device-optimizer (needs --device-backward): the Adam step is the device's too.  The training pass is DeviceMLP.forward with no autograd
+node behind it, loss.backward() leaves the loss's gradient to the outputs, and DeviceAdam.backward_step turns it into the weight gradients
+and the step, written into the parameters where they lie: five launches, the same weights on every run.
 """
 import argparse
 import os
@@ -46,16 +49,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, DeviceMLP, SearchLoss, SelfPlay, UCTSearch  # noqa: E402
+from snac_amd import BatchedDMPEnv, DeviceAdam, DeviceMLP, SearchLoss, SelfPlay, UCTSearch  # noqa: E402
 
 
 def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, batch=256, capacity=64, hidden=64, seed=1, normalise=False,
           gumbel=None, gumbel_interior=False, reanalyse=0, td_steps=None, prioritized=False, per_alpha=1.0, per_beta=0.4, device_loss=False, huber=None,
           vf_coef=1.0, info=None, dirichlet=None, noise_eps=0.25, temperature=None, counter_noise=False, device_evaluator=False,
-          device_backward=False):
+          device_backward=False, device_optimizer=False):
     """`steps` rounds of play(moves) -> [reanalyse()] -> targets() -> sample(batch) -> one optimiser step.  Returns (losses, the
     SelfPlay).  info: a dict that receives bad_rows and the last step's statistics of the device loss, and evaluator_bad_rows of the
-    device evaluator."""
+    device evaluator, and bad_steps of the device optimiser (the steps refused for a gradient that was not finite)."""
+    if device_optimizer and not device_backward:
+        raise ValueError("device_optimizer needs device_backward: the flat gradient of DeviceMLP.backward")
     if not device_loss and (huber is not None or vf_coef != 1.0):
         raise ValueError("huber and vf_coef belong to device_loss")
     env = BatchedDMPEnv(kind, True, envs, seed=seed)
@@ -75,6 +80,8 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
     trainer = None
     if device_backward:                                              # refused here if the network is not one a DeviceMLP runs
         trainer = evaluator if device_evaluator else DeviceMLP(net, env)
+    if device_optimizer:
+        opt = DeviceAdam(trainer, lr=1e-3)
 
     def noise(priors):                                               # exploration at the roots: the caller's (here: a uniform share)
         return 0.75 * priors + 0.25 / A
@@ -106,14 +113,24 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
             play.reanalyse(again, iterations, **(dict(prioritized=True) if prioritized else {}))
         play.targets(td_steps=td_steps)
         b = play.sample(batch, **(dict(prioritized=True, beta=per_beta) if prioritized else {}))
-        y = trainer.train_forward(b["obs"]) if device_backward else net(b["obs"])
+        if device_optimizer:                                         # no autograd node for the network: y is the leaf the loss differentiates
+            y = trainer.forward(b["obs"]).requires_grad_()
+        else:
+            y = trainer.train_forward(b["obs"]) if device_backward else net(b["obs"])
+
+        def update(loss):
+            if device_optimizer:
+                loss.backward()                                      # leaves y.grad
+                opt.backward_step(b["obs"], y.grad)                  # weight gradients and Adam: five launches
+            else:
+                opt.zero_grad()
+                loss.backward()
+                opt.step()
         if device_loss:                                              # both heads as contiguous tensors; pi, z and the weights are read from b
             loss, _, priority = search_loss.loss(y[:, :A].contiguous(), y[:, A].contiguous(), b, want_per_sample=True)
             if prioritized:
                 play.update_priorities(b["index"], priority if per_alpha == 1.0 else priority ** per_alpha)
-            opt.zero_grad()
-            loss.backward()
-            opt.step()
+            update(loss)
             losses.append(loss.detach())
             continue
         if prioritized:                                              # the importance weights undo the sampling bias
@@ -124,12 +141,12 @@ def train(kind=2, envs=64, steps=20, moves=4, iterations=8, paths=4, nodes=256, 
             policy_loss = -(b["pi"] * torch.log_softmax(y[:, :A], 1)).sum(1).mean()
             value_loss = ((y[:, A] - b["z"]) ** 2).mean()
         loss = policy_loss + value_loss
-        opt.zero_grad()
-        loss.backward()
-        opt.step()
+        update(loss)
         losses.append(loss.detach())
     if info is not None and device_loss:
         info.update(search_loss.stats_dict(), bad_rows=int(search_loss.bad_rows.cpu()[0]))
+    if info is not None and device_optimizer:
+        info.update(bad_steps=int(opt.bad_steps.cpu()[0]))
     if info is not None and device_evaluator:
         info.update(evaluator_bad_rows=int(evaluator.bad_rows.cpu()[0]))
     return [float(x) for x in torch.stack(losses).cpu()], play
@@ -157,7 +174,10 @@ def main():
     ap.add_argument("--counter-noise", action="store_true", help="with --gumbel M: the Gumbel noise from the counter RNG")
     ap.add_argument("--device-evaluator", action="store_true", help="the search's network as one device launch (DeviceMLP), fused into the search")
     ap.add_argument("--device-backward", action="store_true", help="the training step's forward pass and weight gradients from the device (DeviceMLP)")
+    ap.add_argument("--device-optimizer", action="store_true", help="with --device-backward: the Adam step from the device (DeviceAdam)")
     args = ap.parse_args()
+    if args.device_optimizer and not args.device_backward:
+        ap.error("--device-optimizer needs --device-backward")
     if args.gumbel_interior and args.gumbel is None:
         ap.error("--gumbel-interior needs --gumbel M")
     if args.gumbel is not None and (args.dirichlet is not None or args.temperature is not None):
@@ -173,7 +193,7 @@ def main():
                          prioritized=args.prioritized, per_alpha=args.per_alpha, per_beta=args.per_beta, device_loss=args.device_loss,
                          huber=args.huber, vf_coef=args.vf_coef, dirichlet=args.dirichlet, noise_eps=args.noise_eps, temperature=args.temperature,
                          counter_noise=args.counter_noise, device_evaluator=args.device_evaluator,
-                         device_backward=args.device_backward)
+                         device_backward=args.device_backward, device_optimizer=args.device_optimizer)
     print("moves played per tree: %d, samples in the ring: %d, episodes finished: %d" % (play.moves, len(play), int(play.done.sum())))
     if args.reanalyse:
         print("entries reanalysed: %d" % int(play.refreshed.sum()))

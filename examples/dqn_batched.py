@@ -36,6 +36,11 @@ Q-network's parameters acts inside the env launch) instead of one observe, forwa
 --device-backward: the online network's pass of the update and the gradients of its weights come from the device (DeviceMLP.train_forward:
 one forward launch, three for the backward pass, float64 chains in a stated order) instead of torch's modules and autograd's pass back
 through them; the optimiser stays torch's.  Not with --distributional.
+
+--device-optimizer (needs --device-backward): the Adam step is the device's too.  The online pass is DeviceMLP.forward with no autograd node
+behind it, loss.backward() leaves the loss's gradient to the Q-values, DeviceAdam.backward_step turns it into the weight gradients and the
+step (five launches, the same weights on every run), and the target network is copied by one launch (sync_target) in place of
+load_state_dict's copy per parameter.
 """
 import argparse
 import os
@@ -47,7 +52,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, CategoricalSupport, DeviceMLP, ReplayRing, TDLoss  # noqa: E402
+from snac_amd import BatchedDMPEnv, CategoricalSupport, DeviceAdam, DeviceMLP, ReplayRing, TDLoss  # noqa: E402
 
 
 class QNet(nn.Module):
@@ -62,7 +67,7 @@ class QNet(nn.Module):
 
 def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefill=64, seed=1, log=print, prioritized=False, beta=0.4, n_step=None,
         device_sampling=False, distributional=False, atoms=51, vmin=None, vmax=None, info=None, projection=None, device_loss=False, huber=None,
-        double=False, device_rollout=None, device_backward=False):
+        double=False, device_rollout=None, device_backward=False, device_optimizer=False):
     """distributional: the C51 head and target (the module's docstring); vmin / vmax None: 0 and 5 / (1 - gamma).  info: an optional dict
     that receives the run's device counters ("bad_rows": the samples project() and the device loss zeroed; with prioritized also
     "priorities", a copy of the priority tree's leaves at the end).  device_loss: the DQN loss from TDLoss (the module's docstring), with
@@ -72,7 +77,11 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     independent of the sharding and of torch's generator) instead of torch.rand / torch.randint / argmax.  device_rollout: K, the ticks
     collected per update by one fused launch (the module's docstring); not with distributional, whose actions need the expected values.
     device_backward: the online network's pass of the update and its weight gradients come from the device (DeviceMLP.train_forward: the
-    module's docstring); not with distributional, whose head is wider than a DeviceMLP's 64 outputs."""
+    module's docstring); not with distributional, whose head is wider than a DeviceMLP's 64 outputs.  device_optimizer: with
+    device_backward, the Adam step and the target's copy are the device's as well (DeviceAdam: the module's docstring); info then receives
+    "bad_steps", the steps refused for a gradient that was not finite."""
+    if device_optimizer and not device_backward:
+        raise ValueError("device_optimizer needs device_backward: the flat gradient of DeviceMLP.backward")
     if device_backward and distributional:
         raise ValueError("device_backward is not for distributional: its head of actions * atoms outputs is wider than a DeviceMLP runs")
     if device_rollout is not None and (distributional or isinstance(device_rollout, bool) or not isinstance(device_rollout, int) or device_rollout < 1):
@@ -105,8 +114,15 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
     target.load_state_dict(net.state_dict())
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     mlp = DeviceMLP(net.body, None) if device_rollout or device_backward else None     # the Q-network's parameters, read in place by every launch
+    if device_optimizer:                                           # tau = 1: a step leaves the target alone, sync_target() copies it
+        opt = DeviceAdam(mlp, lr=lr, target=DeviceMLP(target.body, None))
+    held = {}
 
     def online(s, pl):                                             # the Q-values the loss differentiates
+        if device_optimizer:                                       # no autograd node for the network: y is the leaf the loss differentiates
+            held["x"] = torch.cat([s, pl.flatten(1)], dim=1)
+            held["y"] = mlp.forward(held["x"]).requires_grad_()
+            return held["y"]
         if device_backward:                                        # forward and backward on the device: float64 chains in a stated order
             return mlp.train_forward(torch.cat([s, pl.flatten(1)], dim=1))
         return net(s, pl)
@@ -180,12 +196,19 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
                 ring.update_priorities(mb["index"], td.detach().abs())
             else:
                 loss = nn.functional.mse_loss(q, y)
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
+        if device_optimizer:
+            loss.backward()                                        # leaves y.grad
+            opt.backward_step(held["x"], held["y"].grad)           # weight gradients and Adam: five launches
+        else:
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
         losses.append(float(loss.detach()))
         if (tick + 1) % replace == 0:
-            target.load_state_dict(net.state_dict())
+            if device_optimizer:
+                opt.sync_target()                                  # one launch
+            else:
+                target.load_state_dict(net.state_dict())
             st = env.episodic_stats()
             returns.append(st["return_sum"] / max(st["episodes"], 1))
             log("tick %4d  eps %.2f  loss %.4f  episodes %d  mean return %.2f  mean IoU %.4f  (%.0f env-steps/s incl. learning)" % (
@@ -197,6 +220,8 @@ def run(envs=4096, ticks=200, batch=2048, gamma=0.95, lr=1e-4, replace=50, prefi
         if not distributional:
             info["bad_rows"] = int(td_loss.bad_rows.cpu()[0])
         info["stats"] = (support if distributional else td_loss).stats_dict()
+    if info is not None and device_optimizer:
+        info["bad_steps"] = int(opt.bad_steps.cpu()[0])
     if info is not None and prioritized:
         info["priorities"] = ring.tree.weights().clone()
     return losses, returns
@@ -219,9 +244,12 @@ if __name__ == "__main__":
     ap.add_argument("--double", action="store_true", help="--device-loss: double DQN, the online network chooses the next action")
     ap.add_argument("--device-rollout", type=int, default=None, metavar="K", help="collect K epsilon-greedy ticks per update in one fused launch")
     ap.add_argument("--device-backward", action="store_true", help="the update's forward pass and weight gradients from the device (DeviceMLP.train_forward)")
+    ap.add_argument("--device-optimizer", action="store_true", help="with --device-backward: the Adam step and the target's copy from the device (DeviceAdam)")
     a = ap.parse_args()
+    if a.device_optimizer and not a.device_backward:
+        ap.error("--device-optimizer needs --device-backward")
     if a.device_backward and a.distributional:
         ap.error("--device-backward is not for --distributional")
     run(a.envs, a.ticks, a.batch, prioritized=a.prioritized, n_step=a.n_step, device_sampling=a.device_sampling, distributional=a.distributional,
         atoms=a.atoms, vmin=a.vmin, vmax=a.vmax, device_loss=a.device_loss, huber=a.huber, double=a.double, device_rollout=a.device_rollout,
-        device_backward=a.device_backward)
+        device_backward=a.device_backward, device_optimizer=a.device_optimizer)

@@ -17,7 +17,12 @@ With --device-backward (which needs --device-rollout's network) the update's for
 device too (DeviceMLP.train_forward: float64 chains in a stated order, three launches for the backward pass); the optimiser and the
 gradient clip stay torch's.
 
-    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]] [--device-rollout [--device-backward]]
+With --device-optimizer (which needs --device-backward) they come from the device as well: the network's pass is DeviceMLP.forward with no
+autograd node behind it, loss.backward() leaves the loss's gradient to the outputs, and DeviceAdam.backward_step turns it into the weight
+gradients, their global norm, the clip at 0.5 and the Adam step, written into the parameters where they lie: five launches, the same
+weights on every run.
+
+    python examples/ppo_batched.py --envs 4096 --iterations 20 [--device-loss [--clip-vf 0.2]] [--device-rollout [--device-backward [--device-optimizer]]]
 """
 import argparse
 import os
@@ -29,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 
-from snac_amd import BatchedDMPEnv, DeviceMLP, PPOLoss, RolloutBuffer  # noqa: E402
+from snac_amd import BatchedDMPEnv, DeviceAdam, DeviceMLP, PPOLoss, RolloutBuffer  # noqa: E402
 
 
 class ActorCritic(nn.Module):
@@ -60,7 +65,7 @@ class ActorCriticMLP(nn.Module):
 
 def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, lam=0.95, clip=0.2, vf_coef=0.5, ent_coef=0.01, lr=3e-4, seed=1,
         log=print, device_sampling=False, device_loss=False, clip_vf=None, info=None, device_rollout=False,
-        device_backward=False):
+        device_backward=False, device_optimizer=False):
     """-> (the loss of every minibatch update, the mean episodic return after every iteration).  device_sampling: draw the actions and
     their log-probabilities with one launch per tick (RolloutBuffer.act_logits: counter-RNG stream 5, independent of the sharding and of
     torch's generator) instead of torch.distributions.  device_loss: the loss, its gradient and its statistics from PPOLoss (one call per
@@ -68,7 +73,11 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
     as the composition).  info: a dict that receives the run's device counters with device_loss ("bad_rows": the samples PPOLoss
     zeroed) and the statistics of the last minibatch ("stats").  device_rollout: the horizon is collected by one fused launch with a DeviceMLP as
     the actor-critic (the module's docstring); the draws are device_sampling's.  device_backward: with device_rollout, the update's pass
-    through the network and its weight gradients are the device's (DeviceMLP.train_forward)."""
+    through the network and its weight gradients are the device's (DeviceMLP.train_forward).  device_optimizer: with device_backward, the
+    gradient clip and the Adam step are the device's too (DeviceAdam.backward_step: the module's docstring); info then receives
+    "bad_steps", the steps refused for a gradient that was not finite."""
+    if device_optimizer and not device_backward:
+        raise ValueError("device_optimizer needs device_backward: the flat gradient of DeviceMLP.backward")
     if device_backward and not device_rollout:
         raise ValueError("device_backward needs device_rollout: the actor-critic a DeviceMLP can run")
     if clip_vf is not None and not device_loss:
@@ -80,7 +89,7 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
     buf = RolloutBuffer(env, horizon, gamma, lam)
     net = (ActorCriticMLP if device_rollout else ActorCritic)(env.obs_dim, 400, env.num_actions).to(dev)
     mlp = DeviceMLP(net.body, env) if device_rollout else None
-    opt = torch.optim.Adam(net.parameters(), lr=lr)
+    opt = DeviceAdam(mlp, lr=lr, max_norm=0.5) if device_optimizer else torch.optim.Adam(net.parameters(), lr=lr)
     ppo = PPOLoss(env, clip, -1.0 if clip_vf is None else clip_vf, vf_coef, ent_coef) if device_loss else None
     t0, losses, returns = time.time(), [], []
     for it in range(iterations):
@@ -102,7 +111,11 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
                 _, bootstrap = net(env.observe().float(), env.input_plan().float())
         buf.finish(bootstrap)                                      # advantages and returns of the horizon: one launch
         for mb in buf.minibatches(batch, epochs):                  # one gather launch each
-            if device_backward:
+            if device_optimizer:                                   # no autograd node for the network: y is the leaf the loss differentiates
+                x = torch.cat([mb["s"], mb["plan"].flatten(1)], dim=1)
+                y = mlp.forward(x).requires_grad_()
+                logits, value = y[:, :env.num_actions].contiguous(), y[:, env.num_actions].contiguous()
+            elif device_backward:
                 y = mlp.train_forward(torch.cat([mb["s"], mb["plan"].flatten(1)], dim=1))
                 logits, value = y[:, :env.num_actions].contiguous(), y[:, env.num_actions].contiguous()     # what PPOLoss reads
             else:
@@ -115,6 +128,11 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
                 surrogate = torch.min(ratio * mb["adv"], torch.clamp(ratio, 1.0 - clip, 1.0 + clip) * mb["adv"]).mean()
                 value_loss = 0.5 * ((value - mb["ret"]) ** 2).mean()
                 loss = -surrogate + vf_coef * value_loss - ent_coef * dist.entropy().mean()
+            if device_optimizer:
+                loss.backward()                                    # leaves y.grad
+                opt.backward_step(x, y.grad)                       # weight gradients, norm, clip and Adam: five launches
+                losses.append(float(loss.detach()))
+                continue
             opt.zero_grad(set_to_none=True)
             loss.backward()
             nn.utils.clip_grad_norm_(net.parameters(), 0.5)
@@ -131,6 +149,8 @@ def run(envs=4096, iterations=20, horizon=32, epochs=4, batch=8192, gamma=0.99, 
                 st["approx_kl"], st["clip_fraction"], st["entropy"], st["value_loss"]))
     if info is not None and device_loss:
         info.update(bad_rows=int(ppo.bad_rows.cpu()[0]), stats=ppo.stats_dict())
+    if info is not None and device_optimizer:
+        info["bad_steps"] = int(opt.bad_steps.cpu()[0])
     return losses, returns
 
 
@@ -146,8 +166,11 @@ if __name__ == "__main__":
     ap.add_argument("--clip-vf", type=float, default=None, help="with --device-loss: clip the value function by this range, as PPO2 does")
     ap.add_argument("--device-rollout", action="store_true", help="collect the horizon in one fused launch with a DeviceMLP actor-critic")
     ap.add_argument("--device-backward", action="store_true", help="with --device-rollout: the update's forward pass and weight gradients from the device")
+    ap.add_argument("--device-optimizer", action="store_true", help="with --device-backward: the gradient clip and the Adam step from the device (DeviceAdam)")
     a = ap.parse_args()
+    if a.device_optimizer and not a.device_backward:
+        ap.error("--device-optimizer needs --device-backward")
     if a.device_backward and not a.device_rollout:
         ap.error("--device-backward needs --device-rollout")
     run(a.envs, a.iterations, a.horizon, a.epochs, a.batch, device_sampling=a.device_sampling, device_loss=a.device_loss, clip_vf=a.clip_vf,
-        device_rollout=a.device_rollout, device_backward=a.device_backward)
+        device_rollout=a.device_rollout, device_backward=a.device_backward, device_optimizer=a.device_optimizer)

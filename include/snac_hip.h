@@ -869,6 +869,54 @@ int64_t snac_mlp_backward_work_bytes(const snac_mlp* net, int32_t rows);
 int snac_mlp_backward(const snac_mlp* net, const void* x, int x_is_f64, int32_t rows, const float* grad_y, float* grad, int32_t accumulate,
                       void* work, int64_t work_bytes, void* stream);
 
+/* ---- Optimiser step of the device network (snac_amd/optim.py: DeviceAdam; k_adam.hip, adam_rule.h): the global gradient norm, the
+ * clip, Adam and the slow copy of a target network, read from the flat gradient of the section above and written into the parameters
+ * where they lie, by a float64 rule in a stated order, as two launches with nothing waiting.  After it a whole update of the network is
+ * device calls whose every output byte is stated here: forward, loss, backward, step.
+ *
+ * Notation.  The network is snac_mlp as above; P and the flat layout are snac_mlp_backward's: per layer the weights row-major, then the
+ * bias.  theta[p] is the parameter at flat index p, read and written in the array w[l] / b[l] it belongs to: no flat copy of the
+ * parameters exists.  g (the flat gradient, read only), m and v (Adam's moments, the caller's, read and written) are float32 [P],
+ * 4-byte aligned.  Every float64 operation below is one operation of the rule, rounded on its own (no contraction).
+ * Sum of squares, in the order of "PPO loss" with one column.  W = ceil(P / 64).  Lane j of wave w holds
+ *     u = (double)g[p] * (double)g[p]   for p = 64 w + j < P,   else 0.0                  (the product of two float32 is exact)
+ *   the xor butterfly u_j = u_j + u_{j ^ off}, off = 32, 16, .., 1 gives partials[w].  Stage two: lane j adds partials[j],
+ *   partials[j + 64], .. in ascending order from 0.0, and the same butterfly gives ss.
+ * Norm and clip.  norm = sqrt(ss).  max_norm == 0: coef = 1.0.  Otherwise c = max_norm / (norm + 1e-6) and coef = c < 1.0 ? c : 1.0
+ *   (torch's clip_grad_norm_ and its constants).
+ * A bad step: ss is not finite, that is, some g is a NaN or an infinity.  No byte of any parameter, of m, v or the target is written;
+ *   bad_steps[0] gets an atomic add of 1; norm_out, where given, receives {norm, 0.0}.
+ * Per parameter, with lr, beta1, beta2, eps, bias1 = 1 - beta1^t and bias2 = 1 - beta2^t given as doubles by the caller (nothing here
+ * raises to a power):
+ *     gd     = coef * (double)g[p]
+ *     m'     = (float)(beta1 * (double)m[p] + (1.0 - beta1) * gd)
+ *     v'     = (float)(beta2 * (double)v[p] + (1.0 - beta2) * (gd * gd))
+ *     denom  = sqrt((double)v') / sqrt(bias2) + eps
+ *     theta' = (float)((double)theta[p] - (lr / bias1) * ((double)m' / denom))
+ *   The stored, rounded m' and v' are what the update reads, so a step continued from stored state is the same step.  Float32
+ *   subnormals are kept, not flushed.  Nothing but ss is screened: eps = 0 with v' = 0 gives what IEEE says.
+ * Target (optional): a second snac_mlp of the same dims, written in place.  tau == 1.0: tgt' = theta', the bits copied; otherwise
+ *     tgt' = (float)((double)tgt + tau * ((double)theta' - (double)tgt))
+ * How flat indices are mapped to blocks and lanes is free and cannot be seen in the result.  No float atomics.
+ *
+ * snac_mlp_adam_step   THIS AND snac_mlp_lerp ARE THE ONLY ENTRY POINTS THAT WRITE THE ARRAYS A snac_mlp POINTS TO (its fields are
+ *   declared const float* for every reader; here the network's w[l] / b[l], and the target's, are outputs).  target may be NULL; tau is
+ *   then ignored.  norm_out: double[2] = {norm, coef}, 8-byte aligned, may be NULL.  bad_steps: int32, may be NULL.  partials:
+ *   ceil(P / 64) doubles of the caller's scratch, 8-byte aligned, never NULL; nothing past them is written.  Two launches on `stream`,
+ *   k_adam_sumsq and k_adam_update: every block of the second redoes stage two from the partials -- the same order, so the same bits in
+ *   every block -- so neither a grid synchronisation nor a third launch is needed.  Each launch's error is looked at before the next; no
+ *   host synchronisation; snac_last_kernel() names k_adam_update.  The kernels read grad and write only the parameter arrays, m, v, the
+ *   target's arrays, partials, norm_out and bad_steps.  Checks, all before any HIP call: the network as in snac_mlp_forward; grad, m, v
+ *   and partials non-null and aligned (norm_out and bad_steps aligned where given); grad, m and v pairwise distinct; lr and eps finite
+ *   and >= 0; beta1 and beta2 in [0, 1); bias1 and bias2 in (0, 1]; max_norm finite and >= 0; with a target: its layers and every dim
+ *   equal to the network's, its pointers non-null, 4-byte aligned and none equal to a pointer of the network, and tau in (0, 1].
+ * snac_mlp_lerp   the target's rule alone, with theta in place of theta': DQN's hard copy every K ticks (tau = 1) and SAC's lerp per
+ *   step.  One launch (k_mlp_lerp); the network's checks and the target's checks above. */
+int snac_mlp_adam_step(const snac_mlp* net, const float* grad, float* m, float* v, double lr, double beta1, double beta2, double eps,
+                       double bias1, double bias2, double max_norm, const snac_mlp* target, double tau, double* norm_out, double* partials,
+                       int32_t* bad_steps, void* stream);
+int snac_mlp_lerp(const snac_mlp* target, const snac_mlp* net, double tau, void* stream);
+
 /* ---- Acting with the device network over a rollout (snac_amd/batched.py: rollout_policy; k_policy_roll.hip): T ticks of
  * observe -> network -> draw -> step in ONE launch, the env state on chip from the first tick to the last.  The join of snac_rollout_rec
  * (whose actions are the counter RNG's or the caller's) and snac_mlp_forward / snac_policy_act (one launch each per tick): a model-free

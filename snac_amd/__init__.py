@@ -6,7 +6,7 @@ implementation.  See DESIGN.md / INTEGRATION.md.
 from ._lib import SnacError, build  # noqa: F401
 from . import plans  # noqa: F401
 
-__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "RolloutBuffer", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "UCTSearch", "SelfPlay", "PriorityTree", "CategoricalSupport", "SoftValue", "PPOLoss", "TDLoss", "SearchLoss", "DeviceMLP", "SnacError", "build", "plans"]
+__all__ = ["BatchedDMPEnv", "VectorizedEnvWrapper", "ReplayRing", "RolloutBuffer", "NodePool", "NodePool1D", "NodePool2D", "NodePool3D", "UCTSearch", "SelfPlay", "PriorityTree", "CategoricalSupport", "SoftValue", "PPOLoss", "TDLoss", "SearchLoss", "DeviceMLP", "DeviceAdam", "SnacError", "build", "plans"]
 
 
 def __getattr__(name):  # torch is imported lazily so that `import snac_amd` stays cheap
@@ -62,6 +62,10 @@ def __getattr__(name):  # torch is imported lazily so that `import snac_amd` sta
         from .mlp import DeviceMLP
 
         return DeviceMLP
+    if name == "DeviceAdam":
+        from .optim import DeviceAdam
+
+        return DeviceAdam
     if name == "VectorizedEnvWrapper":
         from .vector import VectorizedEnvWrapper
 

@@ -64,6 +64,10 @@
 //                                 activations recomputed by mlp_dev.h's layer loop and parked, the deltas downward with 16 rows per block,
 //                                 then the sums over the batch as float64 chains per chunk of rows and over the chunks, in a stated order
 //                                 (mlp_grad_rule.h: the rule per step, host and device)
+//   k_adam.hip      k_adam_sumsq / k_adam_update / k_mlp_lerp   the optimiser step of that network from the flat gradient: the sum of
+//                                 squares by batch_sum.h's butterfly per wave, then, with every block redoing the second stage from the
+//                                 partials, the clip, Adam and the target's slow copy per parameter, written where the parameters lie
+//                                 (adam_rule.h: the rule per parameter, host and device); the only kernels that write a snac_mlp's arrays
 //   k_policy_roll.hip  k_policy_rollout   T ticks of observe -> network -> draw -> step in one launch: a block of 256 threads owns 16 envs,
 //                                 their K image (wave 0: lane = env, as k_rollout) and their activations in LDS (mlp_dev.h: the layer loop,
 //                                 for this unit and k_mlp.hip; policy_dev.h: the draw of snac_policy_act, for this unit and k_policy.hip)

@@ -8,7 +8,8 @@ sum in index order: the same inputs give the same bytes on every run.  The param
 they lie, so an optimiser step enqueued on the stream is seen by the next launch and nothing is copied.  Training: train_forward(x) is
 forward(x) as an autograd function whose backward is the device's own (backward(): the gradient of every weight and bias in one flat
 buffer, float64 chains in a stated order, three launches), so the weight gradients are as reproducible as the outputs; the optimiser
-stays torch's.  Going through the module with autograd, as before, still works: both read the same parameters.
+stays torch's.  Going through the module with autograd, as before, still works: both read the same parameters.  DeviceAdam
+(snac_amd/optim.py) takes the flat gradient of backward() through the clip and an Adam step on the device instead.
 
     net = torch.nn.Sequential(torch.nn.Linear(env.obs_dim, 64), torch.nn.ReLU(), torch.nn.Linear(64, A + 1)).to(env.device)
     mlp = DeviceMLP(net, env)                                        # or DeviceMLP([(w0, b0), (w1, b1)], 5, device="cuda:0")
