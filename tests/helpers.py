@@ -48,14 +48,23 @@ def traj_file(dim, dyn):
     return np.load(os.path.join(GOLDEN, "traj_%dd_%s.npz" % (dim, "dynamic" if dyn else "static")))
 
 
+def npz_names(z):
+    """The cases of a golden file."""
+    return z["cases"].tolist()
+
+
+def npz_case(z, name):
+    """The arrays of one case of a golden file, by their names within the case."""
+    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
+
+
 def golden_cases():
     """Yield (dim, dyn, case_name, dict-of-arrays)."""
     for dim in (1, 2, 3):
         for dyn in (False, True):
             z = traj_file(dim, dyn)
-            for name in z["cases"].tolist():
-                rec = {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-                yield dim, dyn, name, rec
+            for name in npz_names(z):
+                yield dim, dyn, name, npz_case(z, name)
 
 
 def case_ids():
@@ -68,8 +77,13 @@ def case_ids():
 
 
 def load_case(dim, dyn, name):
-    z = traj_file(dim, dyn)
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
+    return npz_case(traj_file(dim, dyn), name)
+
+
+def cases_per_action(make_case, actions, rows):
+    """(A, make_case(a generator seeded with A, rows, A)) for every action count: the inputs of a loss rule's host tests."""
+    for A in actions:
+        yield A, make_case(np.random.default_rng(A), rows, A)
 
 
 def obs_from_golden(rec, t, dim):

@@ -10,15 +10,16 @@ compiled for the host with the system compiler and compared with adam_rule byte 
 under the address and undefined-behaviour sanitizers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err, _net
 import helpers
+from hostcode import _vp, load_shared, run_sanitized
 from snac_amd import _lib
-from test_mlp_backward_host import _hostless, num_params
-from test_mlp_host import PH, _compiler, _err, _net, _vp
+from specmath import butterfly
+from test_mlp_backward_host import hostless_mlp, num_params
 
 F32, F64 = np.float32, np.float64
 U24, U53 = 2.0 ** -24, 2.0 ** -53
@@ -31,14 +32,6 @@ TAUS = (None, 0.005, 1.0)
 
 
 # ---- the rule, in numpy: every ufunc call below is one float64 operation, rounded on its own ----------------------------------------------
-def butterfly(u):
-    """u float64 [.., 64]: u_j = u_j + u_{j ^ off} for off = 32 .. 1; every place holds the sum afterwards."""
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        u = u + u[..., lane ^ off]
-    return u
-
-
 def sumsq_rule(g):
     """(ss, partials float64 [W]) of the float32 gradient g [P] in the stated order."""
     P = len(g)
@@ -445,17 +438,17 @@ def test_device_adam_refuses_before_it_touches_a_device():
     from snac_amd import DeviceAdam
 
     dims = (51, 64, 6)
-    mlp, other = _hostless(dims), _hostless(dims)
+    mlp, other = hostless_mlp(dims), hostless_mlp(dims)
     P = num_params(dims)
     with pytest.raises(ValueError, match="mlp must be a DeviceMLP"):
         DeviceAdam(torch.nn.Linear(3, 4))
     with pytest.raises(ValueError, match="target must be a DeviceMLP or None"):
         DeviceAdam(mlp, target=torch.nn.Linear(3, 4))
     with pytest.raises(ValueError, match="the target's dims"):
-        DeviceAdam(mlp, target=_hostless((51, 65, 6)))
+        DeviceAdam(mlp, target=hostless_mlp((51, 65, 6)))
     with pytest.raises(ValueError, match="shares a parameter"):
         DeviceAdam(mlp, target=mlp)
-    shared = _hostless(dims)
+    shared = hostless_mlp(dims)
     shared._params[1] = (shared._params[1][0], mlp._params[1][1])
     with pytest.raises(ValueError, match="shares a parameter"):
         DeviceAdam(mlp, target=shared)
@@ -505,13 +498,7 @@ MAIN_SIZES, MAIN_RUNS = 11, 2                                        # adam_host
 
 
 def _host_fn(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "adam_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    lib = C.CDLL(so)
+    lib = load_shared(tmp_path, "adam_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600)
     vp, d = C.c_void_p, C.c_double
     lib.adam_host.restype, lib.adam_host.argtypes = C.c_int, [C.c_int64, vp, vp, vp, vp, d, d, d, d, d, d, d, vp, d, vp, vp]
     lib.lerp_host.restype, lib.lerp_host.argtypes = C.c_int, [C.c_int64, vp, vp, d]
@@ -564,17 +551,5 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tm
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers(tmp_path):
     """A stand-alone program (adam_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "adam_host_main")
-    b = subprocess.run([cxx] + san + ["-DADAM_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "adam_host_main", ["-DADAM_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count(", off 0") == MAIN_SIZES * MAIN_RUNS and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

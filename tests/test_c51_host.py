@@ -9,8 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err
 from snac_amd import _lib
-from test_uct_selfplay_host import PH
 
 SUPPORTS = ((51, -10.0, 10.0), (2, -1.0, 1.0), (33, -100.0, 300.0), (63, 0.0, 200.0), (64, -3.0, 7.0))
 ACTIONS = (3, 5, 8)
@@ -268,11 +268,6 @@ def _expect(L, B=4, A=5, K=51, vmin=-10.0, vmax=10.0, p=PH, q=PH):
 
 def _project(L, B=4, A=5, K=51, vmin=-10.0, vmax=10.0, p_next=PH, p_select=None, ret=PH, discount=PH, m=PH, a_star=PH, q_star=PH, bad=PH):
     return L.snac_c51_project(B, A, K, vmin, vmax, p_next, p_select, ret, discount, m, a_star, q_star, bad, None)
-
-
-def _err(L, rc, code, word):
-    assert rc == code, rc
-    assert word in L.snac_last_error(), L.snac_last_error()
 
 
 def test_the_library_exports_the_entry_points():

@@ -9,17 +9,17 @@ touch a device."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import ODD, PH, _desc, _err
 import helpers
+from hostcode import load_shared, run_sanitized
 import rng_spec
 from snac_amd import _lib
-from test_policy_act_host import spec_exp, spec_log
-from test_sac_host import _compiler
-from test_uct_selfplay_host import ODD, PH, _desc, _err, _search, _tree_checks
+from specmath import spec_exp, spec_log
+from test_uct_selfplay_host import hostless_search, tree_checks
 
 ACTIONS = (3, 5, 8)
 ALPHAS = (0.03, 0.3, 1.0, 2.5)
@@ -416,17 +416,17 @@ def test_temperature_one_is_the_integer_rule_and_zero_is_greedy():
 
 # ---- the C entry points -----------------------------------------------------------------------------------------------------------------
 def _dir(L, desc=True, A=5, stats=PH, rows=100, B=4, cap=8, mask=PH, t=3, alpha=0.3, eps=0.25, attempts=16, bad=PH):
-    d = _desc()
+    d = _desc(2)
     return L.snac_explore_root_dirichlet(C.byref(d) if desc else None, A, stats, rows, B, cap, mask, t, alpha, eps, attempts, bad, None)
 
 
 def _gum(L, desc=True, A=5, stats=PH, rows=100, B=4, cap=8, noisy=PH, t=3, scores=PH):
-    d = _desc()
+    d = _desc(2)
     return L.snac_explore_gumbel_scores(C.byref(d) if desc else None, A, stats, rows, B, cap, noisy, t, scores, None)
 
 
 def _tmp(L, desc=True, A=5, stats=PH, rows=100, B=4, cap=8, greedy=PH, t=3, temperature=PH, temp=1.0, action=PH, pi=PH, value=PH):
-    d = _desc()
+    d = _desc(2)
     return L.snac_explore_pick_moves_temp(C.byref(d) if desc else None, A, stats, rows, B, cap, greedy, t, temperature, temp, action, pi, value, None)
 
 
@@ -444,7 +444,7 @@ def test_the_exploration_entry_points_validate_their_arguments_before_any_hip_ca
     L = _lib.lib()
     none = dict(action=None, pi=None, value=None)
     for call in (_dir, _gum, _tmp):
-        _tree_checks(L, call)
+        tree_checks(L, call)
         _err(L, call(L, desc=False), b"null desc")
     for x in (0.0, 2.0 ** -11, np.nextafter(2.0 ** -10, 0), np.nextafter(1024.0, 2048.0), 2048.0, -0.3, float("nan"), float("inf")):
         _err(L, _dir(L, alpha=float(x)), b"alpha must be in")
@@ -469,7 +469,7 @@ def test_the_wrappers_reject_bad_arguments_before_touching_a_device():
     import torch
     from snac_amd import SelfPlay
 
-    s = _search()
+    s = hostless_search()
     for T in (-0.5, float("nan"), "1", True, torch.ones(3), torch.ones(4, dtype=torch.float64), torch.ones(4, 1), [1.0] * 4):
         with pytest.raises(ValueError, match="temperature"):
             s.pick_moves(greedy=False, temperature=T)
@@ -506,13 +506,7 @@ HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I", _lib.CSRC, HOST_SRC]
 
 
 def test_the_kernels_code_compiled_for_the_host_equals_the_rules_byte_for_byte(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "explore_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    H = C.CDLL(so)
+    H = load_shared(tmp_path, "explore_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600)
     head = [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_uint32]
     H.explore_dirichlet_host.restype, H.explore_dirichlet_host.argtypes = C.c_int, head + [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32,
                                                                                           C.c_void_p]
@@ -566,17 +560,5 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rules_byte_for_byte(t
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers(tmp_path):
     """A stand-alone program (explore_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "explore_host_main")
-    b = subprocess.run([cxx] + san + ["-DEXPLORE_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "explore_host_main", ["-DEXPLORE_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count("bad ") == 54 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

@@ -11,6 +11,7 @@
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import rng_spec
 
 pytestmark = pytest.mark.gpu
@@ -82,12 +83,6 @@ def _same_state(a, b):
     assert a.episodic_stats() == b.episodic_stats()
 
 
-def _last_kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
-
-
 def _advance(env, T, explicit_probs):
     """rollout(T) without outputs: the env's own draw, or the actions drawn on the host with explicit_probs."""
     import torch
@@ -109,7 +104,7 @@ def _run(case, probs, explicit_probs=None):
     rec = _record(env, T)
     obs, rew, done = env.rollout(T, actions=acts, record=rec)
     torch.cuda.synchronize()
-    return env, obs, rew, done, rec, _last_kernel()
+    return env, obs, rew, done, rec, _kernel()
 
 
 def _assert_same(a, b):
@@ -159,7 +154,7 @@ def _step_run(case, probs, explicit_probs, ticks=6):
             acts = torch.from_numpy(_host_actions(env, explicit_probs, 1, env.t)[0]).to(env.device)
         obs, rew, done = env.step(acts, None, auto_reset=True)
         torch.cuda.synchronize()
-        kerns.append(_last_kernel())
+        kerns.append(_kernel())
         outs.append((_b(obs), _b(rew), _b(done)))
     return env, outs, kerns
 

@@ -15,11 +15,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from devmem import _example, _place, _vp
 import guard
 from test_adam_host import (ADAM_NETS, CLIPS, TAUS, adam_rule, adam_seed, bad_case, biases_of, flatten, lerp_rule, make_adam_case, order_case, same_step,
                             split, step_of, subnormal_case)
-from test_gpu_mlp import _place, _vp
-from test_gpu_mlp_backward import _example, _loss_inputs
+from test_gpu_mlp_backward import loss_inputs
 from test_mlp_backward_host import CHUNK, mlp_backward_rule, num_params
 
 pytestmark = pytest.mark.gpu
@@ -214,7 +214,7 @@ def test_device_adam_on_a_sequential_equals_the_rules_over_five_steps(which):
     hyper = dict(lr=1e-2, betas=(0.9, 0.99), eps=1e-8)
     opt = DeviceAdam(mlp, max_norm=0.5, target=tmlp, tau=0.005, **hyper)
     assert opt.sync_every_step and not DeviceAdam(mlp, target=tmlp).sync_every_step
-    loss_of = _loss_inputs(which, rows, A, dev)
+    loss_of = loss_inputs(which, rows, A, dev)
     x = torch.randn(rows, dims[0], generator=torch.Generator().manual_seed(5)).to(dev)
     theta, tgt, m, v = _flat_of(net), _flat_of(tnet), np.zeros(P, np.float32), np.zeros(P, np.float32)
     twin = state = None

@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from devmem import _place_floats, _shifts, _vp, short_env
 import guard
 import helpers
 from test_c51_host import ACTIONS, SORTS, SUPPORTS, bad_rows_of, c51_expect_rule, c51_rule, make_case
@@ -24,22 +25,6 @@ SIZES = (1, 2, 63, 64, 65, 257, 1031)                                # a wave ta
 OUTPUTS = ("a_star", "q_star", "bad_rows")
 
 
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _place(arr, offset, dev):
-    """(flat tensor, view of arr's shape in it): arr on the device, one float into a larger tensor when offset."""
-    import torch
-
-    flat = torch.full((arr.size + 9,), 7.0, dtype=torch.float32, device=dev)
-    at = 1 if offset else 0
-    view = flat[at:at + arr.size].view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert view.data_ptr() % 16 == (4 if offset else 0) and view.is_contiguous()
-    return flat, view
-
-
 def _call(K, vmin, vmax, case, select=True, want=OUTPUTS, offset=False):
     """One snac_c51_project and two snac_c51_expect calls (of p_next and of p_select) with their outputs in a guard arena -> dict of numpy
     arrays (None where not asked for)."""
@@ -48,7 +33,7 @@ def _call(K, vmin, vmax, case, select=True, want=OUTPUTS, offset=False):
 
     L, dev = _lib.lib(), torch.device("cuda", torch.cuda.current_device())
     B, A, _ = case["p_next"].shape
-    ins = {k: _place(case[k], offset, dev) for k in ("p_next", "p_select", "ret", "discount")}
+    ins = {k: _place_floats(case[k], offset, dev) for k in ("p_next", "p_select", "ret", "discount")}
     before = {k: flat.clone() for k, (flat, _) in ins.items()}
     arena = guard.Arena(B * (4 * K + 5 + 8 * A) + 4 + 8 * (guard.BAND + 1024), dev)
     off4, off1 = (4, 1) if offset else (0, 0)
@@ -98,16 +83,12 @@ def _want(case, vmin, vmax, select):
     return w
 
 
-def _shifts(B):
-    return range(len(SORTS)) if B <= 2 else (B % len(SORTS),)        # one or two samples take every sort in turn
-
-
 # ---- the kernels against the rule --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", SIZES)
 @pytest.mark.parametrize("A", ACTIONS)
 def test_both_kernels_equal_the_rule_byte_for_byte_and_write_nothing_else(A, B):
     for n, (K, vmin, vmax) in enumerate(SUPPORTS):
-        for shift in _shifts(B):
+        for shift in _shifts(B, SORTS):
             case = make_case(np.random.default_rng(10000 * n + 100 * A + B + shift), B, A, K, vmin, vmax, shift)
             for select, offset in ((True, False), (True, True), (False, True)):
                 want = _want(case, vmin, vmax, select)
@@ -173,10 +154,8 @@ def test_categorical_support_takes_an_envs_actions_device_and_stream():
     import torch
     from snac_amd import CategoricalSupport
 
-    from test_gpu_replay_nstep import _env
-
     for kind, A in ((1, 3), (2, 5), (3, 8)):
-        env, _ = _env(kind, 65, True, seed=3)
+        env, _ = short_env(kind, 65, True, seed=3)
         cs = CategoricalSupport(env, atoms=33, vmin=-100.0, vmax=300.0)
         assert cs.num_actions == env.num_actions == A and cs.device == env.device and cs.env is env
         case = make_case(np.random.default_rng(kind), 65, A, 33, -100.0, 300.0)

@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+from devmem import _raw, _tag
 import guard
 import helpers
 from test_explore_host import (ACTIONS, ALPHAS, bad_rows_of, dirichlet_rule, env_ids_of, gumbel_rule, make_counts, make_priors, make_temps,
@@ -171,10 +172,6 @@ GAMMA = 0.97
 RING = ("obs", "pi", "value", "action", "reward", "done", "move", "z")
 
 
-def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
-
-
 def _env(n, off=0, kind=2, **kw):
     """An env of n rows with base BASE + off over the kind's plan table, every plan fulfilled by its first 2 .. 5 bricks and a time limit
     of 6, so that episodes end at different moves."""
@@ -196,10 +193,6 @@ def _search(env, K=2, its=6, gumbel=None, cap=48):
                   evaluator=make_evaluator(env.num_actions, False), **kw)
     s.reset()
     return s
-
-
-def _raw(t):
-    return t.cpu().numpy().tobytes()
 
 
 @pytest.mark.parametrize("K", [1, 5])

@@ -35,6 +35,7 @@ import time
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import guard
 import helpers
 
@@ -144,12 +145,6 @@ def _flush_report(name, seconds):
     _REPORT.clear()
 
 
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
-
-
 def _allocations(views):
     """The outputs that a call of BatchedDMPEnv allocates itself (reset, observe, iou, transition, step without out=) come from the arena."""
     from snac_amd import batched
@@ -157,7 +152,7 @@ def _allocations(views):
     return guard.allocations(batched, views)
 
 
-def _tables(kind, dyn):
+def plan_tables(kind, dyn):
     table = helpers.plan_table(kind, dyn, ("sin_train" if kind == 1 else "dense_train") if dyn else "p0")[:16]
     return table, (table if kind == 1 else table.reshape(len(table), 26, 26))
 
@@ -169,7 +164,7 @@ class Case:
         import torch
         from snac_amd import BatchedDMPEnv
 
-        table, shaped = _tables(kind, dyn)
+        table, shaped = plan_tables(kind, dyn)
         mk = lambda: BatchedDMPEnv(kind, dyn, n, plans=shaped, seed=seed, env_id_base=7, total_step=5, obs_dtype=torch.float32 if f32 else torch.float64)  # noqa: E731
         self.env, self.sh = mk(), mk()
         self.orc = helpers.oracle().OracleBatch(kind, dyn, n, table, seed=seed, env_id_base=7)
@@ -488,7 +483,7 @@ def _state_case(kind, dyn, n, f32, weak=False, rows=16, seed=11):
 
     L = _lib.lib()
     sz = _lib.env_sizes(kind, dyn)
-    table, shaped = _tables(kind, dyn)
+    table, shaped = plan_tables(kind, dyn)
     table, shaped = table[:rows], shaped[:rows]
     packed, tb = plans.pack_plans(kind, np.array(shaped, np.float64))
     P = len(packed)

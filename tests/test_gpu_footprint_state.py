@@ -19,10 +19,10 @@ import pytest
 
 import guard
 import helpers
+from test_gpu_footprint import plan_tables
 import test_prio_host as ref
-from test_gpu_footprint import _tables
 from test_gpu_footprint_nodes import EDGES
-from test_gpu_prio import S, SEED, SAMPLER, _check, _priorities
+from test_gpu_prio import S, SAMPLER, SEED, check_tree, make_priorities
 
 pytestmark = pytest.mark.gpu
 
@@ -68,7 +68,7 @@ def test_priority_tree_writers(entries):
     w, mx = np.zeros(entries, np.uint32), 1 << S
 
     def check(what):
-        _check(tree, w, mx, what)
+        check_tree(tree, w, mx, what)
         A.check()
 
     check("init")
@@ -77,7 +77,7 @@ def test_priority_tree_writers(entries):
         if n >= 64:                                                    # out of range on both sides, and duplicates with different priorities
             idx[[3, 17, 40, 41]] = (-1, entries, -(1 << 31), (1 << 31) - 1)
             idx[50:56] = idx[20]
-        p = _priorities(rng, n)
+        p = make_priorities(rng, n)
         if n == 1:
             p[0] = 0.75
         index = A.carve((n,), torch.int32, name="index (input) n = %d" % n).copy_(torch.from_numpy(idx))
@@ -124,7 +124,7 @@ def restore(env, saved):
 def _env(kind, n, seed=11, rows=TABLE_ROWS, ticks=4):
     from snac_amd import BatchedDMPEnv
 
-    _, shaped = _tables(kind, True)
+    _, shaped = plan_tables(kind, True)
     env = BatchedDMPEnv(kind, True, n, plans=shaped[:rows], seed=seed, total_step=12)
     env.reset()
     env.rollout(ticks, obs=None)

@@ -25,8 +25,8 @@ import time
 
 import pytest
 
+from devmem import _env
 import guard
-from test_gpu_uct_paths import _env
 from test_gpu_uct_puct import make_evaluator
 
 pytestmark = pytest.mark.gpu

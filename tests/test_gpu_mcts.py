@@ -19,7 +19,7 @@ def _tag(dim, dyn):
     return ("dense_train" if dim > 1 else "sin_train") if dyn else ("p1" if dim == 3 else "p0")
 
 
-def _same_state(env, orc, rows=None):
+def same_state(env, orc, rows=None):
     st = orc.state()
     rows = np.arange(orc.n) if rows is None else np.asarray(rows)
     mem = env.environment_memory().cpu().numpy().reshape(env.num_envs, -1)
@@ -51,7 +51,7 @@ def test_transition_matches_oracle(dim, dyn):
     orc = helpers.oracle().OracleBatch(dim, dyn, pool, table, seed=seed)
     env.reset(); orc.reset()
     env.rollout(23, obs=None); orc.rollout(23, obs=None)
-    _same_state(env, orc)
+    same_state(env, orc)
     stats0 = env.episodic_stats()
     rng = np.random.default_rng(100 + dim)
     A = env.num_actions
@@ -76,14 +76,14 @@ def test_transition_matches_oracle(dim, dyn):
         assert o.cpu().numpy().tobytes() == oo.tobytes() and r.cpu().numpy().tobytes() == ro.tobytes()
         assert np.array_equal(d.cpu().numpy().astype(np.uint8), do)
     assert used <= pool
-    _same_state(env, orc)
+    same_state(env, orc)
     assert env.episodic_stats() == stats0                       # a search is not an episode
     # identity form (no index arrays) on the first m rows, no observation wanted
     acts = rng.integers(0, A, 500).astype(np.int8)
     o, r, d = env.transition(acts, want_obs=False)
     _, ro, do = orc.transition(acts)
     assert o is None and r.cpu().numpy().tobytes() == ro.tobytes() and np.array_equal(d.cpu().numpy().astype(np.uint8), do)
-    _same_state(env, orc)
+    same_state(env, orc)
     # the pool keeps working as an env batch afterwards
     oe, re_, de = env.step(auto_reset=True)
     oo, ro, do = orc.step(env.t - 1, auto_reset=True)
@@ -191,7 +191,7 @@ def test_import_states_matches_oracle_set_state():
         env.import_states(pos if dim != 1 else pos[:, 0], cb, cs, mem, plan_idx=pidx)
         for i in range(n):
             orc.set_state(i, mem[i].astype(np.int32), int(pos[i, 0]) if dim == 1 else pos[i], int(cb[i]), int(cs[i]), plan_idx=int(pidx[i]))
-        _same_state(env, orc)
+        same_state(env, orc)
         assert env.iou().cpu().numpy().tobytes() == orc.iou().tobytes()
         acts = rng.integers(0, env.num_actions, n).astype(np.int8)
         ks = rng.integers(1, 4, n).astype(np.int8)
@@ -199,7 +199,7 @@ def test_import_states_matches_oracle_set_state():
         oo, ro, do = orc.transition(acts, ks)
         assert o.cpu().numpy().tobytes() == oo.tobytes() and r.cpu().numpy().tobytes() == ro.tobytes()
         assert np.array_equal(d.cpu().numpy().astype(np.uint8), do)
-        _same_state(env, orc)
+        same_state(env, orc)
         assert env.iou().cpu().numpy().tobytes() == orc.iou().tobytes()
 
 

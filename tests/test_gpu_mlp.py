@@ -16,31 +16,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from devmem import _place, _vp
 import guard
-from test_mlp_host import HEADS, NETS, _same, bad_rows_of, case_seed, derived_bound, make_mlp_case, rows_of, rule_of, shifts_of
+from specmath import _same
+from test_mlp_host import HEADS, NETS, bad_rows_of, case_seed, derived_bound, make_mlp_case, rows_of, rule_of, shifts_of
 
 pytestmark = pytest.mark.gpu
 
 OUTPUTS = ("priors", "value", "logits", "bad_rows")
 
 
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _place(arr, offset, dev):
-    """(flat tensor, view of arr's shape in it): arr on the device, one element into a larger tensor when offset."""
-    import torch
-
-    flat = torch.zeros((arr.size + 9,), dtype=torch.from_numpy(arr).dtype, device=dev)
-    at = 1 if offset else 0
-    view = flat[at:at + arr.size].view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert view.data_ptr() % 16 == (arr.itemsize if offset else 0) and view.is_contiguous()
-    return flat, view
-
-
-class _Placed:
+class PlacedNet:
     """A case's network and rows on the device, and the descriptor that points at them."""
 
     def __init__(self, case, f64, offset):
@@ -73,7 +59,7 @@ def _forward(case, f64, offset):
     import torch
     from snac_amd import _lib
 
-    p = _Placed(case, f64, offset)
+    p = PlacedNet(case, f64, offset)
     N = case["dims"][-1]
     arena = guard.Arena(p.rows * N * 4 + 16 + 3 * (guard.BAND + 1024), p.dev)
     y = arena.carve((p.rows, N), torch.float32, offset=4 if offset else 0, name="y")
@@ -89,7 +75,7 @@ def _policy_value(case, f64, offset, want=OUTPUTS):
     import torch
     from snac_amd import _lib
 
-    p = _Placed(case, f64, offset)
+    p = PlacedNet(case, f64, offset)
     A, rows = case["A"], p.rows
     arena = guard.Arena(rows * (8 * A + 16) + 64 + 6 * (guard.BAND + 1024), p.dev)
     off4, off8 = (4, 8) if offset else (0, 0)
@@ -170,7 +156,7 @@ def test_null_outputs_stay_untouched_and_the_others_unchanged():
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------------------------
-def _module(case, dev):
+def module_of(case, dev):
     import torch
 
     mods = []
@@ -192,7 +178,7 @@ def test_device_mlp_follows_the_rule_and_the_parameters_in_place(dims, A):
     rows = 257
     case = make_mlp_case(np.random.default_rng(case_seed(dims, rows, 2)), dims, rows, A, 2)
     want = rule_of(case)
-    net = _module(case, dev)
+    net = module_of(case, dev)
     mlp = DeviceMLP(net, A)
     assert mlp.device == dev and mlp.dims == tuple(dims) and mlp.num_actions == A
     for dtype in (torch.float32, torch.float64):
@@ -242,7 +228,7 @@ def test_the_module_in_float64_torch_stays_within_the_derived_bound():
     case = make_mlp_case(np.random.default_rng(case_seed(dims, rows, 1)), dims, rows, A, 1)
     out = rule_of(case)
     good = ~out["bad"] & np.isfinite(out["y"]).all(axis=1)
-    net = _module(case, dev)
+    net = module_of(case, dev)
     x = torch.from_numpy(case["x"]).to(dev).to(torch.float32)
     y = DeviceMLP(net, A).forward(x).cpu().numpy()[good].astype(np.float64)
     with torch.no_grad():

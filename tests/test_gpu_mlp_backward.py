@@ -13,18 +13,17 @@ written between forward and backward and of a double backward, the module in flo
 examples for a few ticks."""
 import copy
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
+from devmem import _example, _place, _vp
 import guard
-import helpers
-from test_gpu_mlp import _Placed, _module, _place, _vp
+from specmath import _same
+from test_gpu_mlp import PlacedNet, module_of
 from test_mlp_backward_host import (CHUNK, DIMS, accumulate_case, autograd_reference, backward_bound, backward_of, backward_seed, bound_case, layer_views,
                                     make_backward_case, mlp_backward_rule, num_params, work_bytes_formula)
-from test_mlp_host import WIDE, _same
+from test_mlp_host import WIDE
 
 pytestmark = pytest.mark.gpu
 
@@ -38,7 +37,7 @@ def _backward(case, f64, offset, accumulate, g_old):
     import torch
     from snac_amd import _lib
 
-    p = _Placed(case, f64, offset)
+    p = PlacedNet(case, f64, offset)
     dims = case["dims"]
     P = num_params(dims)
     gy_flat, gy = _place(case["grad_y"], offset, p.dev)
@@ -114,7 +113,7 @@ def _rule_of_module(net, x, grad_y, **kw):
                              grad_y.cpu().numpy(), CHUNK, **kw)["flat"]
 
 
-def _loss_inputs(which, rows, A, dev):
+def loss_inputs(which, rows, A, dev):
     """A loss of the outputs y [rows, A (+ 1)] as a function y -> 0-dim tensor, from fixed random minibatch tensors."""
     import torch
     from snac_amd import PPOLoss, SearchLoss, TDLoss
@@ -144,10 +143,10 @@ def test_train_forward_with_the_device_losses_gives_the_rules_gradients(which):
     A, rows = 5, CHUNK + 1
     dims = (51, 64, A) if which == "td" else (51, 64, A + 1)
     case = make_backward_case(np.random.default_rng(backward_seed(dims, rows) + 5), dims, rows, cancel=False)
-    net = _module(case, dev)
+    net = module_of(case, dev)
     mlp = DeviceMLP(net)
     assert mlp.num_params == num_params(dims)
-    loss_of = _loss_inputs(which, rows, A, dev)
+    loss_of = loss_inputs(which, rows, A, dev)
     for dtype in (torch.float32, torch.float64):
         x = torch.from_numpy(case["x"]).to(dev).to(dtype)
         plain = mlp.forward(x)
@@ -182,7 +181,7 @@ def test_an_adam_step_between_two_calls_is_seen_by_the_next_and_any_torch_loss_w
     dev = torch.device("cuda", torch.cuda.current_device())
     dims, rows = (51, 65, 1, 9), 33
     case = make_backward_case(np.random.default_rng(backward_seed(dims, rows) + 7), dims, rows, cancel=False)
-    net = _module(case, dev)
+    net = module_of(case, dev)
     mlp = DeviceMLP(net)
     opt = torch.optim.Adam(net.parameters(), lr=1e-2)
     x = torch.from_numpy(case["x"]).to(dev)
@@ -213,7 +212,7 @@ def test_a_parameter_written_between_forward_and_backward_and_a_double_backward_
     dev = torch.device("cuda", torch.cuda.current_device())
     dims, rows = (7, 5, 4), 17
     case = make_backward_case(np.random.default_rng(backward_seed(dims, rows) + 9), dims, rows, cancel=False)
-    net = _module(case, dev)
+    net = module_of(case, dev)
     mlp = DeviceMLP(net)
     x = torch.from_numpy(case["x"]).to(dev)
     for p in net.parameters():
@@ -242,7 +241,7 @@ def test_the_module_in_float64_torch_stays_within_the_derived_bound():
     dims = (51, 64, 6)
     case, generated = bound_case(dims)
     assert len(case["x"]) >= 128 and generated - len(case["x"]) <= 0.02 * generated
-    net = _module(case, dev)
+    net = module_of(case, dev)
     x = torch.from_numpy(case["x"]).to(dev).to(torch.float32)
     grad_y = torch.from_numpy(case["grad_y"]).to(dev)
     flat, _ = DeviceMLP(net).backward(x, grad_y)
@@ -259,13 +258,6 @@ def test_the_module_in_float64_torch_stays_within_the_derived_bound():
 
 
 # ---- the examples ------------------------------------------------------------------------------------------------------------------------
-def _example(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(helpers.ROOT, "examples", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 @pytest.mark.parametrize("device_loss", (False, True))
 def test_the_dqn_example_with_the_device_backward_finishes_with_finite_losses(device_loss):
     mod = _example("dqn_batched")

@@ -94,7 +94,7 @@ def test_pack_unpack_round_trip_and_decoded_fields(kind, dyn):
 @pytest.mark.parametrize("kind,dyn", KINDS)
 def test_edges_on_node_records_equal_the_batch_pool_and_the_oracle(kind, dyn, f32):
     import torch
-    from test_gpu_mcts import _same_state
+    from test_gpu_mcts import same_state
 
     pool, roots = 6000, 500
     env, twin, orc, nodes, torch = _pools(kind, dyn, pool, 11, torch.float32 if f32 else None)
@@ -126,7 +126,7 @@ def test_edges_on_node_records_equal_the_batch_pool_and_the_oracle(kind, dyn, f3
     _same_records(nodes, twin)
     # back into a batch: the unpacked rows are the oracle's states; observe works on them
     nodes.store()
-    _same_state(env, orc)
+    same_state(env, orc)
     assert torch.equal(env._hdr, twin._hdr) and torch.equal(env._grid, twin._grid) and torch.equal(env.observe(), twin.observe())
 
 

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from devmem import _tag
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -13,10 +14,6 @@ pytestmark = pytest.mark.gpu
 KINDS = [(1, False), (1, True), (2, False), (2, True), (3, False), (3, True)]
 T0 = {1: 37, 2: 600, 3: 21}                                         # pre-rollout: some rows end on a terminal step (as test_gpu_mcts.py)
 H = {1: 300, 2: 700, 3: 400}                                        # horizons long enough for most leaves to end, not all
-
-
-def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
 
 
 def _env(kind, dyn, n, seed, **kw):

@@ -4,15 +4,12 @@ ones (SNAC_FLAG_NEED_RESET) included.  The records come from a few hundred rando
 import numpy as np
 import pytest
 
+from devmem import _tag
 import helpers
 
 pytestmark = pytest.mark.gpu
 
 KINDS = [(1, False), (1, True), (2, False), (2, True), (3, False), (3, True)]
-
-
-def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
 
 
 def _make(kind, dyn, n, f32, seed):

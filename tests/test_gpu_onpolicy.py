@@ -13,19 +13,16 @@ import os
 import numpy as np
 import pytest
 
+from devmem import _vp, short_env
 import guard
 import helpers
-from test_gpu_replay_nstep import _constructed, _env, _equal, _stack
+from test_gpu_replay_nstep import constructed_ring, equal_gather, stack_rows
 from test_onpolicy_host import GAMMA, LAM, SIZES, gae_rule, make_span, onpolicy_rule, span_cases, span_seed, span_slots
 from test_replay_nstep_host import FILLS, addressable, ring_seed
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("s", "action", "value", "logp", "adv", "ret")
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 # ---- snac_gae -----------------------------------------------------------------------------------------------------------------------
@@ -63,7 +60,7 @@ def _buffer(env, cells, layout, cap, head, ticks, seed):
     from snac_amd import RolloutBuffer
 
     buf = RolloutBuffer(env, cap - 1, GAMMA, LAM, layout=layout)
-    buf.ring, R = _constructed(env, cells, layout, cap, head, ticks, seed)
+    buf.ring, R = constructed_ring(env, cells, layout, cap, head, ticks, seed)
     rng = np.random.default_rng(seed + 1)
     V = {k: (10.0 * rng.normal(size=(cap, env.num_envs))).astype(np.float32) for k in ("value", "logp", "adv", "ret")}
     for k, v in V.items():
@@ -87,20 +84,20 @@ def _check_buffer(buf, R, V, norm, rng):
         got = buf.gather(slot, env, normalise=normalise)
         assert "s_next" not in got
         assert got["s"].cpu().numpy().tobytes() == old["s"].cpu().numpy().tobytes() and got["plan"].cpu().numpy().tobytes() == old["plan"].cpu().numpy().tobytes()
-        _equal(got, _stack(rows[normalise], KEYS + ("plan",)), KEYS + ("plan",), "all, normalise %s" % normalise)
+        equal_gather(got, stack_rows(rows[normalise], KEYS + ("plan",)), KEYS + ("plan",), "all, normalise %s" % normalise)
     for B, with_plan, normalise in ((1, False, True), (5, True, False), (67, False, False), (67, True, True)):
         pick = rng.integers(0, len(pairs), B)
         got = buf.gather(slot[pick], env[pick], normalise=normalise, with_plan=with_plan)
         keys = KEYS + (("plan",) if with_plan else ())
         assert ("plan" in got) == with_plan
-        _equal(got, _stack([rows[normalise][j] for j in pick], keys), keys, "batch %d" % B)
+        equal_gather(got, stack_rows([rows[normalise][j] for j in pick], keys), keys, "batch %d" % B)
 
 
 @pytest.mark.parametrize("N,layout", [(5, "ticks"), (70, "ticks"), (70, "tiled")])
 @pytest.mark.parametrize("f32", [False, True], ids=["f64ring", "f32ring"])
 @pytest.mark.parametrize("kind", [1, 2, 3])
 def test_constructed_rings_equal_the_rule_and_the_existing_gather(kind, f32, N, layout):
-    env, cells = _env(kind, N, f32)
+    env, cells = short_env(kind, N, f32)
     rng = np.random.default_rng(kind)
     for cap, head, ticks in FILLS:
         _check_buffer(*_buffer(env, cells, layout, cap, head, ticks, ring_seed(kind, f32, N, cap, head)), rng)
@@ -108,7 +105,7 @@ def test_constructed_rings_equal_the_rule_and_the_existing_gather(kind, f32, N, 
 
 @pytest.mark.parametrize("kind,layout", [(1, "ticks"), (2, "tiled")])
 def test_constructed_rings_with_the_position_tail(kind, layout):
-    env, cells = _env(kind, 70, False, obs_tail=("position",))
+    env, cells = short_env(kind, 70, False, obs_tail=("position",))
     assert env.obs_dim == (8 if kind == 1 else 53)
     _check_buffer(*_buffer(env, cells, layout, 7, 3, 10, 41 + kind), np.random.default_rng(9))
 
@@ -123,7 +120,7 @@ def test_the_gather_writes_nothing_outside_its_outputs(kind, layout):
     from snac_amd import RolloutBuffer, onpolicy
 
     for f32 in (False, True):
-        env, _ = _env(kind, 67, f32)
+        env, _ = short_env(kind, 67, f32)
         buf = RolloutBuffer(env, 7, GAMMA, LAM, layout=layout)
         gen = torch.Generator().manual_seed(kind)
         for _ in range(7):
@@ -159,7 +156,7 @@ def test_rollout_buffer_on_real_envs(kind, layout):
     from snac_amd import RolloutBuffer
 
     N, H = 200, 29
-    env, _ = _env(kind, N, True)
+    env, _ = short_env(kind, N, True)
     buf = RolloutBuffer(env, H, GAMMA, LAM, layout=layout)
     gen = torch.Generator().manual_seed(kind)
     with pytest.raises(ValueError, match="needs 29 ticks"):

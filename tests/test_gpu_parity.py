@@ -4,15 +4,12 @@ float64 observation scalars are single IEEE divisions (compared as raw bytes).""
 import numpy as np
 import pytest
 
+from devmem import _ids
 import helpers
 
 pytestmark = pytest.mark.gpu
 
 KINDS = [(1, False), (1, True), (2, False), (2, True), (3, False), (3, True)]
-
-
-def _ids(v):
-    return "%dd_%s" % (v[0], "dyn" if v[1] else "sta") if isinstance(v, tuple) else str(v)
 
 
 def _table(dim, dyn):
@@ -40,7 +37,7 @@ def _same_bits(a, b):
     return a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
-def _check_state(env, orc):
+def check_state(env, orc):
     st = orc.state()
     H, W = (1, 34) if env.kind == 1 else (26, 26)
     mem = env.environment_memory().cpu().numpy()
@@ -86,7 +83,7 @@ def test_step_explicit_inputs_vs_oracle(kind):
         assert _same_bits(og.cpu().numpy(), oc), (kind, t)
         assert _same_bits(rg.cpu().numpy(), rc), (kind, t)
         assert np.array_equal(dg.cpu().numpy().astype(np.uint8), dc), (kind, t)
-    _check_state(env, orc)
+    check_state(env, orc)
     assert _same_bits(env.observe().cpu().numpy(), _observe_all(orc))
 
 
@@ -112,7 +109,7 @@ def test_rollout_counter_rng_vs_oracle(kind):
     assert _same_bits(og.cpu().numpy(), oc)
     assert _same_bits(rg.cpu().numpy(), rc)
     assert np.array_equal(dg.cpu().numpy().astype(np.uint8), dc)
-    _check_state(env, orc)
+    check_state(env, orc)
     # a second launch continues the same streams (tick t0 = T) and equals stepping one by one
     og, rg, dg = env.rollout(37, obs="last")
     oc, rc, dc = orc.rollout(37, t0=T, obs="last", nthreads=8)
@@ -121,7 +118,7 @@ def test_rollout_counter_rng_vs_oracle(kind):
         og, rg, dg = env.step(auto_reset=True)
         oc, rc, dc = orc.step(T + 37 + t, auto_reset=True)
         assert _same_bits(og.cpu().numpy(), oc) and _same_bits(rg.cpu().numpy(), rc)
-    _check_state(env, orc)
+    check_state(env, orc)
 
 
 @pytest.mark.parametrize("kind", KINDS, ids=_ids)
@@ -244,7 +241,7 @@ def test_3d_plan_table_paths(dyn):
             assert _same_bits(og.cpu().numpy(), oc) and _same_bits(rg.cpu().numpy(), rc)
             assert np.array_equal(dg.cpu().numpy().astype(np.uint8), dc)
             t0 += T
-        _check_state(env, orc)
+        check_state(env, orc)
 
 
 @pytest.mark.parametrize("kind", KINDS, ids=_ids)

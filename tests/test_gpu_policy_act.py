@@ -6,24 +6,17 @@ policy_rule, with every output carved from a guard arena: nothing lands outside 
 output is not written, the count of bad rows is exact.  `scores` is also taken one float into a larger tensor (a base aligned to 4 bytes
 only).  Then sharding, the Python surface, RolloutBuffer.act_logits against act() fed with the rule's arrays, and the two examples."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
+from devmem import _example, _vp, short_env
 import guard
-import helpers
-from test_gpu_replay_nstep import _env
 from test_policy_act_host import ACTIONS, CATEGORICAL, EPS_GREEDY, GREEDY, bad_rows_of, make_scores, policy_rule
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 63, 64, 65, 257, 4099)                                   # ragged waves, several blocks, a ragged last block
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _desc(kind, seed, base):
@@ -148,7 +141,7 @@ def test_sample_actions_and_epsilon_greedy_follow_env_t(kind):
     import torch
 
     N = 65
-    env, _ = _env(kind, N, True, seed=9, env_id_base=1000)
+    env, _ = short_env(kind, N, True, seed=9, env_id_base=1000)
     A, ids = env.num_actions, 1000 + np.arange(N, dtype=np.uint64)
     scores = make_scores(np.random.default_rng(kind), N, A)
     logits = torch.from_numpy(scores).to(env.device)
@@ -188,7 +181,7 @@ def test_act_logits_equals_act_with_the_rules_arrays():
     from snac_amd import RolloutBuffer
 
     N, H, kind = 65, 4, 2
-    bufs = [RolloutBuffer(_env(kind, N, True, seed=5)[0], H, 0.97, 0.9) for _ in range(2)]
+    bufs = [RolloutBuffer(short_env(kind, N, True, seed=5)[0], H, 0.97, 0.9) for _ in range(2)]
     rng = np.random.default_rng(4)
     for tick in range(H):
         scores, value = make_scores(rng, N, 5, tick), rng.normal(size=N).astype(np.float32)
@@ -210,13 +203,6 @@ def test_act_logits_equals_act_with_the_rules_arrays():
 
 
 # ---- the examples ------------------------------------------------------------------------------------------------------------------------
-def _example(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(helpers.ROOT, "examples", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_the_ppo_example_with_device_sampling_repeats_itself():
     mod = _example("ppo_batched")
     runs = [mod.run(envs=256, iterations=2, horizon=8, epochs=1, batch=1024, device_sampling=True, log=lambda line: None) for _ in range(2)]

@@ -3,15 +3,14 @@
 every output in a guard arena; against the per-tick composition of the entry points that were there before; across shards; and through
 BatchedDMPEnv.rollout_policy, ReplayRing.collect_policy, RolloutBuffer.collect_policy and the two examples."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
+from devmem import _example, _vp
 import guard
 import helpers
-from test_gpu_parity import _check_state
+from test_gpu_parity import check_state
 from test_policy_act_host import ACTIONS, CATEGORICAL, EPS_GREEDY, GREEDY
 from test_policy_rollout_host import (CASES, OBS_ALL, OBS_LAST, OBS_NONE, PRELUDE_TICKS, TOTAL_STEP, case_id, make_net, make_rollout_case, plan_cells,
                                       plan_table, rollout_rule, start)
@@ -20,10 +19,6 @@ pytestmark = pytest.mark.gpu
 
 OUTPUTS = ("obs", "reward", "done", "actions", "step_size", "plan_idx", "first", "value", "logp", "entropy")
 MODE_NAMES = {CATEGORICAL: "categorical", GREEDY: "greedy", EPS_GREEDY: "eps_greedy"}
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _env(kind, dyn, N, f32, seed, base=0, started=True):
@@ -139,7 +134,7 @@ def test_the_launch_equals_the_rule_byte_for_byte_and_writes_nothing_else(case):
     _same(got, c, case)
     assert bad == c["want"]["bad_rows"]
     assert env.t == PRELUDE_TICKS                                    # the entry point knows nothing of env.t
-    _check_state(env, c["orc"])                                      # headers, grids, episode counters, episodic sums: the rule's
+    check_state(env, c["orc"])                                       # headers, grids, episode counters, episodic sums: the rule's
 
 
 def test_each_optional_output_may_be_null():
@@ -152,7 +147,7 @@ def test_each_optional_output_may_be_null():
             assert bad == c["want"]["bad_rows"]
         got, bad, env = _call(case, want=())                         # nothing but the state and bad_rows
         assert all(v is None for v in got.values())
-        _check_state(env, c["orc"])
+        check_state(env, c["orc"])
 
 
 # ---- through BatchedDMPEnv.rollout_policy ------------------------------------------------------------------------------------------------
@@ -218,7 +213,7 @@ def test_rollout_policy_equals_the_rule_and_the_composition_of_the_existing_entr
     assert env.t == PRELUDE_TICKS + T and res["done"].dtype == torch.bool
     _same({k: v.cpu().numpy() for k, v in res.items()}, c, case)
     assert int(env.policy_bad_rows.cpu()[0]) == c["want"]["bad_rows"]
-    _check_state(env, c["orc"])
+    check_state(env, c["orc"])
     # per tick, with the entry points that were there before: masked reset, observe, forward, draw, step
     twin = _env(kind, dyn, N, f32, c["seed"])
     mlp, A = _mlp(c, twin), twin.num_actions
@@ -297,7 +292,7 @@ def test_the_weights_are_read_in_place_at_every_call():
         assert got["obs"].cpu().numpy().tobytes() == want["obs"].astype(np.float32 if f32 else np.float64).tobytes()
     stale = rollout_rule(_oracle_after(kind, dyn, N, c, T), cells, c["weights"], c["biases"], T, PRELUDE_TICKS + T, GREEDY, 0.0, c["seed"])
     assert stale["actions"].tobytes() != w2["actions"].tobytes()     # the old weights would have acted otherwise
-    _check_state(env, orc)
+    check_state(env, orc)
 
 
 def _oracle_after(kind, dyn, N, c, T):
@@ -326,7 +321,7 @@ def test_collect_policy_across_a_ring_wrap_equals_appending_the_rules_actions():
         assert getattr(rings[0], name).cpu().numpy().tobytes() == getattr(rings[1], name).cpu().numpy().tobytes(), name
     assert torch.equal(rings[0].tree.weights(), rings[1].tree.weights())
     assert _state_bytes(envs[0]) == _state_bytes(envs[1])
-    _check_state(envs[0], c["orc"])
+    check_state(envs[0], c["orc"])
     with pytest.raises(ValueError, match="layout='ticks'"):
         ReplayRing(envs[1], 8, layout="tiled").collect_policy(mlp, 2)
 
@@ -366,13 +361,6 @@ def test_the_buffers_collect_policy_equals_act_logits_tick_by_tick():
 
 
 # ---- the examples ------------------------------------------------------------------------------------------------------------------------
-def _example(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(helpers.ROOT, "examples", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_the_ppo_example_with_the_device_rollout_finishes_with_finite_losses():
     losses, returns = _example("ppo_batched").run(envs=256, iterations=2, horizon=8, epochs=1, batch=1024, device_rollout=True, log=lambda line: None)
     assert len(losses) == 2 * 2 and all(np.isfinite(losses)) and len(returns) == 2

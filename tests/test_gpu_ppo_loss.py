@@ -18,31 +18,17 @@ import os
 import numpy as np
 import pytest
 
+from devmem import _equal, _place, _shifts, _vp, short_env
 import guard
 import helpers
-from test_ppo_loss_host import ACTIONS, CLIP, CLIP_VFS, ENT_COEF, SORTS, VF_COEF, _same, bad_rows_of, make_case, rule_of
+from specmath import _same
+from test_ppo_loss_host import ACTIONS, CLIP, CLIP_VFS, ENT_COEF, SORTS, VF_COEF, bad_rows_of, make_case, rule_of
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 2, 63, 64, 65, 257, 4095, 4096, 4097, 8193)              # a block is one wave of 64 samples; 64 waves fill the second kernel once
 OUTPUTS = ("loss", "grad_logits", "grad_value", "stats", "mean_loss", "bad_rows")
 INPUTS = ("logits", "action", "logp", "adv", "value", "value_old", "ret")
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _place(arr, offset, dev):
-    """(flat tensor, view of arr's shape in it): arr on the device, one element into a larger tensor when offset."""
-    import torch
-
-    flat = torch.zeros((arr.size + 9,), dtype=torch.from_numpy(arr).dtype, device=dev)
-    at = 1 if offset else 0
-    view = flat[at:at + arr.size].view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert view.data_ptr() % 16 == (arr.itemsize if offset else 0) and view.is_contiguous()
-    return flat, view
 
 
 def _call(case, clip_vf, want=OUTPUTS, offset=False, scale=1.0):
@@ -85,26 +71,11 @@ def _call(case, clip_vf, want=OUTPUTS, offset=False, scale=1.0):
     return got
 
 
-def _equal(got, want, what):
-    for k in OUTPUTS + ("partials",):
-        g = got[k]
-        if g is None:
-            continue
-        if k == "bad_rows":
-            assert int(g[0]) == want[k], (what, k, int(g[0]), want[k])
-        else:
-            _same(g, np.ascontiguousarray(want[k]), (what, k))
-
-
-def _shifts(B):
-    return range(len(SORTS)) if B <= 2 else (B % len(SORTS),)        # one or two samples take every sort in turn
-
-
 # ---- the kernels against the rule --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", SIZES)
 @pytest.mark.parametrize("A", ACTIONS)
 def test_the_kernels_equal_the_rule_byte_for_byte_and_write_nothing_else(A, B):
-    for shift in _shifts(B):
+    for shift in _shifts(B, SORTS):
         case = make_case(np.random.default_rng(100 * A + B + shift), B, A, shift)
         for clip_vf in CLIP_VFS:
             want = rule_of(case, clip_vf, 1.0 / B)
@@ -112,7 +83,7 @@ def test_the_kernels_equal_the_rule_byte_for_byte_and_write_nothing_else(A, B):
             first = None
             for offset in (False, True):                             # both placements; and two runs give the same bytes
                 got = _call(case, clip_vf, offset=offset, scale=1.0 / B)
-                _equal(got, want, (A, B, shift, clip_vf, offset))
+                _equal(got, want, (A, B, shift, clip_vf, offset), OUTPUTS)
                 if first is not None:
                     for k, g in got.items():
                         assert g.tobytes() == first[k].tobytes(), (A, B, shift, clip_vf, k)
@@ -131,7 +102,7 @@ def test_every_subset_of_null_outputs_leaves_them_untouched_and_the_others_uncha
                     continue                                         # mean_loss is stats[0]: refused, on the host
                 calls += 1
                 expect = dict(want, bad_rows=want["bad_rows"] if subset else 0)      # nothing asked for: nothing is launched, nothing counted
-                _equal(_call(case, clip_vf, want=subset, offset=bool(n % 2), scale=1.0 / B), expect, (clip_vf, subset))
+                _equal(_call(case, clip_vf, want=subset, offset=bool(n % 2), scale=1.0 / B), expect, (clip_vf, subset), OUTPUTS)
         assert calls == 48
 
 
@@ -237,10 +208,8 @@ def test_ppo_loss_takes_an_envs_actions_device_and_stream():
     import torch
     from snac_amd import PPOLoss
 
-    from test_gpu_replay_nstep import _env
-
     for kind, A in ((1, 3), (2, 5), (3, 8)):
-        env, _ = _env(kind, 65, True, seed=3)
+        env, _ = short_env(kind, 65, True, seed=3)
         ppo = PPOLoss(env)
         assert ppo.num_actions == env.num_actions == A and ppo.device == env.device and ppo.env is env
         case = make_case(np.random.default_rng(kind), 65, A)

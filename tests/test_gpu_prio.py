@@ -8,8 +8,8 @@ levels, each with a ragged last group."""
 import numpy as np
 import pytest
 
+from devmem import _env
 import test_prio_host as ref
-from test_gpu_uct_paths import _env
 from test_gpu_uct_puct import make_evaluator
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +31,7 @@ def image(entries, w, max_weight):
     return buf
 
 
-def _check(tree, w, max_weight, what):
+def check_tree(tree, w, max_weight, what):
     got = tree.buffer.cpu().numpy()
     want = image(tree.entries, w, max_weight)
     assert got.shape == want.shape, what
@@ -55,7 +55,7 @@ def _dev(a, dtype=None):
 SPECIAL = np.float32([0.0, np.nan, -1.0, 1e-9, 1e9, 1.0, 0.5, 2.5 / 65536, np.inf, -0.0])
 
 
-def _priorities(rng, n):
+def make_priorities(rng, n):
     p = (rng.random(n) * 4.0).astype(np.float32)
     k = rng.random(n) < 0.4                                          # the special values, each of them for n >= 64
     p[k] = SPECIAL[rng.integers(0, len(SPECIAL), int(k.sum()))]
@@ -71,7 +71,7 @@ def test_init_update_and_fill_equal_the_reference(entries):
     tree = _tree(entries)
     assert (tree.bytes, tree.levels) == ref.layout(entries)[:2] and tree.levels == SIZES.index(entries) + 1
     w, mx = np.zeros(entries, np.uint32), 1 << S
-    _check(tree, w, mx, "init")
+    check_tree(tree, w, mx, "init")
     assert tree.weights().dtype == torch.uint32 and tuple(tree.weights().shape) == (entries,)
     assert tree.total() == 0 and tree.max_priority() == 1.0 and tree.head() == [1 << S, entries, tree.levels]
     for n in (1, 64, 65, 4096):
@@ -79,12 +79,12 @@ def test_init_update_and_fill_equal_the_reference(entries):
         if n >= 64:                                                  # out of range on both sides, and duplicates with different priorities
             idx[[3, 17, 40, 41]] = (-1, entries, -(1 << 31), (1 << 31) - 1)
             idx[50:56] = idx[20]
-        p = _priorities(rng, n)
+        p = make_priorities(rng, n)
         if n == 1:
             p[0] = 0.75
         tree.update(_dev(idx), _dev(p))
         mx = max(mx, ref.apply_update(w, idx.astype(np.int64), p, S))
-        _check(tree, w, mx, "update n = %d" % n)
+        check_tree(tree, w, mx, "update n = %d" % n)
     assert mx == 0xFFFFFFFF and tree.max_priority() == 0xFFFFFFFF / 65536.0     # the clamp entered max_weight
     # duplicates: the largest weight wins wherever it stands in the batch, a zero among them included
     i, j = entries - 1, entries // 2
@@ -93,22 +93,22 @@ def test_init_update_and_fill_equal_the_reference(entries):
     tree.update(_dev(idx), _dev(p))
     ref.apply_update(w, idx.astype(np.int64), p, S)
     assert w[i] == (2 << S if i != j else 3 << S) and w[j] == 3 << S
-    _check(tree, w, mx, "duplicates")
+    check_tree(tree, w, mx, "duplicates")
     tree.update(_dev(np.int32([j, j])), _dev(np.float32([0.0, 0.0])))            # and only zeros: the entry leaves the draw
     w[j] = 0
-    _check(tree, w, mx, "zeros")
+    check_tree(tree, w, mx, "zeros")
     tree.update(_dev(np.zeros(0, np.int32)), _dev(np.zeros(0, np.float32)))      # the empty job
     tree.update(_dev(np.int32([-5, entries])), _dev(np.float32([7.0, 9.0])))     # nothing in range: nothing changes, max_weight neither
-    _check(tree, w, mx, "nothing in range")
+    check_tree(tree, w, mx, "nothing in range")
     # fill: a single entry, a span across a 64- and a 4096-entry boundary (as far as the tree goes), the whole tree
     spans = [(entries - 1, 1), (min(50, entries - 1), min(4100, entries - min(50, entries - 1))), (0, entries)]
     for first, count in spans:
         for p, weight in ((0.25, 1 << (S - 2)), (None, mx), (0.0, 0), (1e6, 0xFFFFFFFF), (1e-9, 1)):
             tree.fill(first, count, p)
             w[first:first + count] = weight
-            _check(tree, w, mx, "fill %d + %d with %r" % (first, count, p))      # max_weight follows update() only
+            check_tree(tree, w, mx, "fill %d + %d with %r" % (first, count, p))  # max_weight follows update() only
     tree.fill(0, 0)
-    _check(tree, w, mx, "the empty fill")
+    check_tree(tree, w, mx, "the empty fill")
     assert tree.total() == int(w.sum(dtype=np.uint64))
 
 
@@ -117,17 +117,17 @@ def test_fill_reads_the_largest_weight_on_the_device():
     tree.fill(0, 100)                                                # before any update: priority 1.0
     w = np.zeros(200, np.uint32)
     w[:100] = 1 << S
-    _check(tree, w, 1 << S, "fill before an update")
+    check_tree(tree, w, 1 << S, "fill before an update")
     tree.update(_dev(np.int32([150])), _dev(np.float32([0.5])))      # a smaller weight does not lower it
     w[150] = 1 << (S - 1)
     tree.fill(100, 10)
     w[100:110] = 1 << S
-    _check(tree, w, 1 << S, "fill after a smaller update")
+    check_tree(tree, w, 1 << S, "fill after a smaller update")
     tree.update(_dev(np.int32([151])), _dev(np.float32([2.5])))
     w[151] = 5 << (S - 1)
     tree.fill(110, 10)
     w[110:120] = 5 << (S - 1)
-    _check(tree, w, 5 << (S - 1), "fill after a larger update")
+    check_tree(tree, w, 5 << (S - 1), "fill after a larger update")
 
 
 def _weights_cases(entries, rng):

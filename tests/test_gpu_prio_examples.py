@@ -1,22 +1,13 @@
 """GPU: the two examples run with --prioritized -- prioritised sampling, importance-weighted losses and the priority updates on one
 stream, a few seconds -- and leave a tree whose priorities are the ones the training loop stored."""
-import importlib.util
 import math
-import os
 
 import numpy as np
 import pytest
 
-import helpers
+from devmem import _example
 
 pytestmark = pytest.mark.gpu
-
-
-def _example(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(helpers.ROOT, "examples", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_the_self_play_example_trains_with_prioritised_replay_and_reanalyse():

@@ -13,37 +13,20 @@ not change.  Then repeatability, the Python surface against the rule, the priori
 and the examples.  snac_c51_loss likewise on make_c51_case against c51_loss_rule: a ragged block, a full block, one sample in a second
 block, B = 4097 where a lane of the second stage adds two partials; K = 2, 33, 51, 64 and the three action counts."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
+from devmem import _equal, _example, _place, _shifts, _vp, short_env
 import guard
-import helpers
-from test_qloss_host import (ACTIONS, C51_INPUTS, C51_SORTS, DELTA, INPUTS, MODES, SORTS, _same, bad_rows_of, c51_bad_rows_of, c51_rule_of, make_c51_case,
-                             make_case, rule_of)
+from specmath import _same
+from test_qloss_host import (ACTIONS, C51_INPUTS, C51_SORTS, DELTA, INPUTS, MODES, SORTS, bad_rows_of, c51_bad_rows_of, c51_rule_of, make_c51_case, make_case,
+                             rule_of)
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 2, 63, 64, 65, 257, 4095, 4096, 4097, 8193)              # a block is one wave of 64 samples; 64 waves fill the second kernel once
 OUTPUTS = ("loss", "priority", "y_out", "grad_q", "stats", "mean_loss", "bad_rows")
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _place(arr, offset, dev):
-    """(flat tensor, view of arr's shape in it): arr on the device, one element into a larger tensor when offset."""
-    import torch
-
-    flat = torch.zeros((arr.size + 9,), dtype=torch.from_numpy(arr).dtype, device=dev)
-    at = 1 if offset else 0
-    view = flat[at:at + arr.size].view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert view.data_ptr() % 16 == (arr.itemsize if offset else 0) and view.is_contiguous()
-    return flat, view
 
 
 def _call(case, mode="double", weighted=True, delta=DELTA, want=OUTPUTS, offset=False, scale=1.0):
@@ -88,21 +71,6 @@ def _call(case, mode="double", weighted=True, delta=DELTA, want=OUTPUTS, offset=
     return got
 
 
-def _equal(got, want, what):
-    for k in OUTPUTS + ("partials",):
-        g = got[k]
-        if g is None:
-            continue
-        if k == "bad_rows":
-            assert int(g[0]) == want[k], (what, k, int(g[0]), want[k])
-        else:
-            _same(g, np.ascontiguousarray(want[k]), (what, k))
-
-
-def _shifts(B):
-    return range(len(SORTS)) if B <= 2 else (B % len(SORTS),)        # one or two samples take every sort in turn
-
-
 # ---- the kernels against the rule --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", SIZES)
 @pytest.mark.parametrize("A", ACTIONS)
@@ -111,7 +79,7 @@ def test_the_kernels_equal_the_rule_byte_for_byte_and_write_nothing_else(A, B):
     combos = [("double", True, DELTA)]
     if B in (65, 4097):
         combos += [("y", True, DELTA), ("next", True, DELTA), ("double", True, 0.0), ("double", False, DELTA), ("y", False, 0.0), ("next", False, 0.0)]
-    for shift in _shifts(B):
+    for shift in _shifts(B, SORTS):
         case = make_case(np.random.default_rng(100 * A + B + shift), B, A, shift)
         for mode, weighted, delta in combos:
             want = rule_of(case, mode, weighted, delta, 1.0 / B)
@@ -119,7 +87,7 @@ def test_the_kernels_equal_the_rule_byte_for_byte_and_write_nothing_else(A, B):
             first = None
             for offset in (False, True):                             # both placements; and two runs give the same bytes
                 got = _call(case, mode, weighted, delta, offset=offset, scale=1.0 / B)
-                _equal(got, want, (A, B, shift, mode, weighted, delta, offset))
+                _equal(got, want, (A, B, shift, mode, weighted, delta, offset), OUTPUTS)
                 if first is not None:
                     for k, g in got.items():
                         assert g.tobytes() == first[k].tobytes(), (A, B, shift, mode, k)
@@ -136,7 +104,7 @@ def test_null_outputs_stay_untouched_and_the_others_unchanged():
         want = rule_of(case, mode, True, DELTA, 1.0 / B)
         for n, subset in enumerate(subsets):
             expect = dict(want, bad_rows=want["bad_rows"] if subset else 0)      # nothing asked for: nothing is launched, nothing counted
-            _equal(_call(case, mode, want=subset, offset=bool(n % 2), scale=1.0 / B), expect, (mode, subset))
+            _equal(_call(case, mode, want=subset, offset=bool(n % 2), scale=1.0 / B), expect, (mode, subset), OUTPUTS)
 
 
 def test_the_sums_are_the_stated_tree_not_a_plain_sum():
@@ -214,10 +182,8 @@ def test_td_loss_takes_an_envs_actions_device_and_stream():
     import torch
     from snac_amd import TDLoss
 
-    from test_gpu_replay_nstep import _env
-
     for kind, A in ((1, 3), (2, 5), (3, 8)):
-        env, _ = _env(kind, 65, True, seed=3)
+        env, _ = short_env(kind, 65, True, seed=3)
         td = TDLoss(env, huber=DELTA)
         assert td.num_actions == env.num_actions == A and td.device == env.device and td.env is env
         case = make_case(np.random.default_rng(kind), 65, A)
@@ -380,10 +346,8 @@ def test_categorical_support_loss_follows_the_rule_and_its_backward_gives_the_cl
     import torch
     from snac_amd import CategoricalSupport, PriorityTree, _lib
 
-    from test_gpu_replay_nstep import _env
-
     B, K = 4097, 51
-    env, _ = _env({3: 1, 5: 2, 8: 3}[A], 65, True, seed=3)           # the env's actions, device and stream are taken
+    env, _ = short_env({3: 1, 5: 2, 8: 3}[A], 65, True, seed=3)      # the env's actions, device and stream are taken
     dev = env.device
     sup = CategoricalSupport(env, atoms=K, vmin=0.0, vmax=100.0)
     assert sup.num_actions == A and sup.env is env
@@ -446,13 +410,6 @@ def test_the_device_cross_entropy_is_no_farther_from_float64_than_the_float32_co
 
 
 # ---- the examples ------------------------------------------------------------------------------------------------------------------------
-def _example(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(helpers.ROOT, "examples", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 @pytest.mark.parametrize("how", [dict(), dict(double=True, huber=1.0, prioritized=True, n_step=3), dict(distributional=True, prioritized=True)],
                          ids=["plain", "double_huber_prioritized_nstep", "distributional_prioritized"])
 def test_the_dqn_example_trains_with_the_device_loss(how):

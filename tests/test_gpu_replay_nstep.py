@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+from devmem import short_env
 import guard
 import helpers
 from test_replay_nstep_host import FILLS, GAMMA, LENGTHS, NSTEPS, addressable, make_ring, nstep_rule, ring_seed, window_rule
@@ -24,19 +25,7 @@ NSTEP_KEYS = ("s", "s_next", "action", "return", "discount", "done", "steps")
 WINDOW_KEYS = ("s", "s_next", "action", "reward", "done", "mask", "length")
 
 
-def _env(kind, n, f32, seed=3, **kw):
-    import torch
-    from snac_amd import BatchedDMPEnv
-
-    table = helpers.plan_table(kind, True, "sin_train" if kind == 1 else "dense_train")[:16]
-    full = table.reshape(len(table), 30) if kind == 1 else table.reshape(len(table), 26, 26)
-    env = BatchedDMPEnv(kind, True, n, plans=full, seed=seed, total_step=12, obs_dtype=torch.float32 if f32 else torch.float64, **kw)
-    env.reset()
-    cells = (full if kind == 1 else full[:, 3:23, 3:23].reshape(len(full), -1)).astype(np.float32)
-    return env, cells
-
-
-def _constructed(env, cells, layout, cap, head, ticks, seed):
+def constructed_ring(env, cells, layout, cap, head, ticks, seed):
     """A real ring with generated contents, and the same contents for the numpy rules."""
     import torch
     from snac_amd import ReplayRing
@@ -53,11 +42,11 @@ def _constructed(env, cells, layout, cap, head, ticks, seed):
     return ring, R
 
 
-def _stack(rows, keys):
+def stack_rows(rows, keys):
     return {k: np.stack([np.asarray(r[k]) for r in rows]) for k in keys}
 
 
-def _equal(got, want, keys, what):
+def equal_gather(got, want, keys, what):
     for k in keys:
         g = got[k].cpu().numpy()
         g = g.reshape(len(g), -1) if k == "plan" else g
@@ -73,40 +62,40 @@ def _check_ring(ring, R, rng):
     cap = ring.cap
     for n in NSTEPS(cap):
         rows = [nstep_rule(R, t, i, n, GAMMA) for t, i in pairs]
-        _equal(ring.gather_nstep(slot, env, n, GAMMA), _stack(rows, NSTEP_KEYS + ("plan",)), NSTEP_KEYS + ("plan",), "n = %d" % n)
+        equal_gather(ring.gather_nstep(slot, env, n, GAMMA), stack_rows(rows, NSTEP_KEYS + ("plan",)), NSTEP_KEYS + ("plan",), "n = %d" % n)
         for B, with_plan in ((1, False), (5, True), (67, False)):
             pick = rng.integers(0, len(pairs), B)
             got = ring.gather_nstep(slot[pick], env[pick], n, GAMMA, with_plan=with_plan)
             keys = NSTEP_KEYS + (("plan",) if with_plan else ())
             assert ("plan" in got) == with_plan
-            _equal(got, _stack([rows[j] for j in pick], keys), keys, "n = %d, batch %d" % (n, B))
+            equal_gather(got, stack_rows([rows[j] for j in pick], keys), keys, "n = %d, batch %d" % (n, B))
     for L in LENGTHS:
         rows = [window_rule(R, t, i, L) for t, i in pairs]
-        _equal(ring.gather_windows(slot, env, L), _stack(rows, WINDOW_KEYS + ("plan",)), WINDOW_KEYS + ("plan",), "L = %d" % L)
+        equal_gather(ring.gather_windows(slot, env, L), stack_rows(rows, WINDOW_KEYS + ("plan",)), WINDOW_KEYS + ("plan",), "L = %d" % L)
         for B, with_plan in ((1, True), (5, False), (67, True)):
             pick = rng.integers(0, len(pairs), B)
             got = ring.gather_windows(slot[pick], env[pick], L, with_plan=with_plan)
             keys = WINDOW_KEYS + (("plan",) if with_plan else ())
             assert ("plan" in got) == with_plan
-            _equal(got, _stack([rows[j] for j in pick], keys), keys, "L = %d, batch %d" % (L, B))
+            equal_gather(got, stack_rows([rows[j] for j in pick], keys), keys, "L = %d, batch %d" % (L, B))
 
 
 @pytest.mark.parametrize("N,layout", [(5, "ticks"), (70, "ticks"), (70, "tiled")])
 @pytest.mark.parametrize("f32", [False, True], ids=["f64ring", "f32ring"])
 @pytest.mark.parametrize("kind", [1, 2, 3])
 def test_constructed_rings_equal_the_numpy_rules_at_every_addressable_entry(kind, f32, N, layout):
-    env, cells = _env(kind, N, f32)
+    env, cells = short_env(kind, N, f32)
     rng = np.random.default_rng(kind)
     for cap, head, ticks in FILLS:
-        ring, R = _constructed(env, cells, layout, cap, head, ticks, ring_seed(kind, f32, N, cap, head))
+        ring, R = constructed_ring(env, cells, layout, cap, head, ticks, ring_seed(kind, f32, N, cap, head))
         _check_ring(ring, R, rng)
 
 
 @pytest.mark.parametrize("kind,layout", [(1, "ticks"), (2, "tiled")])
 def test_constructed_rings_with_the_position_tail(kind, layout):
-    env, cells = _env(kind, 70, False, obs_tail=("position",))
+    env, cells = short_env(kind, 70, False, obs_tail=("position",))
     assert env.obs_dim == (8 if kind == 1 else 53)
-    ring, R = _constructed(env, cells, layout, 7, 3, 10, 41 + kind)
+    ring, R = constructed_ring(env, cells, layout, 7, 3, 10, 41 + kind)
     assert R["reset"][-1] == (2.0 if kind == 1 else 3.0)             # the tail of the reset observation: the start position
     _check_ring(ring, R, np.random.default_rng(9))
 
@@ -159,7 +148,7 @@ def test_real_data_equals_compositions_of_the_existing_gather(layout):
     last = {key: np.stack([steps[k][key] for k in range(n)])[m - 1, np.arange(B)] for key in ("s_next", "done")}
     want = {"s": steps[0]["s"], "action": steps[0]["action"], "plan": steps[0]["plan"].reshape(B, -1), "s_next": last["s_next"], "done": last["done"],
             "steps": m, "return": g.astype(np.float32), "discount": np.where(last["done"], 0.0, d).astype(np.float32)}
-    _equal(ring.gather_nstep(slot, env, n, gamma), want, NSTEP_KEYS + ("plan",), "5-step")
+    equal_gather(ring.gather_nstep(slot, env, n, gamma), want, NSTEP_KEYS + ("plan",), "5-step")
     # the conditions of this setup (from the CPU oracle: 16.9 % and 3.3 %)
     assert by_done.mean() >= 0.05 and by_newest.mean() >= 0.01, (by_done.mean(), by_newest.mean())
     # windows: gather() of the flattened steps, zeros and the mask outside
@@ -175,7 +164,7 @@ def test_real_data_equals_compositions_of_the_existing_gather(layout):
     wwant = {k: np.where(inside.reshape(B, L, *([1] * (v.ndim - 1))), v.reshape(B, L, *v.shape[1:]), np.zeros((), v.dtype)) for k, v in flat.items()}
     wwant.update(mask=inside, length=length, plan=steps[0]["plan"].reshape(B, -1))
     got = ring.gather_windows(slot, env, L)
-    _equal(got, wwant, WINDOW_KEYS + ("plan",), "windows")
+    equal_gather(got, wwant, WINDOW_KEYS + ("plan",), "windows")
     assert (length < L).mean() >= 0.10, (length < L).mean()           # about a third
     assert torch.equal(got["s"][:, 1:][got["mask"][:, 1:]], got["s_next"][:, :-1][got["mask"][:, 1:]])   # consecutive tuples chain
 
@@ -239,7 +228,7 @@ def test_neither_entry_point_writes_outside_its_outputs(kind, layout):
 
     n, L = 3, 5
     for f32 in (False, True):
-        env, _ = _env(kind, 67, f32)
+        env, _ = short_env(kind, 67, f32)
         env.rollout(3, obs=None)
         ring = ReplayRing(env, 8, layout=layout)
         ring.collect(6)

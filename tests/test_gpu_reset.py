@@ -7,17 +7,12 @@ stay on the tile kernel with the same results."""
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
 
 CONFIGS = [(1, False), (1, True), (2, False), (2, True), (3, False), (3, True)]
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 def _pair(dim, dyn, n, seed, f32=False, total_step=30):

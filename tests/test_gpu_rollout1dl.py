@@ -7,16 +7,11 @@ an unaligned output) stays on the kernels behind it with the same rows; the layo
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import helpers
 import test_gpu_rollout1d as base
 
 pytestmark = pytest.mark.gpu
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])

@@ -8,6 +8,7 @@ batch (forced by an unaligned output, which the 16-byte stores do not take)."""
 import numpy as np
 import pytest
 
+from devmem import _compare, _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -29,19 +30,6 @@ def _pair(dyn, n, seed, tag=None, total_step=None, obs_dtype=None, brick_gt=Fals
     o = orc.reset()
     assert env.reset().cpu().numpy().tobytes() == (o.astype(np.float32) if obs_dtype == torch.float32 else o).tobytes()
     return env, orc
-
-
-def _compare(env, orc, T, t0, f32=False, actions=None, step_size=None):
-    import torch
-
-    a = None if actions is None else torch.from_numpy(actions).to(env.device)
-    k = None if step_size is None else torch.from_numpy(step_size).to(env.device)
-    og, rg, dg = env.rollout(T, actions=a, step_size=k)
-    oc, rc, dc = orc.rollout(T, t0=t0, actions=actions, step_size=step_size, nthreads=16)
-    want = oc.astype(np.float32) if f32 else oc
-    assert og.cpu().numpy().tobytes() == want.tobytes(), "observations"
-    assert rg.cpu().numpy().tobytes() == rc.tobytes(), "rewards"
-    assert np.array_equal(dg.cpu().numpy().view(np.uint8), dc), "done flags"
 
 
 def _end_state(env, orc):
@@ -222,12 +210,6 @@ def test_a_full_episode_length_on_a_generated_table_of_2000_plans():
     _end_state(env, orc)
 
 
-def _last_kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
-
-
 VARIANTS = [
     dict(layout="lnet2d"),                                           # 51 + position, frame value 2, normalised scalars on a static plan
     dict(layout="ppo"),                                              # 451 values: window, raw counters, the 400 plan cells
@@ -261,7 +243,7 @@ def test_layout_variants_on_the_staged_kernel(kw, f32):
     t0 = 0
     for T in (1, 5, 2):
         og, rg, dg = env.rollout(T)
-        assert _last_kernel() == "k_rollout2d"
+        assert _kernel() == "k_rollout2d"
         oc, rc, dc = orc.rollout(T, t0=t0, nthreads=16)
         assert og.cpu().numpy().tobytes() == cast(oc).tobytes(), "observations"
         assert rg.cpu().numpy().tobytes() == rc.tobytes() and np.array_equal(dg.cpu().numpy().view(np.uint8), dc)
@@ -276,15 +258,15 @@ def test_layout_variants_on_the_staged_kernel(kw, f32):
     twin = env.fork(torch.arange(n, device=env.device))
     T = 16
     o1, r1, d1 = env.rollout(T)
-    assert _last_kernel() == "k_rollout2d"
+    assert _kernel() == "k_rollout2d"
     raw = torch.empty(T * n * env.obs_dim + 1, dtype=dt, device=env.device)
     o2, r2, d2 = twin.rollout(T, out=raw[1:].view(T, n, env.obs_dim))
-    assert _last_kernel() == "k_rollout" and o2.data_ptr() % 16 != 0
+    assert _kernel() == "k_rollout" and o2.data_ptr() % 16 != 0
     assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
     assert torch.equal(env._hdr, twin._hdr) and torch.equal(env._grid, twin._grid)
     # tile-major output of the same layout
     tw2 = env.fork(torch.arange(n, device=env.device))
     ot, _, _ = env.rollout(3, obs="tiled")
-    assert _last_kernel() == "k_rollout2d"
+    assert _kernel() == "k_rollout2d"
     on, _, _ = tw2.rollout(3)
     assert torch.equal(env.untile(ot), on)

@@ -10,18 +10,13 @@ record tails) take the same kernel from 6148 to 32 768 envs (blocks of 128 envs 
 import numpy as np
 import pytest
 
+from devmem import _end_state, _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
 
 N1 = 12288                                                        # blocks of 64 envs
 N2 = 16384                                                        # blocks of 128 envs
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 def _pair(dyn, n, seed, tag=None, total_step=None, f32=False, brick_gt=False, time_gt=False, base=0):
@@ -55,14 +50,6 @@ def _compare(env, orc, T, t0, f32=False, actions=None, step_size=None):
         raise AssertionError("observations: %d values differ, first at (t, env, value) %s: %r != %r" % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
     assert rg.cpu().numpy().tobytes() == rc.tobytes(), "rewards"
     assert np.array_equal(dg.cpu().numpy().view(np.uint8), dc), "done flags"
-
-
-def _end_state(env, orc):
-    s, e = orc.stats(), env.episodic_stats()
-    assert (e["episodes"], e["return_sum"], e["iou_fx_sum"]) == (int(s["episodes"].sum()), int(s["ret"].sum()), int(s["iou_fx"].sum()))
-    assert env.iou().cpu().numpy().tobytes() == orc.iou().tobytes()
-    st = orc.state()
-    assert np.array_equal(env.environment_memory().cpu().numpy().reshape(env.num_envs, -1), st["grid"])
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])

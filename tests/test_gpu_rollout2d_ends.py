@@ -17,6 +17,7 @@ import sys
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -25,12 +26,6 @@ INNER = os.environ.get("SNAC_TEST_ENDS2D_INNER") == "1"
 inner = pytest.mark.skipif(not INNER, reason="runs in the child processes of test_both_tile_orders_in_child_processes")
 SIZES = [4, 64, 68, 2048, 2304 + 36, 4352]
 LAUNCHES = (1, 2, 7, 1, 2, 7)
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 def _pair(dyn, n, f32, seed=5, kw=None):

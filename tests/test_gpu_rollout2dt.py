@@ -9,15 +9,10 @@ border), the `>` rule bits, both dtypes, the record outputs and explicit inputs,
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 def _pair(dyn, n, seed, total_step=None, obs_dtype=None, brick_gt=False, time_gt=False, tag=None):

@@ -8,6 +8,7 @@ outputs -- and, bit for bit, the rows k_rollout3d writes for the same batch (for
 import numpy as np
 import pytest
 
+from devmem import _compare, _end_state
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -29,27 +30,6 @@ def _pair(dyn, n, seed, tag=None, total_step=None, obs_dtype=None, brick_gt=Fals
     o = orc.reset()
     assert env.reset().cpu().numpy().tobytes() == (o.astype(np.float32) if obs_dtype == torch.float32 else o).tobytes()
     return env, orc
-
-
-def _compare(env, orc, T, t0, f32=False, actions=None, step_size=None):
-    import torch
-
-    a = None if actions is None else torch.from_numpy(actions).to(env.device)
-    k = None if step_size is None else torch.from_numpy(step_size).to(env.device)
-    og, rg, dg = env.rollout(T, actions=a, step_size=k)
-    oc, rc, dc = orc.rollout(T, t0=t0, actions=actions, step_size=step_size, nthreads=16)
-    want = oc.astype(np.float32) if f32 else oc
-    assert og.cpu().numpy().tobytes() == want.tobytes(), "observations"
-    assert rg.cpu().numpy().tobytes() == rc.tobytes(), "rewards"
-    assert np.array_equal(dg.cpu().numpy().view(np.uint8), dc), "done flags"
-
-
-def _end_state(env, orc):
-    s, e = orc.stats(), env.episodic_stats()
-    assert (e["episodes"], e["return_sum"], e["iou_fx_sum"]) == (int(s["episodes"].sum()), int(s["ret"].sum()), int(s["iou_fx"].sum()))
-    assert env.iou().cpu().numpy().tobytes() == orc.iou().tobytes()
-    st = orc.state()
-    assert np.array_equal(env.environment_memory().cpu().numpy().reshape(env.num_envs, -1), st["grid"])
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])

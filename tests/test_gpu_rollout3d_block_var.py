@@ -13,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+from devmem import _end_state, _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
@@ -20,12 +21,6 @@ pytestmark = pytest.mark.gpu
 N0 = 6144
 INNER = os.environ.get("SNAC_TEST_VAR3D_INNER") == "1"
 inner = pytest.mark.skipif(not INNER, reason="runs in the child process of test_rows_with_the_plan_tail_in_a_child_process")
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 def _pair(dyn, n, seed, kw, tag=None, total_step=None, f32=False, brick_gt=False, time_gt=False, base=0):
@@ -62,14 +57,6 @@ def _compare(env, orc, T, t0, f32=False, actions=None, step_size=None, kernel="k
         raise AssertionError("observations: %d values differ, first at (t, env, value) %s: %r != %r" % (len(bad), bad[0], got[tuple(bad[0])], want[tuple(bad[0])]))
     assert rg.cpu().numpy().tobytes() == rc.tobytes(), "rewards"
     assert np.array_equal(dg.cpu().numpy().view(np.uint8), dc), "done flags"
-
-
-def _end_state(env, orc):
-    s, e = orc.stats(), env.episodic_stats()
-    assert (e["episodes"], e["return_sum"], e["iou_fx_sum"]) == (int(s["episodes"].sum()), int(s["ret"].sum()), int(s["iou_fx"].sum()))
-    assert env.iou().cpu().numpy().tobytes() == orc.iou().tobytes()
-    st = orc.state()
-    assert np.array_equal(env.environment_memory().cpu().numpy().reshape(env.num_envs, -1), st["grid"])
 
 
 SHORT = [dict(obs_tail=("record",)), dict(obs_tail=("position", "record"), obs_scalars="raw"), dict(obs_tail=("position",)), dict(obs_scalars="raw"),

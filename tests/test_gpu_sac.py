@@ -15,6 +15,7 @@ import os
 import numpy as np
 import pytest
 
+from devmem import _place_floats, _shifts, _vp, short_env
 import guard
 import helpers
 from test_sac_host import ACTIONS, ALPHAS, SORTS, bad_rows_of, make_case, soft_rule
@@ -26,22 +27,6 @@ VALUES = ("v", "y", "entropy", "grad")
 INPUTS = ("logits", "q1", "q2", "ret", "discount")
 
 
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _place(arr, offset, dev):
-    """(flat tensor, view of arr's shape in it): arr on the device, one float into a larger tensor when offset."""
-    import torch
-
-    flat = torch.full((arr.size + 9,), 7.0, dtype=torch.float32, device=dev)
-    at = 1 if offset else 0
-    view = flat[at:at + arr.size].view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert view.data_ptr() % 16 == (4 if offset else 0) and view.is_contiguous()
-    return flat, view
-
-
 def _call(case, alpha, two=True, want=VALUES + ("bad_rows",), offset=False, scale=1.0):
     """One snac_soft_value call with its outputs in a guard arena -> dict of numpy arrays (None where not asked for)."""
     import torch
@@ -49,8 +34,8 @@ def _call(case, alpha, two=True, want=VALUES + ("bad_rows",), offset=False, scal
 
     L, dev = _lib.lib(), torch.device("cuda", torch.cuda.current_device())
     B, A = case["logits"].shape
-    ins = {k: _place(case[k], offset, dev) for k in INPUTS}
-    ins["alpha"] = _place(np.array([alpha], np.float32), offset, dev)
+    ins = {k: _place_floats(case[k], offset, dev) for k in INPUTS}
+    ins["alpha"] = _place_floats(np.array([alpha], np.float32), offset, dev)
     before = {k: flat.clone() for k, (flat, _) in ins.items()}
     arena = guard.Arena(B * (4 * A + 12) + 4 + 7 * (guard.BAND + 1024), dev)
     off4 = 4 if offset else 0
@@ -99,15 +84,11 @@ def _same(got, want, what):
         assert diff.size == 0, (what, k, "first sample that differs", int(diff[0]), g[diff[0]], w[diff[0]])
 
 
-def _shifts(B):
-    return range(len(SORTS)) if B <= 2 else (B % len(SORTS),)        # one or two samples take every sort in turn
-
-
 # ---- the kernel against the rule ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", SIZES)
 @pytest.mark.parametrize("A", ACTIONS)
 def test_the_kernel_equals_the_rule_byte_for_byte_and_writes_nothing_else(A, B):
-    for shift in _shifts(B):
+    for shift in _shifts(B, SORTS):
         case = make_case(np.random.default_rng(100 * A + B + shift), B, A, shift)
         for n, alpha in enumerate(ALPHAS):
             for two in (True, False):
@@ -131,11 +112,9 @@ def test_the_kernel_equals_the_rule_byte_for_byte_and_writes_nothing_else(A, B):
 def test_the_entropy_is_sample_actions_and_two_runs_give_the_same_bytes():
     import torch
 
-    from test_gpu_replay_nstep import _env
-
     for kind, A in ((1, 3), (2, 5), (3, 8)):
         B = 1031
-        env, _ = _env(kind, B, True, seed=5)
+        env, _ = short_env(kind, B, True, seed=5)
         case = make_case(np.random.default_rng(kind), B, A)
         first, second = (_call(case, 0.2, offset=bool(j)) for j in range(2))
         for k in first:
@@ -213,10 +192,8 @@ def test_soft_value_takes_an_envs_actions_device_and_stream():
     import torch
     from snac_amd import SoftValue
 
-    from test_gpu_replay_nstep import _env
-
     for kind, A in ((1, 3), (2, 5), (3, 8)):
-        env, _ = _env(kind, 65, True, seed=3)
+        env, _ = short_env(kind, 65, True, seed=3)
         sv = SoftValue(env)
         assert sv.num_actions == env.num_actions == A and sv.device == env.device and sv.env is env
         case = make_case(np.random.default_rng(kind), 65, A)

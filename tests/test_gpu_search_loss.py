@@ -13,36 +13,19 @@ guard arena: nothing lands outside the outputs, the inputs keep their bytes, a N
 Then repeatability, the Python surface against the rule, the priorities into a PriorityTree, the float32 torch composition, and the
 example."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
+from devmem import _equal, _example, _place, _shifts, _vp, short_env
 import guard
-import helpers
-from test_search_loss_host import ACTIONS, DELTA, INPUTS, SORTS, VF_COEF, _plain, _same, bad_rows_of, make_search_case, rule_of
+from specmath import _same
+from test_search_loss_host import ACTIONS, DELTA, INPUTS, SORTS, VF_COEF, bad_rows_of, make_search_case, plain_sum, rule_of
 
 pytestmark = pytest.mark.gpu
 
 SIZES = (1, 2, 63, 64, 65, 257, 4095, 4096, 4097, 8193)              # a block is one wave of 64 samples; 64 waves fill the second kernel once
 OUTPUTS = ("loss", "priority", "grad_logits", "grad_value", "stats", "mean_loss", "bad_rows")
-
-
-def _vp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _place(arr, offset, dev):
-    """(flat tensor, view of arr's shape in it): arr on the device, one element into a larger tensor when offset."""
-    import torch
-
-    flat = torch.zeros((arr.size + 9,), dtype=torch.from_numpy(arr).dtype, device=dev)
-    at = 1 if offset else 0
-    view = flat[at:at + arr.size].view(arr.shape)
-    view.copy_(torch.from_numpy(arr))
-    assert view.data_ptr() % 16 == (arr.itemsize if offset else 0) and view.is_contiguous()
-    return flat, view
 
 
 def _call(case, weighted=True, delta=DELTA, want=OUTPUTS, offset=False, scale=1.0):
@@ -86,21 +69,6 @@ def _call(case, weighted=True, delta=DELTA, want=OUTPUTS, offset=False, scale=1.
     return got
 
 
-def _equal(got, want, what):
-    for k in OUTPUTS + ("partials",):
-        g = got[k]
-        if g is None:
-            continue
-        if k == "bad_rows":
-            assert int(g[0]) == want[k], (what, k, int(g[0]), want[k])
-        else:
-            _same(g, np.ascontiguousarray(want[k]), (what, k))
-
-
-def _shifts(B):
-    return range(len(SORTS)) if B <= 2 else (B % len(SORTS),)        # one or two samples take every sort in turn
-
-
 # ---- the kernel against the rule ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", SIZES)
 @pytest.mark.parametrize("A", ACTIONS)
@@ -109,7 +77,7 @@ def test_the_kernel_equals_the_rule_byte_for_byte_and_writes_nothing_else(A, B):
     combos = [(True, DELTA)]
     if B in (65, 4097):
         combos += [(True, 0.0), (False, DELTA), (False, 0.0)]
-    for shift in _shifts(B):
+    for shift in _shifts(B, SORTS):
         case = make_search_case(np.random.default_rng(100 * A + B + shift), B, A, shift)
         for weighted, delta in combos:
             want = rule_of(case, weighted, delta, 1.0 / B)
@@ -117,7 +85,7 @@ def test_the_kernel_equals_the_rule_byte_for_byte_and_writes_nothing_else(A, B):
             first = None
             for offset in (False, True):                             # both placements; and two runs give the same bytes
                 got = _call(case, weighted, delta, offset=offset, scale=1.0 / B)
-                _equal(got, want, (A, B, shift, weighted, delta, offset))
+                _equal(got, want, (A, B, shift, weighted, delta, offset), OUTPUTS)
                 if first is not None:
                     for k, g in got.items():
                         assert g.tobytes() == first[k].tobytes(), (A, B, shift, k)
@@ -133,7 +101,7 @@ def test_null_outputs_stay_untouched_and_the_others_unchanged():
     want = rule_of(case, True, DELTA, 1.0 / B)
     for n, subset in enumerate(subsets):
         expect = dict(want, bad_rows=want["bad_rows"] if subset else 0)          # nothing asked for: nothing is launched, nothing counted
-        _equal(_call(case, want=subset, offset=bool(n % 2), scale=1.0 / B), expect, subset)
+        _equal(_call(case, want=subset, offset=bool(n % 2), scale=1.0 / B), expect, subset, OUTPUTS)
 
 
 def test_the_sums_are_the_stated_tree_not_a_plain_sum():
@@ -144,7 +112,7 @@ def test_the_sums_are_the_stated_tree_not_a_plain_sum():
         case = make_search_case(np.random.default_rng(100 * A + B), B, A, B % len(SORTS))
         want = rule_of(case)
         got = _call(case, want=("stats",))
-        assert got["stats"].tobytes() == want["stats"].tobytes() and got["stats"][0] != _plain(want["u"][:, 0]) / np.float64(B)
+        assert got["stats"].tobytes() == want["stats"].tobytes() and got["stats"][0] != plain_sum(want["u"][:, 0]) / np.float64(B)
 
 
 # ---- the Python surface ------------------------------------------------------------------------------------------------------------------
@@ -203,10 +171,8 @@ def test_search_loss_takes_an_envs_actions_device_and_stream():
     import torch
     from snac_amd import SearchLoss
 
-    from test_gpu_replay_nstep import _env
-
     for kind, A in ((1, 3), (2, 5), (3, 8)):
-        env, _ = _env(kind, 65, True, seed=3)
+        env, _ = short_env(kind, 65, True, seed=3)
         sl = SearchLoss(env, vf_coef=VF_COEF, huber=DELTA)
         assert sl.num_actions == env.num_actions == A and sl.device == env.device and sl.env is env
         case = make_search_case(np.random.default_rng(kind), 65, A)
@@ -269,13 +235,6 @@ def test_the_device_mean_is_no_farther_from_float64_than_the_float32_composition
 
 
 # ---- the example -------------------------------------------------------------------------------------------------------------------------
-def _example(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(helpers.ROOT, "examples", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 SMALL = dict(envs=16, steps=2, moves=2, iterations=4)
 
 

@@ -6,15 +6,10 @@ explicit inputs biased to moves and to drops, scalar inputs, steps without obser
 import numpy as np
 import pytest
 
+from devmem import _kernel
 import helpers
 
 pytestmark = pytest.mark.gpu
-
-
-def _kernel():
-    from snac_amd import _lib
-
-    return _lib.lib().snac_last_kernel().decode()
 
 
 def _pair(dyn, n, seed, f32=False, total_step=40, brick_gt=False, time_gt=False):

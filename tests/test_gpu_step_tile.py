@@ -7,15 +7,12 @@ every edge of the plan area (the 3D window loads clamp their first column into t
 import numpy as np
 import pytest
 
+from devmem import _ids
 import helpers
 
 pytestmark = pytest.mark.gpu
 
 KINDS = [(2, False), (2, True), (3, False), (3, True)]
-
-
-def _ids(v):
-    return "%dd_%s" % (v[0], "dyn" if v[1] else "sta") if isinstance(v, tuple) else str(v)
 
 
 def _pair(dim, dyn, n, seed, total_step=None, f32=False, base=0):

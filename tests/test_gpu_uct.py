@@ -7,7 +7,7 @@ import math
 import numpy as np
 import pytest
 
-import helpers
+from devmem import _env, _raw
 
 pytestmark = pytest.mark.gpu
 
@@ -17,20 +17,6 @@ H = {1: 300, 2: 600, 3: 200}
 # action mix of test_search_follows_the_action_distribution (the restatements read env.seed and env.env_id_base)
 NON_DEFAULT_SEED = (9 << 32) | 3
 NON_DEFAULT = dict(env_id_base=1000, brick_gt=True, time_gt=True, total_step=9, action_probs=[1, 3, 0, 2, 2])
-
-
-def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
-
-
-def _env(kind, dyn, n, seed, **kw):
-    from snac_amd import BatchedDMPEnv
-
-    table = helpers.plan_table(kind, dyn, _tag(kind, dyn))
-    full = table.reshape((-1, 30) if kind == 1 else (-1, 26, 26))
-    env = BatchedDMPEnv(kind, dyn, n, plans=full, seed=seed, **kw)
-    env.reset()
-    return env
 
 
 class Restatement:
@@ -113,10 +99,6 @@ class Restatement:
                 g = float(self.reward[p]) + self.gamma * g
                 x = p
         self.it += 1
-
-
-def _raw(t):
-    return t.cpu().numpy().tobytes()
 
 
 def _same(search, ref):

@@ -7,9 +7,10 @@ import math
 import numpy as np
 import pytest
 
+from devmem import _env, _subtree
 import helpers  # noqa: F401
 import rng_spec
-from test_gpu_uct import H, KINDS, NON_DEFAULT, NON_DEFAULT_SEED, Restatement, _env
+from test_gpu_uct import H, KINDS, NON_DEFAULT, NON_DEFAULT_SEED, Restatement
 
 pytestmark = pytest.mark.gpu
 
@@ -191,15 +192,6 @@ def test_advance_on_a_non_default_env_equals_the_restatement_bit_for_bit(kind, d
     assert untried and tried
     _run(search, ref, 25)
     assert search.iterations == 75
-
-
-def _subtree(ch, x, out):
-    """Canonical traversal: preorder, children in action order."""
-    out.append(x)
-    for c in ch[x]:
-        if c >= 0:
-            _subtree(ch, int(c), out)
-    return out
 
 
 @pytest.mark.parametrize("kind,dyn", [(2, True), (3, False), (1, True)])

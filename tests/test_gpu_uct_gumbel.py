@@ -14,8 +14,9 @@ except improved_policy(), a float64 torch computation compared with a float64 Nu
 import numpy as np
 import pytest
 
+from devmem import _env
 from test_gpu_uct_norm import NormPuctRestatement, _empty, _same, scaled_evaluator
-from test_gpu_uct_paths import _env, _outputs
+from test_gpu_uct_paths import _outputs
 from test_gpu_uct_puct import C as CPUCT
 from test_gpu_uct_puct import GAMMA
 from test_gpu_uct_selfplay import _near_the_end, pick, restart

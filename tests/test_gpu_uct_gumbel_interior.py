@@ -16,9 +16,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from devmem import _env
 from test_gpu_uct_gumbel import C_SCALE, C_VISIT, PI_ATOL, VL, GumbelRestatement, _cand, _noisy_scores, _phases
 from test_gpu_uct_norm import _empty, scaled_evaluator
-from test_gpu_uct_paths import _env, _outputs
+from test_gpu_uct_paths import _outputs
 from test_gpu_uct_puct import C as CPUCT
 from test_gpu_uct_puct import GAMMA
 from test_gpu_uct_puct import _same_outputs as _same_outputs_puct

@@ -14,10 +14,11 @@ import os
 import numpy as np
 import pytest
 
+from devmem import _env, _vp
 import guard
 import helpers
-from test_gpu_mlp import _Placed, _same, _vp
-from test_gpu_uct_paths import _env
+from specmath import _same
+from test_gpu_mlp import PlacedNet
 from test_mlp_host import bad_rows_of, case_seed, leaves_rule, make_leaves, make_mlp_case, rule_of
 
 pytestmark = pytest.mark.gpu
@@ -114,7 +115,7 @@ def _leaves(case, lv, f64, offset, want=OUTPUTS):
     import torch
     from snac_amd import _lib
 
-    p = _Placed(case, f64, offset)
+    p = PlacedNet(case, f64, offset)
     A, S = case["A"], p.rows
     dev = p.dev
     ins = {k: torch.from_numpy(np.ascontiguousarray(lv[k])).to(dev) for k in ("first_has", "first_idx", "done", "stats", "leaf")}

@@ -16,7 +16,8 @@ import math
 import numpy as np
 import pytest
 
-from test_gpu_uct_paths import H, VL, Restatement, _env, _outputs
+from devmem import _env
+from test_gpu_uct_paths import H, VL, Restatement, _outputs
 from test_gpu_uct_paths import _same as _same_rollout
 from test_gpu_uct_paths import _same_outputs as _same_outputs_rollout
 from test_gpu_uct_puct import C as CPUCT

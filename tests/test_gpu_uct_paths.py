@@ -18,7 +18,7 @@ import math
 import numpy as np
 import pytest
 
-import helpers
+from devmem import _env, _subtree
 from test_gpu_uct import NON_DEFAULT, NON_DEFAULT_SEED
 
 pytestmark = pytest.mark.gpu
@@ -26,20 +26,6 @@ pytestmark = pytest.mark.gpu
 KINDS = [(1, False), (1, True), (2, False), (2, True), (3, False), (3, True)]
 H = {1: 300, 2: 600, 3: 200}
 VL = 0.5                                                             # of the order of a step reward
-
-
-def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
-
-
-def _env(kind, dyn, n, seed, **kw):
-    from snac_amd import BatchedDMPEnv
-
-    table = helpers.plan_table(kind, dyn, _tag(kind, dyn))
-    full = table.reshape((-1, 30) if kind == 1 else (-1, 26, 26))
-    env = BatchedDMPEnv(kind, dyn, n, plans=full, seed=seed, **kw)
-    env.reset()
-    return env
 
 
 class Restatement:
@@ -426,15 +412,6 @@ def test_terminal_roots_and_terminal_fresh_nodes(kind, dyn):
             w += float(r[x])                                          # every visit adds exactly the stored reward (0 at a root)
         assert W[x].tobytes() == np.float64(w).tobytes()
     assert (search.tree_sizes().cpu().numpy()[2::9] == 1).all() and (vis[roots[2::9]] == its * K).all()
-
-
-def _subtree(ch, x, out):
-    """Canonical traversal: preorder, children in action order."""
-    out.append(x)
-    for c in ch[x]:
-        if c >= 0:
-            _subtree(ch, int(c), out)
-    return out
 
 
 @pytest.mark.parametrize("kind,dyn,K", [(2, True, 5), (3, False, 16), (1, True, 4)])

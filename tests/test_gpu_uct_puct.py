@@ -16,8 +16,9 @@ import math
 import numpy as np
 import pytest
 
+from devmem import _env, _subtree
 from test_gpu_uct import NON_DEFAULT, NON_DEFAULT_SEED
-from test_gpu_uct_paths import H, KINDS, Restatement, _env, _outputs, _subtree
+from test_gpu_uct_paths import H, KINDS, Restatement, _outputs
 
 pytestmark = pytest.mark.gpu
 

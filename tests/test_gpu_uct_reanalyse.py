@@ -13,7 +13,7 @@ import functools
 import numpy as np
 import pytest
 
-from test_gpu_uct_paths import _env
+from devmem import _env
 from test_gpu_uct_puct import C as CPUCT
 from test_gpu_uct_puct import GAMMA, VL, PuctRestatement, make_evaluator
 from test_gpu_uct_puct import _same as _same_puct

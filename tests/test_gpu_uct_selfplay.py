@@ -14,9 +14,10 @@ import math
 import numpy as np
 import pytest
 
+from devmem import _env
 import rng_spec
 from test_gpu_uct import NON_DEFAULT, NON_DEFAULT_SEED
-from test_gpu_uct_paths import H, KINDS, Restatement, _env
+from test_gpu_uct_paths import H, KINDS, Restatement
 from test_gpu_uct_paths import _same as _same_rollout
 from test_gpu_uct_puct import C as CPUCT
 from test_gpu_uct_puct import GAMMA, HIGH, VL, PuctRestatement, make_evaluator

@@ -13,6 +13,7 @@ tree by stream 1 and (env_id_base + b, episode)."""
 import numpy as np
 import pytest
 
+from devmem import _raw, _tag
 import helpers
 import rng_spec
 from test_gpu_uct_puct import C as CPUCT
@@ -29,10 +30,6 @@ PATHS = [1, 4]
 STREAM_PICK = 3
 FIELDS = ("children", "parent", "action", "reward", "terminal", "visits", "value_sum", "tree_sizes", "records", "root_visits", "root_q",
           "root_priors", "prior")
-
-
-def _tag(kind, dyn):
-    return ("sin_train" if kind == 1 else "dense_train") if dyn else ("p0" if kind == 1 else "p1")
 
 
 def _same_env_rows(shard, whole, off):
@@ -162,10 +159,6 @@ def _sampled(search, t):
     w = rng_spec.words(env.seed, STREAM_PICK, np.uint64(env.env_id_base) + np.arange(B, dtype=np.uint64), t)
     u = (w * total) >> np.uint64(32)
     return np.where(total > 0, (np.cumsum(visits, 1) <= u[:, None]).sum(1), 0).astype(np.int8)
-
-
-def _raw(t):
-    return t.cpu().numpy().tobytes()
 
 
 # ---- 1. the search ------------------------------------------------------------------------------------------------------------------------

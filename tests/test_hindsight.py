@@ -20,17 +20,8 @@ def _file():
     return _Z
 
 
-def _names():
-    return _file()["cases"].tolist()
-
-
-def _rec(name):
-    z = _file()
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
 def _replay(name, make_env, step, reset, state):
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     dim, pc = int(name[0]), int(name.split(".")[1][1:])
     env = make_env(dim, pc)
     starts = dict((int(s), e) for e, s in enumerate(rec["ep_start"]))
@@ -53,7 +44,7 @@ def _replay(name, make_env, step, reset, state):
             assert np.float64(iou).tobytes() == np.float64(rec["ep_iou"][e]).tobytes()
 
 
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_oracle_replays_hindsight_goldens(name):
     orc = helpers.oracle()
     plan = {}
@@ -67,7 +58,7 @@ def test_oracle_replays_hindsight_goldens(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_hindsight_facades_on_hip(name):
     mods = {1: ("1D", "DMP_Env_1D_static_hindsight_replay"), 2: ("2D", "DMP_Env_2D_static_hindsight_replay"),
             3: ("3D", "DMP_simulator_3d_static_circle_hindsight_replay")}

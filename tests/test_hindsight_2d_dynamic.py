@@ -25,22 +25,13 @@ def _file():
     return _Z
 
 
-def _names():
-    return _file()["cases"].tolist()
-
-
-def _rec(name):
-    z = _file()
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
 def _table(name):
     dens, split = name.split(".")[1].split("-")
     return helpers.plan_table(2, True, "%s_%s" % (dens, split)), dens == "sparse"
 
 
 def _replay(name, reset, step, state):
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     starts = dict((int(s), e) for e, s in enumerate(rec["ep_start"]))
     S = len(rec["actions"])
     for t in range(S):
@@ -59,14 +50,14 @@ def _replay(name, reset, step, state):
             assert np.float64(iou).tobytes() == np.float64(rec["ep_iou"][e]).tobytes()
 
 
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_oracle_and_rng_twin_replay_the_recording(name):
     """The oracle env (dataset dynamics, raw counters, caller's step sizes) reproduces every observation / reward / done; a
     RandomState twin that consumes numpy's stream the way reset() does -- two randint(0, 20, size=3) per attempt while the oracle's
     rasteriser reports an area <= 50 (dense) / 20 (sparse), then randint(0, len) for the plan when the choice is random -- lands on
     the recorded plan rows and on the recorded next word of the global stream."""
     orc = helpers.oracle()
-    rec0 = _rec(name)
+    rec0 = helpers.npz_case(_file(), name)
     table, sparse = _table(name)
     env = orc.OracleEnv(2, True).configure(obs_norm=0, rules_dyn=1)
     st = np.random.RandomState(int(rec0["seed"]))
@@ -97,13 +88,13 @@ def test_oracle_and_rng_twin_replay_the_recording(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_drop_in_class_replays_the_recording_from_the_seed(name):
     path = os.path.join(helpers.ROOT, "snac_amd", "Env", "2D")
     if path not in sys.path:
         sys.path.append(path)
     cls = getattr(importlib.import_module("DMP_Env_2D_dynamic_hindsight_replay_usedata"), "deep_mobile_printing_2d1r_hindsight")
-    rec0 = _rec(name)
+    rec0 = helpers.npz_case(_file(), name)
     dens, split = name.split(".")[1].split("-")
     np.random.seed(int(rec0["seed"]))
     env = cls(data_path="/nonexistent/data_2d_dynamic_%s_envplan_500_%s.pkl" % (dens, split), random_choose_paln=bool(int(rec0["random_choose"])))
@@ -136,8 +127,8 @@ def test_batched_path_replays_all_recordings_at_once():
     import torch
     from snac_amd import BatchedDMPEnv
 
-    for name in _names():
-        rec = _rec(name)
+    for name in helpers.npz_names(_file()):
+        rec = helpers.npz_case(_file(), name)
         table, _ = _table(name)
         env = BatchedDMPEnv(2, True, 4, plans=table.reshape(len(table), 26, 26), obs_scalars="raw", seed=1)     # four copies of the one env
         starts = dict((int(s), e) for e, s in enumerate(rec["ep_start"]))

@@ -20,19 +20,10 @@ def _file():
     return _Z
 
 
-def _names():
-    return _file()["cases"].tolist()
-
-
-def _rec(name):
-    z = _file()
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_oracle_replays_lnet_goldens(name):
     orc = helpers.oracle()
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     dim, pc = int(name[0]), int(name.split(".")[1][1:])
     env = orc.OracleEnv(dim, False)
     if dim == 2:
@@ -59,10 +50,10 @@ def test_oracle_replays_lnet_goldens(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_lnet_facades_on_hip_from_seed(name):
     mods = {1: ("1D", "DMP_Env_1D_static_Lnet"), 2: ("2D", "DMP_Env_2D_static_Lnet_test"), 3: ("3D", "DMP_simulator_3d_static_circle_Lnet")}
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     dim, pc = int(name[0]), int(name.split(".")[1][1:])
     sub, mod = mods[dim]
     path = os.path.join(helpers.ROOT, "snac_amd", "Env", sub)

@@ -20,15 +20,6 @@ def _file():
     return _Z
 
 
-def _names():
-    return _file()["cases"].tolist()
-
-
-def _rec(name):
-    z = _file()
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
 def _kind(name):
     if name.startswith("3dhd"):
         return 3, True
@@ -36,7 +27,7 @@ def _kind(name):
 
 
 def _replay(name, reset, step, state):
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     starts = dict((int(s), e) for e, s in enumerate(rec["ep_start"]))
     S = len(rec["actions"])
     for t in range(S):
@@ -55,7 +46,7 @@ def _replay(name, reset, step, state):
             assert np.float64(iou).tobytes() == np.float64(rec["ep_iou"][e]).tobytes()
 
 
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_oracle_replays_misc_goldens(name):
     orc = helpers.oracle()
     dim, dyn = _kind(name)
@@ -75,14 +66,14 @@ def test_oracle_replays_misc_goldens(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_misc_facades_on_hip(name):
     dim, dyn = _kind(name)
     sub = "%dD" % dim
     path = os.path.join(helpers.ROOT, "snac_amd", "Env", sub)
     if path not in sys.path:
         sys.path.append(path)
-    rec0 = _rec(name)
+    rec0 = helpers.npz_case(_file(), name)
     np.random.seed(int(rec0["seed"]))
     if dyn:
         cls = getattr(importlib.import_module("DMP_simulator_3d_dynamic_triangle_hindsight_replay"), "deep_mobile_printing_3d1r_hindsight")

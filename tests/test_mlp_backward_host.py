@@ -11,14 +11,16 @@ system compiler and compared with mlp_backward_rule byte for byte, and the same 
 undefined-behaviour sanitizers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err, _net
 import helpers
+from hostcode import _vp, load_shared, run_sanitized
 from snac_amd import _lib
-from test_mlp_host import NETS, PH, U24, U53, WIDE, _chain, _compiler, _err, _net, _same, _vp, make_mlp_net, mlp_rule
+from specmath import _same
+from test_mlp_host import NETS, U24, U53, WIDE, layer_chain, make_mlp_net, mlp_rule
 
 CHUNK = _lib.MLP_GRAD_CHUNK                                          # the header's SNAC_MLP_GRAD_CHUNK: nothing below hard-codes it
 BIG = 2.0 ** 40
@@ -298,7 +300,7 @@ def backward_bound(c, out):
             K = W.shape[1]
             x64 = h[l].astype(np.float64)
             size = np.abs(b64)[None, :] + np.abs(x64) @ np.abs(W64).T
-            acc = _chain(W, b, h[l])
+            acc = layer_chain(W, b, h[l])
             err = (K + 2) * U53 * size + U24 * np.abs(acc) + err_h[l] @ np.abs(W64).T
             pre = ref @ W64.T + b64[None, :]
             if l < L - 1:
@@ -416,7 +418,7 @@ def test_work_bytes_is_the_formula_of_the_header_and_refuses_bad_networks():
             grows = len(dims) > 2 or -(-rows // CHUNK) > chunks       # with every row where rows are parked, else with every chunk
             assert got > last if grows else got == last, (dims, rows, got, last)
             last, chunks = got, -(-rows // CHUNK)
-    assert _wb(L, _net((51, 64, 6), w=[0, 0], b=[0, 0]), 4) == work_bytes_formula((51, 64, 6), 4)     # host only: the pointers are not looked at
+    assert _wb(L, _net((51, 64, 6), w=[0, 0], b=[0, 0]), 4) == work_bytes_formula((51, 64, 6), 4)  # host only: the pointers are not looked at
     _err(L, _wb(L, None, 4), -1, b"null net")
     for layers in (0, -1, 5):
         _err(L, _wb(L, _net(layers=layers), 4), -1, b"layers must be 1 .. 4")
@@ -469,7 +471,7 @@ def test_backward_validates_its_arguments_before_any_hip_call():
 
 
 # ---- the wrapper -------------------------------------------------------------------------------------------------------------------------
-def _hostless(dims):
+def hostless_mlp(dims):
     """A DeviceMLP bound to cuda:0 whose parameters lie on the host (its constructor refuses them: the fields are set here): every
     refusal of backward() and train_forward() comes before the device or the library is touched, so it needs neither."""
     import torch
@@ -486,7 +488,7 @@ def test_device_mlp_backward_refuses_before_it_touches_a_device():
     import torch
 
     dims = (51, 64, 6)
-    mlp = _hostless(dims)
+    mlp = hostless_mlp(dims)
     P = num_params(dims)
     assert mlp.num_params == P
     x, gy = torch.zeros(4, 51), torch.zeros(4, 6)
@@ -525,13 +527,7 @@ HOST_NETS = ((7, 4), (51, 64, 6), (51, 65, 1, 9), (502, 256, 256, 6))
 
 
 def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "mlp_grad_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    fn = C.CDLL(so).mlp_grad_host
+    fn = load_shared(tmp_path, "mlp_grad_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600).mlp_grad_host
     vp = C.c_void_p
     fn.restype = C.c_int
     fn.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_int, C.c_int32, vp, C.c_int32, C.c_int32, vp]
@@ -556,17 +552,5 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tm
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers(tmp_path):
     """A stand-alone program (mlp_grad_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "mlp_grad_host_main")
-    b = subprocess.run([cxx] + san + ["-DMLP_GRAD_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "mlp_grad_host_main", ["-DMLP_GRAD_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count(", off 0") == 7 * 4 * 2 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

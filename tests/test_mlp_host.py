@@ -10,18 +10,16 @@ compiled for the host with the system compiler and compared with mlp_rule byte f
 under the address and undefined-behaviour sanitizers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err, _net
 import helpers
+from hostcode import _vp, load_shared, run_sanitized
 from snac_amd import _lib
-from test_policy_act_host import spec_exp, spec_log  # noqa: F401  (spec_log: the rule's LOG, which the head does not need)
-from test_ppo_loss_host import _same
-from test_sac_host import _compiler
+from specmath import _same, spec_exp
 
-PH = C.c_void_p(1 << 20)                                             # an aligned placeholder: never dereferenced
 BIG = 2.0 ** 60
 HUGE = 3.0e38                                                        # a float32 whose sums with its like overflow float32, not float64
 # the networks of the GPU tests: (dims, num_actions or None)
@@ -34,7 +32,7 @@ HEADS = ("plain", "masked", "all_masked")
 
 
 # ---- the rule, in numpy: every ufunc call below is one float64 operation, rounded on its own ----------------------------------------------
-def _chain(W, b, x, order="sequential"):
+def layer_chain(W, b, x, order="sequential"):
     """acc [rows, N] float64 of one layer: W float32 [N, K], b float32 [N], x float32 [rows, K].  order: the stated one, or another
     association of the same sum (for the assertion that the generated inputs tell them apart)."""
     W64, x64 = W.astype(np.float64), x.astype(np.float64)
@@ -75,7 +73,7 @@ def mlp_rule(weights, biases, x, num_actions=None, order="sequential"):
         h = np.asarray(x).astype(np.float32)                         # float64 rows are rounded to float32 first
         acts = []
         for l, (W, b) in enumerate(zip(weights, biases)):
-            acc = _chain(W, b, h, order)
+            acc = layer_chain(W, b, h, order)
             if l == len(weights) - 1:
                 h = acc.astype(np.float32)
             else:
@@ -304,7 +302,7 @@ def derived_bound(c, out, good):
             W64, b64 = W.astype(np.float64), b.astype(np.float64)
             K = W.shape[1]
             size = np.abs(b64)[None, :] + np.abs(h.astype(np.float64)) @ np.abs(W64).T
-            acc = _chain(W, b, h)
+            acc = layer_chain(W, b, h)
             err = (K + 2) * U53 * size + U24 * np.abs(acc) + err @ np.abs(W64).T
             ref = ref @ W64.T + b64[None, :]
             if l < L - 1:
@@ -381,17 +379,6 @@ def make_leaves(rng, S, stats_rows, row_words=64, terminal_word=34):
 
 
 # ---- the C entry points ------------------------------------------------------------------------------------------------------------------
-def _net(dims=(51, 64, 6), w=None, b=None, layers=None):
-    net = _lib.Mlp()
-    net.layers = len(dims) - 1 if layers is None else layers
-    for l, d in enumerate(dims[:5]):
-        net.dim[l] = d
-    for l in range(min(4, len(dims) - 1)):
-        net.w[l] = (1 << 20) if w is None else w[l]
-        net.b[l] = (1 << 20) if b is None else b[l]
-    return net
-
-
 def _fwd(L, net=None, x=PH, f64=0, rows=4, y=PH):
     return L.snac_mlp_forward(C.byref(net) if net is not None else None, x, f64, rows, y, None)
 
@@ -404,11 +391,6 @@ def _vl(L, net=None, A=5, obs=PH, f64=0, S=4, first_has=PH, first_idx=PH, done=P
         bad=PH):
     return L.snac_mlp_uct_value_leaves(C.byref(net) if net is not None else None, A, obs, f64, S, first_has, first_idx, done, stats, stats_rows,
                                        leaf, priors, value, est, bad, None)
-
-
-def _err(L, rc, code, word):
-    assert rc == code, (rc, L.snac_last_error())
-    assert word in L.snac_last_error(), L.snac_last_error()
 
 
 def test_the_library_exports_the_entry_points():
@@ -514,18 +496,8 @@ HOST_SRC = os.path.join(helpers.TESTS, "native", "mlp_host.cpp")
 HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I", _lib.CSRC, HOST_SRC]
 
 
-def _vp(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "mlp_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    fn = C.CDLL(so).mlp_host
+    fn = load_shared(tmp_path, "mlp_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600).mlp_host
     vp = C.c_void_p
     fn.restype = C.c_int
     fn.argtypes = [C.c_int32, vp, vp, vp, vp, C.c_int, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
@@ -562,17 +534,5 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tm
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers(tmp_path):
     """A stand-alone program (mlp_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "mlp_host_main")
-    b = subprocess.run([cxx] + san + ["-DMLP_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "mlp_host_main", ["-DMLP_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count("bad ") == 7 * 3 * 2 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

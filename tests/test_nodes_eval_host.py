@@ -4,14 +4,10 @@ import ctypes as C
 
 import pytest
 
+from cabi_checks import PH, _desc
 from snac_amd import _lib
 
 NAMES = ("snac_evaluate_nodes1d", "snac_evaluate_nodes2d", "snac_evaluate_nodes3d")
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
-
-
-def _desc(kind, n=16, frame_value=0):
-    return _lib.EnvDesc(kind, 1, n, 4, 0, 0, 1, 0, 0, 0, frame_value, 0, 0, 0)
 
 
 def _call(L, name, d, st, pool=PH, pool_rows=16, m=4, node_rows=None, H=8, gpow=PH, est=PH, steps=None):

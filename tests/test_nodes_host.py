@@ -4,13 +4,10 @@ import ctypes as C
 
 import pytest
 
+from cabi_checks import _desc
 from snac_amd import _lib
 
 NAMES = ("snac_nodes1d_pack", "snac_nodes1d_unpack", "snac_transition_nodes1d", "snac_nodes3d_pack", "snac_nodes3d_unpack", "snac_transition_nodes3d")
-
-
-def _desc(kind, n=16, frame_value=0):
-    return _lib.EnvDesc(kind, 1, n, 4, 0, 0, 1, 0, 0, 0, frame_value, 0, 0, 0)
 
 
 def _call(L, name, d, st, pool, pool_rows, m, idx=None):

@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import ODD, PH, _err, _NoDevice
 from snac_amd import _lib
-from test_replay_nstep_host import _desc, gather_rule
-from test_uct_selfplay_host import ODD, PH, _err, _NoDevice
+from test_replay_nstep_host import gather_rule, ring_desc
 
 
 def _gae(L, N=4, cap=8, first=0, count=8, gamma=0.97, lam=0.95, reward=PH, done=PH, value=PH, boot=PH, adv=PH, ret=PH):
@@ -19,7 +19,7 @@ def _gae(L, N=4, cap=8, first=0, count=8, gamma=0.97, lam=0.95, reward=PH, done=
 
 def _gather(L, desc=True, st=True, kind=2, tail=0, cap=8, tiled=0, obs=PH, first=PH, plan_idx=PH, action=PH, value=PH, logp=PH, adv=PH, ret=PH,
             norm=PH, tick=PH, env=PH, batch=4, s=PH, plan=PH, action_out=PH, value_out=PH, logp_out=PH, adv_out=PH, ret_out=PH):
-    d, state = _desc(kind, tail), _lib.State(*[1 << 20] * 8)     # never dereferenced
+    d, state = ring_desc(kind, tail), _lib.State(*[1 << 20] * 8)  # never dereferenced
     return L.snac_replay_gather_onpolicy(C.byref(d) if desc else None, C.byref(state) if st else None, cap, tiled, obs, first, plan_idx, action,
                                          value, logp, adv, ret, norm, tick, env, batch, s, plan, action_out, value_out, logp_out, adv_out,
                                          ret_out, None)

@@ -9,48 +9,20 @@ import math
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err
 import rng_spec
 from snac_amd import _lib
-from test_uct_selfplay_host import PH, _err
+from specmath import spec_exp, spec_log
 
 CATEGORICAL, GREEDY, EPS_GREEDY = 0, 1, 2
 STREAM_POLICY = 5
 ACTIONS = {1: 3, 2: 5, 3: 8}                                         # num_actions of the three kinds
-LOG2E, LN2_HI, LN2_LO = float.fromhex("0x1.71547652b82fep+0"), float.fromhex("0x1.62e42feep-1"), float.fromhex("0x1.a39ef35793c76p-33")
-SQRT_HALF = float.fromhex("0x1.6a09e667f3bcdp-1")
-EXP_C = [np.float64(1.0) / np.float64(math.factorial(n)) for n in range(14)]
-LOG_D = [np.float64(1.0) / np.float64(2 * n + 1) for n in range(11)]
 # the fixed seed of the two statistical checks below: both statistics stay below their 99.9 % quantiles for it (the draws are a pure
 # function of the seed, so the checks are deterministic; about one seed in a thousand would miss each)
 STAT_SEED = 20261020
 
 
 # ---- the rule, in numpy: every ufunc call below is one float64 operation, rounded on its own --------------------------------------------
-def spec_exp(x):
-    x = np.asarray(x, np.float64)
-    with np.errstate(all="ignore"):
-        xc = np.where(x < -45.0, -45.0, x)
-        k = np.rint(xc * LOG2E)
-        r = (xc - k * LN2_HI) - k * LN2_LO
-        p = np.full_like(xc, EXP_C[13])
-        for n in range(12, -1, -1):
-            p = p * r + EXP_C[n]
-        return np.where(x < -45.0, 0.0, np.ldexp(p, k.astype(np.int32)))
-
-
-def spec_log(s):
-    s = np.asarray(s, np.float64)
-    f, e = np.frexp(s)
-    low = f < SQRT_HALF
-    f, e = np.where(low, f * 2.0, f), np.where(low, e - 1, e).astype(np.float64)
-    z = (f - 1.0) / (f + 1.0)
-    z2 = z * z
-    q = np.full_like(z, LOG_D[10])
-    for n in range(9, -1, -1):
-        q = q * z2 + LOG_D[n]
-    return e * LN2_HI + ((2.0 * z) * q + e * LN2_LO)
-
-
 def weights_of(scores):
     """(bad [N] bool, greedy [N], x [N, A] float64, e [N, A] float64, w [N, A] uint64) of float32 rows, bad rows taken as all zeros."""
     s = np.array(scores, np.float32, ndmin=2)

@@ -8,12 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err, _net
 import helpers
 import rng_spec
 from snac_amd import _lib
-from test_mlp_host import _err, _net, mlp_rule
+from test_mlp_host import mlp_rule
 from test_policy_act_host import ACTIONS, CATEGORICAL, EPS_GREEDY, GREEDY, eps_fx_of, policy_rule
-from test_uct_selfplay_host import PH
 
 OBS_NONE, OBS_ALL, OBS_LAST, OBS_TILED = 0, 1, 2, 3
 OBS_DIM = {1: 7, 2: 51, 3: 51}

@@ -9,44 +9,22 @@ compiled for the host with the system compiler and compared with ppo_rule byte f
 under the address and undefined-behaviour sanitizers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err
 import helpers
+from hostcode import load_shared, run_sanitized
 from snac_amd import _lib
-from test_policy_act_host import spec_exp, spec_log
-from test_sac_host import _compiler, soft_rule
-from test_uct_selfplay_host import PH
+from specmath import _same, spec_exp, spec_log, tree_sums
+from test_sac_host import soft_rule
 
 ACTIONS = (3, 5, 8)
 CLIP, VF_COEF, ENT_COEF = 0.2, 0.5, 0.01
 CLIP_VFS = (-1.0, 0.2)                                               # off, on
 LOGRATIO_MAX = 20.0
 STATS = ("total", "Lpi", "Lv", "H", "kl", "clipped", "good", "clamped")
-
-
-# ---- the reduction: two stages, each in the header's order ---------------------------------------------------------------------------------
-def tree_sums(u):
-    """u float64 [B, 8], the samples' contributions -> (partials [W, 8], sums [8])."""
-    B = len(u)
-    W = (B + 63) // 64
-    v = np.zeros((W * 64, u.shape[1]))
-    v[:B] = u                                                        # the last wave is filled up with 0.0
-    v = v.reshape(W, 64, -1)
-    for h in (32, 16, 8, 4, 2, 1):
-        v = v[:, :h] + v[:, h:]
-    partials = v[:, 0]
-    rounds = (W + 63) // 64
-    p = np.zeros((rounds * 64, u.shape[1]))
-    p[:W] = partials                                                 # a lane without a row in a round adds nothing: t + 0.0 is t (t is never -0.0)
-    t = np.zeros((64, u.shape[1]))
-    for k in range(rounds):
-        t = t + p[64 * k:64 * k + 64]
-    for h in (32, 16, 8, 4, 2, 1):
-        t = t[:h] + t[h:]
-    return partials, t[0]
 
 
 # ---- the rule, in numpy: every ufunc call below is one float64 operation, rounded on its own --------------------------------------------
@@ -230,13 +208,8 @@ def rule_of(c, clip_vf=CLIP_VFS[1], scale=1.0, **kw):
                     clip_vf=clip_vf, scale=scale, **kw)
 
 
-def _cases(rows=len(SORTS) * 48):
-    for A in ACTIONS:
-        yield A, make_case(np.random.default_rng(A), rows, A)
-
-
 def test_the_generated_inputs_contain_every_sort_and_the_order_of_the_sums_shows():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         sort = c["sort"]
         B = len(sort)
         on, off = rule_of(c, CLIP_VFS[1]), rule_of(c, CLIP_VFS[0])
@@ -283,7 +256,7 @@ def test_the_generated_inputs_contain_every_sort_and_the_order_of_the_sums_shows
 
 # ---- properties --------------------------------------------------------------------------------------------------------------------------
 def test_the_entropy_has_soft_rules_bytes_on_good_samples():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         for clip_vf in CLIP_VFS:
             out = rule_of(c, clip_vf)
             want = soft_rule(c["logits"])["entropy"]
@@ -382,7 +355,7 @@ def test_loss_and_gradients_stay_within_the_derived_bound_of_float64_torch_and_a
     left out of the comparison: under 1 % of the rows."""
     seen = np.zeros(3)
     rows_seen = 0
-    for A, c in _cases(len(SORTS) * 240):
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 240):
         for clip_vf in CLIP_VFS:
             for scale in (1.0, 1.0 / 4096.0):
                 out = rule_of(c, clip_vf, scale)
@@ -408,7 +381,7 @@ def test_loss_and_gradients_stay_within_the_derived_bound_of_float64_torch_and_a
 
 
 def test_bad_samples_give_zeros_add_nothing_and_are_counted():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         B = len(c["sort"])
         for clip_vf in CLIP_VFS:
             out = rule_of(c, clip_vf, 1.0 / B)
@@ -433,11 +406,6 @@ def _ppo(L, B=4, A=5, logits=PH, action=PH, logp=PH, adv=PH, value=PH, value_old
          scale=1.0, loss=PH, gl=PH, gv=PH, stats=PH, mean=PH, partials=PH, bad=PH):
     return L.snac_ppo_loss(B, A, logits, action, logp, adv, value, value_old, ret, clip, clip_vf, vf_coef, ent_coef, scale, loss, gl, gv, stats, mean,
                            partials, bad, None)
-
-
-def _err(L, rc, code, word):
-    assert rc == code, rc
-    assert word in L.snac_last_error(), L.snac_last_error()
 
 
 def test_the_library_exports_the_entry_point():
@@ -518,30 +486,13 @@ def test_ppo_loss_checks_its_arguments_before_it_touches_a_device():
 
 
 # ---- the kernel's code on the host -------------------------------------------------------------------------------------------------------
-def _same(got, want, what):
-    """Byte for byte, but a NaN of the rule is any NaN."""
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), (what, "NaNs")
-    word = np.uint32 if got.dtype == np.float32 else np.uint64
-    g, w = np.where(nan, 0, got).astype(got.dtype), np.where(nan, 0, want).astype(got.dtype)
-    diff = np.nonzero((g.view(word).reshape(len(g), -1) != w.view(word).reshape(len(w), -1)).any(axis=1))[0]
-    assert diff.size == 0, (what, "first row that differs", int(diff[0]), g[diff[0]], w[diff[0]])
-
-
 OUTPUTS = ("loss", "grad_logits", "grad_value", "stats", "mean_loss", "partials")
 HOST_SRC = os.path.join(helpers.TESTS, "native", "ppo_host.cpp")
 HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I", _lib.CSRC, HOST_SRC]
 
 
 def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "ppo_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    fn = C.CDLL(so).ppo_host
+    fn = load_shared(tmp_path, "ppo_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600).ppo_host
     fn.restype, fn.argtypes = C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 7 + [C.c_double] * 5 + [C.c_void_p] * 6
     vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     for A in ACTIONS:
@@ -569,17 +520,5 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tm
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers_with_actions_out_of_range(tmp_path):
     """A stand-alone program (ppo_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "ppo_host_main")
-    b = subprocess.run([cxx] + san + ["-DPPO_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "ppo_host_main", ["-DPPO_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count("bad ") == 18 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

@@ -10,10 +10,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import ODD, PH, _err, _NoDevice
 import rng_spec
 from snac_amd import _lib
-from test_uct_reanalyse_host import _play
-from test_uct_selfplay_host import ODD, PH, _err, _NoDevice, _search
+from test_uct_reanalyse_host import hostless_play
+from test_uct_selfplay_host import hostless_search
 
 STREAM_PRIO = 4
 LIMIT = (1 << 31) - 64
@@ -222,11 +223,11 @@ def test_selfplay_rejects_bad_priority_arguments_before_touching_a_device():
 
     for p in (1, 0, None, "yes"):
         with pytest.raises(ValueError, match="prioritized"):
-            SelfPlay(_search(), 8, prioritized=p)
+            SelfPlay(hostless_search(), 8, prioritized=p)
     for s in (-1, 32, 1.5, True):
         with pytest.raises(ValueError, match="priority_scale_log2"):
-            SelfPlay(_search(), 8, prioritized=True, priority_scale_log2=s)
-    p = _play()
+            SelfPlay(hostless_search(), 8, prioritized=True, priority_scale_log2=s)
+    p = hostless_play()
     p.tree = None                                                    # a ring built without a tree
     with pytest.raises(ValueError, match="prioritized=True needs the priority tree"):
         p.sample(4, prioritized=True)

@@ -11,17 +11,15 @@ snac_c51_loss (c51_loss_rule, make_c51_case, float64 log_softmax and autograd, L
 CategoricalSupport.loss); its kernel has no host form: lane = atom."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err
 import helpers
+from hostcode import load_shared, run_sanitized
 from snac_amd import _lib
-from test_policy_act_host import spec_exp, spec_log
-from test_ppo_loss_host import _same, tree_sums
-from test_sac_host import _compiler
-from test_uct_selfplay_host import PH
+from specmath import _same, spec_exp, spec_log, tree_sums
 
 assert {"snac_td_loss", "snac_c51_loss"} <= set(_lib.EXPORTS), "include/snac_hip.h declares the entry points this file is about"
 
@@ -201,13 +199,8 @@ def rule_of(c, mode="double", weighted=True, delta=DELTA, scale=1.0):
     return td_rule(c["q"], c["action"], weight=c["weight"] if weighted else None, delta=delta, scale=scale, **kw)
 
 
-def _cases(rows=len(SORTS) * 48):
-    for A in ACTIONS:
-        yield A, make_case(np.random.default_rng(A), rows, A)
-
-
 def test_the_generated_inputs_contain_every_sort_in_its_branch_and_the_order_of_the_sums_shows():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         sort = c["sort"]
         B = len(sort)
         n = B // len(SORTS)
@@ -310,7 +303,7 @@ def test_loss_and_gradient_stay_within_the_derived_bound_of_float64_torch_and_au
     seen = np.zeros(3)
     rows_seen = 0
     tiny = 1e-300                                                    # 0 / 0 where a sample's numbers are all zero
-    for A, c in _cases(len(SORTS) * 240):
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 240):
         for mode in MODES:
             for weighted in (False, True):
                 for delta in DELTAS:
@@ -335,7 +328,7 @@ def test_loss_and_gradient_stay_within_the_derived_bound_of_float64_torch_and_au
 
 
 def test_bad_samples_give_zeros_add_nothing_and_are_counted():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         B = len(c["sort"])
         for mode in MODES:
             for weighted in (False, True):
@@ -358,11 +351,6 @@ def _td(L, B=4, A=5, q=PH, action=PH, y=None, q_next=PH, q_select=PH, ret=PH, di
         y_out=PH, gq=PH, stats=PH, mean=PH, partials=PH, bad=PH):
     return L.snac_td_loss(B, A, q, action, y, q_next, q_select, ret, discount, weight, delta, scale, loss, prio, y_out, gq, stats, mean, partials, bad,
                           None)
-
-
-def _err(L, rc, code, word):
-    assert rc == code, rc
-    assert word in L.snac_last_error(), L.snac_last_error()
 
 
 MODE_Y = dict(y=PH, q_next=None, q_select=None, ret=None, discount=None)
@@ -455,13 +443,7 @@ HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I", _lib.CSRC, HOST_SRC]
 
 
 def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "td_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    fn = C.CDLL(so).td_host
+    fn = load_shared(tmp_path, "td_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600).td_host
     fn.restype, fn.argtypes = C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.c_double] * 2 + [C.c_void_p] * 7
     vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
 
@@ -493,19 +475,7 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tm
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers_with_actions_out_of_range(tmp_path):
     """A stand-alone program (td_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "td_host_main")
-    b = subprocess.run([cxx] + san + ["-DTD_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "td_host_main", ["-DTD_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count("bad ") == 54 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 

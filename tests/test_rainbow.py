@@ -21,21 +21,12 @@ def _file():
     return _Z
 
 
-def _names():
-    return _file()["cases"].tolist()
-
-
-def _rec(name):
-    z = _file()
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
 def _kind(name):
     return int(name[0]), name.split(".")[0].endswith("dynamic")
 
 
 def _replay(name, reset, step, state):
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     dim, dyn = _kind(name)
     starts = dict((int(s), e) for e, s in enumerate(rec["ep_start"]))
     S = len(rec["actions"])
@@ -57,7 +48,7 @@ def _replay(name, reset, step, state):
             assert np.float64(iou).tobytes() == np.float64(rec["ep_iou"][e]).tobytes()
 
 
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_oracle_replays_rainbow_goldens(name):
     orc = helpers.oracle()
     dim, dyn = _kind(name)
@@ -76,14 +67,14 @@ def test_oracle_replays_rainbow_goldens(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_rainbow_facades_on_hip(name):
     dim, dyn = _kind(name)
     path = os.path.join(helpers.ROOT, "snac_amd", "script", "Rainbow", "env", "Env%dD.py" % dim)
     spec = importlib.util.spec_from_file_location("rainbow_shim_%d" % dim, path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    rec0 = _rec(name)
+    rec0 = helpers.npz_case(_file(), name)
     uniform = bool(rec0["uniform"])
     plan = name.split(".")[1]
     args = types.SimpleNamespace(plan_choose=None if dyn else int(plan), half_window_size=2 if dim == 1 else 3, history_length=4,

@@ -22,15 +22,6 @@ def _file():
     return _Z
 
 
-def _names():
-    return _file()["cases"].tolist()
-
-
-def _rec(name):
-    z = _file()
-    return {k.split("/", 1)[1]: z[k] for k in z.files if k.startswith(name + "/")}
-
-
 def _new_plan(dim, final_grid, orig_plan):
     g = final_grid.astype(np.float64)
     if dim == 1:
@@ -40,10 +31,10 @@ def _new_plan(dim, final_grid, orig_plan):
     return p
 
 
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_oracle_relabels_like_the_reference(name):
     orc = helpers.oracle()
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     dim, pc = int(name[0]), int(name.split(".")[1][1:])
     orig = orc.static_plan(dim, pc)
     env = orc.OracleEnv(dim, False)
@@ -58,11 +49,11 @@ def test_oracle_relabels_like_the_reference(name):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", _names())
+@pytest.mark.parametrize("name", helpers.npz_names(_file()))
 def test_hindsight_class_relabel_flow_on_hip(name):
     mods = {1: ("1D", "DMP_Env_1D_static_hindsight_replay"), 2: ("2D", "DMP_Env_2D_static_hindsight_replay"),
             3: ("3D", "DMP_simulator_3d_static_circle_hindsight_replay")}
-    rec = _rec(name)
+    rec = helpers.npz_case(_file(), name)
     dim, pc = int(name[0]), int(name.split(".")[1][1:])
     sub, mod = mods[dim]
     path = os.path.join(helpers.ROOT, "snac_amd", "Env", sub)
@@ -93,8 +84,8 @@ def test_batched_relabel_in_one_launch(dim):
     import torch
     from snac_amd.hindsight import relabel_rewards
 
-    names = [n for n in _names() if n.startswith("%dd." % dim)]
-    recs = [_rec(n) for n in names]
+    names = [n for n in helpers.npz_names(_file()) if n.startswith("%dd." % dim)]
+    recs = [helpers.npz_case(_file(), n) for n in names]
     T = max(len(r["actions"]) for r in recs)
     N = len(recs)
     A = np.zeros((T, N), np.int8)
@@ -130,8 +121,8 @@ def test_relabel_of_a_device_batch_without_synchronising(dim):
     from snac_amd import BatchedDMPEnv
     from snac_amd.hindsight import relabel_batch
 
-    names = [n for n in _names() if n.startswith("%dd." % dim)]
-    recs = [_rec(n) for n in names]
+    names = [n for n in helpers.npz_names(_file()) if n.startswith("%dd." % dim)]
+    recs = [helpers.npz_case(_file(), n) for n in names]
     T = max(len(r["actions"]) for r in recs)
     N = len(recs)
     A = np.zeros((T, N), np.int8)

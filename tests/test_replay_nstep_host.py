@@ -9,24 +9,24 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import ODD, PH, _err, _NoDevice
 from snac_amd import _lib
-from test_uct_selfplay_host import ODD, PH, _err, _NoDevice
 
 
-def _desc(kind=2, tail=0):
+def ring_desc(kind=2, tail=0):
     return _lib.EnvDesc(kind, 1, 16, 4, 0, 0, 1, 0, 0, 0, 0, 0, tail, 0)
 
 
 def _nstep(L, desc=True, st=True, kind=2, tail=0, cap=8, tiled=0, obs=PH, first=PH, done=PH, reward=PH, action=PH, plan_idx=PH, newest=3, tick=PH,
            env=PH, batch=4, n=3, gamma=0.97, s=PH, s_next=PH, plan=PH, action_out=PH, ret=PH, disc=PH, done_out=PH, steps=PH):
-    d, state = _desc(kind, tail), _lib.State(*[1 << 20] * 8)     # never dereferenced
+    d, state = ring_desc(kind, tail), _lib.State(*[1 << 20] * 8)  # never dereferenced
     return L.snac_replay_gather_nstep(C.byref(d) if desc else None, C.byref(state) if st else None, cap, tiled, obs, first, done, reward, action,
                                       plan_idx, newest, tick, env, batch, n, gamma, s, s_next, plan, action_out, ret, disc, done_out, steps, None)
 
 
 def _windows(L, desc=True, st=True, kind=2, tail=0, cap=8, tiled=0, obs=PH, first=PH, done=PH, reward=PH, action=PH, plan_idx=PH, oldest=3, tick=PH,
              env=PH, batch=4, length=5, s=PH, s_next=PH, plan=PH, action_out=PH, reward_out=PH, done_out=PH, mask=PH, length_out=PH):
-    d, state = _desc(kind, tail), _lib.State(*[1 << 20] * 8)
+    d, state = ring_desc(kind, tail), _lib.State(*[1 << 20] * 8)
     return L.snac_replay_gather_windows(C.byref(d) if desc else None, C.byref(state) if st else None, cap, tiled, obs, first, done, reward, action,
                                         plan_idx, oldest, tick, env, batch, length, s, s_next, plan, action_out, reward_out, done_out, mask,
                                         length_out, None)
@@ -96,7 +96,7 @@ def test_gather_windows_validates_its_arguments_before_any_hip_call():
 
 def _plain(L, fn="snac_replay_gather", desc=True, st=True, kind=2, tail=0, cap=8, obs=PH, first=PH, plan_idx=PH, tick=PH, env=PH, batch=4, s=PH,
            s_next=PH, plan=PH):
-    d, state = _desc(kind, tail), _lib.State(*[1 << 20] * 8)     # never dereferenced
+    d, state = ring_desc(kind, tail), _lib.State(*[1 << 20] * 8)  # never dereferenced
     return getattr(L, fn)(C.byref(d) if desc else None, C.byref(state) if st else None, cap, obs, first, plan_idx, tick, env, batch, s, s_next,
                           plan, None)
 

@@ -7,16 +7,17 @@ and SoftValue checks its tensors before it touches a device.  Last, the per-samp
 is compiled for the host with the system compiler and compared with soft_rule byte for byte."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err
 import helpers
+from hostcode import _compiler
 from snac_amd import _lib
-from test_policy_act_host import CATEGORICAL, policy_rule, spec_exp, spec_log
-from test_uct_selfplay_host import PH
+from specmath import _same, spec_exp, spec_log
+from test_policy_act_host import CATEGORICAL, policy_rule
 
 ACTIONS = (3, 5, 8)
 ALPHAS = (0.0, 0.2, 1.0)
@@ -152,18 +153,13 @@ def bad_rows_of(B, shift=0, want_y=True):
     return sum(SORTS[(i + shift) % len(SORTS)] in bad for i in range(B))
 
 
-def _cases(rows=len(SORTS) * 48):
-    for A in ACTIONS:
-        yield A, make_case(np.random.default_rng(A), rows, A)
-
-
 def _rule(c, alpha=0.2, two=True, want_y=True, scale=1.0, q1=None, q2=None):
     q1, q2 = c["q1"] if q1 is None else q1, c["q2"] if q2 is None else q2
     return soft_rule(c["logits"], q1, q2 if two else None, alpha, c["ret"] if want_y else None, c["discount"] if want_y else None, scale)
 
 
 def test_the_generated_inputs_contain_every_sort():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         l, q1, q2, ret, discount, sort = (c[k] for k in ("logits", "q1", "q2", "ret", "discount", "sort"))
         B = len(ret)
         assert set(sort) == set(SORTS) and bad_rows_of(B) == B // len(SORTS) * 6 and bad_rows_of(B, want_y=False) == B // len(SORTS) * 3
@@ -196,7 +192,7 @@ def test_the_generated_inputs_contain_every_sort():
 def test_the_entropy_is_snac_policy_acts_byte_for_byte():
     """On every sample that is not bad: snac_policy_act draws a bad row as if its scores were 0 and so gives it log(A); here a bad sample
     gives 0.  The logits alone decide the entropy: q, alpha and y change no byte of it."""
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         B = len(c["ret"])
         want = policy_rule(1, np.arange(B), 0, CATEGORICAL, c["logits"])["entropy"]
         alone = soft_rule(c["logits"])
@@ -231,7 +227,7 @@ def test_value_and_gradient_stay_within_1e_12_of_float64_torch_and_autograd():
     not measured.  What is seen is printed: about 1e-15."""
     seen_v = seen_g = 0.0
     rows_seen = 0
-    for A, c in _cases(len(SORTS) * 320):
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 320):
         for alpha in ALPHAS:
             for two in (True, False):
                 out, rows, V, G = _torch_reference(c, alpha, two)
@@ -245,7 +241,7 @@ def test_value_and_gradient_stay_within_1e_12_of_float64_torch_and_autograd():
 
 def test_masked_actions_get_no_gradient_and_their_q_values_change_no_byte():
     rng = np.random.default_rng(7)
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         for alpha in ALPHAS:
             out = _rule(c, alpha)
             assert not out["grad"][~out["live"]].any()               # exactly 0, +0.0 bytes
@@ -262,7 +258,7 @@ def test_masked_actions_get_no_gradient_and_their_q_values_change_no_byte():
 
 
 def test_the_gradient_of_a_sample_sums_to_zero():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         for alpha in ALPHAS:
             for scale in (1.0, 1.0 / 2048.0):
                 out = _rule(c, alpha, want_y=False, scale=scale)
@@ -272,7 +268,7 @@ def test_the_gradient_of_a_sample_sums_to_zero():
 
 
 def test_bad_samples_give_zeros_and_the_exact_count():
-    for A, c in _cases():
+    for A, c in helpers.cases_per_action(make_case, ACTIONS, len(SORTS) * 48):
         B = len(c["ret"])
         out = _rule(c)
         bad = out["bad"]
@@ -297,11 +293,6 @@ def test_bad_samples_give_zeros_and_the_exact_count():
 # ---- the C entry point -------------------------------------------------------------------------------------------------------------------
 def _soft(L, B=4, A=5, logits=PH, q1=PH, q2=PH, alpha=PH, ret=PH, discount=PH, scale=1.0, v=PH, y=PH, entropy=PH, grad=PH, bad=PH):
     return L.snac_soft_value(B, A, logits, q1, q2, alpha, ret, discount, scale, v, y, entropy, grad, bad, None)
-
-
-def _err(L, rc, code, word):
-    assert rc == code, rc
-    assert word in L.snac_last_error(), L.snac_last_error()
 
 
 def test_the_library_exports_the_entry_point():
@@ -370,24 +361,6 @@ def test_soft_value_checks_its_arguments_before_it_touches_a_device():
 
 
 # ---- the kernel's code on the host -------------------------------------------------------------------------------------------------------
-def _compiler():
-    for name in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        path = name and shutil.which(name)
-        if path:
-            return path
-    return None
-
-
-def _same(got, want, what):
-    """Byte for byte, but a NaN of the rule is any NaN."""
-    assert got.dtype == want.dtype == np.float32 and got.shape == want.shape, what
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan), (what, "NaNs")
-    g, w = np.where(nan, np.float32(0), got), np.where(nan, np.float32(0), want)
-    diff = np.nonzero((g.view(np.uint32).reshape(len(g), -1) != w.view(np.uint32).reshape(len(w), -1)).any(axis=1))[0]
-    assert diff.size == 0, (what, "first sample that differs", int(diff[0]), g[diff[0]], w[diff[0]])
-
-
 def test_the_kernels_per_sample_function_compiled_for_the_host_equals_the_rule_byte_for_byte(tmp_path):
     cxx = _compiler()
     if cxx is None:

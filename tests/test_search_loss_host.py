@@ -10,17 +10,15 @@ compiler and compared with search_rule byte for byte, and the same source runs o
 undefined-behaviour sanitizers."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi_checks import PH, _err_code as _err
 import helpers
+from hostcode import load_shared, run_sanitized
 from snac_amd import _lib
-from test_policy_act_host import spec_exp, spec_log
-from test_ppo_loss_host import _same, tree_sums
-from test_sac_host import _compiler
-from test_uct_selfplay_host import PH
+from specmath import _same, spec_exp, spec_log, tree_sums
 
 ACTIONS = (3, 5, 8)
 DELTA = 1.0                                                          # the Huber delta of the generated cases; 0: the squared error
@@ -211,7 +209,7 @@ def _cases(rows=len(SORTS) * 48):
         yield A, make_search_case(np.random.default_rng(A), rows, A)
 
 
-def _plain(col):
+def plain_sum(col):
     s = np.float64(0.0)
     for t in col:
         s = s + t
@@ -286,7 +284,7 @@ def test_the_generated_inputs_contain_every_sort_in_its_branch_and_the_order_of_
     B = 4097
     for A in ACTIONS:
         out = rule_of(make_search_case(np.random.default_rng(100 * A + B), B, A, B % len(SORTS)))
-        plain, tree = _plain(out["u"][:, 0]), tree_sums(out["u"])[1][0]
+        plain, tree = plain_sum(out["u"][:, 0]), tree_sums(out["u"])[1][0]
         assert np.float64(plain).tobytes() != np.float64(tree).tobytes(), (A, plain, tree)
         assert abs(plain - tree) <= 1e-9 * np.abs(out["u"][:, 0]).sum()                          # the same sum, in another order
 
@@ -387,11 +385,6 @@ def _sl(L, B=4, A=5, logits=PH, value=PH, pi=PH, z=PH, weight=PH, vf_coef=1.0, d
     return L.snac_search_loss(B, A, logits, value, pi, z, weight, vf_coef, delta, scale, loss, prio, gl, gv, stats, mean, partials, bad, None)
 
 
-def _err(L, rc, code, word):
-    assert rc == code, rc
-    assert word in L.snac_last_error(), L.snac_last_error()
-
-
 def test_the_library_exports_the_entry_point():
     L = _lib.lib()
     assert L.snac_version() == _lib.ABI_VERSION == 12                # additions only
@@ -475,13 +468,7 @@ HOST_FLAGS = ["-std=c++17", "-ffp-contract=off", "-I", _lib.CSRC, HOST_SRC]
 
 
 def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tmp_path):
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    so = str(tmp_path / "search_host.so")
-    b = subprocess.run([cxx, "-O2", "-fPIC", "-shared"] + HOST_FLAGS + ["-o", so], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    fn = C.CDLL(so).search_host
+    fn = load_shared(tmp_path, "search_host", ["-O2", "-fPIC", "-shared"] + HOST_FLAGS, timeout=600).search_host
     fn.restype, fn.argtypes = C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 5 + [C.c_double] * 3 + [C.c_void_p] * 7
     vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
 
@@ -510,17 +497,5 @@ def test_the_kernels_code_compiled_for_the_host_equals_the_rule_byte_for_byte(tm
 
 def test_the_kernels_code_runs_clean_under_the_host_sanitizers(tmp_path):
     """A stand-alone program (search_host.cpp with its main), not code loaded into python."""
-    cxx = _compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text("int main() { return 0; }\n")
-    if subprocess.run([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], capture_output=True, timeout=300).returncode != 0:
-        pytest.skip("the compiler lacks the sanitizers' runtimes")
-    exe = str(tmp_path / "search_host_main")
-    b = subprocess.run([cxx] + san + ["-DSEARCH_HOST_MAIN"] + HOST_FLAGS + ["-o", exe], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    r = run_sanitized(tmp_path, "search_host_main", ["-DSEARCH_HOST_MAIN"] + HOST_FLAGS, probe_timeout=300, build_timeout=600, run_timeout=300)
     assert r.stdout.count("bad ") == 36 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

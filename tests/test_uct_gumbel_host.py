@@ -6,9 +6,9 @@ import ctypes as C
 
 import pytest
 
+from cabi_checks import PH, _err, _fn, _NoDeviceOfFour
 from snac_amd import _lib
 
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
 OFF8 = C.c_void_p((1 << 20) + 8)                                     # 8-byte aligned only: not a bounds array
 OFF64 = C.c_void_p((1 << 20) + 64)                                   # 16-byte aligned, not 128: not a statistics array
 INT_MAX = 0x7FFFFFFF
@@ -23,12 +23,6 @@ def _select(L, A=5, stats=PH, rows=100, B=4, cap=8, K=3, vl=0.5, fpv=0.0, tlen=1
 
 def _cands(L, A=5, stats=PH, rows=100, B=4, cap=8, mode=HALVE, m=4, scores=PH, c_visit=50.0, c_scale=1.0, fpv=0.0, bounds=PH, cand=PH, action=PH):
     return L.snac_uct_gumbel_candidates(A, stats, rows, B, cap, mode, m, scores, c_visit, c_scale, fpv, bounds, cand, action, None)
-
-
-def _err(L, rc, *words):
-    assert rc == -1, rc
-    msg = L.snac_last_error()
-    assert any(w in msg for w in words), msg
 
 
 def test_the_library_exports_the_gumbel_entry_points():
@@ -106,18 +100,6 @@ def test_gumbel_candidates_validates_its_arguments_before_any_hip_call():
     _err(L, _cands(L, mode=HALVE, m=0, action=None, cand=None), b"null cand")
 
 
-class _NoDevice:
-    """Enough of an env for UCTSearch to reach its argument checks; touching anything else is the failure the test looks for."""
-    num_envs = 4
-
-    def __getattr__(self, name):
-        raise AssertionError("UCTSearch touched env.%s before it rejected its arguments" % name)
-
-
-def _fn(obs):
-    raise AssertionError("the evaluator was called")
-
-
 @pytest.mark.parametrize("kw", [dict(gumbel=4), dict(gumbel=4, evaluator=_fn), dict(gumbel=4, q_normalise=True),
                                 dict(gumbel=0, evaluator=_fn, q_normalise=True), dict(gumbel=-3, evaluator=_fn, q_normalise=True),
                                 dict(gumbel=2.0, evaluator=_fn, q_normalise=True), dict(gumbel="4", evaluator=_fn, q_normalise=True),
@@ -130,7 +112,7 @@ def test_uctsearch_rejects_a_gumbel_search_it_cannot_run_before_allocating(kw):
     args = dict(nodes_per_tree=16, horizon=0, gamma=0.9)
     args.update(kw)
     with pytest.raises(ValueError, match="[gG]umbel"):
-        UCTSearch(_NoDevice(), **args)
+        UCTSearch(_NoDeviceOfFour(), **args)
 
 
 class _Search:

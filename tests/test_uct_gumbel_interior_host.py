@@ -8,9 +8,9 @@ import math
 
 import pytest
 
+from cabi_checks import PH, _err, _fn, _NoDeviceOfFour
 from snac_amd import _lib
 
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
 OFF8 = C.c_void_p((1 << 20) + 8)                                     # 8-byte aligned only: not a bounds array
 OFF64 = C.c_void_p((1 << 20) + 64)                                   # 16-byte aligned, not 128: not a statistics array
 INT_MAX = 0x7FFFFFFF
@@ -71,12 +71,6 @@ def _priors(L, A=5, stats=PH, rows=100, m=4, node_rows=PH, priors=PH, value=PH, 
 
 def _policy(L, A=5, stats=PH, rows=100, B=4, cap=8, m=4, node_rows=PH, c_visit=50.0, c_scale=1.0, bounds=PH, pi=PH):
     return L.snac_uct_improved_policy(A, stats, rows, B, cap, m, node_rows, c_visit, c_scale, bounds, pi, None)
-
-
-def _err(L, rc, *words):
-    assert rc == -1, rc
-    msg = L.snac_last_error()
-    assert any(w in msg for w in words), msg
 
 
 def test_the_library_exports_the_gumbel_interior_entry_points():
@@ -169,18 +163,6 @@ def test_improved_policy_validates_its_arguments_before_any_hip_call():
 
 
 # ---- UCTSearch --------------------------------------------------------------------------------------------------------------------------------
-class _NoDevice:
-    """Enough of an env for UCTSearch to reach its argument checks; touching anything else is the failure the test looks for."""
-    num_envs = 4
-
-    def __getattr__(self, name):
-        raise AssertionError("UCTSearch touched env.%s before it rejected its arguments" % name)
-
-
-def _fn(obs):
-    raise AssertionError("the evaluator was called")
-
-
 @pytest.mark.parametrize("kw", [dict(gumbel_interior=True), dict(gumbel_interior=True, evaluator=_fn, q_normalise=True),
                                 dict(gumbel=4, evaluator=_fn, q_normalise=True, gumbel_interior=1),
                                 dict(gumbel=4, evaluator=_fn, q_normalise=True, gumbel_interior=None),
@@ -192,4 +174,4 @@ def test_uctsearch_rejects_a_gumbel_interior_it_cannot_run_before_allocating(kw)
     args = dict(nodes_per_tree=16, horizon=0, gamma=0.9)
     args.update(kw)
     with pytest.raises(ValueError, match="gumbel_interior"):
-        UCTSearch(_NoDevice(), **args)
+        UCTSearch(_NoDeviceOfFour(), **args)

@@ -6,9 +6,9 @@ import ctypes as C
 
 import pytest
 
+from cabi_checks import PH, _err, _fn, _NoDeviceOfFour
 from snac_amd import _lib
 
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
 OFF8 = C.c_void_p((1 << 20) + 8)                                     # 8-byte aligned only: not a bounds array
 OFF64 = C.c_void_p((1 << 20) + 64)                                   # 16-byte aligned, not 128: not a statistics array
 
@@ -29,12 +29,6 @@ def _backup(L, A=5, stats=PH, rows=100, B=4, cap=8, K=3, slots=PH, est=PH, bound
 
 def _bounds(L, stats=PH, rows=100, B=4, cap=8, used=PH, mask=None, bounds=PH):
     return L.snac_uct_bounds(stats, rows, B, cap, used, mask, bounds, None)
-
-
-def _err(L, rc, *words):
-    assert rc == -1, rc
-    msg = L.snac_last_error()
-    assert any(w in msg for w in words), msg
 
 
 def test_the_library_exports_the_normalised_entry_points():
@@ -127,18 +121,6 @@ def test_bounds_validates_its_arguments_before_any_hip_call():
     _err(L, _bounds(L, mask=PH, bounds=None), b"null bounds")        # a mask does not change the checks
 
 
-class _NoDevice:
-    """Enough of an env for UCTSearch to reach its argument checks; touching anything else is the failure the test looks for."""
-    num_envs = 4
-
-    def __getattr__(self, name):
-        raise AssertionError("UCTSearch touched env.%s before it rejected its arguments" % name)
-
-
-def _fn(obs):
-    raise AssertionError("the evaluator was called")
-
-
 @pytest.mark.parametrize("kw", [dict(q_normalise=1), dict(q_normalise="yes"), dict(q_normalise=0), dict(q_normalise=None),
                                 dict(q_normalise=1, evaluator=_fn), dict(q_normalise="yes", evaluator=_fn, paths=4)])
 def test_uctsearch_rejects_a_q_normalise_that_is_not_a_bool_before_allocating(kw):
@@ -147,4 +129,4 @@ def test_uctsearch_rejects_a_q_normalise_that_is_not_a_bool_before_allocating(kw
     args = dict(nodes_per_tree=16, horizon=0, gamma=0.9)
     args.update(kw)
     with pytest.raises(ValueError, match="q_normalise"):
-        UCTSearch(_NoDevice(), **args)
+        UCTSearch(_NoDeviceOfFour(), **args)

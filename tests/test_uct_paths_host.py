@@ -5,9 +5,8 @@ import ctypes as C
 
 import pytest
 
+from cabi_checks import PH, _NoDeviceOfFour
 from snac_amd import _lib
-
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
 
 
 def _select(L, A=5, stats=PH, rows=100, B=4, cap=8, K=3, vl=0.5, tlen=16, ltab=PH, rtab=PH, slots=PH, leaf=PH, first=PH):
@@ -65,14 +64,6 @@ def test_multi_path_entry_points_validate_their_arguments_before_any_hip_call(ca
         err(call(L, est=None), b"null per-slot")
 
 
-class _NoDevice:
-    """Enough of an env for UCTSearch to reach its argument checks; touching anything else is the failure the test looks for."""
-    num_envs = 4
-
-    def __getattr__(self, name):
-        raise AssertionError("UCTSearch touched env.%s before it rejected its arguments" % name)
-
-
 @pytest.mark.parametrize("kw", [dict(paths=0), dict(paths=-1), dict(paths=2.5), dict(paths=2, virtual_loss=float("nan")),
                                 dict(paths=2, virtual_loss=float("inf")), dict(virtual_loss=float("-inf")),
                                 dict(paths=1 << 30, trees=4), dict(paths=2, max_iterations=1 << 30), dict(paths=1 << 29, trees=8)])
@@ -82,11 +73,11 @@ def test_uctsearch_rejects_bad_path_arguments_before_allocating(kw):
     args = dict(nodes_per_tree=16, horizon=10, gamma=0.9)
     args.update(kw)
     with pytest.raises(ValueError):
-        UCTSearch(_NoDevice(), **args)
+        UCTSearch(_NoDeviceOfFour(), **args)
 
 
-class _Sharded(_NoDevice):
-    """_NoDevice with a shard's base: the one attribute the key check reads."""
+class _Sharded(_NoDeviceOfFour):
+    """_NoDeviceOfFour with a shard's base: the one attribute the key check reads."""
 
     def __init__(self, env_id_base):
         self.env_id_base = env_id_base
@@ -104,7 +95,7 @@ def test_uctsearch_rejects_a_base_whose_slot_keys_leave_int64(base, K):
 
 @pytest.mark.parametrize("base,K", [((1 << 62) - 4, 2), (-(1 << 62), 2), (1000, 16), ((1 << 63) - 5, 1)])
 def test_uctsearch_accepts_a_base_whose_slot_keys_fit_int64(base, K):
-    """The key check passes: the constructor goes on to the env's first real attribute, which _NoDevice answers with an AssertionError."""
+    """The key check passes: the constructor goes on to the env's first real attribute, which _NoDeviceOfFour answers with an AssertionError."""
     from snac_amd import UCTSearch
 
     assert K == 1 or -(1 << 63) <= base * K <= (base + 4) * K - 1 < 1 << 63

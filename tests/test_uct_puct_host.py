@@ -5,9 +5,9 @@ import ctypes as C
 
 import pytest
 
+from cabi_checks import PH, _desc, _err, _fn, _NoDeviceOfFour
 from snac_amd import _lib
 
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
 OBSERVE = ("snac_observe_nodes1d", "snac_observe_nodes2d", "snac_observe_nodes3d")
 
 
@@ -28,12 +28,6 @@ def test_the_library_exports_the_puct_entry_points():
         assert n in _lib.EXPORTS
         assert getattr(L, n) is not None
         assert len(getattr(L, n).argtypes) == k
-
-
-def _err(L, rc, *words):
-    assert rc == -1, rc
-    msg = L.snac_last_error()
-    assert any(w in msg for w in words), msg
 
 
 def test_select_puct_validates_its_arguments_before_any_hip_call():
@@ -78,10 +72,6 @@ def test_set_priors_validates_its_arguments_before_any_hip_call():
     assert _priors(L, m=0) == 0                                      # nothing to do: no launch
 
 
-def _desc(kind, n=16, frame_value=0):
-    return _lib.EnvDesc(kind, 1, n, 4, 0, 0, 1, 0, 0, 0, frame_value, 0, 0, 0)
-
-
 def _observe(L, name, d, st, pool, pool_rows, m, idx=None, obs=PH):
     return getattr(L, name)(C.byref(d) if d is not None else None, C.byref(st) if st is not None else None, pool, pool_rows, m, idx, obs, None)
 
@@ -117,18 +107,6 @@ def test_observe_nodes_validates_its_arguments_before_any_hip_call(name):
         assert err(_observe(L, name, _desc(kind, frame_value=2), st, PH, 16, 4), b"canonical") == -3
 
 
-class _NoDevice:
-    """Enough of an env for UCTSearch to reach its argument checks; touching anything else is the failure the test looks for."""
-    num_envs = 4
-
-    def __getattr__(self, name):
-        raise AssertionError("UCTSearch touched env.%s before it rejected its arguments" % name)
-
-
-def _fn(obs):
-    raise AssertionError("the evaluator was called")
-
-
 @pytest.mark.parametrize("kw", [dict(evaluator=3), dict(evaluator="net"), dict(evaluator=_fn, first_play_value=float("nan")),
                                 dict(evaluator=_fn, first_play_value=float("inf")), dict(evaluator=_fn, first_play_value=float("-inf")),
                                 dict(first_play_value=0.0), dict(first_play_value=-1.5), dict(evaluator=_fn, paths=0),
@@ -139,4 +117,4 @@ def test_uctsearch_rejects_bad_evaluator_arguments_before_allocating(kw):
     args = dict(nodes_per_tree=16, horizon=0, gamma=0.9)
     args.update(kw)
     with pytest.raises(ValueError):
-        UCTSearch(_NoDevice(), **args)
+        UCTSearch(_NoDeviceOfFour(), **args)

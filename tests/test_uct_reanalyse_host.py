@@ -9,8 +9,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import ODD, PH, _err, _NoDevice
 from snac_amd import _lib
-from test_uct_selfplay_host import ODD, PH, _err, _NoDevice, _search, _tree_checks
+from test_uct_selfplay_host import hostless_search, tree_checks
 
 PH2 = C.c_void_p(1 << 24)                                            # a second placeholder, far from PH: src beside records
 
@@ -62,7 +63,7 @@ def test_save_roots_validates_its_arguments_before_any_hip_call():
 
 def test_load_roots_validates_its_arguments_before_any_hip_call():
     L = _lib.lib()
-    _tree_checks(L, _load)
+    tree_checks(L, _load)
     _record_checks(L, _load)
     _err(L, _load(L, src=None), b"null src")
     _err(L, _load(L, src=C.c_void_p((1 << 24) + 64)), b"src must be 128-byte")
@@ -80,7 +81,7 @@ def test_load_roots_validates_its_arguments_before_any_hip_call():
 
 def test_store_targets_validates_its_arguments_before_any_hip_call():
     L = _lib.lib()
-    _tree_checks(L, _store)
+    tree_checks(L, _store)
     _err(L, _store(L, index=None), b"null index")
     _err(L, _store(L, entries=-1), b"entries must be")
     _err(L, _store(L, pi=None), b"null ring array")
@@ -117,18 +118,18 @@ def test_returns_nstep_validates_its_arguments_before_any_hip_call():
 
 
 # ---- the python layer -----------------------------------------------------------------------------------------------------------------
-def _play(keep_states=True, trees=4, cap=8, moves=8):
+def hostless_play(keep_states=True, trees=4, cap=8, moves=8):
     """A SelfPlay that was never constructed on a device: the attributes reanalyse() and targets() check, nothing else."""
     from snac_amd import SelfPlay
 
-    s = _search(trees=trees, num_envs=trees)
+    s = hostless_search(trees=trees, num_envs=trees)
     p = object.__new__(SelfPlay)
     p.search, p.env, p.keep_states, p.cap, p.moves, p.head = s, s.env, keep_states, cap, moves, moves % cap
     return p
 
 
 def _second(p, trees=4, evaluator=len, max_iterations=16, num_actions=5):
-    s = _search(trees=trees)
+    s = hostless_search(trees=trees)
     s.env, s.evaluator, s.max_iterations, s.num_actions = p.env, evaluator, max_iterations, num_actions
     return s
 
@@ -138,13 +139,13 @@ def test_selfplay_rejects_a_keep_states_that_is_no_bool_before_touching_a_device
 
     for k in (3, 1, 0, None, "yes"):
         with pytest.raises(ValueError, match="keep_states"):
-            SelfPlay(_search(), 8, keep_states=k)
+            SelfPlay(hostless_search(), 8, keep_states=k)
 
 
 def test_reanalyse_rejects_bad_arguments_before_touching_a_device():
-    p = _play()
+    p = hostless_play()
     with pytest.raises(ValueError, match="keep_states=True"):
-        _play(keep_states=False).reanalyse(_second(p), 4)
+        hostless_play(keep_states=False).reanalyse(_second(p), 4)
     with pytest.raises(ValueError, match="second UCTSearch"):
         p.search.evaluator = len
         p.reanalyse(p.search, 4)                                     # the playing search itself
@@ -159,7 +160,7 @@ def test_reanalyse_rejects_bad_arguments_before_touching_a_device():
     assert len(p) == 32
     with pytest.raises(ValueError, match="33 trees to reanalyse, 32 entries"):
         p.reanalyse(_second(p, trees=33), 4)                         # R > len(play)
-    few = _play(moves=2)
+    few = hostless_play(moves=2)
     assert len(few) == 8
     with pytest.raises(ValueError, match="9 trees to reanalyse, 8 entries"):
         few.reanalyse(_second(few, trees=9), 4)
@@ -169,7 +170,7 @@ def test_reanalyse_rejects_bad_arguments_before_touching_a_device():
 
 
 def test_targets_rejects_bad_td_steps_before_touching_a_device():
-    p = _play()
+    p = hostless_play()
     for n in (0, -2, 1.5, True):
         with pytest.raises(ValueError, match="td_steps"):
             p.targets(td_steps=n)
@@ -181,7 +182,7 @@ def test_load_roots_rejects_wrong_shapes_before_touching_a_device():
     class Pool:
         WORDS, KIND = 32, 2
 
-    s = _search()
+    s = hostless_search()
     s.pool = Pool()
     ok = torch.zeros((6, 128), dtype=torch.uint8)
     for rec in (torch.zeros((6, 127), dtype=torch.uint8), torch.zeros((6, 896), dtype=torch.uint8), torch.zeros(6 * 128, dtype=torch.uint8),

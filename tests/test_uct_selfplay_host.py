@@ -9,18 +9,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from cabi_checks import ODD, PH, _desc, _err, _NoDevice
 from snac_amd import _lib
-
-PH = C.c_void_p(1 << 20)                                             # 128-byte aligned placeholder
-ODD = C.c_void_p((1 << 20) + 64)
-
-
-def _desc():
-    return _lib.EnvDesc(2, 1, 16, 4, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0)
 
 
 def _pick(L, desc=True, A=5, stats=PH, rows=100, B=4, cap=8, greedy=PH, t=3, action=PH, pi=PH, value=PH):
-    d = _desc()
+    d = _desc(2)
     return L.snac_uct_pick_moves(C.byref(d) if desc else None, A, stats, rows, B, cap, greedy, t, action, pi, value, None)
 
 
@@ -32,12 +26,6 @@ def _returns(L, B=4, capm=8, first=0, count=8, gamma=0.97, reward=PH, done=PH, b
     return L.snac_uct_returns(B, capm, first, count, gamma, reward, done, boot, z, None)
 
 
-def _err(L, rc, *words):
-    assert rc == -1, rc
-    msg = L.snac_last_error()
-    assert any(w in msg for w in words), msg
-
-
 def test_the_library_exports_the_self_play_entry_points():
     L = _lib.lib()
     assert L.snac_version() == _lib.ABI_VERSION == 12                # additions only
@@ -47,7 +35,7 @@ def test_the_library_exports_the_self_play_entry_points():
         assert len(getattr(L, n).argtypes) == k
 
 
-def _tree_checks(L, call):
+def tree_checks(L, call):
     for A in (0, 2, 4, 6, 7, 9):
         _err(L, call(L, A=A), b"num_actions")
     _err(L, call(L, stats=None), b"null stats")
@@ -61,7 +49,7 @@ def _tree_checks(L, call):
 
 def test_pick_moves_validates_its_arguments_before_any_hip_call():
     L = _lib.lib()
-    _tree_checks(L, _pick)
+    tree_checks(L, _pick)
     _err(L, _pick(L, desc=False), b"null desc")
     assert _pick(L, action=None, pi=None, value=None) == 0           # nothing asked for: no launch
     assert _pick(L, action=None, pi=None, value=None, greedy=None, rows=36) == 0
@@ -70,7 +58,7 @@ def test_pick_moves_validates_its_arguments_before_any_hip_call():
 
 def test_restart_validates_its_arguments_before_any_hip_call():
     L = _lib.lib()
-    _tree_checks(L, _restart)
+    tree_checks(L, _restart)
     _err(L, _restart(L, records=None), b"null records")
     _err(L, _restart(L, records=ODD), b"records must be 128-byte")
     for rb in (0, 64, 256, 512, 895, 1024):
@@ -101,17 +89,7 @@ def test_returns_validates_its_arguments_before_any_hip_call():
     _err(L, _returns(L, count=0, z=None), b"null ring array")        # the checks come first
 
 
-class _NoDevice:
-    """Enough of an env to reach the argument checks; touching anything else is the failure the tests look for."""
-
-    def __init__(self, **have):
-        self.__dict__.update(have)
-
-    def __getattr__(self, name):
-        raise AssertionError("env.%s was touched before the arguments were rejected" % name)
-
-
-def _search(trees=4, num_envs=4, **kw):
+def hostless_search(trees=4, num_envs=4, **kw):
     """A UCTSearch that was never constructed on a device: the attributes the checks read, nothing else."""
     from snac_amd import UCTSearch
 
@@ -129,22 +107,22 @@ def test_selfplay_rejects_bad_arguments_before_touching_a_device(kw):
     from snac_amd import SelfPlay
 
     with pytest.raises(ValueError):
-        SelfPlay(_search(), **kw)
+        SelfPlay(hostless_search(), **kw)
 
 
 def test_selfplay_needs_a_tree_per_env_row():
     from snac_amd import SelfPlay
 
     with pytest.raises(ValueError, match="tree b to env row b"):
-        SelfPlay(_search(trees=8, num_envs=4), 16)
+        SelfPlay(hostless_search(trees=8, num_envs=4), 16)
     with pytest.raises(ValueError, match="tree b to env row b"):
-        SelfPlay(_search(trees=4, num_envs=8), 16)
+        SelfPlay(hostless_search(trees=4, num_envs=8), 16)
 
 
 def test_play_rejects_a_budget_below_an_episode_of_searches():
     from snac_amd import SelfPlay
 
-    s = _search(total_step=600)
+    s = hostless_search(total_step=600)
     p = object.__new__(SelfPlay)                                     # as constructed, without the ring's device tensors
     p.search, p.env = s, s.env
     s.max_iterations = 601 * 8 - 1
@@ -164,7 +142,7 @@ def test_play_rejects_a_budget_below_an_episode_of_searches():
 def test_pick_moves_and_restart_reject_bad_arguments_before_touching_a_device():
     import torch
 
-    s = _search()
+    s = hostless_search()
     for g in (torch.zeros(3, dtype=torch.uint8), torch.zeros(5, dtype=torch.bool), [True, False], "all", 0.5):
         with pytest.raises(ValueError):
             s.pick_moves(greedy=g)
@@ -182,7 +160,7 @@ def test_pick_moves_and_restart_reject_bad_arguments_before_touching_a_device():
     with pytest.raises(ValueError):
         s.restart(torch.zeros(4, dtype=torch.uint8), rows=torch.zeros(4))
     with pytest.raises(ValueError):
-        _search(trees=8, num_envs=4).restart(torch.zeros(8, dtype=torch.uint8))          # more trees than env rows: rows must be given
+        hostless_search(trees=8, num_envs=4).restart(torch.zeros(8, dtype=torch.uint8))  # more trees than env rows: rows must be given
 
 
 # ---- the sampler's rule, in numpy ---------------------------------------------------------------------------------------------------
